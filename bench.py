@@ -11,10 +11,18 @@ grouped and evaluated into one of 2 ring slots of 81.9 GB (one allocation, slots
 copied to the host.  Tables, queries and
 the ring are resident in HBM when the timed region starts.  N>1: every rank runs the same per-GPU batch on its
 own device (weak scaling), tables replicated, no collective on the data path; with N > 1 the per-GPU batch defaults to
-C4's share (BASELINE configs[3]: 1.25e7 queries per GPU, 5 chunks) and every rank also runs C5's per-GPU share
-(configs[4]) after the timed region -- the line carries both with per-rank clocks.
+C4's share (BASELINE configs[3]: 1.25e7 queries per GPU, 5 chunks) and, with --full, every rank also runs C5's
+per-GPU share (configs[4]) after the timed region -- the line then carries both with per-rank clocks.
+
+A plain run sets up, warms up, times the steps and prints the result line; nothing else runs.  `--full` adds
+everything else the bench measures or checks after the timed region: the sampled-rows check against the CPU oracle,
+the gather-formulation pass, the placement probe, the secondary legs (other BASELINE configs, sizes, precisions),
+the in-process sharded leg, the HBM traffic child runs under rocprofv3 --pmc, the CPU baseline and, with N > 1, the
+per-rank C5-share leg.  `--dump-outputs DIR` writes a fixed, seeded sample of the rows the last timed step computed
+to DIR/rows.npy (float64), so that two builds can be compared output for output.
 
     python bench.py                                  # N=1, Target
+    python bench.py --full --steps 20 --warmup 5     # the same, then every other measurement and check
     python bench.py --gpus 8 --steps 20 --warmup 5   # spawns 8 ranks itself (RCCL barrier / max-reduce only)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   # external launcher: same
     python bench.py --workload c2|c3|c5|c2-linear|c2-f32|c1 ...                    # secondary measurements
@@ -65,6 +73,21 @@ def synth_target_queries(x, nq, chunk, rank):
         m = min(chunk, nq - off)
         parts.append(np.random.default_rng([123, rank, c]).uniform(x[0], x[-1], m))
     return np.concatenate(parts)
+
+
+DUMP_BYTES = 32 << 20     # --dump-outputs: at most this many bytes of output rows per rank
+
+
+def dump_sample(nq, lanes, itemsize=8):
+    """--dump-outputs: the query rows (and, for very wide rows, the lanes) of the output that are written out -- every
+    row when the whole output fits in DUMP_BYTES, otherwise a fixed, seeded sample, the same on every run with the same
+    sizes.  Returns (sorted row indices, sorted lane indices or None for all lanes)."""
+    rows = min(nq, max(1, DUMP_BYTES // (lanes * itemsize)))
+    cols = min(lanes, DUMP_BYTES // (rows * itemsize))
+    rng = np.random.default_rng(20240611)
+    r = np.arange(nq) if rows == nq else np.sort(rng.choice(nq, rows, replace=False))
+    c = None if cols == lanes else np.sort(rng.choice(lanes, cols, replace=False))
+    return r, c
 
 
 def measure_traffic_pmc(args, kernel_substr, timeout_s=90):
@@ -997,10 +1020,27 @@ def run_target(args, pkg, torch, dist, dev, rank, world):
         ring = [torch.empty((chunk, lanes), dtype=torch.float64, device=dev) for _ in range(args.ring_slots)]
     nchunks = (nq + chunk - 1) // chunk
     seen = {"chunks": 0, "rows": 0}
+    # --dump-outputs: during the last timed step the consumer gathers the sampled rows of every chunk into one device
+    # buffer (enqueued on the current stream, so ordered before the slot's reuse); index tensors are made up front
+    dump = None
+    if args.dump_outputs:
+        sample_rows, sample_cols = dump_sample(nq, lanes)
+        dump = {"on": False, "parts": {},
+                "buf": torch.empty((sample_rows.size, lanes if sample_cols is None else sample_cols.size),
+                                   dtype=torch.float64, device=dev),
+                "cols": None if sample_cols is None else torch.as_tensor(sample_cols, device=dev)}
+        for qb in range(0, nq, chunk):
+            lo, hi = np.searchsorted(sample_rows, [qb, qb + chunk])
+            dump["parts"][qb] = (int(lo), int(hi), torch.as_tensor(sample_rows[lo:hi] - qb, device=dev))
 
     def consumer(c, rows):        # a real consumer would enqueue its work on c.stream here
         seen["chunks"] += 1
         seen["rows"] += c.q_count
+        if dump is not None and dump["on"]:
+            lo, hi, idx = dump["parts"][c.q_begin]
+            if hi > lo:
+                sel = rows.index_select(0, idx)
+                dump["buf"][lo:hi] = sel if dump["cols"] is None else sel.index_select(1, dump["cols"])
         return None
 
     def step():
@@ -1022,7 +1062,9 @@ def run_target(args, pkg, torch, dist, dev, rank, world):
     fence()
     step_s = []
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for s in range(args.steps):
+        if dump is not None and s == args.steps - 1:
+            dump["on"] = True
         ts = time.perf_counter()
         step()                       # returns after the step's last kernel has completed (one sync inside)
         step_s.append(time.perf_counter() - ts)
@@ -1031,6 +1073,11 @@ def run_target(args, pkg, torch, dist, dev, rank, world):
     prof = pkg.profile_read(reset=True)
     pkg.profile_enable(False)
     assert seen["chunks"] == nchunks * args.steps and seen["rows"] == nq * args.steps, seen
+    if dump is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "rows.npy" if world == 1 else f"rows_rank{rank}.npy"),
+                dump["buf"].cpu().numpy())
+        dump = None
 
     my_elapsed = elapsed
     my_kernel_ms = prof["eval_ms"] / max(1, prof["eval_launches"])
@@ -1046,11 +1093,11 @@ def run_target(args, pkg, torch, dist, dev, rank, world):
     points_per_step = nq * lanes
     value = world * points_per_step * args.steps / elapsed / 1e6
 
-    # N > 1 (or --c5-leg): BASELINE configs[4]'s per-GPU share on EVERY rank at the same time, after the timed region --
-    # 8192 x 8192 x 16 f32 grid replicated per device, this rank's 1.25e7 of the 1e8 scattered queries, no collective on
-    # the data path; per-rank clocks gathered like the headline's
+    # N > 1 with --full (or --c5-leg): BASELINE configs[4]'s per-GPU share on EVERY rank at the same time, after the timed
+    # region -- 8192 x 8192 x 16 f32 grid replicated per device, this rank's 1.25e7 of the 1e8 scattered queries, no
+    # collective on the data path; per-rank clocks gathered like the headline's
     c5 = None
-    if world > 1 or args.c5_leg:
+    if (world > 1 and args.full) or args.c5_leg:
         fence()
         mine = bilinear_leg(pkg, torch, dev, args.c5_leg_grid, 16, args.c5_leg_queries, steps=10, warmup=2, rank=rank)
         fence()
@@ -1307,9 +1354,23 @@ def main():
     ap.add_argument("--launch-rehearsal", action="store_true",
                     help="no GPU work: only the launch / rendezvous / barrier / max-over-ranks skeleton (gloo), used by "
                          "the CPU tests to cover the N>1 self-launch")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run every other measurement and check (oracle check, gather "
+                         "leg, placement probe, secondary legs, sharded leg, rocprofv3 --pmc traffic, CPU baseline; "
+                         "N > 1: the per-rank C5-share leg); the --no-* options above switch single ones off again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="target: write a fixed, seeded sample (at most 32 MiB) of the rows the last timed step "
+                         "computed to DIR/rows.npy (float64; DIR/rows_rank<r>.npy per rank with N > 1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload != "target":
+        ap.error("--dump-outputs writes the target workload's output; the --workload runs do not support it")
     if args.queries is None:   # N = 1: the Target; N > 1: C4's per-GPU share (BASELINE configs[3]: 1e8 queries over 8 GPUs)
         args.queries = (12_500_000 if args.gpus > 1 else 10_000_000) if args.workload == "target" else 1_000_000
+    if not args.full:          # a plain run does only what the headline needs: no leg after the timed region
+        args.no_check = args.no_gather_leg = args.no_secondary = args.no_pmc = args.no_cpu_baseline = True
+        args.placement_probe = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))          # nothing in this process has touched the GPU
@@ -1336,7 +1397,7 @@ def main():
             ranks = gather_ranks(torch, dist, world, rank, 1.0 + rank, 0.5 + rank,
                                  {"rank": rank, "ordinal": local_rank, "uuid": f"rehearsal-{rank}", "name": "none"}, "cpu")
         c5 = None
-        if world > 1:     # the per-rank C5-share leg's gather (all_gather_object of one dict per rank), with stand-in numbers
+        if world > 1 and args.full:   # the per-rank C5-share leg's gather (all_gather_object of one dict per rank), stand-in numbers
             per = [None] * world
             dist.all_gather_object(per, {"ms_per_step": 0.7 + 0.01 * rank, "kernel_ms": 0.6 + 0.01 * rank})
             c5 = {"per_rank_ms": [p["ms_per_step"] for p in per], "per_rank_kernel_ms": [p["kernel_ms"] for p in per],

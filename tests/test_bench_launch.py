@@ -3,10 +3,13 @@ rank processes before touching the GPU, and the same file must run under an exte
 the two ways the driver may start it (benches/bench_interp1d.rs:49-79 is the reference's
 multi-worker shape).  --launch-rehearsal skips the GPU work; everything else (env, rendezvous, barrier,
 max-over-ranks, single JSON line from rank 0) is the code path of the real run."""
+import importlib.util
 import json
 import os
 import subprocess
 import sys
+
+import numpy as np
 
 from conftest import ROOT
 
@@ -79,7 +82,7 @@ def test_bench_eight_rank_rehearsal_is_c4_with_eight_ranks():
     """The N = 8 launch the driver makes (rehearsed on the CPU over gloo: 8 real GPU ranks are the driver's to start, and a
     1-GPU box admits at most 6 processes on its card): the defaults land on BASELINE configs[3] -- "= C4" --, the line
     carries 8 ranks' clocks and devices, and the per-rank C5-share gather carries 8 entries."""
-    r = _run(["--gpus", "8", "--launch-rehearsal"])
+    r = _run(["--gpus", "8", "--launch-rehearsal", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     line = _one_json_line(r.stdout)
     assert line["n_gpus"] == 8 and line["queries_per_gpu"] == 12_500_000
@@ -91,7 +94,71 @@ def test_bench_eight_rank_rehearsal_is_c4_with_eight_ranks():
     assert len(c5["per_rank_ms"]) == 8 and len(c5["per_rank_kernel_ms"]) == 8 and c5["ms_per_step"] == max(c5["per_rank_ms"])
 
 
+def test_bench_plain_n_rank_run_has_no_c5_leg():
+    """Without --full the N > 1 line is the headline alone: the per-rank C5-share leg is part of --full."""
+    r = _run(["--gpus", "2", "--launch-rehearsal"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _one_json_line(r.stdout)
+    assert line["n_gpus"] == 2 and line["ranks"]["world"] == 2 and line["c5_share"] is None
+
+
+def _load_bench():
+    spec = importlib.util.spec_from_file_location("ndi_bench", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_bench_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs writes a fixed, seeded sample: the same rows on every run, sorted, at most DUMP_BYTES of f64 --
+    every row when the whole output fits, and a lane sample too when one row alone would not."""
+    b = _load_bench()
+    r1, c1 = b.dump_sample(10_000_000, 4096)
+    r2, c2 = b.dump_sample(10_000_000, 4096)
+    assert np.array_equal(r1, r2) and c1 is None and c2 is None and np.all(np.diff(r1) > 0) and r1[-1] < 10_000_000
+    assert r1.size * 4096 * 8 == b.DUMP_BYTES <= 64 << 20
+    r, c = b.dump_sample(1000, 8)
+    assert np.array_equal(r, np.arange(1000)) and c is None
+    r, c = b.dump_sample(50, 8 << 20)
+    assert r.size == 1 and 0 < c.size * 8 <= b.DUMP_BYTES and np.all(np.diff(c) > 0)
+
+
+def test_bench_rejects_bad_options_before_any_gpu_work():
+    for bad in (["--steps", "0"], ["--workload", "c3", "--dump-outputs", "out"]):
+        r = _run(bad, timeout=60)
+        assert r.returncode == 2 and "error" in r.stderr, (bad, r.stderr[-500:])
+
+
 import pytest
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) prints the result line with nothing measured or checked after the timed region, and
+    --dump-outputs writes the sampled rows of the last timed step: the CPU oracle's rows, bit for bit."""
+    n, lanes, nq, chunk = 512, 1024, 400_000, 100_000
+    out = tmp_path / "out"
+    r = _run(["--knots", str(n), "--lanes", str(lanes), "--queries", str(nq), "--chunk", str(chunk), "--steps", "3",
+              "--warmup", "1", "--dump-outputs", str(out)], timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _one_json_line(r.stdout)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "Mpoints/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert not {"check", "gather_formulation", "placement", "secondary", "tail_summary", "cpu_baseline", "c5_share",
+                "in_process_sharded"} & set(line), sorted(line)
+    assert "traffic_detail" not in line["roofline"] and "traffic_measurement_failed" not in line["roofline"]
+    assert sorted(os.listdir(out)) == ["rows.npy"]
+    rows = np.load(out / "rows.npy")
+    b = _load_bench()
+    ridx, cidx = b.dump_sample(nq, lanes)
+    assert cidx is None and ridx.size < nq and rows.shape == (ridx.size, lanes) and rows.dtype == np.float64
+    import oracle
+    x, y, _ = b.synth_c2(n, lanes, 1, 0)
+    q = b.synth_target_queries(x, nq, chunk, 0)
+    st, ta, tb = oracle.cubic_build(x, y)
+    assert st == oracle.OK
+    _, _, ref = oracle.interp1d_cubic(x, y, ta, tb, q[ridx])
+    assert np.array_equal(rows, ref)
 
 
 @pytest.mark.gpu
@@ -100,7 +167,7 @@ def test_bench_six_ranks_on_one_gpu_line_carries_every_rank():
     a small C4-shaped workload, children spawned before any GPU call): 6 ranks' clocks in `ranks`, 6 per-rank entries in
     the C5-share leg, max-over-ranks timing."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "6", "--backend", "gloo",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "6", "--full", "--backend", "gloo",
                         "--device-override", "0", "--knots", "512", "--lanes", "512", "--queries", "200000",
                         "--chunk", "50000", "--steps", "2", "--warmup", "1", "--placement-probe", "0", "--no-check",
                         "--no-gather-leg", "--no-pmc", "--c5-leg-grid", "512", "--c5-leg-queries", "100000"],
@@ -119,7 +186,7 @@ def test_bench_two_ranks_on_one_gpu_line_carries_ranks():
     """The real N = 2 code path on a 1-GPU box (gloo, both ranks on device 0, a small Target-shaped workload): the
     JSON line carries `ranks` with both ranks' clocks, kernel times and the device they ran on."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--backend", "gloo",
                         "--device-override", "0", "--knots", "512", "--lanes", "1024", "--queries", "400000",
                         "--chunk", "100000", "--steps", "3", "--warmup", "1", "--placement-probe", "0",
                         "--no-gather-leg", "--no-pmc", "--c5-leg-grid", "1024", "--c5-leg-queries", "300000"],
@@ -144,7 +211,7 @@ def test_bench_force_dist_runs_the_collectives_on_rccl_with_one_rank():
     all_gather_object of the N > 1 path execute on RCCL with world size 1 -- environment / API breakage shows up on
     the 1-GPU box, before the driver's 8-GPU run."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--knots", "512",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--force-dist", "--knots", "512",
                         "--lanes", "1024", "--queries", "400000", "--chunk", "100000", "--steps", "3", "--warmup", "1",
                         "--placement-probe", "0", "--no-gather-leg", "--no-pmc", "--no-secondary", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, env=env)
@@ -159,8 +226,8 @@ def test_bench_force_dist_runs_the_collectives_on_rccl_with_one_rank():
 def test_bench_in_process_sharded_leg():
     """The leg the N = 1 run adds when its one process sees several devices (one ndi_interp1d_eval_ring_sharded call
     per step over all of them), rehearsed on the 1-GPU box with two replicas on device 0 and a small workload."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--knots", "512", "--lanes", "1024", "--queries",
-                        "400000", "--chunk", "100000", "--steps", "2", "--warmup", "1", "--placement-probe", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--knots", "512", "--lanes", "1024",
+                        "--queries", "400000", "--chunk", "100000", "--steps", "2", "--warmup", "1", "--placement-probe", "0",
                         "--no-gather-leg", "--no-pmc", "--no-cpu-baseline", "--sharded-leg-devices", "0,0"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -4,6 +4,8 @@ argument by argument (order, name, C type) and its return type, every enumerator
 type.  There is no rustc in the build image, so this (not a compiler) is what keeps the two files in step: swapping
 two fields or arguments in either file fails here.  Also: the ctypes binding's structs against the same header."""
 import ctypes as C
+import hashlib
+import json
 import os
 import re
 
@@ -259,12 +261,72 @@ def test_patch_adds_both_hooks_and_the_strategies_override_them():
     assert "pub const NDI_EVAL_FRESH_OUTPUT: i32 = 1;" in ffi and "pub const NDI_EVAL_ROWS_AFTER_ERROR_UNSPECIFIED: i32 = 2;" in ffi
 
 
+PREIMAGE = os.path.join(ROOT, "tests", "golden", "reference_patch_preimage.json")
+
+
+def parse_patch(text):
+    """{file: [(old_start, old_count, old_lines, new_lines)]} of a unified diff; a hunk's lines are read by the counts
+    of its header (a header that miscounts swallows or drops lines and fails the checks below)."""
+    files, cur, hunk, left = {}, None, None, (0, 0)
+    for line in text.splitlines(keepends=True):
+        if left != (0, 0):
+            tag, body = line[:1], line[1:]
+            assert tag in (" ", "-", "+"), f"hunk line without a diff tag: {line!r}"
+            if tag in " -":
+                hunk[2].append(body)
+            if tag in " +":
+                hunk[3].append(body)
+            left = (left[0] - (tag in " -"), left[1] - (tag in " +"))
+            assert min(left) >= 0, f"hunk at -{hunk[0]} holds more lines than its header counts"
+        elif line.startswith("+++ b/"):
+            cur = files.setdefault(line[len("+++ b/"):].strip(), [])
+        elif line.startswith("@@ "):
+            m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", line)
+            hunk = (int(m.group(1)), int(m.group(2) or 1), [], [])
+            cur.append(hunk)
+            left = (hunk[1], int(m.group(4) or 1))
+    assert left == (0, 0), "the last hunk is cut short"
+    return files
+
+
+def preimage_record(patch_text, read_lines):
+    """Per touched file: its length in lines and, per hunk, (old_start, old_count, SHA-256 of those lines) as
+    `read_lines(file)` gives them.  On the reference checkout this made tests/golden/reference_patch_preimage.json."""
+    out = {}
+    for f, hunks in parse_patch(patch_text).items():
+        lines = read_lines(f)
+        out[f] = {"lines": len(lines), "hunks": [[s, n, hashlib.sha256("".join(lines[s - 1:s - 1 + n]).encode()).hexdigest()]
+                                                 for s, n, _, _ in hunks]}
+    return out
+
+
 def test_patch_applies_to_the_reference_sources(tmp_path):
-    """Where the reference checkout is present (this container; not the GPU box): `patch --dry-run` of the hook patch."""
+    """The hook patch against the published ndarray-interp 0.6.0 sources, recorded in tests/golden as line counts and
+    hashes (no source text): every hunk's context and removed lines must hash to the lines the release holds at the
+    hunk's own position -- the patch applies with no offset and no fuzz -- and patch(1) must apply it, unfuzzed, to a
+    stand-in tree that holds exactly those lines at those positions and distinct filler lines everywhere else."""
     import shutil
     import subprocess
-    ref = "/root/reference/src"
-    if not os.path.isdir(ref) or shutil.which("patch") is None:
-        pytest.skip("no reference checkout / no patch(1) here")
-    r = subprocess.run(["patch", "-p1", "--dry-run", "-d", "/root/reference", "-i", PATCH], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    rec = json.load(open(PREIMAGE))["files"]
+    text = open(PATCH).read()
+    hunks = parse_patch(text)
+    assert sorted(hunks) == sorted(rec) and len(hunks) == 4, sorted(hunks)
+    stand_in = {}
+    for f, hs in hunks.items():
+        lines = [f"filler line {i} of {f}\n" for i in range(rec[f]["lines"])]
+        end = 0
+        for s, n, old, _ in hs:
+            assert len(old) == n and s > end and s - 1 + n <= len(lines), (f, s, n)
+            lines[s - 1:s - 1 + n] = old
+            end = s - 1 + n
+        stand_in[f] = lines
+    got = preimage_record(text, lambda f: stand_in[f])
+    for f in rec:
+        assert got[f] == rec[f], f"{f}: the patch's pre-image differs from the release's lines\n  patch   {got[f]}\n  release {rec[f]}"
+    if shutil.which("patch") is not None:
+        for f, lines in stand_in.items():
+            p = tmp_path / f
+            p.parent.mkdir(parents=True, exist_ok=True)
+            p.write_text("".join(lines))
+        r = subprocess.run(["patch", "-p1", "--dry-run", "-F0", "-d", str(tmp_path), "-i", PATCH], capture_output=True, text=True)
+        assert r.returncode == 0 and "offset" not in r.stdout and "fuzz" not in r.stdout, r.stdout + r.stderr

@@ -3,7 +3,7 @@
 : "${GRAFT_REPO_ROOT:?run on the GPU box (gpurun sets GRAFT_REPO_ROOT)}"
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
-cd $R && python bench.py --steps 20 --warmup 5 > $O/r03_bench_default.json 2> $O/r03_bench_default.err
+cd $R && python bench.py --full --steps 20 --warmup 5 > $O/r03_bench_default.json 2> $O/r03_bench_default.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/r03_stats
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r03_stats -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-check --no-gather-leg --placement-probe 0 --no-secondary --no-pmc > $O/r03_target_bench_under_rocprof.json 2>/dev/null

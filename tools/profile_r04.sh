@@ -9,7 +9,7 @@
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 T="--no-cpu-baseline --no-check --no-gather-leg --placement-probe 0 --no-secondary --no-pmc"
-cd $R && python bench.py --steps 20 --warmup 5 > $O/r04_bench_default.json 2> $O/r04_bench_default.err
+cd $R && python bench.py --full --steps 20 --warmup 5 > $O/r04_bench_default.json 2> $O/r04_bench_default.err
 cd /tmp && export TMPDIR=/tmp
 for path in auto gather; do
   tag=$([ $path = auto ] && echo target || echo target_gather)
