@@ -12,9 +12,12 @@
  *  - plain C types only; no exceptions, no panics cross the ABI; every call
  *    returns an ndi_status (ndi_last_error_string() has the text for the calling
  *    thread).
- *  - element type T is selected per handle by ndi_dtype (f32 / f64 only: the GPU
- *    path covers the float types; integer element types stay on the host's generic
- *    per-query path).
+ *  - element type T is selected per handle by ndi_dtype: f32 / f64 (every strategy), and -- added in v0.5,
+ *    backward-compatible: new enumerators only -- i32 / i64 for Linear and Bilinear.  Integer T follows the
+ *    reference's `T` arithmetic exactly: division truncates toward zero and an intermediate that does not fit T is
+ *    reported as NDI_INT_OVERFLOW (a Rust debug build panics there).  Integer handles keep slope records {y, m}
+ *    instead of the data on the device, about twice the data's memory.  Other integer widths (unsigned, 8/16-bit)
+ *    stay on the host's generic per-query path, see INTEGRATION.md.
  *  - arrays are C-order and contiguous: data[n][lanes], data2d[nx][ny][lanes];
  *    "lanes" = product of the trailing (non-interpolated) axes.
  *  - every pointer argument carries a memory space (host or device).  Device
@@ -46,10 +49,23 @@ typedef enum ndi_status {
   NDI_NAN_QUERY = 6,       /* reference panics: vector_extensions.rs:83-84                 */
   NDI_HIP_ERROR = 7,       /* no device / HIP runtime failure                              */
   NDI_BAD_ARG = 8,
-  NDI_UNSUPPORTED = 9
+  NDI_UNSUPPORTED = 9,
+  NDI_INT_OVERFLOW = 10    /* integer T: "attempt to {subtract,multiply,add,divide} with overflow" (a Rust debug
+                              build's panic inside Linear::calc_frac, linear.rs:29-36); added in v0.5 */
 } ndi_status;
 
-typedef enum ndi_dtype { NDI_F32 = 0, NDI_F64 = 1 } ndi_dtype;
+/* NDI_I32 / NDI_I64 (v0.5, backward-compatible): NDI_LINEAR and Bilinear only; NDI_CUBIC_SPLINE is refused with
+ * NDI_BAD_ARG (the reference's trait bounds forbid it), ndi_interp1d_coefficients on such a handle is NDI_BAD_ARG and
+ * NDI_PATH_BUCKETED is NDI_UNSUPPORTED (AUTO and GATHER evaluate). */
+typedef enum ndi_dtype { NDI_F32 = 0, NDI_F64 = 1, NDI_I32 = 2, NDI_I64 = 3 } ndi_dtype;
+
+/* The operation of Linear::calc_frac (linear.rs:29-36) that overflowed: ndi_oob_info.axis for NDI_INT_OVERFLOW. */
+typedef enum ndi_int_op {
+  NDI_OP_SUBTRACT = 0,
+  NDI_OP_MULTIPLY = 1,
+  NDI_OP_ADD = 2,
+  NDI_OP_DIVIDE = 3
+} ndi_int_op;
 typedef enum ndi_memspace { NDI_MEM_HOST = 0, NDI_MEM_DEVICE = 1 } ndi_memspace;
 
 /* 1D strategies: Linear (src/interp1d/strategies/linear.rs),
@@ -159,12 +175,16 @@ typedef struct ndi_interp2d ndi_interp2d;
  * (src/interp1d/mod.rs:334-342, src/interp2d/mod.rs:297-306).  `index` is the lowest
  * flat query index that failed, `value` the offending coordinate and `axis` 0 for x,
  * 1 for y (x is tested before y for the same query: bilinear.rs:71-80), so the host
- * can format the reference's message ("x = {x:#?} is not in range"). */
+ * can format the reference's message ("x = {x:#?} is not in range").
+ * Integer handles: the lowest failing query wins whether it is out of bounds or overflows; within a query the range
+ * tests come first (x before y).  For NDI_INT_OVERFLOW `axis` is the ndi_int_op of the first overflowing operation in
+ * the reference's order (lane by lane; z1, z2, then the y step for Bilinear) and `value` the query's x converted to
+ * double -- lossy for i64 beyond 2^53: bindings format messages from the query element itself. */
 typedef struct ndi_oob_info {
   uint64_t index;
   double value;
   int32_t axis;
-  int32_t status; /* NDI_OUT_OF_BOUNDS or NDI_NAN_QUERY */
+  int32_t status; /* NDI_OUT_OF_BOUNDS, NDI_NAN_QUERY or NDI_INT_OVERFLOW */
 } ndi_oob_info;
 
 typedef struct ndi_eval_opts {
@@ -175,7 +195,9 @@ typedef struct ndi_eval_opts {
   int32_t path;         /* ndi_path */
   int32_t async_launch; /* != 0 (device out only): enqueue and return; fetch the batch
                            status later with ndi_interp{1,2}d_finish on the same stream (from the
-                           same host thread); the query array(s) must stay valid until then */
+                           same host thread); the query array(s) must stay valid until then.
+                           Integer (i32 / i64) handles accept the flag but complete the batch inside
+                           the call (no overlap with the caller); finish then reports its status */
   int32_t flags;        /* ndi_eval_flags */
   int32_t reserved;     /* 0 */
 } ndi_eval_opts;
@@ -319,7 +341,9 @@ ndi_status ndi_interp2d_eval_ring(const ndi_interp2d* h, const void* qx, const v
  *   out     the shard's rows, T[hi_i - lo_i][out_row_stride], memory space opts->out_memspace (device pointers
  *           belong to the shard's device).  For one host output array: out = base + lo_i * out_row_stride.
  *   stream  hipStream_t on the shard's device (NULL = its default stream); opts->stream is ignored.
- * The handles must be distinct.  opts->async_launch is ignored (the call returns when every shard has finished). */
+ * The handles must be distinct.  opts->async_launch is ignored (the call returns when every shard has finished).
+ * Integer (i32 / i64) handles: the shards are visited one after another from the calling thread (no worker threads),
+ * so a multi-device integer batch does not overlap across devices; results and first-error semantics are the same. */
 typedef struct ndi_shard_io {
   const void* q;
   const void* qy;

@@ -15,7 +15,15 @@ def is_torch(a) -> bool:
     return torch is not None and isinstance(a, torch.Tensor)
 
 
-_NP2ID = {np.dtype(np.float32): _capi.F32, np.dtype(np.float64): _capi.F64}
+_NP2ID = {np.dtype(np.float32): _capi.F32, np.dtype(np.float64): _capi.F64,
+          np.dtype(np.int32): _capi.I32, np.dtype(np.int64): _capi.I64}
+DEVICE_INT_DTYPES = (np.dtype(np.int32), np.dtype(np.int64))   # Linear / Bilinear only
+
+
+def torch_dtype(dt):
+    """The torch dtype of a device element type (None for the others)."""
+    return {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
+            np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64}.get(np.dtype(dt))
 
 
 def np_dtype_of(a):
@@ -28,7 +36,7 @@ def np_dtype_of(a):
 def dtype_id(dt) -> int:
     dt = np.dtype(dt)
     if dt not in _NP2ID:
-        raise TypeError(f"the MI355X path covers float32/float64 only, got {dt} "
+        raise TypeError(f"the MI355X path covers float32/float64 (and int32/int64 for Linear / Bilinear), got {dt} "
                         "(other element types stay on the host's generic per-query path)")
     return _NP2ID[dt]
 
@@ -38,8 +46,9 @@ class Buf:
 
     def __init__(self, arr, dt=None):
         if is_torch(arr):
-            t = arr if dt is None else arr.to({np.dtype(np.float32): torch.float32,
-                                               np.dtype(np.float64): torch.float64}[np.dtype(dt)])
+            if dt is not None and np.dtype(dt) in DEVICE_INT_DTYPES and arr.dtype != torch_dtype(dt):
+                _check_int_values(arr, dt)
+            t = arr if dt is None else arr.to(torch_dtype(dt))
             t = t.contiguous()
             self.keep = t
             self.shape = tuple(t.shape)
@@ -54,6 +63,8 @@ class Buf:
                 self.ptr = t.data_ptr()
             self.np_dtype = np_dtype_of(t)
         else:
+            if dt is not None and np.dtype(dt) in DEVICE_INT_DTYPES and np.asarray(arr).dtype != np.dtype(dt):
+                _check_int_values(np.asarray(arr), dt)
             a = np.ascontiguousarray(arr, dtype=dt)
             self.keep = a
             self.shape = a.shape
@@ -62,6 +73,68 @@ class Buf:
             self.device = None
             self.ptr = a.ctypes.data
             self.np_dtype = a.dtype
+
+
+def _check_int_values(a, dt):
+    """Values converted to an integer element type must be values of it (the reference's query type IS the element
+    type): the same TypeError as generic_host._scalar -- "not a value of" for NaN / infinite / fractional values, "out
+    of range for" for values outside T -- instead of a silent truncation or wrap.  Vectorised; numpy arrays and torch
+    tensors (on either device).  Sources whose every value fits T (narrower integers, bool) pass unchecked."""
+    from .generic_host import _scalar
+    info = np.iinfo(dt)
+    lo, hi_excl = float(info.min), -float(info.min)          # -2^(w-1) and 2^(w-1): exact in float64
+    if is_torch(a):
+        if a.dtype == torch.bool:
+            return
+        if a.is_floating_point():
+            bad = ~torch.isfinite(a) | (a != torch.trunc(a)) | (a < lo) | (a >= hi_excl)
+        elif not a.is_complex():
+            si = torch.iinfo(a.dtype)
+            if si.min >= info.min and si.max <= info.max:
+                return
+            bad = (a < int(info.min)) | (a > int(info.max))
+        else:
+            raise TypeError(f"queries of element type {a.dtype} are not values of {np.dtype(dt)}")
+        flat = bad.reshape(-1)
+        if not bool(flat.any()):
+            return
+        v = a.reshape(-1)[int(torch.nonzero(flat)[0])].cpu().numpy()[()]    # a numpy scalar, as the host loop sees
+    else:
+        a = np.asarray(a)
+        if a.dtype.kind == "b":
+            return
+        if a.dtype.kind in "iu":
+            si = np.iinfo(a.dtype)
+            if si.min >= info.min and si.max <= info.max:
+                return
+            bad = (a < int(info.min)) | (a > int(info.max))
+        elif a.dtype.kind == "f":
+            with np.errstate(invalid="ignore"):
+                bad = ~np.isfinite(a) | (a != np.trunc(a)) | (a < lo) | (a >= hi_excl)
+        else:
+            for v in a.reshape(-1):                              # object arrays: element by element
+                _scalar(v, dt)
+            return
+        flat = bad.reshape(-1)
+        if not flat.any():
+            return
+        v = a.reshape(-1)[int(np.argmax(flat))]
+    _scalar(v, dt)
+    raise TypeError(f"query {v!r} is not a value of the element type {np.dtype(dt)}")
+
+
+def int_query(dt, bufs, info):
+    """For an integer element type: a callable axis -> the failing query's coordinate as a Python int (read from the
+    query buffer itself: ndi_oob_info.value is a double, lossy for i64 beyond 2^53); None for float types."""
+    if np.dtype(dt) not in DEVICE_INT_DTYPES:
+        return None
+
+    def q(axis):
+        if not bufs:
+            return int(info.value)
+        b = bufs[min(axis, len(bufs) - 1)].keep
+        return int(b.reshape(-1)[int(info.index)].item() if is_torch(b) else b.reshape(-1)[int(info.index)])
+    return q
 
 
 def current_stream_ptr(device: int):

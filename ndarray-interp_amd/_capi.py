@@ -17,9 +17,12 @@ if not os.path.isabs(LIB_PATH):
 
 # ndi_status
 OK, NOT_ENOUGH_DATA, MONOTONIC, SHAPE, VALUE, OUT_OF_BOUNDS, NAN_QUERY, HIP_ERROR, BAD_ARG, UNSUPPORTED = range(10)
+INT_OVERFLOW = 10
 STATUS_NAMES = ["OK", "NOT_ENOUGH_DATA", "MONOTONIC", "SHAPE", "VALUE", "OUT_OF_BOUNDS", "NAN_QUERY",
-                "HIP_ERROR", "BAD_ARG", "UNSUPPORTED"]
-F32, F64 = 0, 1
+                "HIP_ERROR", "BAD_ARG", "UNSUPPORTED", "INT_OVERFLOW"]
+F32, F64, I32, I64 = 0, 1, 2, 3
+OP_SUBTRACT, OP_MULTIPLY, OP_ADD, OP_DIVIDE = range(4)   # ndi_int_op
+OP_NAMES = ["subtract", "multiply", "add", "divide"]
 MEM_HOST, MEM_DEVICE = 0, 1
 LINEAR, CUBIC_SPLINE = 0, 1
 BC_NOT_A_KNOT, BC_NATURAL, BC_CLAMPED, BC_FIRST_DERIV, BC_SECOND_DERIV = range(5)

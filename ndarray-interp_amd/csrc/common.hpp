@@ -53,5 +53,13 @@ template <>
 struct DType<double> {
   static constexpr int id = NDI_F64;
 };
+template <>
+struct DType<int32_t> {
+  static constexpr int id = NDI_I32;
+};
+template <>
+struct DType<int64_t> {
+  static constexpr int id = NDI_I64;
+};
 
 }  // namespace ndi

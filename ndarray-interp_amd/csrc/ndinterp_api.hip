@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -4273,6 +4274,11 @@ static ndi_status sharded2d(Job2<T>& J, ndi_oob_info* info) {
   return J.H[w]->report(J.qx_src(w, n), J.qy_src(w, n), J.o.q_memspace, lx, ly, lo, info);
 }
 
+// ---------------------------------------------------------------------------------------------
+// integer element types (i32 / i64): Linear and Bilinear
+// ---------------------------------------------------------------------------------------------
+#include "int_host.hpp"
+
 }  // namespace ndi
 
 // =============================================================================================
@@ -4330,9 +4336,14 @@ static ndi_status need_device(int device) {
 NDI_API ndi_status ndi_interp1d_create(const ndi_interp1d_desc* desc, ndi_interp1d** out) {
   if (!desc || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
   *out = nullptr;
-  if (desc->dtype != NDI_F32 && desc->dtype != NDI_F64) return ndi::fail(NDI_BAD_ARG, "unknown dtype");
+  if (desc->dtype != NDI_F32 && desc->dtype != NDI_F64 && desc->dtype != NDI_I32 && desc->dtype != NDI_I64)
+    return ndi::fail(NDI_BAD_ARG, "unknown dtype");
   if (desc->strategy != NDI_LINEAR && desc->strategy != NDI_CUBIC_SPLINE)
     return ndi::fail(NDI_BAD_ARG, "unknown strategy");
+  const bool int_t = desc->dtype == NDI_I32 || desc->dtype == NDI_I64;
+  if (int_t && desc->strategy == NDI_CUBIC_SPLINE)
+    return ndi::fail(NDI_BAD_ARG, "CubicSpline needs a float element type (f32 / f64): the reference's trait bounds "
+                     "rule out integer splines; integer data takes Linear");
   // Builder checks that need no device come first, so they behave the same everywhere.
   if (desc->validate && desc->memspace == NDI_MEM_HOST && desc->x) {
     ndi_status st = ndi_validate1d(desc->dtype, desc->x, desc->x_len, desc->n, desc->strategy);
@@ -4345,8 +4356,10 @@ NDI_API ndi_status ndi_interp1d_create(const ndi_interp1d_desc* desc, ndi_interp
   if (ds != NDI_OK) return ds;
   NDI_TRY
   ndi::Interp1DBase* impl = nullptr;
-  ndi_status st = desc->dtype == NDI_F32 ? ndi::create1d<float>(*desc, &impl)
-                                         : ndi::create1d<double>(*desc, &impl);
+  ndi_status st = desc->dtype == NDI_F32   ? ndi::create1d<float>(*desc, &impl)
+                  : desc->dtype == NDI_F64 ? ndi::create1d<double>(*desc, &impl)
+                  : desc->dtype == NDI_I32 ? ndi::create1d_int<int32_t>(*desc, &impl)
+                                           : ndi::create1d_int<int64_t>(*desc, &impl);
   if (st != NDI_OK) return st;
   *out = new ndi_interp1d{impl};
   return NDI_OK;
@@ -4366,7 +4379,8 @@ NDI_API void ndi_interp1d_destroy(ndi_interp1d* h) {
 NDI_API ndi_status ndi_interp2d_create(const ndi_interp2d_desc* desc, ndi_interp2d** out) {
   if (!desc || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
   *out = nullptr;
-  if (desc->dtype != NDI_F32 && desc->dtype != NDI_F64) return ndi::fail(NDI_BAD_ARG, "unknown dtype");
+  if (desc->dtype != NDI_F32 && desc->dtype != NDI_F64 && desc->dtype != NDI_I32 && desc->dtype != NDI_I64)
+    return ndi::fail(NDI_BAD_ARG, "unknown dtype");
   if (desc->validate && desc->memspace == NDI_MEM_HOST && desc->x && desc->y) {
     ndi_status st = ndi_validate2d(desc->dtype, desc->x, desc->x_len, desc->y, desc->y_len, desc->nx, desc->ny);
     if (st != NDI_OK) return st;
@@ -4375,8 +4389,10 @@ NDI_API ndi_status ndi_interp2d_create(const ndi_interp2d_desc* desc, ndi_interp
   if (ds != NDI_OK) return ds;
   NDI_TRY
   ndi::Interp2DBase* impl = nullptr;
-  ndi_status st = desc->dtype == NDI_F32 ? ndi::create2d<float>(*desc, &impl)
-                                         : ndi::create2d<double>(*desc, &impl);
+  ndi_status st = desc->dtype == NDI_F32   ? ndi::create2d<float>(*desc, &impl)
+                  : desc->dtype == NDI_F64 ? ndi::create2d<double>(*desc, &impl)
+                  : desc->dtype == NDI_I32 ? ndi::create2d_int<int32_t>(*desc, &impl)
+                                           : ndi::create2d_int<int64_t>(*desc, &impl);
   if (st != NDI_OK) return st;
   *out = new ndi_interp2d{impl};
   return NDI_OK;
@@ -4547,6 +4563,16 @@ NDI_API ndi_status ndi_interp1d_eval_sharded(const ndi_interp1d* const* handles,
   const int dtype = handles[0]->impl->dtype;
   ndi_eval_opts o{};
   if (const ndi_status vs__ = ndi::take_opts(opts, o); vs__ != NDI_OK) return vs__;
+  if (dtype == NDI_I32) {
+    std::vector<ndi::Interp1DIntImpl<int32_t>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_int<int32_t>(H, q, nullptr, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
+  }
+  if (dtype == NDI_I64) {
+    std::vector<ndi::Interp1DIntImpl<int64_t>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_int<int64_t>(H, q, nullptr, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
+  }
   if (dtype == NDI_F32) {
     ndi::Job1<float> J{{}, q, nq, io, out_row_stride, nullptr, nullptr, nullptr, o};
     st = gather_handles(handles, n_shards, dtype, J.H);
@@ -4569,6 +4595,16 @@ NDI_API ndi_status ndi_interp1d_eval_ring_sharded(const ndi_interp1d* const* han
   const int dtype = handles[0]->impl->dtype;
   ndi_eval_opts o{};
   if (const ndi_status vs__ = ndi::take_opts(opts, o); vs__ != NDI_OK) return vs__;
+  if (dtype == NDI_I32) {
+    std::vector<ndi::Interp1DIntImpl<int32_t>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_int<int32_t>(H, q, nullptr, nq, io, 0, rings, consume, user, o, info);
+  }
+  if (dtype == NDI_I64) {
+    std::vector<ndi::Interp1DIntImpl<int64_t>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_int<int64_t>(H, q, nullptr, nq, io, 0, rings, consume, user, o, info);
+  }
   if (dtype == NDI_F32) {
     ndi::Job1<float> J{{}, q, nq, io, 0, rings, consume, user, o};
     st = gather_handles(handles, n_shards, dtype, J.H);
@@ -4591,6 +4627,16 @@ NDI_API ndi_status ndi_interp2d_eval_sharded(const ndi_interp2d* const* handles,
   const int dtype = handles[0]->impl->dtype;
   ndi_eval_opts o{};
   if (const ndi_status vs__ = ndi::take_opts(opts, o); vs__ != NDI_OK) return vs__;
+  if (dtype == NDI_I32) {
+    std::vector<ndi::Interp2DIntImpl<int32_t>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_int<int32_t>(H, qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
+  }
+  if (dtype == NDI_I64) {
+    std::vector<ndi::Interp2DIntImpl<int64_t>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_int<int64_t>(H, qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
+  }
   if (dtype == NDI_F32) {
     ndi::Job2<float> J{{}, qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, o};
     st = gather_handles(handles, n_shards, dtype, J.H);
@@ -4614,6 +4660,16 @@ NDI_API ndi_status ndi_interp2d_eval_ring_sharded(const ndi_interp2d* const* han
   const int dtype = handles[0]->impl->dtype;
   ndi_eval_opts o{};
   if (const ndi_status vs__ = ndi::take_opts(opts, o); vs__ != NDI_OK) return vs__;
+  if (dtype == NDI_I32) {
+    std::vector<ndi::Interp2DIntImpl<int32_t>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_int<int32_t>(H, qx, qy, nq, io, 0, rings, consume, user, o, info);
+  }
+  if (dtype == NDI_I64) {
+    std::vector<ndi::Interp2DIntImpl<int64_t>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_int<int64_t>(H, qx, qy, nq, io, 0, rings, consume, user, o, info);
+  }
   if (dtype == NDI_F32) {
     ndi::Job2<float> J{{}, qx, qy, nq, io, 0, rings, consume, user, o};
     st = gather_handles(handles, n_shards, dtype, J.H);
@@ -4653,13 +4709,16 @@ NDI_API ndi_status ndi_locator_create(int32_t dtype, int32_t device, const void*
                                       int32_t memspace, ndi_locator** out) {
   if (!knots || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
   *out = nullptr;
-  if (dtype != NDI_F32 && dtype != NDI_F64) return ndi::fail(NDI_BAD_ARG, "unknown dtype");
+  if (dtype != NDI_F32 && dtype != NDI_F64 && dtype != NDI_I32 && dtype != NDI_I64)
+    return ndi::fail(NDI_BAD_ARG, "unknown dtype");
   ndi_status ds = need_device(device);
   if (ds != NDI_OK) return ds;
   NDI_TRY
   ndi::LocatorBase* impl = nullptr;
-  ndi_status st = dtype == NDI_F32 ? ndi::create_locator<float>(device, knots, n, memspace, &impl)
-                                   : ndi::create_locator<double>(device, knots, n, memspace, &impl);
+  ndi_status st = dtype == NDI_F32   ? ndi::create_locator<float>(device, knots, n, memspace, &impl)
+                  : dtype == NDI_F64 ? ndi::create_locator<double>(device, knots, n, memspace, &impl)
+                  : dtype == NDI_I32 ? ndi::create_int_locator<int32_t>(device, knots, n, memspace, &impl)
+                                     : ndi::create_int_locator<int64_t>(device, knots, n, memspace, &impl);
   if (st != NDI_OK) return st;
   *out = new ndi_locator{impl};
   return NDI_OK;
@@ -4700,12 +4759,16 @@ NDI_API ndi_status ndi_get_lower_index_batch(int32_t dtype, int32_t device, cons
 
 NDI_API int32_t ndi_monotonic_prop(int32_t dtype, const void* host_v, uint64_t n) {
   if (dtype == NDI_F32) return ndi::monotonic_scan<float>((const float*)host_v, n);
+  if (dtype == NDI_I32) return ndi::monotonic_scan<int32_t>((const int32_t*)host_v, n);
+  if (dtype == NDI_I64) return ndi::monotonic_scan<int64_t>((const int64_t*)host_v, n);
   return ndi::monotonic_scan<double>((const double*)host_v, n);
 }
 
 NDI_API ndi_status ndi_validate1d(int32_t dtype, const void* host_x, uint64_t x_len, uint64_t n, int32_t strategy) {
   if (dtype == NDI_F32) return ndi::check_axis_1d<float>((const float*)host_x, x_len, n, strategy);
   if (dtype == NDI_F64) return ndi::check_axis_1d<double>((const double*)host_x, x_len, n, strategy);
+  if (dtype == NDI_I32) return ndi::check_axis_1d<int32_t>((const int32_t*)host_x, x_len, n, strategy);
+  if (dtype == NDI_I64) return ndi::check_axis_1d<int64_t>((const int64_t*)host_x, x_len, n, strategy);
   return ndi::fail(NDI_BAD_ARG, "unknown dtype");
 }
 
@@ -4715,6 +4778,10 @@ NDI_API ndi_status ndi_validate2d(int32_t dtype, const void* host_x, uint64_t x_
     return ndi::check_axes_2d<float>((const float*)host_x, x_len, (const float*)host_y, y_len, nx, ny);
   if (dtype == NDI_F64)
     return ndi::check_axes_2d<double>((const double*)host_x, x_len, (const double*)host_y, y_len, nx, ny);
+  if (dtype == NDI_I32)
+    return ndi::check_axes_2d<int32_t>((const int32_t*)host_x, x_len, (const int32_t*)host_y, y_len, nx, ny);
+  if (dtype == NDI_I64)
+    return ndi::check_axes_2d<int64_t>((const int64_t*)host_x, x_len, (const int64_t*)host_y, y_len, nx, ny);
   return ndi::fail(NDI_BAD_ARG, "unknown dtype");
 }
 

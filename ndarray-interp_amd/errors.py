@@ -89,13 +89,22 @@ def _rust_float(v: float) -> str:
     return repr(float(v))
 
 
-def raise_eval(status: int, info: "_capi.OobInfo"):
+def raise_eval(status: int, info: "_capi.OobInfo", query=None):
+    """`query`: for integer element types, a callable giving the failing query's coordinate (axis) as an int."""
+    if callable(query):
+        query = query(int(info.axis)) if status == _capi.OUT_OF_BOUNDS else None
     if status == _capi.OUT_OF_BOUNDS:
         name = "x" if info.axis == 0 else "y"
         # linear.rs:81-83, cubic_spline.rs:799-801, bilinear.rs:72-79
+        if query is not None:     # integer element types: `{x:?}` of the query element itself (no decimal point)
+            raise InterpolateError.OutOfBounds(f"{name} = {int(query)} is not in range", index=int(info.index),
+                                               value=int(query), axis=int(info.axis))
         raise InterpolateError.OutOfBounds(f"{name} = {_rust_float(info.value)} is not in range",
                                            index=int(info.index), value=float(info.value), axis=int(info.axis))
+    if status == _capi.INT_OVERFLOW:
+        # Linear::calc_frac in T (linear.rs:29-36): a Rust debug build's arithmetic-overflow panic
+        raise Panic(f"attempt to {_capi.OP_NAMES[info.axis]} with overflow", index=int(info.index))
     if status == _capi.NAN_QUERY:
         # vector_extensions.rs:83-84 (unimplemented! -> panic)
         raise Panic("not implemented: failed to convert NaN to usize", index=int(info.index))
-    raise DeviceError(f"{_capi.STATUS_NAMES[status] if 0 <= status < 10 else status}: {_capi.last_error()}")
+    raise DeviceError(f"{_capi.STATUS_NAMES[status] if 0 <= status < 11 else status}: {_capi.last_error()}")

@@ -14,7 +14,8 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._arrays import OUTPUT_OWNED_MIN_BYTES, Buf, current_stream_ptr, dtype_id, is_torch, np_dtype_of, output_empty
+from ._arrays import (DEVICE_INT_DTYPES, OUTPUT_OWNED_MIN_BYTES, Buf, current_stream_ptr, dtype_id, int_query, is_torch,
+                      np_dtype_of, output_empty, torch_dtype)
 from .errors import BuilderError, InterpolateError, Panic, raise_builder, raise_eval
 from .vector_extensions import Monotonic, get_lower_index, monotonic_prop
 
@@ -162,7 +163,7 @@ class _DeviceStrategy1D(Interp1DStrategy):
         st = _capi.lib().ndi_interp1d_eval(self._h, qb.ptr, qb.size, optr, max(stride, self._lanes),
                                            C.byref(opts), C.byref(info))
         if st != _capi.OK:
-            raise_eval(st, info)
+            raise_eval(st, info, int_query(self._np_dtype, [qb], info))
 
     def finish(self):
         """Completes `async_launch` evaluations on the current stream and raises their error, if any."""
@@ -170,7 +171,7 @@ class _DeviceStrategy1D(Interp1DStrategy):
         st = _capi.lib().ndi_interp1d_finish(self._h, current_stream_ptr(self._device), C.byref(info))
         self._inflight.clear()
         if st != _capi.OK:
-            raise_eval(st, info)
+            raise_eval(st, info, int_query(self._np_dtype, None, info))
 
     def trim(self):
         """Frees the handle's idle scratch sets and a library-owned ring (ndi_interp1d_trim)."""
@@ -236,7 +237,7 @@ class _DeviceStrategy1D(Interp1DStrategy):
         if failed:
             raise failed[0]
         if st != _capi.OK:
-            raise_eval(st, info)
+            raise_eval(st, info, int_query(self._np_dtype, [qb], info))
 
     def interp_into(self, interpolator, target, x):
         # single query through the same device path (Q = 1)
@@ -290,7 +291,12 @@ class Linear(Interp1DStrategyBuilder, _DeviceStrategy1D):
         return self
 
     def build(self, x, data):
-        if np_dtype_of(data) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        dt = np_dtype_of(data)
+        on_device = self._device_req is not None or (is_torch(data) and data.is_cuda)
+        if dt in DEVICE_INT_DTYPES and on_device:
+            # i32 / i64 on the device when asked for (.device(d) or a GPU tensor); plain host arrays keep the generic path
+            return self._create(x, data, extrapolate=self._extrapolate, device=self._device_req)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
             # integer (and other non-f32/f64) element types: the reference's generic per-query path
             from .generic_host import HostLinear
             return HostLinear(_host(x), _host(data), self._extrapolate)
@@ -396,6 +402,9 @@ class CubicSpline(Interp1DStrategyBuilder):
         return self
 
     def build(self, x, data) -> "CubicSplineStrategy":
+        if np_dtype_of(data) not in (np.dtype(np.float32), np.dtype(np.float64)):
+            # the reference's trait bounds (Pow / Euclid on T) keep the spline to float element types
+            raise TypeError(f"CubicSpline covers float32/float64 only, got {np_dtype_of(data)}")
         bc = self._boundary
         strat = CubicSplineStrategy()
         kw = dict(extrapolate=self._extrapolate, device=self._device_req,
@@ -539,8 +548,7 @@ class Interp1D:
         if is_torch(xs) and xs.is_cuda:
             import torch
             # element type of the *data* (the kernels write that; queries are converted to it)
-            tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}.get(
-                np_dtype_of(self.data))
+            tdt = torch_dtype(np_dtype_of(self.data))
             if tdt is None:
                 raise TypeError("device query tensors need f32 / f64 data; other element types use host arrays")
             nbytes = int(np.prod(shape, dtype=np.int64)) * np_dtype_of(self.data).itemsize

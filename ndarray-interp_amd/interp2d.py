@@ -7,7 +7,8 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._arrays import OUTPUT_OWNED_MIN_BYTES, Buf, current_stream_ptr, dtype_id, is_torch, np_dtype_of, output_empty
+from ._arrays import (DEVICE_INT_DTYPES, OUTPUT_OWNED_MIN_BYTES, Buf, current_stream_ptr, dtype_id, int_query, is_torch,
+                      np_dtype_of, output_empty, torch_dtype)
 from .errors import BuilderError, InterpolateError, Panic, raise_builder, raise_eval
 from .interp1d import _check_out_dtype, _default_device, _host, _to_device
 from .vector_extensions import Monotonic, get_lower_index, monotonic_prop
@@ -71,7 +72,9 @@ class Bilinear(Interp2DStrategyBuilder, Interp2DStrategy):
 
     def build(self, x, y, data, device=None):
         dt = np_dtype_of(data)
-        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        on_device = device is not None or self._device_req is not None or (is_torch(data) and data.is_cuda)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)) and not (dt in DEVICE_INT_DTYPES and on_device):
+            # i32 / i64 take the device when asked for (.device(d) or a GPU tensor); plain host arrays stay here
             # integer (and other non-f32/f64) element types: the reference's generic per-query path
             from .generic_host import HostBilinear
             return HostBilinear(_host(x), _host(y), _host(data), self._extrapolate)
@@ -168,14 +171,14 @@ class Bilinear(Interp2DStrategyBuilder, Interp2DStrategy):
         st = _capi.lib().ndi_interp2d_eval(self._h, qx.ptr, qy.ptr, qx.size, optr, max(stride, self._lanes),
                                            C.byref(opts), C.byref(info))
         if st != _capi.OK:
-            raise_eval(st, info)
+            raise_eval(st, info, int_query(self._np_dtype, [qx, qy], info))
 
     def finish(self):
         info = _capi.OobInfo()
         st = _capi.lib().ndi_interp2d_finish(self._h, current_stream_ptr(self._device), C.byref(info))
         self._inflight.clear()
         if st != _capi.OK:
-            raise_eval(st, info)
+            raise_eval(st, info, int_query(self._np_dtype, None, info))
 
     def trim(self):
         _capi.lib().ndi_interp2d_trim(self._h)
@@ -246,7 +249,7 @@ class Bilinear(Interp2DStrategyBuilder, Interp2DStrategy):
         if failed:
             raise failed[0]
         if st != _capi.OK:
-            raise_eval(st, info)
+            raise_eval(st, info, int_query(self._np_dtype, [qx, qy], info))
 
     def interp_into(self, interpolator, target, x, y):
         out = np.empty((1, self._lanes), dtype=self._np_dtype)
@@ -322,8 +325,7 @@ class Interp2D:
         shape = self.get_buffer_shape(tuple(xs.shape))
         if is_torch(xs) and xs.is_cuda:
             import torch
-            tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}.get(
-                np_dtype_of(self.data))
+            tdt = torch_dtype(np_dtype_of(self.data))
             if tdt is None:
                 raise TypeError("device query tensors need f32 / f64 data; other element types use host arrays")
             nbytes = int(np.prod(shape, dtype=np.int64)) * np_dtype_of(self.data).itemsize

@@ -19,10 +19,18 @@ pub const NDI_NAN_QUERY: i32 = 6;
 pub const NDI_HIP_ERROR: i32 = 7;
 pub const NDI_BAD_ARG: i32 = 8;
 pub const NDI_UNSUPPORTED: i32 = 9;
+pub const NDI_INT_OVERFLOW: i32 = 10; // v0.5 addition: integer T, an intermediate overflowed
 
 /// `ndi_dtype`
 pub const NDI_F32: i32 = 0;
 pub const NDI_F64: i32 = 1;
+pub const NDI_I32: i32 = 2; // v0.5 addition: Linear / Bilinear only
+pub const NDI_I64: i32 = 3;
+
+pub const NDI_OP_SUBTRACT: i32 = 0; // ndi_int_op: ndi_oob_info.axis of NDI_INT_OVERFLOW
+pub const NDI_OP_MULTIPLY: i32 = 1;
+pub const NDI_OP_ADD: i32 = 2;
+pub const NDI_OP_DIVIDE: i32 = 3;
 /// `ndi_memspace`
 pub const NDI_MEM_HOST: i32 = 0;
 pub const NDI_MEM_DEVICE: i32 = 1;

@@ -198,7 +198,7 @@ where
 {
     let Some(dtype) = dtype_of::<T>() else {
         return Err(BuilderError::ValueError(
-            "the MI355X strategies cover f32 and f64; use the generic Linear / Bilinear for other element types".into(),
+            "this shim dispatches f32 and f64 (the C ABI also takes i32 / i64 Linear / Bilinear, not wired here yet); use the generic Linear / Bilinear for other element types".into(),
         ));
     };
     // Interp1DBuilder::build has validated x / data already (interp1d/mod.rs:449-471) -> validate: 0
@@ -610,7 +610,7 @@ where
     ) -> Result<Self::FinishedStrat, BuilderError> {
         let Some(dtype) = dtype_of::<Sd::Elem>() else {
             return Err(BuilderError::ValueError(
-                "the MI355X strategies cover f32 and f64; use the generic Bilinear for other element types".into(),
+                "this shim dispatches f32 and f64 (the C ABI also takes i32 / i64 Bilinear, not wired here yet); use the generic Bilinear for other element types".into(),
             ));
         };
         let (x, y, data) = (x.as_standard_layout(), y.as_standard_layout(), data.as_standard_layout());
