@@ -18,6 +18,11 @@
  *    reported as NDI_INT_OVERFLOW (a Rust debug build panics there).  Integer handles keep slope records {y, m}
  *    instead of the data on the device, about twice the data's memory.  Other integer widths (unsigned, 8/16-bit)
  *    stay on the host's generic per-query path, see INTEGRATION.md.
+ *    Also v0.5, backward-compatible: f16 / bf16 (IEEE binary16 and bfloat16, passed as their 16-bit patterns) for
+ *    Linear and Bilinear.  They follow the `half` crate's arithmetic: every operation converts its operands to f32
+ *    exactly, does one IEEE f32 operation and rounds to T with ties to even (overflow gives inf), so results are
+ *    bit-exact.  Only the float errors exist (NDI_OUT_OF_BOUNDS, NDI_NAN_QUERY).  Half handles keep the data as
+ *    given plus f32 images of the knots; async_launch and the sharded calls behave as for f32 / f64.
  *  - arrays are C-order and contiguous: data[n][lanes], data2d[nx][ny][lanes];
  *    "lanes" = product of the trailing (non-interpolated) axes.
  *  - every pointer argument carries a memory space (host or device).  Device
@@ -56,8 +61,9 @@ typedef enum ndi_status {
 
 /* NDI_I32 / NDI_I64 (v0.5, backward-compatible): NDI_LINEAR and Bilinear only; NDI_CUBIC_SPLINE is refused with
  * NDI_BAD_ARG (the reference's trait bounds forbid it), ndi_interp1d_coefficients on such a handle is NDI_BAD_ARG and
- * NDI_PATH_BUCKETED is NDI_UNSUPPORTED (AUTO and GATHER evaluate). */
-typedef enum ndi_dtype { NDI_F32 = 0, NDI_F64 = 1, NDI_I32 = 2, NDI_I64 = 3 } ndi_dtype;
+ * NDI_PATH_BUCKETED is NDI_UNSUPPORTED (AUTO and GATHER evaluate).  NDI_F16 / NDI_BF16 (v0.5, backward-compatible):
+ * the same restrictions. */
+typedef enum ndi_dtype { NDI_F32 = 0, NDI_F64 = 1, NDI_I32 = 2, NDI_I64 = 3, NDI_F16 = 4, NDI_BF16 = 5 } ndi_dtype;
 
 /* The operation of Linear::calc_frac (linear.rs:29-36) that overflowed: ndi_oob_info.axis for NDI_INT_OVERFLOW. */
 typedef enum ndi_int_op {

@@ -15,22 +15,51 @@ def is_torch(a) -> bool:
     return torch is not None and isinstance(a, torch.Tensor)
 
 
+# numpy has no bfloat16: the mirror names it by a 2-byte structured dtype of its own (never used to hold values; bf16
+# data and results travel as torch.bfloat16 tensors)
+BF16 = np.dtype([("bfloat16", "<u2")])
 _NP2ID = {np.dtype(np.float32): _capi.F32, np.dtype(np.float64): _capi.F64,
-          np.dtype(np.int32): _capi.I32, np.dtype(np.int64): _capi.I64}
+          np.dtype(np.int32): _capi.I32, np.dtype(np.int64): _capi.I64,
+          np.dtype(np.float16): _capi.F16, BF16: _capi.BF16}
 DEVICE_INT_DTYPES = (np.dtype(np.int32), np.dtype(np.int64))   # Linear / Bilinear only
+DEVICE_HALF_DTYPES = (np.dtype(np.float16), BF16)               # Linear / Bilinear only
 
 
 def torch_dtype(dt):
     """The torch dtype of a device element type (None for the others)."""
     return {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
-            np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64}.get(np.dtype(dt))
+            np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64,
+            np.dtype(np.float16): torch.float16, BF16: torch.bfloat16}.get(np.dtype(dt))
 
 
 def np_dtype_of(a):
     if is_torch(a):
-        return {torch.float32: np.dtype(np.float32), torch.float64: np.dtype(np.float64)}.get(a.dtype) \
-            or np.dtype(str(a.dtype).replace("torch.", ""))
+        return {torch.float32: np.dtype(np.float32), torch.float64: np.dtype(np.float64),
+                torch.bfloat16: BF16}.get(a.dtype) or np.dtype(str(a.dtype).replace("torch.", ""))
     return np.asarray(a).dtype
+
+
+def is_bf16(dt) -> bool:
+    return dt is not None and np.dtype(dt) == BF16
+
+
+def as_bf16_source(a):
+    """Values headed for a bf16 buffer, as a torch.bfloat16 tensor on the source's device: every value rounded to bf16
+    ONCE, to nearest with ties to even (what numpy does for f16).  bf16, f16 and f32 sources are rounded by torch's
+    f32 -> bf16 conversion; everything else goes through f64 (exact for integers up to 2^53) and is rounded to odd in
+    f32 first -- torch's f64 -> bf16 conversion would round to nearest twice -- which makes the second rounding the
+    single correct one (f32 keeps 24 >= 8 + 2 significand bits, down to bf16's subnormals)."""
+    t = a if is_torch(a) else torch.as_tensor(np.ascontiguousarray(a))
+    if t.dtype in (torch.bfloat16, torch.float16, torch.float32):
+        return t.to(torch.bfloat16)
+    t = t.to(torch.float64)
+    f = t.to(torch.float32)                       # to nearest (inf beyond the f32 range)
+    back = f.to(torch.float64)
+    inexact = back != t                           # NaN counts as inexact; it stays NaN below
+    f = torch.where(inexact & (back.abs() > t.abs()), torch.nextafter(f, torch.zeros_like(f)), f)   # toward zero
+    bits = f.view(torch.int32)
+    bits = torch.where(inexact, bits | 1, bits)   # round to odd: the sticky bit
+    return bits.view(torch.float32).to(torch.bfloat16)
 
 
 def dtype_id(dt) -> int:
@@ -45,6 +74,8 @@ class Buf:
     """A contiguous buffer handed to the C ABI: pointer, memory space and a keep-alive."""
 
     def __init__(self, arr, dt=None):
+        if is_bf16(dt):
+            arr = as_bf16_source(arr)
         if is_torch(arr):
             if dt is not None and np.dtype(dt) in DEVICE_INT_DTYPES and arr.dtype != torch_dtype(dt):
                 _check_int_values(arr, dt)

@@ -20,7 +20,7 @@ OK, NOT_ENOUGH_DATA, MONOTONIC, SHAPE, VALUE, OUT_OF_BOUNDS, NAN_QUERY, HIP_ERRO
 INT_OVERFLOW = 10
 STATUS_NAMES = ["OK", "NOT_ENOUGH_DATA", "MONOTONIC", "SHAPE", "VALUE", "OUT_OF_BOUNDS", "NAN_QUERY",
                 "HIP_ERROR", "BAD_ARG", "UNSUPPORTED", "INT_OVERFLOW"]
-F32, F64, I32, I64 = 0, 1, 2, 3
+F32, F64, I32, I64, F16, BF16 = 0, 1, 2, 3, 4, 5
 OP_SUBTRACT, OP_MULTIPLY, OP_ADD, OP_DIVIDE = range(4)   # ndi_int_op
 OP_NAMES = ["subtract", "multiply", "add", "divide"]
 MEM_HOST, MEM_DEVICE = 0, 1

@@ -5178,3 +5178,4 @@ __global__ __launch_bounds__(64) void spline_build_periodic_kernel(BuildArgs<T> 
 
 }  // namespace ndi
 #include "int_kernels.hpp"
+#include "half_kernels.hpp"

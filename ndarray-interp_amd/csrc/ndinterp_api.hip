@@ -4279,6 +4279,11 @@ static ndi_status sharded2d(Job2<T>& J, ndi_oob_info* info) {
 // ---------------------------------------------------------------------------------------------
 #include "int_host.hpp"
 
+// ---------------------------------------------------------------------------------------------
+// half-precision element types (f16 / bf16): Linear and Bilinear
+// ---------------------------------------------------------------------------------------------
+#include "half_host.hpp"
+
 }  // namespace ndi
 
 // =============================================================================================
@@ -4336,14 +4341,17 @@ static ndi_status need_device(int device) {
 NDI_API ndi_status ndi_interp1d_create(const ndi_interp1d_desc* desc, ndi_interp1d** out) {
   if (!desc || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
   *out = nullptr;
-  if (desc->dtype != NDI_F32 && desc->dtype != NDI_F64 && desc->dtype != NDI_I32 && desc->dtype != NDI_I64)
-    return ndi::fail(NDI_BAD_ARG, "unknown dtype");
+  if (desc->dtype < NDI_F32 || desc->dtype > NDI_BF16) return ndi::fail(NDI_BAD_ARG, "unknown dtype");
   if (desc->strategy != NDI_LINEAR && desc->strategy != NDI_CUBIC_SPLINE)
     return ndi::fail(NDI_BAD_ARG, "unknown strategy");
   const bool int_t = desc->dtype == NDI_I32 || desc->dtype == NDI_I64;
   if (int_t && desc->strategy == NDI_CUBIC_SPLINE)
     return ndi::fail(NDI_BAD_ARG, "CubicSpline needs a float element type (f32 / f64): the reference's trait bounds "
                      "rule out integer splines; integer data takes Linear");
+  const bool half_t = desc->dtype == NDI_F16 || desc->dtype == NDI_BF16;
+  if (half_t && desc->strategy == NDI_CUBIC_SPLINE)
+    return ndi::fail(NDI_BAD_ARG, "CubicSpline needs f32 / f64: the reference's SplineNum bounds (Pow, ScalarOperand, "
+                     "Euclid) rule out f16 / bf16 splines; half-precision data takes Linear");
   // Builder checks that need no device come first, so they behave the same everywhere.
   if (desc->validate && desc->memspace == NDI_MEM_HOST && desc->x) {
     ndi_status st = ndi_validate1d(desc->dtype, desc->x, desc->x_len, desc->n, desc->strategy);
@@ -4359,7 +4367,9 @@ NDI_API ndi_status ndi_interp1d_create(const ndi_interp1d_desc* desc, ndi_interp
   ndi_status st = desc->dtype == NDI_F32   ? ndi::create1d<float>(*desc, &impl)
                   : desc->dtype == NDI_F64 ? ndi::create1d<double>(*desc, &impl)
                   : desc->dtype == NDI_I32 ? ndi::create1d_int<int32_t>(*desc, &impl)
-                                           : ndi::create1d_int<int64_t>(*desc, &impl);
+                  : desc->dtype == NDI_I64 ? ndi::create1d_int<int64_t>(*desc, &impl)
+                  : desc->dtype == NDI_F16 ? ndi::create1d_half<ndi::HF_F16>(*desc, &impl)
+                                           : ndi::create1d_half<ndi::HF_BF16>(*desc, &impl);
   if (st != NDI_OK) return st;
   *out = new ndi_interp1d{impl};
   return NDI_OK;
@@ -4379,8 +4389,7 @@ NDI_API void ndi_interp1d_destroy(ndi_interp1d* h) {
 NDI_API ndi_status ndi_interp2d_create(const ndi_interp2d_desc* desc, ndi_interp2d** out) {
   if (!desc || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
   *out = nullptr;
-  if (desc->dtype != NDI_F32 && desc->dtype != NDI_F64 && desc->dtype != NDI_I32 && desc->dtype != NDI_I64)
-    return ndi::fail(NDI_BAD_ARG, "unknown dtype");
+  if (desc->dtype < NDI_F32 || desc->dtype > NDI_BF16) return ndi::fail(NDI_BAD_ARG, "unknown dtype");
   if (desc->validate && desc->memspace == NDI_MEM_HOST && desc->x && desc->y) {
     ndi_status st = ndi_validate2d(desc->dtype, desc->x, desc->x_len, desc->y, desc->y_len, desc->nx, desc->ny);
     if (st != NDI_OK) return st;
@@ -4392,7 +4401,9 @@ NDI_API ndi_status ndi_interp2d_create(const ndi_interp2d_desc* desc, ndi_interp
   ndi_status st = desc->dtype == NDI_F32   ? ndi::create2d<float>(*desc, &impl)
                   : desc->dtype == NDI_F64 ? ndi::create2d<double>(*desc, &impl)
                   : desc->dtype == NDI_I32 ? ndi::create2d_int<int32_t>(*desc, &impl)
-                                           : ndi::create2d_int<int64_t>(*desc, &impl);
+                  : desc->dtype == NDI_I64 ? ndi::create2d_int<int64_t>(*desc, &impl)
+                  : desc->dtype == NDI_F16 ? ndi::create2d_half<ndi::HF_F16>(*desc, &impl)
+                                           : ndi::create2d_half<ndi::HF_BF16>(*desc, &impl);
   if (st != NDI_OK) return st;
   *out = new ndi_interp2d{impl};
   return NDI_OK;
@@ -4573,6 +4584,16 @@ NDI_API ndi_status ndi_interp1d_eval_sharded(const ndi_interp1d* const* handles,
     st = gather_handles(handles, n_shards, dtype, H);
     return st != NDI_OK ? st : ndi::sharded_int<int64_t>(H, q, nullptr, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
   }
+  if (dtype == NDI_F16) {
+    std::vector<ndi::Interp1DHalfImpl<ndi::HF_F16>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_F16>(H, q, nullptr, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
+  }
+  if (dtype == NDI_BF16) {
+    std::vector<ndi::Interp1DHalfImpl<ndi::HF_BF16>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_BF16>(H, q, nullptr, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
+  }
   if (dtype == NDI_F32) {
     ndi::Job1<float> J{{}, q, nq, io, out_row_stride, nullptr, nullptr, nullptr, o};
     st = gather_handles(handles, n_shards, dtype, J.H);
@@ -4604,6 +4625,16 @@ NDI_API ndi_status ndi_interp1d_eval_ring_sharded(const ndi_interp1d* const* han
     std::vector<ndi::Interp1DIntImpl<int64_t>*> H;
     st = gather_handles(handles, n_shards, dtype, H);
     return st != NDI_OK ? st : ndi::sharded_int<int64_t>(H, q, nullptr, nq, io, 0, rings, consume, user, o, info);
+  }
+  if (dtype == NDI_F16) {
+    std::vector<ndi::Interp1DHalfImpl<ndi::HF_F16>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_F16>(H, q, nullptr, nq, io, 0, rings, consume, user, o, info);
+  }
+  if (dtype == NDI_BF16) {
+    std::vector<ndi::Interp1DHalfImpl<ndi::HF_BF16>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_BF16>(H, q, nullptr, nq, io, 0, rings, consume, user, o, info);
   }
   if (dtype == NDI_F32) {
     ndi::Job1<float> J{{}, q, nq, io, 0, rings, consume, user, o};
@@ -4637,6 +4668,16 @@ NDI_API ndi_status ndi_interp2d_eval_sharded(const ndi_interp2d* const* handles,
     st = gather_handles(handles, n_shards, dtype, H);
     return st != NDI_OK ? st : ndi::sharded_int<int64_t>(H, qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
   }
+  if (dtype == NDI_F16) {
+    std::vector<ndi::Interp2DHalfImpl<ndi::HF_F16>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_F16>(H, qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
+  }
+  if (dtype == NDI_BF16) {
+    std::vector<ndi::Interp2DHalfImpl<ndi::HF_BF16>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_BF16>(H, qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
+  }
   if (dtype == NDI_F32) {
     ndi::Job2<float> J{{}, qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, o};
     st = gather_handles(handles, n_shards, dtype, J.H);
@@ -4669,6 +4710,16 @@ NDI_API ndi_status ndi_interp2d_eval_ring_sharded(const ndi_interp2d* const* han
     std::vector<ndi::Interp2DIntImpl<int64_t>*> H;
     st = gather_handles(handles, n_shards, dtype, H);
     return st != NDI_OK ? st : ndi::sharded_int<int64_t>(H, qx, qy, nq, io, 0, rings, consume, user, o, info);
+  }
+  if (dtype == NDI_F16) {
+    std::vector<ndi::Interp2DHalfImpl<ndi::HF_F16>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_F16>(H, qx, qy, nq, io, 0, rings, consume, user, o, info);
+  }
+  if (dtype == NDI_BF16) {
+    std::vector<ndi::Interp2DHalfImpl<ndi::HF_BF16>*> H;
+    st = gather_handles(handles, n_shards, dtype, H);
+    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_BF16>(H, qx, qy, nq, io, 0, rings, consume, user, o, info);
   }
   if (dtype == NDI_F32) {
     ndi::Job2<float> J{{}, qx, qy, nq, io, 0, rings, consume, user, o};
@@ -4709,8 +4760,7 @@ NDI_API ndi_status ndi_locator_create(int32_t dtype, int32_t device, const void*
                                       int32_t memspace, ndi_locator** out) {
   if (!knots || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
   *out = nullptr;
-  if (dtype != NDI_F32 && dtype != NDI_F64 && dtype != NDI_I32 && dtype != NDI_I64)
-    return ndi::fail(NDI_BAD_ARG, "unknown dtype");
+  if (dtype < NDI_F32 || dtype > NDI_BF16) return ndi::fail(NDI_BAD_ARG, "unknown dtype");
   ndi_status ds = need_device(device);
   if (ds != NDI_OK) return ds;
   NDI_TRY
@@ -4718,7 +4768,9 @@ NDI_API ndi_status ndi_locator_create(int32_t dtype, int32_t device, const void*
   ndi_status st = dtype == NDI_F32   ? ndi::create_locator<float>(device, knots, n, memspace, &impl)
                   : dtype == NDI_F64 ? ndi::create_locator<double>(device, knots, n, memspace, &impl)
                   : dtype == NDI_I32 ? ndi::create_int_locator<int32_t>(device, knots, n, memspace, &impl)
-                                     : ndi::create_int_locator<int64_t>(device, knots, n, memspace, &impl);
+                  : dtype == NDI_I64 ? ndi::create_int_locator<int64_t>(device, knots, n, memspace, &impl)
+                  : dtype == NDI_F16 ? ndi::create_half_locator<ndi::HF_F16>(device, knots, n, memspace, &impl)
+                                     : ndi::create_half_locator<ndi::HF_BF16>(device, knots, n, memspace, &impl);
   if (st != NDI_OK) return st;
   *out = new ndi_locator{impl};
   return NDI_OK;
@@ -4761,6 +4813,8 @@ NDI_API int32_t ndi_monotonic_prop(int32_t dtype, const void* host_v, uint64_t n
   if (dtype == NDI_F32) return ndi::monotonic_scan<float>((const float*)host_v, n);
   if (dtype == NDI_I32) return ndi::monotonic_scan<int32_t>((const int32_t*)host_v, n);
   if (dtype == NDI_I64) return ndi::monotonic_scan<int64_t>((const int64_t*)host_v, n);
+  if (dtype == NDI_F16) return ndi::monotonic_scan<float>(ndi::half_images<ndi::HF_F16>(host_v, n).data(), n);
+  if (dtype == NDI_BF16) return ndi::monotonic_scan<float>(ndi::half_images<ndi::HF_BF16>(host_v, n).data(), n);
   return ndi::monotonic_scan<double>((const double*)host_v, n);
 }
 
@@ -4769,6 +4823,11 @@ NDI_API ndi_status ndi_validate1d(int32_t dtype, const void* host_x, uint64_t x_
   if (dtype == NDI_F64) return ndi::check_axis_1d<double>((const double*)host_x, x_len, n, strategy);
   if (dtype == NDI_I32) return ndi::check_axis_1d<int32_t>((const int32_t*)host_x, x_len, n, strategy);
   if (dtype == NDI_I64) return ndi::check_axis_1d<int64_t>((const int64_t*)host_x, x_len, n, strategy);
+  if (dtype == NDI_F16 || dtype == NDI_BF16) {   // monotonicity on T = on its exact, order-preserving f32 images
+    const std::vector<float> x = dtype == NDI_F16 ? ndi::half_images<ndi::HF_F16>(host_x, x_len)
+                                                  : ndi::half_images<ndi::HF_BF16>(host_x, x_len);
+    return ndi::check_axis_1d<float>(x.data(), x_len, n, strategy);
+  }
   return ndi::fail(NDI_BAD_ARG, "unknown dtype");
 }
 
@@ -4782,6 +4841,14 @@ NDI_API ndi_status ndi_validate2d(int32_t dtype, const void* host_x, uint64_t x_
     return ndi::check_axes_2d<int32_t>((const int32_t*)host_x, x_len, (const int32_t*)host_y, y_len, nx, ny);
   if (dtype == NDI_I64)
     return ndi::check_axes_2d<int64_t>((const int64_t*)host_x, x_len, (const int64_t*)host_y, y_len, nx, ny);
+  if (dtype == NDI_F16 || dtype == NDI_BF16) {
+    const bool f16 = dtype == NDI_F16;
+    const std::vector<float> x = f16 ? ndi::half_images<ndi::HF_F16>(host_x, x_len)
+                                     : ndi::half_images<ndi::HF_BF16>(host_x, x_len);
+    const std::vector<float> y = f16 ? ndi::half_images<ndi::HF_F16>(host_y, y_len)
+                                     : ndi::half_images<ndi::HF_BF16>(host_y, y_len);
+    return ndi::check_axes_2d<float>(x.data(), x_len, y.data(), y_len, nx, ny);
+  }
   return ndi::fail(NDI_BAD_ARG, "unknown dtype");
 }
 

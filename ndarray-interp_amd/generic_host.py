@@ -3,7 +3,8 @@
 The reference's `Linear` and `Bilinear` are generic over `T: Num + PartialOrd + ...`
 (src/interp1d/strategies/linear.rs:13-20, src/interp2d/strategies/bilinear.rs:20-27), so its own tests
 interpolate `i32` data on `i32` axes (tests/interp1d.rs:122-140, tests/interp2d.rs:14-61).  The MI355X kernels
-cover f32 / f64, and i32 / i64 Linear / Bilinear when the device is asked for; every other case takes the strategy trait's *default* batched
+cover f32 / f64, and i32 / i64 and f16 Linear / Bilinear when the device is asked for (bf16
+always runs there); every other case -- host float16 arrays included -- takes the strategy trait's *default* batched
 hook -- the reference's serial query loop (interp1d/mod.rs:326-343) -- over the per-query bodies below, which
 restate `interp_into` with the element type's own arithmetic (integer division truncates toward zero, as
 `i32 / i32` does in Rust).  f32 / f64 never come here: for them the HIP library is the only path.

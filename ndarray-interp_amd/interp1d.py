@@ -14,8 +14,8 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._arrays import (DEVICE_INT_DTYPES, OUTPUT_OWNED_MIN_BYTES, Buf, current_stream_ptr, dtype_id, int_query, is_torch,
-                      np_dtype_of, output_empty, torch_dtype)
+from ._arrays import (DEVICE_HALF_DTYPES, DEVICE_INT_DTYPES, OUTPUT_OWNED_MIN_BYTES, Buf, current_stream_ptr, dtype_id,
+                      int_query, is_bf16, is_torch, np_dtype_of, output_empty, torch_dtype)
 from .errors import BuilderError, InterpolateError, Panic, raise_builder, raise_eval
 from .vector_extensions import Monotonic, get_lower_index, monotonic_prop
 
@@ -241,6 +241,12 @@ class _DeviceStrategy1D(Interp1DStrategy):
 
     def interp_into(self, interpolator, target, x):
         # single query through the same device path (Q = 1)
+        if is_bf16(self._np_dtype):   # bf16: torch tensors throughout (numpy has no bfloat16)
+            import torch
+            out = torch.empty((1, self._lanes), dtype=torch.bfloat16, device=f"cuda:{self._device}")
+            self.interp_array_into(interpolator, _one_query(x), out)
+            target[...] = out.reshape(target.shape)
+            return
         out = np.empty((1, self._lanes), dtype=self._np_dtype)
         self.interp_array_into(interpolator, np.array([x], dtype=self._np_dtype), out)
         target[...] = out.reshape(target.shape)
@@ -293,8 +299,9 @@ class Linear(Interp1DStrategyBuilder, _DeviceStrategy1D):
     def build(self, x, data):
         dt = np_dtype_of(data)
         on_device = self._device_req is not None or (is_torch(data) and data.is_cuda)
-        if dt in DEVICE_INT_DTYPES and on_device:
-            # i32 / i64 on the device when asked for (.device(d) or a GPU tensor); plain host arrays keep the generic path
+        if (dt in DEVICE_INT_DTYPES or dt in DEVICE_HALF_DTYPES) and (on_device or is_bf16(dt)):
+            # i32 / i64 / f16 on the device when asked for (.device(d) or a GPU tensor); plain host arrays keep the
+            # generic path.  bf16 (torch.bfloat16 on either device) has no host path: it always takes the device
             return self._create(x, data, extrapolate=self._extrapolate, device=self._device_req)
         if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
             # integer (and other non-f32/f64) element types: the reference's generic per-query path
@@ -404,7 +411,8 @@ class CubicSpline(Interp1DStrategyBuilder):
     def build(self, x, data) -> "CubicSplineStrategy":
         if np_dtype_of(data) not in (np.dtype(np.float32), np.dtype(np.float64)):
             # the reference's trait bounds (Pow / Euclid on T) keep the spline to float element types
-            raise TypeError(f"CubicSpline covers float32/float64 only, got {np_dtype_of(data)}")
+            got = "bfloat16" if is_bf16(np_dtype_of(data)) else np_dtype_of(data)
+            raise TypeError(f"CubicSpline covers float32/float64 only, got {got}")
         bc = self._boundary
         strat = CubicSplineStrategy()
         kw = dict(extrapolate=self._extrapolate, device=self._device_req,
@@ -477,7 +485,33 @@ class CubicSplineStrategy(_DeviceStrategy1D):
 # Interp1D / Interp1DBuilder (src/interp1d/mod.rs)
 # ------------------------------------------------------------------------------------------------
 def _host(a) -> np.ndarray:
+    if is_torch(a) and is_bf16(np_dtype_of(a)):   # numpy has no bfloat16: a host tensor instead
+        return a.detach().cpu()
     return a.detach().cpu().numpy() if is_torch(a) else np.asarray(a)
+
+
+def _zeros(shape, dt, device=None):
+    """Array::zeros of the data's element type: numpy, or a torch.bfloat16 tensor for bf16 (on `device`, else the
+    host)."""
+    if is_bf16(dt):
+        import torch
+        return torch.zeros(shape, dtype=torch.bfloat16, device=device if device is not None else "cpu")
+    return np.zeros(shape, dtype=dt)
+
+
+def _one_query(v):
+    """A single query for a bf16 strategy as a 1-element tensor; Python numbers stay exact (f64) until the one
+    rounding to bf16 (_arrays.as_bf16_source)."""
+    import torch
+    return v.reshape(1) if is_torch(v) else torch.tensor([float(v)], dtype=torch.float64)
+
+
+def _default_axis(n, dt):
+    """0..n cast to T (interp1d/mod.rs:402-406)."""
+    if is_bf16(dt):
+        import torch
+        return torch.arange(n).to(torch.bfloat16)
+    return np.arange(n).astype(dt)
 
 
 class Interp1D:
@@ -521,13 +555,13 @@ class Interp1D:
         """interp1d/mod.rs:108-114 (data must be 1-D)."""
         if len(self.data.shape) != 1:
             raise TypeError("interp_scalar needs 1-D data; use interp()")
-        buf = np.zeros((), dtype=np_dtype_of(self.data))
+        buf = _zeros((), np_dtype_of(self.data))
         self.strategy.interp_into(self, buf, x)
         return buf[()]
 
     def interp(self, x):
         """interp1d/mod.rs:150-156."""
-        target = np.zeros(self._lanes_shape(), dtype=np_dtype_of(self.data))
+        target = _zeros(self._lanes_shape(), np_dtype_of(self.data))
         self.strategy.interp_into(self, target, x)
         return target
 
@@ -552,12 +586,16 @@ class Interp1D:
             if tdt is None:
                 raise TypeError("device query tensors need f32 / f64 data; other element types use host arrays")
             nbytes = int(np.prod(shape, dtype=np.int64)) * np_dtype_of(self.data).itemsize
-            if nbytes >= OUTPUT_OWNED_MIN_BYTES:     # Array::zeros through the library's placement-checked allocator
+            if nbytes >= OUTPUT_OWNED_MIN_BYTES and not is_bf16(np_dtype_of(self.data)):
+                # Array::zeros through the library's placement-checked allocator
                 ys = output_empty(shape, np_dtype_of(self.data), xs.device.index or 0)
             else:
                 ys = torch.empty(shape, dtype=tdt, device=xs.device)
             # the reference hands back zeros for rows it never reached only on Err, where the buffer
             # is dropped anyway (:210); no memset of the output is needed
+        elif is_bf16(np_dtype_of(self.data)):
+            # bf16 results are torch tensors: on the interpolator's device
+            ys = _zeros(shape, np_dtype_of(self.data), f"cuda:{self.strategy._device}")
         else:
             ys = np.zeros(shape, dtype=np_dtype_of(self.data))
         # the buffer is this call's own and is dropped on Err (:210): strategies that can use the knowledge are told
@@ -647,7 +685,7 @@ class Interp1DBuilder:
         n = shape[0]
         dt = np_dtype_of(data)
         if self._x is None:  # default axis 0..len cast to T (:402-406)
-            x = np.arange(n).astype(dt)
+            x = _default_axis(n, dt)
         else:
             x = self._x
         need = type(strategy).MINIMUM_DATA_LENGHT

@@ -7,10 +7,10 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._arrays import (DEVICE_INT_DTYPES, OUTPUT_OWNED_MIN_BYTES, Buf, current_stream_ptr, dtype_id, int_query, is_torch,
-                      np_dtype_of, output_empty, torch_dtype)
+from ._arrays import (DEVICE_HALF_DTYPES, DEVICE_INT_DTYPES, OUTPUT_OWNED_MIN_BYTES, Buf, current_stream_ptr, dtype_id,
+                      int_query, is_bf16, is_torch, np_dtype_of, output_empty, torch_dtype)
 from .errors import BuilderError, InterpolateError, Panic, raise_builder, raise_eval
-from .interp1d import _check_out_dtype, _default_device, _host, _to_device
+from .interp1d import _check_out_dtype, _default_axis, _default_device, _host, _one_query, _to_device, _zeros
 from .vector_extensions import Monotonic, get_lower_index, monotonic_prop
 
 
@@ -73,8 +73,10 @@ class Bilinear(Interp2DStrategyBuilder, Interp2DStrategy):
     def build(self, x, y, data, device=None):
         dt = np_dtype_of(data)
         on_device = device is not None or self._device_req is not None or (is_torch(data) and data.is_cuda)
-        if dt not in (np.dtype(np.float32), np.dtype(np.float64)) and not (dt in DEVICE_INT_DTYPES and on_device):
-            # i32 / i64 take the device when asked for (.device(d) or a GPU tensor); plain host arrays stay here
+        device_t = (dt in DEVICE_INT_DTYPES or dt in DEVICE_HALF_DTYPES) and (on_device or is_bf16(dt))
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)) and not device_t:
+            # i32 / i64 / f16 take the device when asked for (.device(d) or a GPU tensor); plain host arrays stay here
+            # (bf16 always takes the device: it has no host path)
             # integer (and other non-f32/f64) element types: the reference's generic per-query path
             from .generic_host import HostBilinear
             return HostBilinear(_host(x), _host(y), _host(data), self._extrapolate)
@@ -252,6 +254,12 @@ class Bilinear(Interp2DStrategyBuilder, Interp2DStrategy):
             raise_eval(st, info, int_query(self._np_dtype, [qx, qy], info))
 
     def interp_into(self, interpolator, target, x, y):
+        if is_bf16(self._np_dtype):   # bf16: torch tensors throughout (numpy has no bfloat16)
+            import torch
+            out = torch.empty((1, self._lanes), dtype=torch.bfloat16, device=f"cuda:{self._device}")
+            self.interp_array_into(interpolator, _one_query(x), _one_query(y), out)
+            target[...] = out.reshape(target.shape)
+            return
         out = np.empty((1, self._lanes), dtype=self._np_dtype)
         self.interp_array_into(interpolator, np.array([x], dtype=self._np_dtype),
                                np.array([y], dtype=self._np_dtype), out)
@@ -299,12 +307,12 @@ class Interp2D:
         """interp2d/mod.rs:107-113 (data must be 2-D)."""
         if len(self.data.shape) != 2:
             raise TypeError("interp_scalar needs 2-D data; use interp()")
-        buf = np.zeros((), dtype=np_dtype_of(self.data))
+        buf = _zeros((), np_dtype_of(self.data))
         self.strategy.interp_into(self, buf, x, y)
         return buf[()]
 
     def interp(self, x, y):
-        target = np.zeros(self._lanes_shape(), dtype=np_dtype_of(self.data))
+        target = _zeros(self._lanes_shape(), np_dtype_of(self.data))
         self.strategy.interp_into(self, target, x, y)
         return target
 
@@ -329,10 +337,14 @@ class Interp2D:
             if tdt is None:
                 raise TypeError("device query tensors need f32 / f64 data; other element types use host arrays")
             nbytes = int(np.prod(shape, dtype=np.int64)) * np_dtype_of(self.data).itemsize
-            if nbytes >= OUTPUT_OWNED_MIN_BYTES:     # Array::zeros through the library's placement-checked allocator
+            if nbytes >= OUTPUT_OWNED_MIN_BYTES and not is_bf16(np_dtype_of(self.data)):
+                # Array::zeros through the library's placement-checked allocator
                 zs = output_empty(shape, np_dtype_of(self.data), xs.device.index or 0)
             else:
                 zs = torch.empty(shape, dtype=tdt, device=xs.device)
+        elif is_bf16(np_dtype_of(self.data)):
+            # bf16 results are torch tensors: on the interpolator's device
+            zs = _zeros(shape, np_dtype_of(self.data), f"cuda:{self.strategy._device}")
         else:
             zs = np.zeros(shape, dtype=np_dtype_of(self.data))
         # the buffer is this call's own and is dropped on Err (:193-195): strategies that can use the knowledge are told
@@ -431,8 +443,8 @@ class Interp2DBuilder:
                 "The 1-dimension has not enough data for the chosen interpolation strategy. "
                 f"Provided: {shape[1]}, Reqired: {need}")
         dt = np_dtype_of(data)
-        x = np.arange(shape[0]).astype(dt) if self._x is None else self._x
-        y = np.arange(shape[1]).astype(dt) if self._y is None else self._y
+        x = _default_axis(shape[0], dt) if self._x is None else self._x
+        y = _default_axis(shape[1], dt) if self._y is None else self._y
         x_len = int(np.prod(x.shape, dtype=np.int64))
         y_len = int(np.prod(y.shape, dtype=np.int64))
         if x_len != shape[0]:

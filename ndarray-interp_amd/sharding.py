@@ -172,7 +172,8 @@ def interp_array_sharded(replicas, xs, ys=None, *, out=None):
             lo, _hi = shard_bounds(nq, i, n)
             io[i].out = out.ctypes.data + lo * lanes * out.itemsize
     else:
-        tdt = torch.float64 if dt.itemsize == 8 else torch.float32
+        from ._arrays import DEVICE_HALF_DTYPES, torch_dtype
+        tdt = torch_dtype(dt) if dt in DEVICE_HALF_DTYPES else torch.float64 if dt.itemsize == 8 else torch.float32
         opts.out_memspace = _capi.MEM_DEVICE
         outs = []
         for i, st in enumerate(strategies):

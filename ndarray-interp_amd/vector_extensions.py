@@ -57,6 +57,8 @@ def _monotonic_generic(v: np.ndarray) -> Monotonic:
 
 def monotonic_prop(v) -> Monotonic:
     """VectorExtensions::monotonic_prop (src/vector_extensions.rs:40-53)."""
+    if is_torch(v) and str(v.dtype) == "torch.bfloat16":
+        v = v.float()   # exact and order-preserving: the same answer as on bf16
     a = v.detach().cpu().numpy() if is_torch(v) else np.asarray(v)
     if a.dtype in (np.float32, np.float64):
         a = np.ascontiguousarray(a)

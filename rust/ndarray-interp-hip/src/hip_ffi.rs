@@ -26,6 +26,8 @@ pub const NDI_F32: i32 = 0;
 pub const NDI_F64: i32 = 1;
 pub const NDI_I32: i32 = 2; // v0.5 addition: Linear / Bilinear only
 pub const NDI_I64: i32 = 3;
+pub const NDI_F16: i32 = 4; // v0.5 addition: Linear / Bilinear only (the `half` crate's arithmetic)
+pub const NDI_BF16: i32 = 5;
 
 pub const NDI_OP_SUBTRACT: i32 = 0; // ndi_int_op: ndi_oob_info.axis of NDI_INT_OVERFLOW
 pub const NDI_OP_MULTIPLY: i32 = 1;
