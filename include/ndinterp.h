@@ -1,7 +1,8 @@
 /* include/ndinterp.h -- C ABI of libndinterp_hip.so (MI355X / gfx950).
  *
  * Drop-in boundary for the batched `interp_array` hot path of the Rust crate
- * ndarray-interp v0.6.0 (1D Linear, 1D CubicSpline, 2D Bilinear).  The reference
+ * ndarray-interp v0.6.0 (1D Linear, 1D CubicSpline, 2D Bilinear), plus three 1D strategies the
+ * reference leaves to user code: Pchip, Akima and CubicHermite (ndi_strategy1d).  The reference
  * has no FFI of its own: its boundary is the strategy trait pair plus the inherent
  * methods of Interp1D / Interp2D.  Each entry point below names the reference
  * interface it replaces (paths relative to the reference tree).  A Rust
@@ -75,8 +76,39 @@ typedef enum ndi_int_op {
 typedef enum ndi_memspace { NDI_MEM_HOST = 0, NDI_MEM_DEVICE = 1 } ndi_memspace;
 
 /* 1D strategies: Linear (src/interp1d/strategies/linear.rs),
- * CubicSpline (src/interp1d/strategies/cubic_spline.rs). */
-typedef enum ndi_strategy1d { NDI_LINEAR = 0, NDI_CUBIC_SPLINE = 1 } ndi_strategy1d;
+ * CubicSpline (src/interp1d/strategies/cubic_spline.rs).
+ *
+ * NDI_PCHIP, NDI_AKIMA, NDI_CUBIC_HERMITE (backward-compatible: new enumerators only; f32 / f64) are local C1 cubics.  The
+ * reference leaves them to user strategies; here they are built on the device.  CubicSplineStrategy::interp_into
+ * (cubic_spline.rs:811-828) evaluates the cubic Hermite form for any knot derivatives k once the tables
+ *   a_i = k_i h_i - dy,  b_i = dy - k_{i+1} h_i        (dy = y[i+1] - y[i], h_i = x[i+1] - x[i]; cubic_spline.rs:362-363)
+ * exist, so these strategies only choose k differently; their handles take every evaluation entry point, path and AUTO
+ * rule of a CubicSpline handle of the same shape.  `extrapolate` != 0 continues the first / last interval's polynomial.
+ * Numerical contract -- this project's own, there is no Rust to follow: per lane, every line one IEEE operation in T in
+ * this order, nothing fused; delta_i = dy / h_i; sgn(v) is -1, 0 or 1; +0 is positive zero.
+ *  NDI_PCHIP (>= 2 knots; what scipy's PchipInterpolator computes).  n == 2: k_0 = k_1 = delta_0.  Interior knots:
+ *      if delta_{i-1} == 0 or delta_i == 0 or (delta_{i-1} > 0) != (delta_i > 0):  k_i = +0
+ *      else  w1 = (h_i + h_i) + h_{i-1};  w2 = h_i + (h_{i-1} + h_{i-1});  k_i = (w1 + w2) / (w1 / delta_{i-1} + w2 / delta_i)
+ *    ends: k_0 = edge(h_0, h_1, delta_0, delta_1),  k_{n-1} = edge(h_{n-2}, h_{n-3}, delta_{n-2}, delta_{n-3}) with
+ *      edge(h0, h1, m0, m1):  d = (((h0 + h0) + h1) m0 - h0 m1) / (h0 + h1)
+ *                             sgn(d) != sgn(m0): +0;  else sgn(m0) != sgn(m1) and |d| > 3 |m0|: 3 m0;  else d
+ *  NDI_AKIMA (>= 3 knots; Akima 1970, scipy's Akima1DInterpolator with method="akima").  m_j = delta_j (0 <= j <= n-2),
+ *    m_{-1} = (m_0 + m_0) - m_1,  m_{-2} = (m_{-1} + m_{-1}) - m_0,  m_{n-1} = (m_{n-2} + m_{n-2}) - m_{n-3},
+ *    m_n = (m_{n-1} + m_{n-1}) - m_{n-2};  for every knot:
+ *      w1 = |m_{i+1} - m_i|;  w2 = |m_{i-1} - m_{i-2}|;  s = w1 + w2
+ *      k_i = s == 0 ? 0.5 (m_{i-1} + m_i) : (w1 m_{i-1} + w2 m_i) / s
+ *    Deviation from scipy: scipy takes the average below a threshold relative to the largest s of the whole array (a global
+ *    reduction for a rounding-level effect); here the test is the exact s == 0.
+ *  NDI_CUBIC_HERMITE (>= 2 knots): k is given by the caller, see ndi_interp1d_create_hermite.
+ * For these three a non-zero `periodic`, `build_flags`, boundary field or lane_* pointer of the descriptor is NDI_BAD_ARG
+ * (they are spline notions), and so is an integer or half-precision dtype. */
+typedef enum ndi_strategy1d {
+  NDI_LINEAR = 0,
+  NDI_CUBIC_SPLINE = 1,
+  NDI_PCHIP = 2,
+  NDI_AKIMA = 3,
+  NDI_CUBIC_HERMITE = 4
+} ndi_strategy1d;
 
 /* SingleBoundary (cubic_spline.rs:204-217).  Natural == SecondDeriv(0),
  * Clamped == FirstDeriv(0) (:287-296). */
@@ -228,6 +260,11 @@ typedef enum ndi_eval_flags {
 
 /* ---- build ------------------------------------------------------------------ */
 ndi_status ndi_interp1d_create(const ndi_interp1d_desc* desc, ndi_interp1d** out);
+/* NDI_CUBIC_HERMITE: the cubic Hermite interpolant of `desc->data` with the caller's knot derivatives k = dydx,
+ * T[n * lanes] in desc->memspace, laid out like the data (ndi_strategy1d states the tables; no rule is applied to k, so
+ * there is nothing of scipy's to deviate from).  desc->strategy must be NDI_CUBIC_HERMITE; ndi_interp1d_create refuses that
+ * strategy with NDI_BAD_ARG.  The handle is an ndi_interp1d like any other. */
+ndi_status ndi_interp1d_create_hermite(const ndi_interp1d_desc* desc, const void* dydx, ndi_interp1d** out);
 void ndi_interp1d_destroy(ndi_interp1d* h);
 ndi_status ndi_interp2d_create(const ndi_interp2d_desc* desc, ndi_interp2d** out);
 void ndi_interp2d_destroy(ndi_interp2d* h);

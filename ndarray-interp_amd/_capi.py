@@ -24,7 +24,7 @@ F32, F64, I32, I64, F16, BF16 = 0, 1, 2, 3, 4, 5
 OP_SUBTRACT, OP_MULTIPLY, OP_ADD, OP_DIVIDE = range(4)   # ndi_int_op
 OP_NAMES = ["subtract", "multiply", "add", "divide"]
 MEM_HOST, MEM_DEVICE = 0, 1
-LINEAR, CUBIC_SPLINE = 0, 1
+LINEAR, CUBIC_SPLINE, PCHIP, AKIMA, CUBIC_HERMITE = 0, 1, 2, 3, 4
 BC_NOT_A_KNOT, BC_NATURAL, BC_CLAMPED, BC_FIRST_DERIV, BC_SECOND_DERIV = range(5)
 BUILD_DEFAULT, BUILD_REFERENCE_ORDER = 0, 1
 EVAL_DEFAULT, EVAL_FRESH_OUTPUT, EVAL_ROWS_AFTER_ERROR_UNSPECIFIED = 0, 1, 2
@@ -99,6 +99,7 @@ RING_CONSUMER = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.POINTER(RingChunk))
 _P = C.c_void_p
 SYMBOLS = {
     "ndi_interp1d_create": (C.c_int, [C.POINTER(Interp1DDesc), C.POINTER(_P)]),
+    "ndi_interp1d_create_hermite": (C.c_int, [C.POINTER(Interp1DDesc), _P, C.POINTER(_P)]),
     "ndi_interp1d_destroy": (None, [_P]),
     "ndi_interp2d_create": (C.c_int, [C.POINTER(Interp2DDesc), C.POINTER(_P)]),
     "ndi_interp2d_destroy": (None, [_P]),

@@ -46,7 +46,8 @@ int monotonic_scan(const T* v, uint64_t n) {
 
 inline uint64_t min_len_1d(int strategy) {
   // MINIMUM_DATA_LENGHT: Linear 2 (linear.rs:52), CubicSpline 3 (cubic_spline.rs:751)
-  return strategy == NDI_CUBIC_SPLINE ? 3 : 2;
+  // Pchip 2, Akima 3 (its end extension needs two slopes), CubicHermite 2
+  return strategy == NDI_CUBIC_SPLINE || strategy == NDI_AKIMA ? 3 : 2;
 }
 
 // Interp1DBuilder::build, src/interp1d/mod.rs:449-471 (check order preserved).

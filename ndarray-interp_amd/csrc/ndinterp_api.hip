@@ -28,6 +28,7 @@
 #include "common.hpp"
 #include "host_logic.hpp"
 #include "kernels.hpp"
+#include "hermite_kernels.hpp"
 
 #define NDI_API extern "C" __attribute__((visibility("default")))
 
@@ -894,10 +895,11 @@ struct Interp1DBase {
 
 template <class T>
 struct Interp1DImpl final : Interp1DBase {
-  int strategy = NDI_LINEAR;
+  int strategy = NDI_LINEAR;   // the evaluation class: NDI_CUBIC_SPLINE = "has a / b tables" (Pchip, Akima, CubicHermite too)
+  int rule = HR_SPLINE;        // ... and which rule chose the knot derivatives behind those tables (HermiteRule)
   int mode = EX_NO;
   uint64_t n = 0;
-  DevBuf arena;   // small handles: ONE allocation behind pyr.buf / data / ca / cb / ck (create1d); declared first: freed last
+  DevBuf arena;  // small handles: ONE allocation behind pyr.buf / data / ca / cb / ck (create1d); declared first: freed last
   DevicePyramid<T> pyr;
   DevBuf data, ca, cb;
   DevBuf ck;   // the spline's derivatives k [n][lanes]: kept by builds whose {y, k} fit LDS (eval_fused_kernel, TLDS == 2)
@@ -970,7 +972,7 @@ struct Interp1DImpl final : Interp1DBase {
 
   uint64_t signature() const override {
     uint64_t h = fnv1a(FNV_SEED, pyr.host_knots.data(), pyr.host_knots.size() * sizeof(T));
-    const uint64_t f[3] = {n, (uint64_t)strategy, (uint64_t)mode};
+    const uint64_t f[3] = {n, (uint64_t)strategy | ((uint64_t)rule << 8), (uint64_t)mode};
     return fnv1a(h, f, sizeof(f));
   }
 
@@ -1323,6 +1325,58 @@ struct Interp1DImpl final : Interp1DBase {
                          (hipStream_t) nullptr, A);
     NDI_HIP(hipGetLastError());
     NDI_HIP(hipDeviceSynchronize());
+    return NDI_OK;
+  }
+
+  // ---- build of the local cubics: Pchip, Akima, CubicHermite (hermite_kernels.hpp) -----------------------
+  // One launch, no host plan, no temporaries: the knots are the pyramid's level 0, already resident.  `dydx` (HR_GIVEN):
+  // the caller's derivatives in `memspace`.  Like the spline build it runs on the NULL stream and the tables are complete
+  // when create returns.
+  template <int RULE>
+  void launch_hermite(const HermiteArgs<T>& A, bool vec) {
+    constexpr int VN = Wide<T>::N;
+    const uint64_t total = (n - 1) * (vec ? lanes / VN : lanes);
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + BLOCK - 1) / BLOCK, 1u << 20));
+    if (vec) hipLaunchKernelGGL((hermite_build_kernel<T, RULE, VN>), dim3(grid), dim3(BLOCK), 0, (hipStream_t) nullptr, A);
+    else hipLaunchKernelGGL((hermite_build_kernel<T, RULE, 1>), dim3(grid), dim3(BLOCK), 0, (hipStream_t) nullptr, A);
+  }
+
+  ndi_status build_hermite(const void* dydx, int memspace) {
+    Range rg("ndi:hermite_build");
+    const size_t tab = (size_t)(n - 1) * lanes * sizeof(T);
+    ca.reserve(tab);
+    cb.reserve(tab);
+    HermiteArgs<T> A{};
+    A.data = data.as<T>();
+    A.x = pyr.view.lv0;
+    A.ca = ca.as<T>();
+    A.cb = cb.as<T>();
+    A.n = n;
+    A.lanes = lanes;
+    A.kout = reserve_k();
+    DevBuf tmp;
+    if (rule == HR_GIVEN) {
+      if (memspace == NDI_MEM_DEVICE) {
+        A.dydx = static_cast<const T*>(dydx);
+      } else {   // host derivatives: uploaded into the kept k table where there is one, else into a temporary
+        T* dst = A.kout;
+        if (!dst) {
+          tmp.reserve((size_t)n * lanes * sizeof(T));
+          dst = tmp.as<T>();
+        }
+        NDI_HIP(hipMemcpy(dst, dydx, (size_t)n * lanes * sizeof(T), hipMemcpyHostToDevice));
+        A.dydx = dst;
+        A.kout = nullptr;
+      }
+    }
+    auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool vec = lanes % Wide<T>::N == 0 && aligned(A.data) && aligned(A.ca) && aligned(A.cb) && aligned(A.kout) &&
+                     aligned(A.dydx);
+    if (rule == HR_PCHIP) launch_hermite<HR_PCHIP>(A, vec);
+    else if (rule == HR_AKIMA) launch_hermite<HR_AKIMA>(A, vec);
+    else launch_hermite<HR_GIVEN>(A, vec);
+    NDI_HIP(hipGetLastError());
+    NDI_HIP(hipStreamSynchronize(nullptr));   // the tables are complete when create() returns: any stream may read them
     return NDI_OK;
   }
 
@@ -2331,7 +2385,7 @@ struct Interp1DImpl final : Interp1DBase {
   ndi_status clone_to(int dev, Interp1DBase** out) override {
     std::unique_ptr<Interp1DImpl<T>> h(new Interp1DImpl<T>());
     h->dtype = dtype; h->device = dev; h->lanes = lanes;
-    h->strategy = strategy; h->mode = mode; h->n = n;
+    h->strategy = strategy; h->rule = rule; h->mode = mode; h->n = n;
     {
       DeviceGuard dg(device);
       NDI_HIP(hipDeviceSynchronize());     // the source tables are complete
@@ -2381,13 +2435,16 @@ static std::vector<T> fetch_axis(const void* p, uint64_t len, int memspace) {
 }
 
 template <class T>
-static ndi_status create1d(const ndi_interp1d_desc& d, Interp1DBase** out) {
+static ndi_status create1d(const ndi_interp1d_desc& d, Interp1DBase** out, const void* dydx = nullptr) {
   DeviceGuard dg(d.device);
   Range rg("ndi_interp1d_create");
   std::unique_ptr<Interp1DImpl<T>> h(new Interp1DImpl<T>());
   h->dtype = d.dtype;
   h->device = d.device;
-  h->strategy = d.strategy;
+  // Pchip / Akima / CubicHermite handles are of the cubic evaluation class: a / b tables, every evaluation form of the spline
+  const bool cubic = d.strategy != NDI_LINEAR;
+  h->strategy = cubic ? NDI_CUBIC_SPLINE : NDI_LINEAR;
+  h->rule = d.strategy == NDI_PCHIP ? HR_PCHIP : d.strategy == NDI_AKIMA ? HR_AKIMA : d.strategy == NDI_CUBIC_HERMITE ? HR_GIVEN : HR_SPLINE;
   h->mode = d.extrapolate ? EX_YES : EX_NO;
   h->n = d.n;
   h->lanes = d.lanes;
@@ -2412,8 +2469,8 @@ static ndi_status create1d(const ndi_interp1d_desc& d, Interp1DBase** out) {
     while ((uint64_t)64 * block < d.n) block *= 2;
     const size_t pyr_b = al((d.n + (d.n + block - 1) / block) * sizeof(T));
     const size_t data_b = al((size_t)d.n * d.lanes * sizeof(T));
-    const size_t tab_b = d.strategy == NDI_CUBIC_SPLINE ? al((size_t)(d.n - 1) * d.lanes * sizeof(T)) : 0;
-    const size_t k_b = (d.strategy == NDI_CUBIC_SPLINE && 2 * data_b <= FUSED_LDS_LIMIT) ? data_b : 0;
+    const size_t tab_b = cubic ? al((size_t)(d.n - 1) * d.lanes * sizeof(T)) : 0;
+    const size_t k_b = (cubic && 2 * data_b <= FUSED_LDS_LIMIT) ? data_b : 0;
     const size_t total = pyr_b + data_b + 2 * tab_b + k_b;
     constexpr int arena_env = 1;
     if (arena_env && total <= ((size_t)1 << 20)) {
@@ -2439,6 +2496,10 @@ static ndi_status create1d(const ndi_interp1d_desc& d, Interp1DBase** out) {
     ndi_status st = h->build_spline(d);
     if (st != NDI_OK) return st;
     clk.mark("build_spline");
+  } else if (cubic) {
+    ndi_status st = h->build_hermite(dydx, d.memspace);
+    if (st != NDI_OK) return st;
+    clk.mark("build_hermite");
   }
   *out = h.release();
   return NDI_OK;
@@ -4338,20 +4399,53 @@ static ndi_status need_device(int device) {
   return NDI_OK;
 }
 
-NDI_API ndi_status ndi_interp1d_create(const ndi_interp1d_desc* desc, ndi_interp1d** out) {
+static const char* strategy1d_name(int strategy) {
+  switch (strategy) {
+    case NDI_LINEAR: return "Linear";
+    case NDI_CUBIC_SPLINE: return "CubicSpline";
+    case NDI_PCHIP: return "Pchip";
+    case NDI_AKIMA: return "Akima";
+    case NDI_CUBIC_HERMITE: return "CubicHermite";
+  }
+  return "?";
+}
+
+// ndi_interp1d_create (dydx == nullptr) and ndi_interp1d_create_hermite.  Every check that needs no device comes first,
+// so it behaves the same everywhere.
+static ndi_status create1d_checked(const ndi_interp1d_desc* desc, const void* dydx, bool hermite_entry, ndi_interp1d** out) {
   if (!desc || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
   *out = nullptr;
   if (desc->dtype < NDI_F32 || desc->dtype > NDI_BF16) return ndi::fail(NDI_BAD_ARG, "unknown dtype");
-  if (desc->strategy != NDI_LINEAR && desc->strategy != NDI_CUBIC_SPLINE)
+  if (desc->strategy < NDI_LINEAR || desc->strategy > NDI_CUBIC_HERMITE)
     return ndi::fail(NDI_BAD_ARG, "unknown strategy");
+  if (hermite_entry && desc->strategy != NDI_CUBIC_HERMITE)
+    return ndi::fail(NDI_BAD_ARG, "ndi_interp1d_create_hermite builds NDI_CUBIC_HERMITE only (strategy %d: %s takes "
+                     "ndi_interp1d_create)", (int)desc->strategy, strategy1d_name(desc->strategy));
+  if (!hermite_entry && desc->strategy == NDI_CUBIC_HERMITE)
+    return ndi::fail(NDI_BAD_ARG, "CubicHermite needs the knot derivatives: build it with ndi_interp1d_create_hermite");
+  const bool local_cubic = desc->strategy >= NDI_PCHIP;
+  const char* name = strategy1d_name(desc->strategy);
   const bool int_t = desc->dtype == NDI_I32 || desc->dtype == NDI_I64;
   if (int_t && desc->strategy == NDI_CUBIC_SPLINE)
     return ndi::fail(NDI_BAD_ARG, "CubicSpline needs a float element type (f32 / f64): the reference's trait bounds "
                      "rule out integer splines; integer data takes Linear");
+  if (int_t && local_cubic)
+    return ndi::fail(NDI_BAD_ARG, "%s needs a float element type (f32 / f64); integer data takes Linear", name);
   const bool half_t = desc->dtype == NDI_F16 || desc->dtype == NDI_BF16;
   if (half_t && desc->strategy == NDI_CUBIC_SPLINE)
     return ndi::fail(NDI_BAD_ARG, "CubicSpline needs f32 / f64: the reference's SplineNum bounds (Pow, ScalarOperand, "
                      "Euclid) rule out f16 / bf16 splines; half-precision data takes Linear");
+  if (half_t && local_cubic)
+    return ndi::fail(NDI_BAD_ARG, "%s needs f32 / f64; half-precision data takes Linear", name);
+  if (local_cubic) {   // the spline's notions do not apply
+    if (desc->periodic) return ndi::fail(NDI_BAD_ARG, "%s has no periodic mode (periodic must be 0)", name);
+    if (desc->build_flags) return ndi::fail(NDI_BAD_ARG, "%s takes no build_flags (NDI_BUILD_REFERENCE_ORDER is the spline's)", name);
+    if (desc->left.kind || desc->left.value != 0.0 || desc->right.kind || desc->right.value != 0.0)
+      return ndi::fail(NDI_BAD_ARG, "%s takes no boundary condition (left / right must be zero)", name);
+    if (desc->lane_left_kind || desc->lane_left_value || desc->lane_right_kind || desc->lane_right_value)
+      return ndi::fail(NDI_BAD_ARG, "%s takes no per-lane boundary conditions (lane_* must be NULL)", name);
+  }
+  if (hermite_entry && !dydx) return ndi::fail(NDI_BAD_ARG, "null dydx pointer");
   // Builder checks that need no device come first, so they behave the same everywhere.
   if (desc->validate && desc->memspace == NDI_MEM_HOST && desc->x) {
     ndi_status st = ndi_validate1d(desc->dtype, desc->x, desc->x_len, desc->n, desc->strategy);
@@ -4364,8 +4458,8 @@ NDI_API ndi_status ndi_interp1d_create(const ndi_interp1d_desc* desc, ndi_interp
   if (ds != NDI_OK) return ds;
   NDI_TRY
   ndi::Interp1DBase* impl = nullptr;
-  ndi_status st = desc->dtype == NDI_F32   ? ndi::create1d<float>(*desc, &impl)
-                  : desc->dtype == NDI_F64 ? ndi::create1d<double>(*desc, &impl)
+  ndi_status st = desc->dtype == NDI_F32   ? ndi::create1d<float>(*desc, &impl, dydx)
+                  : desc->dtype == NDI_F64 ? ndi::create1d<double>(*desc, &impl, dydx)
                   : desc->dtype == NDI_I32 ? ndi::create1d_int<int32_t>(*desc, &impl)
                   : desc->dtype == NDI_I64 ? ndi::create1d_int<int64_t>(*desc, &impl)
                   : desc->dtype == NDI_F16 ? ndi::create1d_half<ndi::HF_F16>(*desc, &impl)
@@ -4374,6 +4468,14 @@ NDI_API ndi_status ndi_interp1d_create(const ndi_interp1d_desc* desc, ndi_interp
   *out = new ndi_interp1d{impl};
   return NDI_OK;
   NDI_CATCH
+}
+
+NDI_API ndi_status ndi_interp1d_create(const ndi_interp1d_desc* desc, ndi_interp1d** out) {
+  return create1d_checked(desc, nullptr, false, out);
+}
+
+NDI_API ndi_status ndi_interp1d_create_hermite(const ndi_interp1d_desc* desc, const void* dydx, ndi_interp1d** out) {
+  return create1d_checked(desc, dydx, true, out);
 }
 
 NDI_API void ndi_interp1d_destroy(ndi_interp1d* h) {

@@ -1,5 +1,6 @@
 """Host-side mirror of the reference's 1-D surface (src/interp1d/mod.rs + strategies/):
-`Interp1DBuilder`, `Interp1D`, the strategy trait pair and the built-in `Linear` and `CubicSpline`.
+`Interp1DBuilder`, `Interp1D`, the strategy trait pair and the built-in `Linear` and `CubicSpline` -- plus
+`Pchip`, `Akima` and `CubicHermite`, which the reference leaves to user strategies and this build runs on the device.
 
 Names, argument meaning and error behaviour follow the reference so that the parity tests read like
 its own tests.  The built-in strategies override the *batched* hook (`interp_array_into`) and call the
@@ -65,7 +66,7 @@ class _DeviceStrategy1D(Interp1DStrategy):
 
     # -- build ------------------------------------------------------------------------------
     def _create(self, x, data, *, extrapolate, periodic=False, left=(0, 0.0), right=(0, 0.0),
-                per_lane=None, device=None, build_flags=0):
+                per_lane=None, device=None, build_flags=0, dydx=None):
         xb_dt = np_dtype_of(data)
         tid = dtype_id(xb_dt)
         db = Buf(data)
@@ -97,7 +98,12 @@ class _DeviceStrategy1D(Interp1DStrategy):
             d.lane_left_kind, d.lane_left_value = lk.ctypes.data, lv.ctypes.data
             d.lane_right_kind, d.lane_right_value = rk.ctypes.data, rv.ctypes.data
         h = C.c_void_p()
-        st = _capi.lib().ndi_interp1d_create(C.byref(d), C.byref(h))
+        if dydx is not None:   # CubicHermite: the derivatives travel in the same memory space as the data
+            kb = Buf(_host(dydx), xb_dt) if db.memspace == _capi.MEM_HOST else Buf(_to_device(dydx, db.keep.device), xb_dt)
+            keep.append(kb)
+            st = _capi.lib().ndi_interp1d_create_hermite(C.byref(d), kb.ptr, C.byref(h))
+        else:
+            st = _capi.lib().ndi_interp1d_create(C.byref(d), C.byref(h))
         del keep
         if st != _capi.OK:
             raise_builder(st)
@@ -479,6 +485,104 @@ class CubicSplineStrategy(_DeviceStrategy1D):
     def _create(self, x, data, **kw):
         self._n = data.shape[0]
         return super()._create(x, data, **kw)
+
+
+# ---- local C1 cubics: Pchip, Akima, CubicHermite (include/ndinterp.h, ndi_strategy1d) -------------------------
+class PchipStrategy(CubicSplineStrategy):
+    """Finished `Pchip`: a / b tables on the device, evaluated by the spline's kernels."""
+
+    _kind = _capi.PCHIP
+
+
+class AkimaStrategy(CubicSplineStrategy):
+    """Finished `Akima`."""
+
+    _kind = _capi.AKIMA
+
+
+class CubicHermiteStrategy(CubicSplineStrategy):
+    """Finished `CubicHermite`."""
+
+    _kind = _capi.CUBIC_HERMITE
+
+
+class _LocalCubic(Interp1DStrategyBuilder):
+    """Shared builder body of Pchip / Akima / CubicHermite: `.extrapolate(b)` and `.device(d)` as `CubicSpline` has
+    them (`extrapolate(True)` continues the first / last interval's polynomial); f32 / f64 only."""
+
+    _finished = None
+
+    def __init__(self):
+        self._extrapolate = False
+        self._device_req = None
+
+    def device(self, ordinal: int):
+        """Build-side option of this mirror: the HIP device that holds the tables (see Linear.device)."""
+        self._device_req = int(ordinal)
+        return self
+
+    def extrapolate(self, extrapolate: bool):
+        self._extrapolate = bool(extrapolate)
+        return self
+
+    def _check_dtype(self, data):
+        if np_dtype_of(data) not in (np.dtype(np.float32), np.dtype(np.float64)):
+            got = "bfloat16" if is_bf16(np_dtype_of(data)) else np_dtype_of(data)
+            raise TypeError(f"{type(self).__name__} covers float32/float64 only, got {got}")
+
+    def build(self, x, data):
+        self._check_dtype(data)
+        return self._finished()._create(x, data, extrapolate=self._extrapolate, device=self._device_req)
+
+
+class Pchip(_LocalCubic):
+    """Piecewise cubic Hermite interpolating polynomial: Fritsch-Butland derivatives with the three-point
+    shape-preserving end formula (what scipy's `PchipInterpolator` computes).  Monotone data gives a monotone
+    interpolant: no overshoot on steps and plateaus.  Built on the device in one pass."""
+
+    MINIMUM_DATA_LENGHT = 2
+    _finished = PchipStrategy
+
+    @staticmethod
+    def new() -> "Pchip":
+        return Pchip()
+
+
+class Akima(_LocalCubic):
+    """Akima's 1970 interpolant (scipy's `Akima1DInterpolator`, `method="akima"`): no ringing next to outliers.
+    Where both weights vanish (`s == 0` exactly) the two neighbouring slopes are averaged; scipy switches to the
+    average below a threshold relative to the largest `s` of the whole array."""
+
+    MINIMUM_DATA_LENGHT = 3
+    _finished = AkimaStrategy
+
+    @staticmethod
+    def new() -> "Akima":
+        return Akima()
+
+
+class CubicHermite(_LocalCubic):
+    """Cubic Hermite interpolation with the caller's knot derivatives: `CubicHermite.new(dydx)`, `dydx` of the
+    data's shape (a numpy array or a tensor)."""
+
+    MINIMUM_DATA_LENGHT = 2
+    _finished = CubicHermiteStrategy
+
+    def __init__(self, dydx):
+        super().__init__()
+        self._dydx = dydx
+
+    @staticmethod
+    def new(dydx) -> "CubicHermite":
+        return CubicHermite(dydx)
+
+    def build(self, x, data):
+        self._check_dtype(data)
+        if tuple(self._dydx.shape) != tuple(data.shape):
+            raise BuilderError.ShapeError(
+                f"dydx has wrong shape. Expected: {list(data.shape)}, got: {list(self._dydx.shape)}")
+        return self._finished()._create(x, data, extrapolate=self._extrapolate, device=self._device_req,
+                                        dydx=self._dydx)
 
 
 # ------------------------------------------------------------------------------------------------

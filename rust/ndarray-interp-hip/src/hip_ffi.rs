@@ -39,6 +39,11 @@ pub const NDI_MEM_DEVICE: i32 = 1;
 /// `ndi_strategy1d`
 pub const NDI_LINEAR: i32 = 0;
 pub const NDI_CUBIC_SPLINE: i32 = 1;
+/// Local C1 cubics built on the device (f32 / f64); the header states their numerical contract
+pub const NDI_PCHIP: i32 = 2;
+pub const NDI_AKIMA: i32 = 3;
+/// Derivatives given by the caller: `ndi_interp1d_create_hermite`
+pub const NDI_CUBIC_HERMITE: i32 = 4;
 /// `ndi_bc_kind`: SingleBoundary (cubic_spline.rs:204-217)
 pub const NDI_BC_NOT_A_KNOT: i32 = 0;
 pub const NDI_BC_NATURAL: i32 = 1;
@@ -214,6 +219,11 @@ pub struct ndi_output_info {
 // ---- functions --------------------------------------------------------------------------------
 extern "C" {
     pub fn ndi_interp1d_create(desc: *const ndi_interp1d_desc, out: *mut *mut ndi_interp1d) -> i32;
+    pub fn ndi_interp1d_create_hermite(
+        desc: *const ndi_interp1d_desc,
+        dydx: *const c_void,
+        out: *mut *mut ndi_interp1d,
+    ) -> i32;
     pub fn ndi_interp1d_destroy(h: *mut ndi_interp1d);
     pub fn ndi_interp2d_create(desc: *const ndi_interp2d_desc, out: *mut *mut ndi_interp2d) -> i32;
     pub fn ndi_interp2d_destroy(h: *mut ndi_interp2d);
