@@ -2,7 +2,8 @@
  *
  * Drop-in boundary for the batched `interp_array` hot path of the Rust crate
  * ndarray-interp v0.6.0 (1D Linear, 1D CubicSpline, 2D Bilinear), plus three 1D strategies the
- * reference leaves to user code: Pchip, Akima and CubicHermite (ndi_strategy1d).  The reference
+ * reference leaves to user code: Pchip, Akima and CubicHermite (ndi_strategy1d), and first / second
+ * derivatives of the four cubics as handles of their own (ndi_interp1d_derivative).  The reference
  * has no FFI of its own: its boundary is the strategy trait pair plus the inherent
  * methods of Interp1D / Interp2D.  Each entry point below names the reference
  * interface it replaces (paths relative to the reference tree).  A Rust
@@ -281,6 +282,46 @@ ndi_status ndi_interp2d_clone(const ndi_interp2d* h, int32_t device, ndi_interp2
  * each T[(n-1) * lanes], to `a_out` / `b_out` (either may be NULL). */
 ndi_status ndi_interp1d_coefficients(const ndi_interp1d* h, void* a_out, void* b_out,
                                      int32_t memspace);
+
+/* Copies the handle's resident data table, T[n * lanes], to `data_out` (any 1-D handle; an integer handle hands back the
+ * values of its slope records).  For a handle made by ndi_interp1d_create it is the caller's data; for a derivative
+ * handle it is Y below. */
+ndi_status ndi_interp1d_data(const ndi_interp1d* h, void* data_out, int32_t memspace);
+
+/* The nu-th derivative of a piecewise cubic interpolant as a NEW HANDLE (scipy: CubicSpline.derivative(nu), cs(x, nu)).
+ * The evaluation computes (1-t) y_l + t y_r + t (1-t) (a (1-t) + b t) for any tables {y, a, b}; the derivative of a
+ * piecewise cubic is a piecewise quadratic, and a quadratic is exactly of that form with a == b.  So the new handle's
+ * three tables are computed from `h`'s three tables by one device pass, and it takes every evaluation entry point, path,
+ * AUTO rule, the ring, ndi_interp1d_clone, the sharded calls, ndi_interp1d_coefficients and ndi_interp1d_data like any
+ * handle.  It is built on h's device (other devices: ndi_interp1d_clone), `h` is only read and stays usable -- also
+ * concurrently -- and is destroyed independently.  Knots, `extrapolate` and the periodic mode are h's.
+ * Numerical contract -- this project's own.  Source tables y[n][L], a[n-1][L], b[n-1][L], knots x[n]; per interval i and
+ * lane, dx = x[i+1] - x[i], dy = y[i+1] - y[i]; each line one IEEE operation in T, in this order, nothing fused:
+ *     Y[i]   = (dy + a[i]) / dx                 i = 0 .. n-2     the derivative at the left end of interval i
+ *     Y[n-1] = (dy - b[n-2]) / dx               with i = n-2     the derivative at the last knot
+ *     A[i]   = B[i] = (3 * (b[i] - a[i])) / dx
+ * {Y, A, B} are the new handle's data and coefficient tables.  (With q(t) = y_l + t dy + t (1-t) (a + (b-a) t): dq/dt is
+ * dy + a at 0 and dy - b at 1, its second t-derivative is -6 (b-a); a quadratic p is (1-t) p0 + t p1 + t (1-t) c with
+ * c = -p''/2.)  nu = 2 is the rule applied twice: there 3 * (B - A) is exactly 0, so the result is the piecewise-linear
+ * interpolant of Y'[i] = ((Y[i+1] - Y[i]) + A[i]) / dx with zero coefficient tables.
+ * Which orders exist -- a table holds one value per knot, so only a derivative that is continuous at the knots:
+ *     CubicSpline (C2; every boundary kind, periodic, per-lane boundaries)   nu = 1, nu = 2
+ *     Pchip, Akima, CubicHermite (C1)                                        nu = 1
+ *     a derivative handle                          as if asked of its origin with the orders added
+ *     Linear, integer, f16 / bf16 handles          none
+ * Everything else (nu < 1, nu > 2, a null pointer included) is NDI_BAD_ARG with a message that names the source's strategy
+ * and the reason, decided before any device work.
+ * Where continuity holds only to rounding, an interior knot carries the value of the interval to its RIGHT: a query at
+ * that knot returns Y[i] exactly, a query just left of it evaluates the left interval's polynomial, whose end value
+ * (dy - b[i-1]) / dx of interval i-1 differs from Y[i] by rounding for a first derivative, and for a spline's second
+ * derivative by the residual of the Thomas solve at that knot.
+ * Y is always re-derived from y, a, b; a k table the source may have kept is never read, so the bits do not depend on
+ * whether it kept one.  For NDI_CUBIC_HERMITE, Y[i] is therefore the caller's dydx[i] up to the rounding of
+ * ((k dx - dy) + dy) / dx, not its bits.  A derivative handle keeps no k table of its own: the evaluation form that holds
+ * {y, k} in LDS re-forms a / b from k and could not reproduce A == B bit for bit, so AUTO gives such handles the forms
+ * that read a / b (scalar and short-row data: a measured cost).
+ * Not provided: antiderivatives / integrals, second derivatives of the C1 strategies, third derivatives. */
+ndi_status ndi_interp1d_derivative(const ndi_interp1d* h, int32_t nu, ndi_interp1d** out);
 
 /* ---- evaluate ----------------------------------------------------------------
  * Replaces Interp1D::interp_array_into for a flattened query array

@@ -374,6 +374,16 @@ struct Interp1DHalfImpl final : Interp1DBase, HalfEngine<F> {
   ndi_status coefficients(void*, void*, int) override {
     return fail(NDI_BAD_ARG, "coefficients: an f16 / bf16 handle is a Linear interpolator (no spline tables)");
   }
+  ndi_status derivative(int, Interp1DBase**) override {
+    return fail(NDI_BAD_ARG, "derivative: an f16 / bf16 handle is a Linear interpolator: its slope jumps at the knots "
+                "(derivative takes f32 / f64 CubicSpline, Pchip, Akima and CubicHermite handles)");
+  }
+  ndi_status data_table(void* data_out, int memspace) override {
+    DeviceGuard dg(device);
+    NDI_HIP(hipMemcpy(data_out, data.p, n * lanes * sizeof(uint16_t),
+                      memspace == NDI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+    return NDI_OK;
+  }
   ndi_status eval_ring(const void* q, uint64_t nq, const ndi_ring_desc* ring, ndi_ring_consumer consume, void* user,
                        const ndi_eval_opts* opts, ndi_oob_info* info) override {
     return this->run_ring(q, nullptr, nq, ring, consume, user, opts, info);

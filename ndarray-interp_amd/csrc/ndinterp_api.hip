@@ -29,6 +29,7 @@
 #include "host_logic.hpp"
 #include "kernels.hpp"
 #include "hermite_kernels.hpp"
+#include "derivative_kernels.hpp"
 
 #define NDI_API extern "C" __attribute__((visibility("default")))
 
@@ -891,12 +892,27 @@ struct Interp1DBase {
   virtual ndi_status trim() = 0;
   virtual uint64_t scratch_sets() = 0;
   virtual ndi_status clone_to(int dev, Interp1DBase** out) = 0;
+  // ndi_interp1d_derivative: the refusals come before any device work
+  virtual ndi_status derivative(int nu, Interp1DBase** out) = 0;
+  // ndi_interp1d_data: the resident data table T[n * lanes]
+  virtual ndi_status data_table(void* data_out, int memspace) = 0;
 };
+
+static const char* hermite_rule_name(int rule) {
+  switch (rule) {
+    case HR_SPLINE: return "CubicSpline";
+    case HR_PCHIP: return "Pchip";
+    case HR_AKIMA: return "Akima";
+    case HR_GIVEN: return "CubicHermite";
+  }
+  return "?";
+}
 
 template <class T>
 struct Interp1DImpl final : Interp1DBase {
   int strategy = NDI_LINEAR;   // the evaluation class: NDI_CUBIC_SPLINE = "has a / b tables" (Pchip, Akima, CubicHermite too)
   int rule = HR_SPLINE;        // ... and which rule chose the knot derivatives behind those tables (HermiteRule)
+  int deriv = 0;               // derivative order: 0 = the interpolant; 1, 2 = ndi_interp1d_derivative of a handle of `rule`
   int mode = EX_NO;
   uint64_t n = 0;
   DevBuf arena;  // small handles: ONE allocation behind pyr.buf / data / ca / cb / ck (create1d); declared first: freed last
@@ -970,9 +986,32 @@ struct Interp1DImpl final : Interp1DBase {
     return true;
   }
 
+  // Small handles: ONE allocation for the knot pyramid, the data and the cubic tables (a / b / k); called before anything
+  // is reserved.  `with_k`: set a slice aside for the k table where {y, k} can fit LDS (reserve_k decides whether it is used).
+  void adopt_arena(bool cubic, bool with_k) {
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    uint64_t block = 1;
+    while ((uint64_t)64 * block < n) block *= 2;
+    const size_t pyr_b = al((n + (n + block - 1) / block) * sizeof(T));
+    const size_t data_b = al((size_t)n * lanes * sizeof(T));
+    const size_t tab_b = cubic ? al((size_t)(n - 1) * lanes * sizeof(T)) : 0;
+    const size_t k_b = (cubic && with_k && 2 * data_b <= FUSED_LDS_LIMIT) ? data_b : 0;
+    const size_t total = pyr_b + data_b + 2 * tab_b + k_b;
+    if (total > ((size_t)1 << 20)) return;
+    arena.reserve(total);
+    char* p0 = static_cast<char*>(arena.p);
+    pyr.buf.adopt(p0, pyr_b);
+    data.adopt(p0 + pyr_b, data_b);
+    if (tab_b) {
+      ca.adopt(p0 + pyr_b + data_b, tab_b);
+      cb.adopt(p0 + pyr_b + data_b + tab_b, tab_b);
+    }
+    if (k_b) ck.adopt(p0 + pyr_b + data_b + 2 * tab_b, k_b);
+  }
+
   uint64_t signature() const override {
     uint64_t h = fnv1a(FNV_SEED, pyr.host_knots.data(), pyr.host_knots.size() * sizeof(T));
-    const uint64_t f[3] = {n, (uint64_t)strategy | ((uint64_t)rule << 8), (uint64_t)mode};
+    const uint64_t f[3] = {n, (uint64_t)strategy | ((uint64_t)rule << 8) | ((uint64_t)deriv << 16), (uint64_t)mode};
     return fnv1a(h, f, sizeof(f));
   }
 
@@ -2385,7 +2424,7 @@ struct Interp1DImpl final : Interp1DBase {
   ndi_status clone_to(int dev, Interp1DBase** out) override {
     std::unique_ptr<Interp1DImpl<T>> h(new Interp1DImpl<T>());
     h->dtype = dtype; h->device = dev; h->lanes = lanes;
-    h->strategy = strategy; h->rule = rule; h->mode = mode; h->n = n;
+    h->strategy = strategy; h->rule = rule; h->deriv = deriv; h->mode = mode; h->n = n;
     {
       DeviceGuard dg(device);
       NDI_HIP(hipDeviceSynchronize());     // the source tables are complete
@@ -2412,6 +2451,68 @@ struct Interp1DImpl final : Interp1DBase {
     const hipMemcpyKind k = memspace == NDI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (a_out) NDI_HIP(hipMemcpy(a_out, ca.p, tab, k));
     if (b_out) NDI_HIP(hipMemcpy(b_out, cb.p, tab, k));
+    return NDI_OK;
+  }
+
+  ndi_status data_table(void* data_out, int memspace) override {
+    DeviceGuard dg(device);
+    NDI_HIP(hipMemcpy(data_out, data.p, (size_t)n * lanes * sizeof(T),
+                      memspace == NDI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+    return NDI_OK;
+  }
+
+  // ---- derivative handles (derivative_kernels.hpp) -----------------------------------------------------------
+  // One application of the rule: a new handle on this handle's device whose {data, a, b} are derived from this handle's
+  // {data, a, b} by one launch (no host plan, no temporaries; NULL stream like the other builds, complete on return).
+  // This handle is only read.  The new handle keeps no k table: the {y, k} LDS form re-forms a / b from k and must
+  // reproduce the table bits, which A == B == c cannot promise.
+  std::unique_ptr<Interp1DImpl<T>> derive_once() const {
+    std::unique_ptr<Interp1DImpl<T>> h(new Interp1DImpl<T>());
+    h->dtype = dtype; h->device = device; h->lanes = lanes;
+    h->strategy = strategy; h->rule = rule; h->deriv = deriv + 1; h->mode = mode; h->n = n;
+    h->adopt_arena(true, false);
+    h->pyr.upload(pyr.host_knots.data(), n);
+    const size_t tab = (size_t)(n - 1) * lanes * sizeof(T);
+    h->data.reserve((size_t)n * lanes * sizeof(T));
+    h->ca.reserve(tab);
+    h->cb.reserve(tab);
+    DerivArgs<T> D{};
+    D.y = data.as<T>(); D.a = ca.as<T>(); D.b = cb.as<T>();
+    D.x = pyr.view.lv0;
+    D.Y = h->data.template as<T>(); D.A = h->ca.template as<T>(); D.B = h->cb.template as<T>();
+    D.n = n; D.lanes = lanes;
+    constexpr int VN = Wide<T>::N;
+    auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool vec = lanes % VN == 0 && aligned(D.y) && aligned(D.a) && aligned(D.b) && aligned(D.Y) && aligned(D.A) &&
+                     aligned(D.B);
+    const uint64_t total = (n - 1) * (vec ? lanes / VN : lanes);
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + BLOCK - 1) / BLOCK, 1u << 20));
+    if (vec) hipLaunchKernelGGL((derivative_build_kernel<T, VN>), dim3(grid), dim3(BLOCK), 0, (hipStream_t) nullptr, D);
+    else hipLaunchKernelGGL((derivative_build_kernel<T, 1>), dim3(grid), dim3(BLOCK), 0, (hipStream_t) nullptr, D);
+    NDI_HIP(hipGetLastError());
+    NDI_HIP(hipStreamSynchronize(nullptr));   // the tables are complete on return: any stream may read them
+    return h;
+  }
+
+  ndi_status derivative(int nu, Interp1DBase** out) override {
+    if (strategy != NDI_CUBIC_SPLINE)
+      return fail(NDI_BAD_ARG, "Linear has no derivative handle: its slope jumps at the knots, and a handle's tables hold one "
+                  "value per knot (derivative takes CubicSpline, Pchip, Akima and CubicHermite handles)");
+    const int total = deriv + nu;
+    const char* name = hermite_rule_name(rule);
+    if (rule != HR_SPLINE && total >= 2)
+      return fail(NDI_BAD_ARG, "%s: the second derivative of a C1 interpolant jumps at the knots, and a handle's tables hold "
+                  "one value per knot (order 1 only; asked for order %d of %s)", name, nu,
+                  deriv ? "its first derivative" : "the interpolant");
+    if (total >= 3)
+      return fail(NDI_BAD_ARG, "%s: the third derivative of a cubic spline jumps at the knots, and a handle's tables hold one "
+                  "value per knot (orders 1 and 2 only; asked for order %d of %s)", name, nu,
+                  deriv == 2 ? "its second derivative" : "its first derivative");
+    DeviceGuard dg(device);
+    Range rg("ndi:derivative_build");
+    std::unique_ptr<Interp1DImpl<T>> h = derive_once();
+    if (nu == 2) h = h->derive_once();   // the rule applied twice; the intermediate tables are freed here
+    *out = h.release();
     return NDI_OK;
   }
 };
@@ -2463,28 +2564,7 @@ static ndi_status create1d(const ndi_interp1d_desc& d, Interp1DBase** out, const
   if (d.n > MAX_KNOTS) return fail(NDI_UNSUPPORTED, "more than %llu knots", (unsigned long long)MAX_KNOTS);
   if (!d.data) return fail(NDI_BAD_ARG, "null data pointer");
   clk.mark("validate");
-  {   // small handles: one allocation for the knot pyramid, the data and the spline's tables (a / b / k)
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    uint64_t block = 1;
-    while ((uint64_t)64 * block < d.n) block *= 2;
-    const size_t pyr_b = al((d.n + (d.n + block - 1) / block) * sizeof(T));
-    const size_t data_b = al((size_t)d.n * d.lanes * sizeof(T));
-    const size_t tab_b = cubic ? al((size_t)(d.n - 1) * d.lanes * sizeof(T)) : 0;
-    const size_t k_b = (cubic && 2 * data_b <= FUSED_LDS_LIMIT) ? data_b : 0;
-    const size_t total = pyr_b + data_b + 2 * tab_b + k_b;
-    constexpr int arena_env = 1;
-    if (arena_env && total <= ((size_t)1 << 20)) {
-      h->arena.reserve(total);
-      char* p0 = static_cast<char*>(h->arena.p);
-      h->pyr.buf.adopt(p0, pyr_b);
-      h->data.adopt(p0 + pyr_b, data_b);
-      if (tab_b) {
-        h->ca.adopt(p0 + pyr_b + data_b, tab_b);
-        h->cb.adopt(p0 + pyr_b + data_b + tab_b, tab_b);
-      }
-      if (k_b) h->ck.adopt(p0 + pyr_b + data_b + 2 * tab_b, k_b);
-    }
-  }
+  h->adopt_arena(cubic, cubic);
   h->pyr.upload(x.data(), d.n);
   clk.mark("knot pyramid");
   const size_t bytes = (size_t)d.n * d.lanes * sizeof(T);
@@ -4549,6 +4629,33 @@ NDI_API ndi_status ndi_interp2d_clone(const ndi_interp2d* h, int32_t device, ndi
   if (st != NDI_OK) return st;
   *out = new ndi_interp2d{impl};
   return NDI_OK;
+  NDI_CATCH
+}
+
+// Every refusal is decided before any device work: the argument checks here, the handle's own in Interp1D*Impl::derivative.
+NDI_API ndi_status ndi_interp1d_derivative(const ndi_interp1d* h, int32_t nu, ndi_interp1d** out) {
+  if (!out) return ndi::fail(NDI_BAD_ARG, "null out pointer");
+  *out = nullptr;
+  if (nu < 1) return ndi::fail(NDI_BAD_ARG, "nu = %d: the derivative order must be 1 or 2", (int)nu);
+  if (nu > 2)
+    return ndi::fail(NDI_BAD_ARG, "nu = %d: the third and higher derivatives of a piecewise cubic jump at the knots, and a "
+                     "handle's tables hold one value per knot (orders 1 and 2 only)", (int)nu);
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  NDI_TRY
+  ndi::Interp1DBase* impl = nullptr;
+  ndi_status st = h->impl->derivative(nu, &impl);
+  if (st != NDI_OK) return st;
+  *out = new ndi_interp1d{impl};
+  return NDI_OK;
+  NDI_CATCH
+}
+
+NDI_API ndi_status ndi_interp1d_data(const ndi_interp1d* h, void* data_out, int32_t memspace) {
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  if (!data_out) return ndi::fail(NDI_BAD_ARG, "null data_out pointer");
+  if (memspace != NDI_MEM_HOST && memspace != NDI_MEM_DEVICE) return ndi::fail(NDI_BAD_ARG, "unknown memspace");
+  NDI_TRY
+  return h->impl->data_table(data_out, memspace);
   NDI_CATCH
 }
 

@@ -1,6 +1,7 @@
 """Host-side mirror of the reference's 1-D surface (src/interp1d/mod.rs + strategies/):
 `Interp1DBuilder`, `Interp1D`, the strategy trait pair and the built-in `Linear` and `CubicSpline` -- plus
-`Pchip`, `Akima` and `CubicHermite`, which the reference leaves to user strategies and this build runs on the device.
+`Pchip`, `Akima` and `CubicHermite`, which the reference leaves to user strategies and this build runs on the device,
+and `Interp1D.derivative(nu)` (scipy's name and meaning) for the four cubics.
 
 Names, argument meaning and error behaviour follow the reference so that the parity tests read like
 its own tests.  The built-in strategies override the *batched* hook (`interp_array_into`) and call the
@@ -107,7 +108,7 @@ class _DeviceStrategy1D(Interp1DStrategy):
         del keep
         if st != _capi.OK:
             raise_builder(st)
-        self._h, self._device, self._np_dtype, self._lanes = h, device, xb_dt, lanes
+        self._h, self._device, self._np_dtype, self._lanes, self._n = h, device, xb_dt, lanes, n
         return self
 
     def release(self):
@@ -131,6 +132,39 @@ class _DeviceStrategy1D(Interp1DStrategy):
         other = copy.copy(self)
         other._h, other._device, other._inflight = h, int(device), []
         return other
+
+    def data_table(self, device: bool = False):
+        """The handle's resident data table `(n, lanes)` (ndi_interp1d_data): a numpy array, or with `device=True` a
+        tensor on the handle's device.  For a derivative handle this is the derivative at the knots."""
+        shape = (self._n, self._lanes)
+        if device or is_bf16(self._np_dtype):
+            import torch
+            out = torch.empty(shape, dtype=torch_dtype(self._np_dtype), device=f"cuda:{self._device}")
+            st = _capi.lib().ndi_interp1d_data(self._h, out.data_ptr(), _capi.MEM_DEVICE)
+        else:
+            out = np.empty(shape, dtype=self._np_dtype)
+            st = _capi.lib().ndi_interp1d_data(self._h, out.ctypes.data, _capi.MEM_HOST)
+        if st != _capi.OK:
+            raise_builder(st)
+        return out
+
+    def derivative(self, nu: int = 1) -> "DerivativeStrategy":
+        """The `nu`-th derivative as a finished strategy of its own (ndi_interp1d_derivative): a new handle on this
+        handle's device whose tables are derived from this handle's on the device.  This strategy stays usable.
+        Orders the library refuses (include/ndinterp.h lists them) raise `ValueError` with its message."""
+        import operator
+        nu = operator.index(nu)
+        h = C.c_void_p()
+        st = _capi.lib().ndi_interp1d_derivative(self._h, nu, C.byref(h))
+        if st == _capi.BAD_ARG:
+            raise ValueError(_capi.last_error())
+        if st != _capi.OK:
+            raise_builder(st)
+        d = DerivativeStrategy()
+        d._h, d._device, d._np_dtype, d._lanes, d._n = h, self._device, self._np_dtype, self._lanes, self._n
+        d.order = getattr(self, "order", 0) + nu
+        d.origin = getattr(self, "origin", type(self))
+        return d
 
     # -- evaluate -----------------------------------------------------------------------------
     _takes_fresh = True   # interp_array() may tell this strategy that the output buffer is its own (ndi_eval_flags)
@@ -506,6 +540,16 @@ class CubicHermiteStrategy(CubicSplineStrategy):
     _kind = _capi.CUBIC_HERMITE
 
 
+class DerivativeStrategy(CubicSplineStrategy):
+    """A derivative of a CubicSpline / Pchip / Akima / CubicHermite strategy (`strategy.derivative(nu)`,
+    `Interp1D.derivative(nu)`): a handle of the cubic evaluation class whose tables were derived on the device.
+    `order`: the derivative order counted from the interpolant (1 or 2); `origin`: the class of the strategy it started
+    from; `coefficients()`: its a / b tables (equal to each other; zero for order 2)."""
+
+    order = 0
+    origin = None
+
+
 class _LocalCubic(Interp1DStrategyBuilder):
     """Shared builder body of Pchip / Akima / CubicHermite: `.extrapolate(b)` and `.device(d)` as `CubicSpline` has
     them (`extrapolate(True)` continues the first / last interval's polynomial); f32 / f64 only."""
@@ -752,6 +796,20 @@ class Interp1D:
         if not hasattr(self.strategy, "clone"):
             raise TypeError("replicate needs a built-in device strategy (f32 / f64 data)")
         return [Interp1D(self.x, self.data, self.strategy.clone(d)) for d in devices]
+
+    def derivative(self, nu: int = 1) -> "Interp1D":
+        """The `nu`-th derivative of this interpolator as an interpolator of its own (scipy's
+        `CubicSpline.derivative(nu)`): same `x`, `data` = the derivative at the knots in this data's shape (a host array
+        for host-built interpolators, a tensor on the strategy's device for device-built ones), strategy a
+        `DerivativeStrategy`.  CubicSpline: `nu` 1 or 2; Pchip / Akima / CubicHermite: 1; orders add up over repeated
+        calls.  Everything else is a `ValueError` with the library's reason; strategies that are not the built-in device
+        ones (user strategies, the generic host path) raise `TypeError`."""
+        if not isinstance(self.strategy, _DeviceStrategy1D):
+            raise TypeError("derivative needs a built-in device strategy (CubicSpline, Pchip, Akima or CubicHermite on "
+                            f"f32 / f64 data), got {type(self.strategy).__name__}")
+        strat = self.strategy.derivative(nu)
+        on_device = is_torch(self.data) and self.data.is_cuda
+        return Interp1D(self.x, strat.data_table(device=on_device).reshape(tuple(self.data.shape)), strat)
 
     def interp_array_ring(self, xs, chunk_queries, consumer=None, *, slots=None, n_slots=2):
         """`interp_array` (interp1d/mod.rs:197-211) for outputs larger than device memory: the flattened

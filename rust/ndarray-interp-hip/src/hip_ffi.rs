@@ -235,6 +235,10 @@ extern "C" {
         b_out: *mut c_void,
         memspace: i32,
     ) -> i32;
+    /// The handle's resident data table `T[n * lanes]` (for a derivative handle: the derivative at the knots)
+    pub fn ndi_interp1d_data(h: *const ndi_interp1d, data_out: *mut c_void, memspace: i32) -> i32;
+    /// The `nu`-th derivative (1, or 2 for CubicSpline) as a new handle; the header states the numerical contract
+    pub fn ndi_interp1d_derivative(h: *const ndi_interp1d, nu: i32, out: *mut *mut ndi_interp1d) -> i32;
     pub fn ndi_interp1d_eval(
         h: *const ndi_interp1d,
         q: *const c_void,
