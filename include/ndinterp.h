@@ -86,7 +86,10 @@ typedef enum ndi_memspace { NDI_MEM_HOST = 0, NDI_MEM_DEVICE = 1 } ndi_memspace;
  * exist, so these strategies only choose k differently; their handles take every evaluation entry point, path and AUTO
  * rule of a CubicSpline handle of the same shape.  `extrapolate` != 0 continues the first / last interval's polynomial.
  * Numerical contract -- this project's own, there is no Rust to follow: per lane, every line one IEEE operation in T in
- * this order, nothing fused; delta_i = dy / h_i; sgn(v) is -1, 0 or 1; +0 is positive zero.
+ * this order, nothing fused; delta_i = dy / h_i; sgn(v) = (v > 0) - (v < 0) is -1, 0 or 1, so sgn(NaN) = 0; +0 is
+ * positive zero.  Non-finite data is not refused: it goes through these lines as IEEE values, and a comparison with a NaN
+ * is false.  For Pchip's ends that means: a NaN slope (m0, m1 or d NaN) makes that end's k NaN, unless sgn(d) != sgn(m0)
+ * has already decided for +0 (d NaN beside a non-zero m0).  tests/test_hostile_inputs.py has the table.
  *  NDI_PCHIP (>= 2 knots; what scipy's PchipInterpolator computes).  n == 2: k_0 = k_1 = delta_0.  Interior knots:
  *      if delta_{i-1} == 0 or delta_i == 0 or (delta_{i-1} > 0) != (delta_i > 0):  k_i = +0
  *      else  w1 = (h_i + h_i) + h_{i-1};  w2 = h_i + (h_{i-1} + h_{i-1});  k_i = (w1 + w2) / (w1 / delta_{i-1} + w2 / delta_i)

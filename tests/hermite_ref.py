@@ -11,6 +11,12 @@ def _col(x):
     return (x[1:] - x[:-1])[:, None]
 
 
+def sgn(v):
+    """The header's sgn: -1, 0 or 1, formed from the two comparisons (v > 0) - (v < 0) -- so sgn(NaN) = 0 and
+    sgn(-0) = sgn(+0) = 0.  (np.sign gives NaN for NaN, and NaN != NaN would read as a sign change.)"""
+    return (v > 0).astype(np.int8) - (v < 0).astype(np.int8)
+
+
 def pchip_k(x, y):
     """Fritsch-Butland derivatives with the three-point shape-preserving end formula (scipy's PchipInterpolator)."""
     T = y.dtype.type
@@ -33,8 +39,8 @@ def pchip_k(x, y):
 
     def edge(h0, h1, m0, m1):
         d = (((h0 + h0) + h1) * m0 - h0 * m1) / (h0 + h1)
-        opp = np.sign(d) != np.sign(m0)
-        big = (np.sign(m0) != np.sign(m1)) & (np.abs(d) > T(3) * np.abs(m0))
+        opp = sgn(d) != sgn(m0)
+        big = (sgn(m0) != sgn(m1)) & (np.abs(d) > T(3) * np.abs(m0))
         return np.where(opp, T(0), np.where(big, T(3) * m0, d))
     k[0] = edge(h[0], h[1], dl[0], dl[1])
     k[-1] = edge(h[-1], h[-2], dl[-1], dl[-2])

@@ -1,0 +1,437 @@
+"""Hostile inputs for the Pchip / Akima / CubicHermite build and the derivative build, and a bit-level comparer.
+
+The rules (include/ndinterp.h, ndi_strategy1d / ndi_interp1d_derivative) have data-dependent branches and rest on plain
+IEEE arithmetic: correctly rounded division, nothing fused, f32 subnormals kept.  The generators here plant every branch
+the header names, zeros of both signs, subnormal / overflowing scales and non-finite values at chosen knots, each in a
+lane of its own, so one (n, L) array carries many cases; lanes beyond the planted ones get seeded draws from the same
+recipes.  `cases()` cuts the recipe list into as many arrays as L needs, so every lane mapping sees every recipe.
+
+`classify()` is the generators' self-check: it evaluates the header's conditions knot by knot (its own code, not
+hermite_ref.pchip_k / akima_k) and counts how often each branch and data class occurs.
+"""
+import collections
+
+import numpy as np
+
+import derivative_ref
+import hermite_ref
+
+RULES = ("pchip", "akima", "hermite")
+CLASSES = ("branch", "zero", "scale", "nonfinite")
+KNOT_KINDS = ("even", "uneven", "adjacent", "huge", "mixed")
+
+
+# ---- the comparer -------------------------------------------------------------------------------------------------------
+def _bits(a):
+    return a.view({2: np.uint16, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+def check_bits(got, ref, what):
+    """Same dtype, same shape; every non-NaN element equal as its bit pattern (-0.0 != +0.0); NaN at the same positions
+    (payload and sign of a NaN are not compared)."""
+    got = np.ascontiguousarray(got); ref = np.ascontiguousarray(ref)
+    assert got.dtype == ref.dtype and got.dtype.kind == "f", f"{what}: dtype {got.dtype} against {ref.dtype}"
+    assert got.shape == ref.shape, f"{what}: shape {got.shape} against {ref.shape}"
+    gn, rn = np.isnan(got), np.isnan(ref)
+    gb, rb = _bits(got), _bits(ref)
+    nanpos = gn != rn
+    bad = nanpos | (~gn & ~rn & (gb != rb))
+    if not bad.any():
+        return
+    zero = bad & ~nanpos & (got == 0) & (ref == 0)
+    value = bad & ~nanpos & ~zero
+    i = tuple(int(v) for v in np.argwhere(bad)[0])
+    w = 2 * got.dtype.itemsize
+    raise AssertionError(
+        f"{what}: {int(bad.sum())} of {bad.size} elements differ (zero sign only: {int(zero.sum())}, NaN position: "
+        f"{int(nanpos.sum())}, value: {int(value.sum())}); first at {i}: got {got[i]!r} = 0x{int(gb[i]):0{w}x}, "
+        f"ref {ref[i]!r} = 0x{int(rb[i]):0{w}x}")
+
+
+# ---- knots --------------------------------------------------------------------------------------------------------------
+def big_step(dtype):
+    return np.dtype(dtype).type(1e30 if np.dtype(dtype) == np.float32 else 1e300)
+
+
+def knots(kind, dtype, n, seed=0):
+    """even: 0, 1, 2 ... (slopes of integer data are exact); uneven: the well-conditioned axis of the other tests;
+    adjacent: neighbouring floats from 1.0 up; huge: steps of 1e30 (f32) / 1e300 (f64) around 0; mixed: both spacings."""
+    T = np.dtype(dtype).type
+    if kind == "even":
+        return np.arange(n).astype(dtype)
+    if kind == "uneven":
+        return np.cumsum(np.random.default_rng(1234 + seed).uniform(0.1, 2.0, n)).astype(dtype)
+    if kind == "huge":
+        return ((np.arange(n) - n // 2).astype(dtype) * big_step(dtype)).astype(dtype)
+    x = np.empty(n, dtype)
+    x[0] = 1.0
+    near = n if kind == "adjacent" else (n + 1) // 2
+    for i in range(1, n):
+        x[i] = np.nextafter(x[i - 1], T(np.inf)) if i < near else x[i - 1] + big_step(dtype)
+    assert kind in ("adjacent", "mixed") and np.all(x[1:] > x[:-1])
+    return x
+
+
+def has_adjacent(x):
+    return bool(np.any(np.nextafter(x[:-1], x.dtype.type(np.inf)) == x[1:]))
+
+
+# ---- lane recipes: f(n, T, rng) -> y column, or (y, dydx) columns -------------------------------------------------------------
+def _bg(n, rng):
+    """background slopes on the unit grid: small integers, zero included"""
+    return rng.integers(-3, 4, n - 1).astype(np.float64)
+
+
+def _col(sl, T, y0=1.0):
+    return np.concatenate([[y0], y0 + np.cumsum(sl)]).astype(T)
+
+
+def _slopes(plant):
+    """a recipe from {slope index (negative: from the end): value}; planted where the index exists, the rest background"""
+    def f(n, T, rng):
+        sl = _bg(n, rng)
+        if all(-(n - 1) <= j < n - 1 for j in plant):
+            # an index may be named from both ends at small n: the later entry wins, as in a dict
+            for j, v in plant.items():
+                sl[j] = v
+        return _col(sl, T)
+    return f
+
+
+def _mid(pattern):
+    """slopes `pattern` centred so that pattern[len // 2 - 1], pattern[len // 2] are delta_{p-1}, delta_p, p = n // 2"""
+    def f(n, T, rng):
+        sl = _bg(n, rng)
+        p = n // 2
+        lo = p - len(pattern) // 2
+        if lo >= 0 and lo + len(pattern) <= n - 1:
+            sl[lo:lo + len(pattern)] = pattern
+        return _col(sl, T)
+    return f
+
+
+def _random_lane(n, T, rng):
+    return rng.normal(size=n).astype(T)
+
+
+def _rounded_lane(n, T, rng):
+    return np.round(rng.normal(size=n)).astype(T)
+
+
+def branch_recipes(rule):
+    r = [("random", _random_lane), ("rounded", _rounded_lane)]
+    if rule == "pchip":
+        r += [("int d0=0", _mid([0, 2])), ("int d1=0", _mid([2, 0])), ("int both 0", _mid([0, 0])),
+              ("int + -", _mid([2, -1])), ("int - +", _mid([-1, 2])), ("int hm ++", _mid([1, 3])), ("int hm --", _mid([-1, -3])),
+              # ends on the unit grid: d = (3 m0 - m1) / 2
+              ("left opp", _slopes({0: 1, 1: 5})), ("left clamp", _slopes({0: 1, 1: -5})), ("left pass", _slopes({0: 2, 1: 1})),
+              ("left m0=0", _slopes({0: 0, 1: 3})),
+              ("right opp", _slopes({-1: 1, -2: 5})), ("right clamp", _slopes({-1: 1, -2: -5})), ("right pass", _slopes({-1: 2, -2: 1})),
+              ("right m0=0", _slopes({-1: 0, -2: -3}))]
+    elif rule == "akima":
+        r += [("ramp", lambda n, T, rng: (3.0 * np.arange(n) - 7.0).astype(T)),
+              ("flat", lambda n, T, rng: np.full(n, 2.5, T)),
+              ("ramp left", _slopes({0: 2, 1: 2, 2: 2})), ("ramp right", _slopes({-1: -2, -2: -2, -3: -2})),
+              ("ramp mid", _mid([1, 1, 1, 1, 1, 1])), ("flat mid", _mid([0, 0, 0, 0])),
+              ("w1=0 low", _slopes({0: 1, 1: 3, 2: 3})), ("w2=0 high", _slopes({-3: 3, -2: 3, -1: 1})),
+              ("w1=0 mid", _mid([1, 3, 2, 2])), ("w2=0 mid", _mid([2, 2, 3, 1]))]
+    return r
+
+
+def zero_recipes(rule):
+    def runs(n, T, rng):
+        return np.where((np.arange(n) // 3) % 2 == 0, T(-0.0), T(0.0)).astype(T)
+
+    def alternating(n, T, rng):
+        return np.where(np.arange(n) % 2 == 0, T(0.0), T(-0.0)).astype(T)
+
+    def plateau(sign, level):
+        def f(n, T, rng):     # level, level, then a plateau of signed zeros, then back: falling and rising steps onto 0
+            y = np.full(n, level, T)
+            y[n // 3:max(n // 3 + 1, 2 * n // 3)] = T(sign * 0.0)
+            return y
+        return f
+    r = [("all -0", lambda n, T, rng: np.full(n, -0.0, T)), ("runs of -0 / +0", runs), ("alternating 0", alternating),
+         ("plateau -0 below 1", plateau(-1.0, 1.0)), ("plateau +0 above -1", plateau(1.0, -1.0)), ("plateau -0 above -1", plateau(-1.0, -1.0))]
+    if rule == "hermite":
+        z = [(name, (lambda f: lambda n, T, rng: (f(n, T, rng), np.full(n, -0.0, T)))(f)) for name, f in r[:3]]
+        r = z + [("dydx +0", lambda n, T, rng: (_rounded_lane(n, T, rng), np.zeros(n, T))),
+                 ("dydx -0", lambda n, T, rng: (_rounded_lane(n, T, rng), np.full(n, -0.0, T))),
+                 ("dydx alternating 0", lambda n, T, rng: (runs(n, T, rng), alternating(n, T, rng)))] + r[3:]
+    return r
+
+
+def scale_recipes(rule):
+    def sub_values(n, T, rng):      # the values themselves subnormal: every difference is (the flush-to-zero detector)
+        return (rng.integers(-4, 5, n).astype(T) * np.finfo(T).smallest_subnormal).astype(T)
+
+    def sub_diffs(n, T, rng):       # normal values one or a few ulps apart at the bottom of the normal range
+        return (np.finfo(T).tiny * (T(1) + rng.integers(0, 9, n).astype(T) * np.finfo(T).eps)).astype(T)
+
+    def half_max(n, T, rng):        # opposite signs near max / 2 .. max: dy overflows
+        s = np.where(np.arange(n) % 2 == 0, 1.0, -1.0) * (1.0 if rng.integers(0, 2) else -1.0)
+        return (s * rng.uniform(0.55, 0.95, n) * float(np.finfo(T).max)).astype(T)
+
+    def tenth_max(n, T, rng):       # dy, a, b finite; 3 (b - a) of the derivative rule not
+        return (rng.choice([-1.0, 1.0], n) * rng.uniform(0.05, 0.12, n) * float(np.finfo(T).max)).astype(T)
+
+    def zigzag(n, T, rng):          # +-0.2 max: every interior Pchip k is +0, b - a = 2 dy = 0.8 max, 3 (b - a) overflows
+        return (np.where(np.arange(n) % 2 == 0, 0.2, -0.2) * float(np.finfo(T).max)).astype(T)
+
+    def w1_over_sub(n, T, rng):     # delta_{p-1} subnormal beside delta_p = 1: w1 / delta_{p-1} = inf, k_p = (w1 + w2) / inf = 0
+        y = _col(np.abs(_bg(n, rng)) + 1.0, T, 0.0)
+        p = n // 2
+        if p >= 1 and p + 1 < n:
+            y[:p] = 0; y[p] = np.finfo(T).smallest_subnormal; y[p + 1:] = y[p + 1:] - y[p + 1] + T(1)
+        return y
+
+    def w2_over_sub(n, T, rng):
+        return (-w1_over_sub(n, T, rng)[::-1]).astype(T)
+
+    def exponents(n, T, rng):       # the whole exponent range in one lane
+        lim = 37 if T == np.float32 else 300
+        with np.errstate(over="ignore"):
+            return (rng.uniform(-1, 1, n) * 10.0 ** rng.uniform(-lim - 8, lim, n)).astype(T)
+    r = [("subnormal values", sub_values), ("subnormal differences", sub_diffs), ("dy overflows", half_max),
+         ("3 (b - a) overflows", tenth_max), ("zigzag 0.2 max", zigzag), ("w1 / delta = inf", w1_over_sub), ("w2 / delta = inf", w2_over_sub),
+         ("all exponents", exponents)]
+    if rule == "hermite":
+        def steep(n, T, rng):       # flat data, k = -0.2 max: a = -0.2 max h, b = 0.2 max h, 3 (b - a) overflows on the unit grid
+            return np.zeros(n, T), np.full(n, -0.2 * float(np.finfo(T).max), T)
+        r = [(name, (lambda f: lambda n, T, rng: (f(n, T, rng), exponents(n, T, rng)))(f)) for name, f in r]
+
+        def all_sub(n, T, rng):     # subnormal data and derivatives: subnormal tables (a_0 = 5 - 1 = 4 units on the unit grid)
+            u = np.finfo(T).smallest_subnormal
+            return (np.cumsum(np.arange(n)).astype(T) * u).astype(T), np.full(n, T(5) * u, T)
+        r += [("dydx -0.2 max", steep), ("dydx subnormal", lambda n, T, rng: (_random_lane(n, T, rng), sub_values(n, T, rng))),
+              ("y and dydx subnormal", all_sub)]
+    return r
+
+
+def nonfinite_rows(n):
+    return sorted({r for r in (0, 1, 2, n // 2, n - 3, n - 2, n - 1) if 0 <= r < n})
+
+
+def nonfinite_recipes(rule, n):
+    def one(row, v, into_k):
+        def f(n, T, rng):
+            y, k = _random_lane(n, T, rng), _random_lane(n, T, rng)
+            (k if into_k else y)[row] = v
+            return (y, k) if rule == "hermite" else y
+        return f
+
+    def pair(v0, v1, into_k):
+        def f(n, T, rng):
+            y, k = _random_lane(n, T, rng), _random_lane(n, T, rng)
+            p = min(n // 2, n - 2)
+            (k if into_k else y)[p:p + 2] = [v0, v1]
+            return (y, k) if rule == "hermite" else y
+        return f
+    def flat_end(right):
+        def f(n, T, rng):      # a finite flat end interval beside a NaN row: m0 = 0, m1 = NaN, where sgn(NaN) = 0 shows in a / b
+            y, k = _random_lane(n, T, rng), _random_lane(n, T, rng)
+            if n >= 3:
+                y[:3] = [y[0], y[0], np.nan]
+                if right:
+                    y = y[::-1].copy()
+            return (y, k) if rule == "hermite" else y
+        return f
+    r = [("flat left end, then NaN", flat_end(False)), ("NaN, then flat right end", flat_end(True))]
+    for into_k in ((False, True) if rule == "hermite" else (False,)):
+        tag = "dydx" if into_k else "y"
+        for v in (np.nan, np.inf, -np.inf):
+            r += [(f"{tag}[{row}] = {v}", one(row, v, into_k)) for row in nonfinite_rows(n)]
+        r += [(f"{tag} pair {v0} {v1}", pair(v0, v1, into_k)) for v0, v1 in ((np.inf, np.inf), (np.inf, -np.inf), (-np.inf, np.inf),
+                                                                            (-np.inf, -np.inf))]
+    return r
+
+
+def recipes(rule, n, classes=CLASSES):
+    r = []
+    for c in classes:
+        r += {"branch": lambda: branch_recipes(rule), "zero": lambda: zero_recipes(rule), "scale": lambda: scale_recipes(rule),
+              "nonfinite": lambda: nonfinite_recipes(rule, n)}[c]()
+    return r
+
+
+# ---- the arrays ---------------------------------------------------------------------------------------------------------
+def generate(rule, dtype, n, L, classes=CLASSES, kind="even", part=0, seed=0):
+    """(x, y, dydx): x of `kind`, y (n, L), dydx (n, L) for rule "hermite" else None.  Lane l carries recipe part * L + l of
+    recipes(rule, n, classes); lanes past the end of the list carry seeded random draws from it."""
+    T = np.dtype(dtype).type
+    rec = recipes(rule, n, classes)
+    rng = np.random.default_rng([seed, n, L, part, KNOT_KINDS.index(kind), RULES.index(rule)])
+    y = np.empty((n, L), dtype)
+    k = np.empty((n, L), dtype)
+    for l in range(L):
+        j = part * L + l
+        f = rec[j][1] if j < len(rec) else rec[int(rng.integers(0, len(rec)))][1]
+        col = f(n, T, rng)
+        if isinstance(col, tuple):
+            y[:, l], k[:, l] = col
+        else:
+            y[:, l] = col
+            k[:, l] = rng.normal(size=n)
+    return knots(kind, dtype, n, seed), y, (k if rule == "hermite" else None)
+
+
+def parts(rule, n, L, classes=CLASSES):
+    return -(-len(recipes(rule, n, classes)) // L)
+
+
+def cases(rule, dtype, n, L, classes=CLASSES, kinds=KNOT_KINDS):
+    """Every array a test of this (rule, dtype, n, L) runs: (tag, x, y, dydx).  Every recipe on the even and the uneven axis;
+    the scale recipes once more on each of the hostile axes."""
+    for kind in kinds:
+        cl = tuple(classes) if kind in ("even", "uneven") else tuple(c for c in classes if c == "scale")
+        if not cl:
+            continue
+        for part in range(parts(rule, n, L, cl)):
+            x, y, k = generate(rule, dtype, n, L, cl, kind, part)
+            yield f"{rule} {np.dtype(dtype).name} n={n} L={L} knots={kind} part={part}", x, y, k
+
+
+def reference(rule, x, y, dydx=None):
+    """the restatement's (a, b) with numpy's floating-point warnings off: overflow and inf - inf are the point here"""
+    with np.errstate(all="ignore"):
+        return hermite_ref.build(rule, x, y, dydx)
+
+
+def derivative_reference(x, y, a, b, nu=1):
+    with np.errstate(all="ignore"):
+        return derivative_ref.derive_nu(x, np.ascontiguousarray(y).reshape(len(x), -1), a, b, nu)
+
+
+def queries(x, extrapolate=True):
+    """every knot, nextafter of every knot in both directions (not where knots are adjacent floats), the interval midpoints;
+    with extrapolation a point half an end interval outside on each side and +-inf"""
+    T = x.dtype.type
+    q = [x, x[:-1] + (x[1:] - x[:-1]) / T(2)]
+    if not has_adjacent(x):
+        q += [np.nextafter(x[:-1], T(np.inf)), np.nextafter(x[1:], T(-np.inf))]
+    if extrapolate:
+        q += [np.array([x[0] - (x[1] - x[0]) / T(2), x[-1] + (x[-1] - x[-2]) / T(2), np.inf, -np.inf], x.dtype)]
+        if not has_adjacent(x):
+            q += [np.array([np.nextafter(x[0], T(-np.inf)), np.nextafter(x[-1], T(np.inf))], x.dtype)]
+    q = np.concatenate(q).astype(x.dtype)
+    return q[np.isfinite(q) | extrapolate]
+
+
+# ---- the self-check -------------------------------------------------------------------------------------------------------
+def _s(v):
+    return np.where(v > 0, 1, np.where(v < 0, -1, 0))
+
+
+def _n(mask):
+    return int(np.count_nonzero(mask))
+
+
+def expected_branches(rule, n):
+    """the names classify() must count at least once for `n` knots"""
+    if rule == "pchip":
+        names = ["pchip interior: delta_{i-1} == 0 only", "pchip interior: delta_i == 0 only", "pchip interior: both 0",
+                 "pchip interior: + then -", "pchip interior: - then +", "pchip interior: harmonic mean, both +",
+                 "pchip interior: harmonic mean, both -"]
+        for side in ("left", "right"):
+            names += [f"pchip {side} end: sgn(d) != sgn(m0)", f"pchip {side} end: 3 m0", f"pchip {side} end: d",
+                      f"pchip {side} end: m0 == 0, m1 != 0", f"pchip {side} end: m0 == 0, m1 NaN: k NaN"]
+        names += ["scale: w / delta = inf"]
+    elif rule == "akima":
+        names = ["akima s == 0 at i = 0", "akima s == 0 at i = 1", "akima s == 0 at i = n-2", "akima s == 0 at i = n-1", "akima s > 0"]
+        if n >= 5:
+            names += ["akima s == 0 at an interior knot"]
+        if n >= 4:
+            names += ["akima s > 0, w1 == 0 only", "akima s > 0, w2 == 0 only"]
+    else:
+        names = ["dydx: -0", "dydx: +0", "dydx: NaN", "dydx: +inf", "dydx: -inf", "dydx: subnormal"]
+    names += ["zero: -0 in y", "zero: dy == 0 between zeros of different sign", "scale: subnormal dy", "scale: dy overflows",
+              "nonfinite: NaN in y", "nonfinite: +inf in y", "nonfinite: -inf in y", "nonfinite: inf - inf", "tables: -0",
+              "tables: subnormal"]
+    # a and b near max / 3 with b - a finite: CubicHermite takes them from dydx; Pchip's k lies between 0 and 3 delta, so it
+    # needs an interval between two interior knots whose k are both 0; Akima's own products w m overflow long before
+    # (|y| >= sqrt(max)), so its tables are never that large and finite
+    if rule == "hermite" or (rule == "pchip" and n >= 4):
+        names += ["derivative: 3 (b - a) overflows, b - a finite"]
+    return names
+
+
+def classify(rule, x, y, dydx=None):
+    """Counter of branch / data-class name -> occurrences over the knots and lanes of one array (n >= 3)."""
+    c = collections.Counter()
+    n = len(x)
+    y = np.ascontiguousarray(y).reshape(n, -1)
+    T = y.dtype.type
+    tiny = np.finfo(T).tiny
+    with np.errstate(all="ignore"):
+        h = x[1:] - x[:-1]
+        dy = y[1:] - y[:-1]
+        dl = dy / h[:, None]
+        if rule == "pchip":
+            for i in range(1, n - 1):
+                d0, d1 = dl[i - 1], dl[i]
+                z0, z1 = d0 == 0, d1 == 0
+                c["pchip interior: delta_{i-1} == 0 only"] += _n(z0 & ~z1)
+                c["pchip interior: delta_i == 0 only"] += _n(~z0 & z1)
+                c["pchip interior: both 0"] += _n(z0 & z1)
+                c["pchip interior: + then -"] += _n((d0 > 0) & (d1 < 0))
+                c["pchip interior: - then +"] += _n((d0 < 0) & (d1 > 0))
+                c["pchip interior: harmonic mean, both +"] += _n((d0 > 0) & (d1 > 0))
+                c["pchip interior: harmonic mean, both -"] += _n((d0 < 0) & (d1 < 0))
+                w1 = (h[i] + h[i]) + h[i - 1]
+                same = ((d0 > 0) & (d1 > 0)) | ((d0 < 0) & (d1 < 0))
+                w2 = h[i] + (h[i - 1] + h[i - 1])
+                c["scale: w / delta = inf"] += _n(same & np.isfinite(d0) & np.isfinite(d1) & (np.isinf(w1 / d0) | np.isinf(w2 / d1)))
+            for side, h0, h1, m0, m1 in (("left", h[0], h[1], dl[0], dl[1]), ("right", h[-1], h[-2], dl[-1], dl[-2])):
+                d = (((h0 + h0) + h1) * m0 - h0 * m1) / (h0 + h1)
+                opp = _s(d) != _s(m0)
+                clamp = ~opp & (_s(m0) != _s(m1)) & (np.abs(d) > T(3) * np.abs(m0))
+                c[f"pchip {side} end: sgn(d) != sgn(m0)"] += _n(opp)
+                c[f"pchip {side} end: 3 m0"] += _n(clamp)
+                c[f"pchip {side} end: d"] += _n(~opp & ~clamp & ~np.isnan(d))
+                c[f"pchip {side} end: m0 == 0, m1 != 0"] += _n((m0 == 0) & (m1 != 0) & ~np.isnan(m1))
+                c[f"pchip {side} end: m0 == 0, m1 NaN: k NaN"] += _n(~opp & ~clamp & (m0 == 0) & np.isnan(m1))
+        elif rule == "akima":
+            m = {j: dl[j] for j in range(n - 1)}
+            m[-1] = (m[0] + m[0]) - m[1]
+            m[-2] = (m[-1] + m[-1]) - m[0]
+            m[n - 1] = (m[n - 2] + m[n - 2]) - m[n - 3]
+            m[n] = (m[n - 1] + m[n - 1]) - m[n - 2]
+            for i in range(n):
+                w1 = np.abs(m[i + 1] - m[i])
+                w2 = np.abs(m[i - 1] - m[i - 2])
+                s0 = (w1 + w2) == 0
+                for name, at in (("i = 0", i == 0), ("i = 1", i == 1), ("i = n-2", i == n - 2), ("i = n-1", i == n - 1),
+                                 ("an interior knot", 2 <= i <= n - 3)):
+                    if at:
+                        c[f"akima s == 0 at {name}"] += _n(s0)
+                c["akima s > 0"] += _n((w1 + w2) > 0)
+                c["akima s > 0, w1 == 0 only"] += _n((w1 == 0) & (w2 > 0))
+                c["akima s > 0, w2 == 0 only"] += _n((w2 == 0) & (w1 > 0))
+        else:
+            k = np.ascontiguousarray(dydx).reshape(n, -1)
+            c["dydx: -0"] += _n((k == 0) & np.signbit(k))
+            c["dydx: +0"] += _n((k == 0) & ~np.signbit(k))
+            c["dydx: NaN"] += _n(np.isnan(k))
+            c["dydx: +inf"] += _n(k == np.inf)
+            c["dydx: -inf"] += _n(k == -np.inf)
+            c["dydx: subnormal"] += _n((k != 0) & (np.abs(k) < tiny))
+        c["zero: -0 in y"] += _n((y == 0) & np.signbit(y))
+        c["zero: dy == 0 between zeros of different sign"] += _n((dy == 0) & (np.signbit(y[1:]) != np.signbit(y[:-1])))
+        c["scale: subnormal dy"] += _n((dy != 0) & (np.abs(dy) < tiny))
+        c["scale: dy overflows"] += _n(np.isinf(dy) & np.isfinite(y[1:]) & np.isfinite(y[:-1]))
+        c["nonfinite: NaN in y"] += _n(np.isnan(y))
+        c["nonfinite: +inf in y"] += _n(y == np.inf)
+        c["nonfinite: -inf in y"] += _n(y == -np.inf)
+        c["nonfinite: inf - inf"] += _n(np.isinf(y[1:]) & (y[1:] == y[:-1]))
+        a, b = hermite_ref.build(rule, x, y, dydx)
+        c["derivative: 3 (b - a) overflows, b - a finite"] += _n(np.isfinite(b - a) & np.isinf(T(3) * (b - a)))
+        c["tables: -0"] += _n(((a == 0) & np.signbit(a)) | ((b == 0) & np.signbit(b)))
+        c["tables: subnormal"] += _n(((a != 0) & (np.abs(a) < tiny)) | ((b != 0) & (np.abs(b) < tiny)))
+    return c
+
+
+def branch_table(rule, dtype, n, L):
+    total = collections.Counter({name: 0 for name in expected_branches(rule, n)})
+    for _, x, y, k in cases(rule, dtype, n, L):
+        total.update(classify(rule, x, y, k))
+    return total

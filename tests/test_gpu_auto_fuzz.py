@@ -108,6 +108,50 @@ def _one_1d(pkg, capfd, rng, dt, kind, wide=False):
     assert np.array_equal(g[:bad], ref[:bad]) and np.all(g[bad:] == -3.0), f"{what}: rows around the first failure {t.plans}"
 
 
+def _one_local_cubic(pkg, capfd, rng, dt, kind):
+    """_one_1d for the Pchip / Akima / CubicHermite and derivative handles: device-built, large device batches, strided and
+    sliced outputs, the first-error cut; the restatement's tables into the oracle, compared bit for bit (zero signs and NaN
+    positions included)."""
+    import torch
+    from hostile_inputs import check_bits
+    from test_gpu_parity import _fuzz_local_cubic
+    dev = torch.device("cuda:0")
+    n = int(rng.choice([3, 4, 7, 33, 100, 257, 1024, 3000]))
+    L = int(rng.choice([1, 1, 2, 3, 4, 5, 7, 8, 12, 16, 24, 32, 64, 100, 128]))
+    Q = _budget_q(rng, L)
+    x, it, (Y, A, B), ext, what = _fuzz_local_cubic(pkg, rng, dt, n, L, kind, device=dev)
+    what = f"{what} Q={Q}"
+    span = float(x[-1] - x[0])
+    m = 0.4 if ext else 0.0
+    q = rng.uniform(x[0] - m * span, x[-1] + m * span, Q).astype(dt)
+    if not ext:
+        q = np.clip(q, x[0], x[-1])
+    q[:min(n, Q)] = x[:min(n, Q)]
+    ref = oracle.interp1d_cubic(x, Y, A, B, q, oracle.EXTRAPOLATE_YES if ext else oracle.EXTRAPOLATE_NO)[2].reshape(Q, L)
+    qd = torch.as_tensor(q, device=dev)
+    with traced(capfd) as t:
+        got = it.interp_array(qd)
+        wide = torch.full((Q + 1, L + 3), -7.0, dtype=_tdt(dt), device=dev)
+        it.strategy.interp_array_into(it, qd, wide[1:, :L])
+    check_bits(got.cpu().numpy().reshape(Q, L), ref, f"{what} interp_array {t.plans}")
+    check_bits(wide[1:, :L].cpu().numpy(), ref, f"{what} strided into {t.plans}")
+    assert bool((wide[1:, L:] == -7.0).all()) and bool((wide[0] == -7.0).all()), f"{what}: wrote outside its rows {t.plans}"
+    if ext:
+        return
+    bad = int(rng.integers(0, Q)); later = min(Q - 1, bad + int(rng.integers(1, 5000)))
+    q2 = q.copy(); q2[bad] = x[-1] + dt(1.0); q2[later] = x[0] - dt(1.0)
+    buf = torch.full((Q, L), -3.0, dtype=_tdt(dt), device=dev)
+    with traced(capfd) as t:
+        with pytest.raises(pkg.InterpolateError.OutOfBounds) as ei:
+            it.interp_array_into(torch.as_tensor(q2, device=dev), buf)
+        with pytest.raises(pkg.InterpolateError.OutOfBounds) as ej:
+            it.interp_array(torch.as_tensor(q2, device=dev))
+    assert ei.value.index == ej.value.index == bad, f"{what}: first failure {ei.value.index}/{ej.value.index} != {bad} {t.plans}"
+    g = buf.cpu().numpy()
+    check_bits(g[:bad], ref[:bad], f"{what}: rows before the first failure {t.plans}")
+    assert np.all(g[bad:] == -3.0), f"{what}: rows after the first failure {t.plans}"
+
+
 def _one_2d(pkg, capfd, rng, dt, tiles=False):
     import torch
     dev = torch.device("cuda:0")
@@ -189,3 +233,12 @@ def test_auto_large_batches_wide_rows_and_tiles(pkg, capfd, seed):
         dt = [np.float64, np.float32][int(rng.integers(0, 2))]
         _one_1d(pkg, capfd, rng, dt, str(rng.choice(["linear", "cubic", "cubic"])), wide=True)
     _one_2d(pkg, capfd, rng, [np.float64, np.float32][seed % 2], tiles=True)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_auto_large_batches_local_cubics_and_derivatives(pkg, capfd, seed):
+    """New seeds beside the fuzz above, whose draws stay what they are."""
+    rng = np.random.default_rng(63_000 + seed)
+    for _ in range(8):
+        dt = [np.float64, np.float32][int(rng.integers(0, 2))]
+        _one_local_cubic(pkg, capfd, rng, dt, str(rng.choice(["pchip", "akima", "hermite", "derivative"])))

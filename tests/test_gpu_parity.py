@@ -820,6 +820,67 @@ def test_fuzz_against_oracle(pkg, seed):
         check_equal(it.interp_array(q), ref, f"fuzz cubic seed={seed} n={n} L={L} per={per} ext={ext} bc=({lk},{rk}) path={path}")
 
 
+def _fuzz_local_cubic(pkg, rng, dt, n, L, kind, device=None):
+    """One draw of the handle kinds the fuzz above does not know: (x, y, interp, (Y, A, B) reference tables, description).
+    `kind`: pchip / akima / hermite, or `derivative` of a random source with an order the source allows.  A quarter of the
+    draws take y (and dydx) from tests/hostile_inputs.py instead of uniform(-1, 1).  Tables: the numpy restatements.
+    `device`: build from tensors on that device (read in place) instead of host arrays."""
+    import derivative_ref
+    import hermite_ref
+    import hostile_inputs as hostile
+    source = kind if kind != "derivative" else str(rng.choice(["pchip", "akima", "hermite", "spline"]))
+    nu = 0 if kind != "derivative" else (int(rng.integers(1, 3)) if source == "spline" else 1)
+    x = knots(str(rng.choice(["rand", "jit", "log", "lin"])), n, rng, dt) if n > 3 else np.arange(n).astype(dt)
+    hostile_draw = bool(rng.integers(0, 4) == 0)
+    rule = source if source != "spline" else "pchip"
+    if hostile_draw:
+        _, y, k = hostile.generate(rule, dt, n, L, kind="even", part=int(rng.integers(0, hostile.parts(rule, n, L))),
+                                   seed=int(rng.integers(0, 1 << 30)))
+    else:
+        y = rng.uniform(-1, 1, (n, L)).astype(dt)
+        k = rng.uniform(-1, 1, (n, L)).astype(dt) if source == "hermite" else None
+    ext = bool(rng.integers(0, 2))
+    up = (lambda v: v) if device is None else (lambda v: __import__("torch").as_tensor(v, device=device))
+    if source == "spline":
+        strat = pkg.CubicSpline.new()
+    else:
+        strat = {"pchip": pkg.Pchip.new, "akima": pkg.Akima.new}[source]() if source != "hermite" else pkg.CubicHermite.new(up(k))
+    it = pkg.Interp1DBuilder.new(up(y)).x(up(x)).strategy(strat.extrapolate(ext)).build()
+    with np.errstate(all="ignore"):
+        if source == "spline":      # (the spline's own tables are the operands: its build is another test's subject)
+            a, b = it.strategy.coefficients()
+        else:
+            a, b = hermite_ref.build(source, x, y, k)
+        tabs = derivative_ref.derive_nu(x, y, a, b, nu)
+    if nu:
+        it = it.derivative(nu)
+    return x, it, tabs, ext, f"{kind}({source}, nu={nu}) {np.dtype(dt).name} n={n} L={L} ext={ext} hostile={hostile_draw}"
+
+
+@pytest.mark.parametrize("seed", range(8))
+def test_fuzz_local_cubics_against_oracle(pkg, seed):
+    """test_fuzz_against_oracle for Pchip / Akima / CubicHermite handles and derivative handles (new seeds: the draws of the
+    fuzz above are unchanged), compared bit for bit, zero signs and NaN positions included."""
+    from hostile_inputs import check_bits
+    rng = np.random.default_rng(19_000 + seed)
+    for _ in range(12):
+        dt = [np.float64, np.float32][int(rng.integers(0, 2))]
+        kind = str(rng.choice(["pchip", "akima", "hermite", "derivative"]))
+        Q = int(rng.integers(1, 3000))
+        path = int(rng.choice([pkg.PATH_AUTO, pkg.PATH_GATHER, pkg.PATH_BUCKETED]))
+        n = int(rng.integers(3, 400))
+        L = int(rng.choice([1, 2, 3, 5, 8, 64, 130, 512, 1024, 1030, 2048]))
+        x, it, (Y, A, B), ext, what = _fuzz_local_cubic(pkg, rng, dt, n, L, kind)
+        span = float(x[-1] - x[0])
+        m = 0.5 if ext else 0.0
+        q = rng.uniform(x[0] - m * span, x[-1] + m * span, Q).astype(dt)
+        if not ext:
+            q = np.clip(q, x[0], x[-1])
+        it.strategy.path = path
+        _, _, ref = oracle.interp1d_cubic(x, Y, A, B, q, oracle.EXTRAPOLATE_YES if ext else oracle.EXTRAPOLATE_NO)
+        check_bits(np.asarray(it.interp_array(q)).reshape(ref.shape), ref, f"fuzz seed={seed} {what} path={path}")
+
+
 def test_infinite_queries_follow_ieee_like_the_cpu(pkg):
     """+-inf queries: out of range without extrapolation (OutOfBounds with the reference's text), and with
     extrapolation the end interval's polynomial evaluated at +-inf -- inf / NaN exactly where the CPU gets them."""

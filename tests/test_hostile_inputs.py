@@ -1,0 +1,320 @@
+"""CPU: the hostile inputs of tests/hostile_inputs.py are what they claim to be.
+
+* every branch the header names, and every data class, occurs in the arrays the GPU tests run (a condition on the
+  generators, printed as a table with -s);
+* check_bits sees the sign of a zero and the position of a NaN;
+* sgn(NaN) = 0: the header's statement, the restatement's `sgn`, and what follows for Pchip's end formula;
+* the restatement on the finite hostile classes still agrees with scipy;
+* mutants of the restatement -- the subtle ways a kernel could be wrong -- are told apart by at least one hostile array.
+"""
+import os
+
+import numpy as np
+import pytest
+
+import derivative_ref
+import hermite_ref
+import hostile_inputs as hostile
+from conftest import GOLDEN, ROOT
+from hostile_inputs import check_bits
+
+# the (n, L) grid of tests/test_gpu_cubic_hostile.py
+NS = (2, 3, 4, 5, 6, 64, 301)
+LS = (1, 3, 8, 130)
+DTYPES = (np.float64, np.float32)
+
+
+# ---- the comparer -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", [np.float64, np.float32, np.float16])
+def test_check_bits(dt):
+    a = np.array([1.0, 0.0, -0.0, np.nan, np.inf, -np.inf, 2.0], dt)
+    check_bits(a, a.copy(), "same")
+    b = a.copy(); b[1] = -0.0
+    assert np.array_equal(a, b, equal_nan=True)                      # what check_equal would accept
+    with pytest.raises(AssertionError, match=r"1 of 7 elements differ \(zero sign only: 1, NaN position: 0, value: 0\); first at \(1,\)"):
+        check_bits(b, a, "zero")
+    # another NaN payload and sign is the same NaN; a NaN that moved is not
+    u = {2: np.uint16, 4: np.uint32, 8: np.uint64}[np.dtype(dt).itemsize]
+    c = a.copy(); cv = c.view(u); cv[3] = cv[3] ^ u(1) ^ (u(1) << u(8 * np.dtype(dt).itemsize - 1))
+    assert np.isnan(c[3]) and c.view(u)[3] != a.view(u)[3]
+    check_bits(c, a, "payload")
+    d = a.copy(); d[3] = 1.0; d[0] = np.nan
+    with pytest.raises(AssertionError, match=r"2 of 7 elements differ \(zero sign only: 0, NaN position: 2, value: 0\)"):
+        check_bits(d, a, "moved")
+    e = a.copy(); e[6] = np.nextafter(dt(2.0), dt(3.0))
+    with pytest.raises(AssertionError, match=r"value: 1\); first at \(6,\): got .* = 0x[0-9a-f]+, ref .* = 0x[0-9a-f]+"):
+        check_bits(e, a, "one ulp")
+    with pytest.raises(AssertionError, match="dtype"):
+        check_bits(a.astype(np.float64), a.astype(np.float32), "dtype")
+    with pytest.raises(AssertionError, match="shape"):
+        check_bits(a[:3], a[:4], "shape")
+
+
+# ---- the generators' self-check -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rule", hostile.RULES)
+def test_every_branch_and_class_occurs(rule):
+    """A condition on the generators: every count > 0 for every (rule, dtype, n >= 3, L) the GPU tests use."""
+    print()
+    for dt in DTYPES:
+        for n in NS:
+            if n < 3:
+                continue
+            worst = None
+            for L in LS:
+                t = hostile.branch_table(rule, dt, n, L)
+                missing = [name for name in hostile.expected_branches(rule, n) if t[name] <= 0]
+                assert not missing, (rule, np.dtype(dt).name, n, L, missing)
+                worst = t if worst is None else {k: min(worst[k], t[k]) for k in t}
+            print(f"{rule} {np.dtype(dt).name} n={n}: smallest count over L in {LS}")
+            for name in hostile.expected_branches(rule, n):
+                print(f"    {worst[name]:8d}  {name}")
+
+
+def test_generators_are_seeded_and_shaped():
+    for rule in hostile.RULES:
+        for n, L in ((2, 3), (3, 1), (64, 8)):
+            if rule == "akima" and n < 3:
+                continue
+            one = list(hostile.cases(rule, np.float32, n, L))
+            two = list(hostile.cases(rule, np.float32, n, L))
+            assert len(one) == len(two) >= 5
+            for (t1, x1, y1, k1), (t2, x2, y2, k2) in zip(one, two):
+                assert t1 == t2 and x1.dtype == y1.dtype == np.float32 and y1.shape == (n, L) and np.all(x1[1:] > x1[:-1])
+                check_bits(x1, x2, t1); check_bits(y1, y2, t1)
+                assert (k1 is None) == (rule != "hermite")
+                if k1 is not None:
+                    check_bits(k1, k2, t1)
+    # the knot families
+    for dt in DTYPES:
+        x = hostile.knots("adjacent", dt, 9)
+        assert np.all(np.nextafter(x[:-1], dt(np.inf)) == x[1:]) and hostile.has_adjacent(x)
+        x = hostile.knots("huge", dt, 301)
+        assert np.all(np.isfinite(x)) and np.all(np.diff(x) >= 0.99 * hostile.big_step(dt)) and not hostile.has_adjacent(x)
+        x = hostile.knots("mixed", dt, 6)
+        assert x[1] == np.nextafter(x[0], dt(np.inf)) and x[-1] - x[-2] >= 0.99 * hostile.big_step(dt)
+        q = hostile.queries(hostile.knots("uneven", dt, 5))
+        assert q.dtype == np.dtype(dt) and np.isinf(q).sum() == 2 and not np.isnan(q).any() and len(q) == 5 + 4 + 8 + 4 + 2
+
+
+# ---- sgn(NaN) -----------------------------------------------------------------------------------------------------------
+def test_sgn_of_the_specification():
+    """include/ndinterp.h: sgn(v) = (v > 0) - (v < 0), so sgn(NaN) = 0.  A NaN slope at an end makes that end's k NaN unless
+    sgn(d) != sgn(m0) has already decided."""
+    header = open(os.path.join(ROOT, "include", "ndinterp.h")).read()
+    assert "sgn(v) = (v > 0) - (v < 0)" in header and "sgn(NaN) = 0" in header
+    nan, inf = np.nan, np.inf
+    v = np.array([nan, -nan, inf, -inf, 0.0, -0.0, 5e-324, -5e-324, 1.0, -2.0])
+    assert hermite_ref.sgn(v).tolist() == [0, 0, 1, -1, 0, 0, 1, -1, 1, -1]
+    assert hermite_ref.sgn(v.astype(np.float32)).tolist() == [0, 0, 1, -1, 0, 0, 0, 0, 1, -1]      # (5e-324 is 0 in f32)
+    # invisible on finite data: equal to np.sign on every finite value of the goldens
+    seen = 0
+    for name in ("hermite_scipy.npz", "derivative_scipy.npz"):
+        g = np.load(os.path.join(GOLDEN, name))
+        for key in g.files:
+            arr = g[key]
+            if arr.dtype.kind == "f":
+                f = arr[np.isfinite(arr)]
+                assert np.array_equal(hermite_ref.sgn(f), np.sign(f).astype(np.int8)), (name, key)
+                seen += f.size
+    assert seen > 10_000
+    # the end formula as a table: x, y -> k (pchip_k); the first two rows are the examples of the open question
+    x = np.array([0.0, 1.0, 2.5, 3.0, 4.5])
+    table = [
+        ([1, 1, nan, 2, 3], {0: nan}),            # m0 = 0, m1 = NaN: d = NaN, sgn all 0 -> d
+        ([1, 2, 3, nan, 5], {4: nan}),            # right end: m0 = NaN
+        ([nan, 1, 2, 3, 4], {0: nan}),            # m0 = NaN itself
+        ([1, 2, nan, 3, 4], {0: 0.0}),            # m0 = 1, m1 = NaN: d = NaN, sgn(d) = 0 != sgn(m0) = 1 decides first: +0
+        ([1, 2, 3, 4, nan], {4: nan, 3: 0.0}),    # right end m0 = NaN; the interior knot before it: (2 > 0) != (NaN > 0), +0
+        ([1, 1, 3, 4, 5], {0: 0.0}),              # m0 = 0, m1 != 0: sgn(d) = -1 != sgn(m0) = 0: +0
+        ([1, 2, -13, 4, 5], {0: 3.0}),            # m0 = 1, m1 = -10: d = (3.5 + 10) / 2.5 > 3: 3 m0
+        ([1, 2, 8, 9, 10], {0: 0.0}),             # m0 = 1, m1 = 4: d = (3.5 - 4) / 2.5 < 0: +0
+        ([1, 2, inf, 3, 4], {0: 0.0}),            # m0 = 1, m1 = inf: d = -inf: +0
+        ([inf, 2, 3, 4, 5], {0: -inf}),           # m0 = -inf, m1 = 2/3: d = -inf, same sign, |d| > 3 |m0| is false: d
+        ([-0.0, -0.0, -0.0, 1, 2], {0: 0.0, 1: 0.0}),     # flat run of -0: +0, never -0
+    ]
+    for y, want in table:
+        for dt in DTYPES:
+            with np.errstate(all="ignore"):
+                k = hermite_ref.pchip_k(x.astype(dt), np.array(y, dt)[:, None]).ravel()
+            for i, v in want.items():
+                check_bits(k[i:i + 1], np.array([v], dt), f"y = {y}: k_{i}")
+    # and what the first example does to the table next to the NaN row: a_0 = k_0 h_0 - dy is NaN, no longer 0
+    with np.errstate(all="ignore"):
+        a, b = hermite_ref.build("pchip", x, np.array([1, 1, nan, 2, 3.0])[:, None])
+    assert np.isnan(a[0, 0]) and b[0, 0] == 0 and np.isnan(a[1, 0])      # (k_1 = +0: delta_0 == 0 decides before the NaN)
+
+
+# ---- the restatement on finite hostile data against scipy ---------------------------------------------------------------
+def _finite_case(x, y):
+    return np.all(np.isfinite(y))
+
+
+@pytest.mark.parametrize("rule", ["pchip", "akima"])
+@pytest.mark.parametrize("dt", DTYPES)
+def test_restatement_on_finite_hostile_data_matches_scipy(rule, dt):
+    """The bound of tests/test_hermite_abi.py: 4 x the deviation stored in tests/golden/hermite_scipy.npz, relative to
+    max|y| + 1; scipy computes in f64 from the same (f32 or f64) inputs.
+
+    Left to the bit comparison alone, because scipy's rule differs there or scipy itself leaves the finite range:
+    * lanes whose f64 slopes or tables overflow the dtype (the "dy overflows", "3 (b - a) overflows" and "all exponents"
+      recipes, the huge / adjacent / mixed axes): the restatement has inf or NaN where scipy, in f64, has finite numbers,
+      or both overflow;
+    * f32 lanes with subnormal differences on their own are kept: scipy sees the same inputs, and the deviation is far
+      below the bound, which is relative to max|y| + 1;
+    * Akima lanes with some s below scipy's threshold (1e-9 of the largest s of the lane) other than exact zeros: scipy
+      averages there, the header does not.  Lanes where every s is either exactly 0 or above the threshold are kept."""
+    scipy_interpolate = pytest.importorskip("scipy.interpolate")
+    g = np.load(os.path.join(GOLDEN, "hermite_scipy.npz"))
+    bound = 4.0 * float(g[f"deviation/{np.dtype(dt).name}/{rule}"])
+    seen, worst = 0, 0.0
+    for n in (3, 4, 5, 6, 64):
+        for tag, x, y, _ in hostile.cases(rule, dt, n, 130, classes=("branch", "zero", "scale"), kinds=("even", "uneven")):
+            ra, rb = hostile.reference(rule, x, y)
+            q = hostile.queries(x, extrapolate=False)
+            with np.errstate(all="ignore"):
+                got = hermite_ref.evaluate(x, y, ra, rb, q).astype(np.float64)
+            x64, y64 = x.astype(np.float64), y.astype(np.float64)
+            for l in range(y.shape[1]):
+                if not (np.all(np.isfinite(y[:, l])) and np.all(np.isfinite(ra[:, l])) and np.all(np.isfinite(rb[:, l]))
+                        and np.all(np.isfinite(got[:, l]))):
+                    continue
+                if np.abs(y64[:, l]).max() > 1e-3 * float(np.finfo(dt).max):
+                    continue
+                if rule == "akima":
+                    with np.errstate(all="ignore"):
+                        s = hermite_ref.akima_k(x64, y64[:, l:l + 1])[1].ravel()
+                    if np.any((s > 0) & (s <= 1e-6 * s.max())):
+                        continue
+                    want = scipy_interpolate.Akima1DInterpolator(x64, y64[:, l])(q.astype(np.float64))
+                else:
+                    want = scipy_interpolate.PchipInterpolator(x64, y64[:, l])(q.astype(np.float64))
+                dev = float(np.abs(got[:, l] - want).max() / (np.abs(y64[:, l]).max() + 1))
+                worst = max(worst, dev)
+                seen += 1
+                assert dev <= bound, (tag, l, dev, bound)
+    assert seen >= 300, seen
+    print(f"{rule} {np.dtype(dt).name}: {seen} finite hostile lanes, largest deviation from scipy {worst:.3e}, bound {bound:.3e}")
+
+
+# ---- mutants ----------------------------------------------------------------------------------------------------------------
+def entry_build(rule, x, y, dydx=None, mutant=None):
+    """The build as the kernel is organised (csrc/hermite_kernels.hpp): one table entry per interval i, the window of rows
+    around it, k_i and k_{i+1} formed per entry -- in numpy over the lanes.  `mutant` switches in one subtle error."""
+    T = y.dtype.type
+    n = len(x)
+    zero = T(-0.0) if mutant == "flat branch returns -0" else T(0)
+    sgn = (lambda v: np.sign(v)) if mutant == "np.sign for NaN" else hermite_ref.sgn
+
+    def interior(hp, hc, dp, dc):
+        flat = (dp == 0) | (dc == 0) | ((dp > 0) != (dc > 0))
+        w1 = (hc + hc) + hp
+        w2 = hc + (hp + hp)
+        return np.where(flat, zero, (w1 + w2) / (w1 / dp + w2 / dc))
+
+    def edge(h0, h1, m0, m1):
+        d = (((h0 + h0) + h1) * m0 - h0 * m1) / (h0 + h1)
+        opp = sgn(d) != sgn(m0)
+        big = (sgn(m0) != sgn(m1)) & (np.abs(d) > T(3) * np.abs(m0))
+        return np.where(opp, T(0), np.where(big, T(3) * m0, d))
+
+    def akima(mm2, mm1, m0, mp1):
+        w1 = np.abs(mp1 - m0)
+        w2 = np.abs(mm1 - mm2)
+        s = w1 + w2
+        return np.where(s == 0, T(0.5) * (mm1 + m0), (w1 * mm1 + w2 * m0) / s)
+    halo = {"pchip": 1, "akima": 2, "hermite": 0}[rule]
+    a = np.empty((n - 1, y.shape[1]), y.dtype)
+    b = np.empty_like(a)
+    with np.errstate(all="ignore"):
+        for i in range(n - 1):
+            rows = [y[i + w - halo] if 0 <= i + w - halo < n else np.zeros(y.shape[1], y.dtype) for w in range(2 + 2 * halo)]
+            xs = [x[i + w - halo] if 0 <= i + w - halo < n else T(0) for w in range(2 + 2 * halo)]
+            hi = xs[halo + 1] - xs[halo]
+            dy = rows[halo + 1] - rows[halo]
+            if rule == "hermite":
+                k0, k1 = dydx[i], dydx[i + 1]
+            else:
+                h = [xs[w + 1] - xs[w] for w in range(len(xs) - 1)]
+                dl = [(rows[w + 1] - rows[w]) / h[w] for w in range(len(xs) - 1)]
+                if rule == "pchip":
+                    if n == 2:
+                        k0 = k1 = dl[1]
+                    else:
+                        k0 = edge(h[1], h[2], dl[1], dl[2]) if i == 0 else interior(h[0], h[1], dl[0], dl[1])
+                        k1 = edge(h[1], h[0], dl[1], dl[0]) if i + 2 == n else interior(h[1], h[2], dl[1], dl[2])
+                else:
+                    m = list(dl)
+                    if i + 1 < 2: m[1] = (m[2] + m[2]) - m[3]
+                    if i + 0 < 2: m[0] = (m[1] + m[1]) - m[2]
+                    if (i + 3 >= n) if mutant == "akima extension i + 3 >= n" else (i + 3 > n): m[3] = (m[2] + m[2]) - m[1]
+                    if i + 4 > n: m[4] = (m[3] + m[3]) - m[2]
+                    k0 = akima(m[0], m[1], m[2], m[3])
+                    k1 = akima(m[1], m[2], m[3], m[4])
+            a[i] = k0 * hi - dy
+            b[i] = dy - k1 * hi
+    return a, b
+
+
+def _flush(v):
+    out = v.copy()
+    out[(out != 0) & (np.abs(out) < np.finfo(v.dtype).tiny)] = 0
+    return out
+
+
+@pytest.mark.parametrize("rule", hostile.RULES)
+@pytest.mark.parametrize("dt", DTYPES)
+def test_entry_formulation_equals_the_restatement(rule, dt):
+    """The per-entry organisation of the kernel and the whole-array restatement are the same numbers, bit for bit, on every
+    hostile array of the small shapes: the stand-in the mutants are applied to is right before it is made wrong."""
+    for n in NS[:6]:
+        if rule == "akima" and n < 3:
+            continue
+        for tag, x, y, k in hostile.cases(rule, dt, n, 130):
+            ra, rb = hostile.reference(rule, x, y, k)
+            ea, eb = entry_build(rule, x, y, k)
+            check_bits(ea, ra, tag + ": a"); check_bits(eb, rb, tag + ": b")
+
+
+MUTANTS = [("pchip", "flat branch returns -0"), ("pchip", "np.sign for NaN"), ("akima", "akima extension i + 3 >= n"),
+           ("pchip", "flushed subnormals"), ("akima", "flushed subnormals"), ("hermite", "flushed subnormals"),
+           ("pchip", "derivative 3 (a - b)"), ("akima", "derivative 3 (a - b)"), ("hermite", "derivative 3 (a - b)")]
+
+
+@pytest.mark.parametrize("rule,mutant", MUTANTS)
+@pytest.mark.parametrize("dt", DTYPES)
+def test_hostile_inputs_tell_a_mutant_from_the_restatement(rule, mutant, dt):
+    """Each mutant is one subtle error a kernel could have; check_bits against the unmodified restatement must fail on at
+    least one hostile array of EVERY (n, L) of the small shapes (n >= 3), so no lane mapping depends on another's luck."""
+    print()
+    for n in (3, 4, 5, 6, 64):
+        for L in LS:
+            caught = []
+            for tag, x, y, k in hostile.cases(rule, dt, n, L):
+                ra, rb = hostile.reference(rule, x, y, k)
+                if mutant == "derivative 3 (a - b)":
+                    ref = hostile.derivative_reference(x, y, ra, rb)
+                    with np.errstate(all="ignore"):
+                        got = (ref[0], (y.dtype.type(3) * (ra - rb)) / (x[1:] - x[:-1])[:, None])
+                    ref = ref[:2]
+                elif mutant == "flushed subnormals":
+                    got = tuple(_flush(t) for t in entry_build(rule, x, _flush(y), None if k is None else _flush(k)))
+                    ref = (ra, rb)
+                else:
+                    got = entry_build(rule, x, y, k, mutant)
+                    ref = (ra, rb)
+                try:
+                    for g, r in zip(got, ref):
+                        check_bits(g, r, tag)
+                except AssertionError as e:
+                    caught.append(str(e))
+            assert caught, f"{mutant}: no hostile array of {rule} {np.dtype(dt).name} n={n} L={L} notices"
+            if (n, L) == (64, 130):
+                print(f"{mutant} / {rule} {np.dtype(dt).name}: {len(caught)} arrays notice, e.g. {caught[0][:230]}")
+
+
+def test_derivative_restatement_keeps_its_order():
+    """3 (b - a) and not 3 (a - b); (dy + a) / dx on the left and (dy - b) / dx at the last knot -- on numbers where each
+    choice shows."""
+    x = np.array([0.0, 2.0, 3.0]); y = np.array([[1.0], [4.0], [2.0]]); a = np.array([[0.5], [-1.0]]); b = np.array([[2.0], [3.0]])
+    Y, A, B = derivative_ref.derive(x, y, a, b)
+    assert Y.ravel().tolist() == [1.75, -3.0, -5.0] and A.ravel().tolist() == [2.25, 12.0] and np.array_equal(A, B)
