@@ -2,15 +2,15 @@
 // namespace ndi, after the integer handles; kernels in half_kernels.hpp).
 //
 // T values travel as their 16-bit patterns (uint16_t); the host keeps f32 images of the knots (exact) for the range
-// bounds, the diagnosis of a failing query and the replica signature.  One engine serves every entry point:
+// bounds, the diagnosis of a failing query and the replica signature.  HalfEngine is the NarrowEngine (narrow_host.hpp:
+// staging, first_fail, eval_rows, the ring, trim, the sharded call) of these handles.  Its own part:
 //   run          ndi_interp{1,2}d_eval.  Caller-owned buffers: the write-free range pre-pass records the first failing
 //                query in a device word and the evaluation kernel, on the same stream, skips the rows at / after it --
 //                no host round trip in between, so async_launch (device output) really returns after the enqueue and
 //                ndi_interp{1,2}d_finish reads the word.  FRESH_OUTPUT / ROWS_AFTER_ERROR_UNSPECIFIED: one fused pass
-//   run_ring     the pre-pass, then the rows below the first failure chunk by chunk
 //   diagnose     the failing query alone, on the host: range test (x before y) or NaN while extrapolating
 // Scratch (staged queries, host-output bounce buffer, the first-failure word) is kept per stream.  Calls on one handle
-// are serialised by its mutex.
+// are serialised by the engine's mutex.
 
 template <int F>
 static float half_to_float_host(uint16_t u) {
@@ -80,18 +80,10 @@ static uint32_t half_glog(uint64_t lanes, bool vec) {
   return g;
 }
 
-struct HalfScratch {
-  DevBuf qx, qy, out, word;
-};
-
 template <int F>
-struct HalfEngine {
-  int dev = 0, emode = EX_NO;
-  uint64_t elanes = 0;
+struct HalfEngine : NarrowEngine<uint16_t> {
   HalfBounds bnd{};
-  std::mutex mu;
-  std::map<void*, std::unique_ptr<HalfScratch>> scratch;   // per stream
-  OwnedRing ring_own;
+  std::map<void*, std::unique_ptr<NarrowScratch>> scratch;   // per stream
   struct Pending {
     bool launched;                  // device output, enqueued: the status is read from the stream's word at finish
     const void *qx, *qy;
@@ -103,64 +95,76 @@ struct HalfEngine {
   };
   std::map<void*, Pending> pending;   // async_launch batches awaiting finish, per stream
 
-  virtual ~HalfEngine() = default;
   virtual void launch_eval(const uint16_t* qx, const uint16_t* qy, uint64_t nq, uint16_t* out, uint64_t stride,
                            hipStream_t s, bool check, const unsigned long long* limit, unsigned long long* w) = 0;
   virtual ndi_status diagnose_at(float x, float y, ndi_oob_info* info) = 0;
 
-  HalfScratch& ws(hipStream_t s) {
-    std::unique_ptr<HalfScratch>& p = scratch[(void*)s];
-    if (!p) p.reset(new HalfScratch());
+  NarrowScratch& ws(hipStream_t s) override {
+    std::unique_ptr<NarrowScratch>& p = scratch[(void*)s];
+    if (!p) p.reset(new NarrowScratch());
     return *p;
   }
-  void release_scratch() { scratch.clear(); }
-
-  const uint16_t* stage(const void* q, uint64_t nq, int memspace, DevBuf& buf, hipStream_t s) {
-    if (!q || memspace == NDI_MEM_DEVICE) return static_cast<const uint16_t*>(q);
-    buf.reserve(nq * sizeof(uint16_t));
-    NDI_HIP(hipMemcpyAsync(buf.p, q, nq * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-    return buf.as<uint16_t>();
+  void release_scratch() override {
+    if (pending.empty()) scratch.clear();   // an async batch still reads its stream's word
   }
-  unsigned long long* reset_word(HalfScratch& W, hipStream_t s) {
-    W.word.reserve(sizeof(unsigned long long));
-    NDI_HIP(hipMemsetAsync(W.word.p, 0xff, sizeof(unsigned long long), s));
-    return W.word.as<unsigned long long>();
+  const char* bucketed_refusal() const override {
+    return "NDI_PATH_BUCKETED is not available for f16 / bf16 (AUTO / GATHER)";
   }
-  uint64_t read_word(HalfScratch& W, hipStream_t s) {
-    unsigned long long f = NO_FAIL;
-    NDI_HIP(hipMemcpyAsync(&f, W.word.p, sizeof(f), hipMemcpyDeviceToHost, s));
-    NDI_HIP(hipStreamSynchronize(s));
-    return f;
-  }
-  void launch_check(const uint16_t* qx, const uint16_t* qy, uint64_t nq, hipStream_t s, unsigned long long* w) {
+  void launch_check(const uint16_t* qx, const uint16_t* qy, uint64_t nq, hipStream_t s,
+                    unsigned long long* w) override {
     hipLaunchKernelGGL(half_check_kernel<F>, dim3(half_grid((nq + BLOCK - 1) / BLOCK, 16)), dim3(BLOCK), 0, s, qx, qy,
                        nq, emode, bnd, w);
-    NDI_HIP(hipGetLastError());
   }
+  void launch_rows(const uint16_t* dx, const uint16_t* dy, uint64_t cnt, uint16_t* out, uint64_t stride,
+                   hipStream_t s) override {
+    launch_eval(dx, dy, cnt, out, stride, s, false, nullptr, nullptr);
+  }
+  // one host thread per shard; what a thread throws becomes the call's status (lowest shard first)
+  ndi_status each_shard(uint32_t ns, const std::function<void(uint32_t)>& fn) override {
+    std::vector<ndi_status> sst(ns, NDI_OK);
+    std::vector<std::string> serr(ns);
+    std::vector<std::thread> th;
+    for (uint32_t i = 0; i < ns; ++i)
+      th.emplace_back([&, i] {
+        try {
+          fn(i);
+        } catch (const HipFailure& f) {
+          sst[i] = from_hip(f);
+          serr[i] = tls_error();
+        } catch (...) {
+          sst[i] = NDI_HIP_ERROR;
+          serr[i] = "unexpected C++ exception in a shard thread";
+        }
+      });
+    for (std::thread& t : th) t.join();
+    for (uint32_t i = 0; i < ns; ++i)
+      if (sst[i] != NDI_OK) {
+        tls_error() = serr[i];
+        return sst[i];
+      }
+    return NDI_OK;
+  }
+
   // Pre-pass + limited evaluation (caller-owned rows) or the fused pass, all enqueued on s; the word holds the first
   // failing query afterwards.
   void enqueue(const uint16_t* dx, const uint16_t* dy, uint64_t nq, uint16_t* out, uint64_t stride, bool fused,
-               HalfScratch& W, hipStream_t s) {
+               NarrowScratch& W, hipStream_t s) {
     unsigned long long* w = reset_word(W, s);
     if (fused) {
       launch_eval(dx, dy, nq, out, stride, s, true, nullptr, w);
     } else {
       launch_check(dx, dy, nq, s, w);
+      NDI_HIP(hipGetLastError());
       launch_eval(dx, dy, nq, out, stride, s, false, w, nullptr);
     }
     NDI_HIP(hipGetLastError());
   }
 
   // The failing query j alone: its x (and y) fetched, the reference's checks replayed in order.
-  ndi_status diagnose(const void* qx, const void* qy, uint64_t j, int qmem, uint64_t index, ndi_oob_info* info) {
+  ndi_status diagnose(const void* qx, const void* qy, uint64_t j, int qmem, uint64_t index,
+                      ndi_oob_info* info) override {
     uint16_t x = 0, y = 0;
-    if (qmem == NDI_MEM_DEVICE) {
-      NDI_HIP(hipMemcpy(&x, static_cast<const uint16_t*>(qx) + j, sizeof(x), hipMemcpyDeviceToHost));
-      if (qy) NDI_HIP(hipMemcpy(&y, static_cast<const uint16_t*>(qy) + j, sizeof(y), hipMemcpyDeviceToHost));
-    } else {
-      x = static_cast<const uint16_t*>(qx)[j];
-      if (qy) y = static_cast<const uint16_t*>(qy)[j];
-    }
+    fetch_query(qx, qy, j, qmem, &x, &y);
     ndi_oob_info tmp{};
     if (!info) info = &tmp;
     ndi_status st = diagnose_at(half_to_float_host<F>(x), half_to_float_host<F>(y), info);
@@ -185,20 +189,13 @@ struct HalfEngine {
   ndi_status run(const void* qx, const void* qy, uint64_t nq, void* out, uint64_t stride, const ndi_eval_opts* opts,
                  ndi_oob_info* info) {
     ndi_eval_opts o{};
-    if (const ndi_status vs = take_opts(opts, o); vs != NDI_OK) return vs;
-    if (o.path == NDI_PATH_BUCKETED)
-      return fail(NDI_UNSUPPORTED, "NDI_PATH_BUCKETED is not available for f16 / bf16 (AUTO / GATHER)");
-    if (stride < elanes)
-      return fail(NDI_BAD_ARG, "out_row_stride (%llu) < lanes (%llu)", (unsigned long long)stride,
-                  (unsigned long long)elanes);
-    if (nq && (!qx || !out)) return fail(NDI_BAD_ARG, "null query or output pointer");
-    if (info) *info = ndi_oob_info{0, 0.0, 0, NDI_OK};
+    if (const ndi_status hs = run_head(opts, o, qx, out, nq, stride, info); hs != NDI_OK) return hs;
     DeviceGuard dg(dev);
     std::lock_guard<std::mutex> lk(mu);
     hipStream_t s = (hipStream_t)o.stream;
     ndi_status st = NDI_OK;
     if (nq) {
-      HalfScratch& W = ws(s);
+      NarrowScratch& W = ws(s);
       const uint16_t* dx = stage(qx, nq, o.q_memspace, W.qx, s);
       const uint16_t* dy = stage(qy, nq, o.q_memspace, W.qy, s);
       const bool fused = (o.flags & (NDI_EVAL_FRESH_OUTPUT | NDI_EVAL_ROWS_AFTER_ERROR_UNSPECIFIED)) != 0;
@@ -216,8 +213,7 @@ struct HalfEngine {
       const uint64_t F_ = read_word(W, s);
       const uint64_t rows = std::min<uint64_t>(F_, nq);
       if (!dev_out && rows) {
-        NDI_HIP(hipMemcpy2DAsync(out, stride * sizeof(uint16_t), W.out.p, elanes * sizeof(uint16_t),
-                                 elanes * sizeof(uint16_t), rows, hipMemcpyDeviceToHost, s));
+        rows_to_host(out, stride, W.out, rows, s);
         NDI_HIP(hipStreamSynchronize(s));
       }
       if (F_ < nq) st = diagnose(qx, qy, F_, o.q_memspace, F_, info);
@@ -245,77 +241,6 @@ struct HalfEngine {
     if (info) *info = p.info;
     if (p.st != NDI_OK) tls_error() = p.err;
     return p.st;
-  }
-
-  // Rows [0, rows) through a device-output ring (rows already cut at the first failure).  q_begin: flat index of qx[0]
-  // in the caller's batch; shard: reported in every chunk.
-  void ring_rows(const uint16_t* dx, const uint16_t* dy, uint64_t rows, const ndi_ring_desc* ring, uint64_t stride,
-                 ndi_ring_consumer consume, void* user, hipStream_t s, uint64_t q_begin, uint32_t shard) {
-    const uint32_t ns = ring->n_slots;
-    std::vector<uint16_t*> slots(ns);
-    uint64_t rstride = stride;
-    std::unique_lock<std::mutex> rl(ring_own.mu, std::defer_lock);
-    if (ring->slots) {
-      for (uint32_t i = 0; i < ns; ++i) slots[i] = static_cast<uint16_t*>(ring->slots[i]);
-    } else {   // library-owned: one allocation, slots interleaved row by row (ndinterp.h)
-      rl.lock();
-      rstride = (uint64_t)ns * stride;
-      ring_own.ensure(1, ring->chunk_queries, rstride * sizeof(uint16_t));
-      for (uint32_t i = 0; i < ns; ++i) slots[i] = ring_own.buf.as<uint16_t>() + (uint64_t)i * stride;
-    }
-    std::vector<hipEvent_t> waits(ns, nullptr);
-    uint64_t k = 0;
-    for (uint64_t b = 0; b < rows; b += ring->chunk_queries, ++k) {
-      const uint64_t cnt = std::min<uint64_t>(ring->chunk_queries, rows - b);
-      const uint32_t slot = (uint32_t)(k % ns);
-      if (waits[slot]) NDI_HIP(hipStreamWaitEvent(s, waits[slot], 0));
-      waits[slot] = nullptr;
-      launch_eval(dx + b, dy ? dy + b : nullptr, cnt, slots[slot], rstride, s, false, nullptr, nullptr);
-      NDI_HIP(hipGetLastError());
-      ndi_ring_chunk c{k, q_begin + b, cnt, slots[slot], rstride, slot, shard, (void*)s};
-      waits[slot] = consume ? (hipEvent_t)consume(user, &c) : nullptr;
-    }
-    NDI_HIP(hipStreamSynchronize(s));
-  }
-
-  // Lowest failing query of [0, nq) (NO_FAIL if none), queries staged into the stream's scratch.
-  uint64_t first_fail(const void* qx, const void* qy, uint64_t nq, int qmem, hipStream_t s, const uint16_t** dx,
-                      const uint16_t** dy) {
-    HalfScratch& W = ws(s);
-    *dx = stage(qx, nq, qmem, W.qx, s);
-    *dy = stage(qy, nq, qmem, W.qy, s);
-    unsigned long long* w = reset_word(W, s);
-    launch_check(*dx, *dy, nq, s, w);
-    return read_word(W, s);
-  }
-
-  ndi_status run_ring(const void* qx, const void* qy, uint64_t nq, const ndi_ring_desc* ring,
-                      ndi_ring_consumer consume, void* user, const ndi_eval_opts* opts, ndi_oob_info* info) {
-    ndi_eval_opts o{};
-    if (const ndi_status vs = take_opts(opts, o); vs != NDI_OK) return vs;
-    if (o.path == NDI_PATH_BUCKETED)
-      return fail(NDI_UNSUPPORTED, "NDI_PATH_BUCKETED is not available for f16 / bf16 (AUTO / GATHER)");
-    uint64_t stride = 0;
-    if (const ndi_status rs = check_ring_desc(ring, elanes, &stride); rs != NDI_OK) return rs;
-    if (nq && !qx) return fail(NDI_BAD_ARG, "null query pointer");
-    if (info) *info = ndi_oob_info{0, 0.0, 0, NDI_OK};
-    if (nq == 0) return NDI_OK;
-    DeviceGuard dg(dev);
-    std::lock_guard<std::mutex> lk(mu);
-    hipStream_t s = (hipStream_t)o.stream;
-    const uint16_t *dx, *dy;
-    const uint64_t F_ = first_fail(qx, qy, nq, o.q_memspace, s, &dx, &dy);
-    ring_rows(dx, dy, std::min<uint64_t>(F_, nq), ring, stride, consume, user, s, 0, 0);
-    return F_ < nq ? diagnose(qx, qy, F_, o.q_memspace, F_, info) : NDI_OK;
-  }
-
-  ndi_status trim_impl() {
-    DeviceGuard dg(dev);
-    std::lock_guard<std::mutex> lk(mu);
-    std::lock_guard<std::mutex> rl(ring_own.mu);
-    if (pending.empty()) release_scratch();   // an async batch still reads its stream's word
-    ring_own.clear();
-    return NDI_OK;
   }
 };
 
@@ -395,8 +320,8 @@ struct Interp1DHalfImpl final : Interp1DBase, HalfEngine<F> {
     std::unique_ptr<Interp1DHalfImpl<F>> c(new Interp1DHalfImpl<F>());
     {
       DeviceGuard dg(d);
-      c->dtype = dtype; c->device = d; c->lanes = lanes; c->n = n; c->hx = hx;
-      c->dev = d; c->elanes = lanes; c->emode = this->emode; c->bnd = this->bnd;
+      set_scalars(*c, dtype, d, this->emode, lanes);
+      c->n = n; c->hx = hx; c->bnd = this->bnd;
       c->kf.reserve(kf.bytes); c->data.reserve(data.bytes);
     }
     copy_across_devices(c->kf.p, d, kf.p, device, kf.bytes);
@@ -411,23 +336,10 @@ static ndi_status create1d_half(const ndi_interp1d_desc& d, Interp1DBase** out) 
   DeviceGuard dg(d.device);
   Range rg("ndi_interp1d_create");
   std::unique_ptr<Interp1DHalfImpl<F>> h(new Interp1DHalfImpl<F>());
-  h->dtype = d.dtype;
-  h->device = h->dev = d.device;
-  h->emode = d.extrapolate ? EX_YES : EX_NO;
+  set_scalars(*h, d.dtype, d.device, d.extrapolate ? EX_YES : EX_NO, d.lanes);
   h->n = d.n;
-  h->lanes = h->elanes = d.lanes;
   h->hx = d.x ? half_images<F>(fetch_axis<uint16_t>(d.x, d.x_len, d.memspace)) : half_default_axis<F>(d.n);
-  const uint64_t x_len = d.x ? d.x_len : d.n;
-  if (d.validate) {
-    ndi_status st = check_axis_1d<float>(h->hx.data(), x_len, d.n, d.strategy);
-    if (st != NDI_OK) return st;
-  } else if (x_len != d.n || d.n < 2) {
-    return fail(NDI_BAD_ARG, "unvalidated create with inconsistent sizes (x_len %llu, n %llu)",
-                (unsigned long long)x_len, (unsigned long long)d.n);
-  }
-  if (d.lanes == 0) return fail(NDI_BAD_ARG, "lanes must be >= 1");
-  if (d.n > MAX_KNOTS) return fail(NDI_UNSUPPORTED, "more than %llu knots", (unsigned long long)MAX_KNOTS);
-  if (!d.data) return fail(NDI_BAD_ARG, "null data pointer");
+  if (const ndi_status st = check_desc_1d(d, h->hx.data()); st != NDI_OK) return st;
   h->bnd = HalfBounds{h->hx[0], h->hx[d.n - 1], 0.0f, 0.0f};
   h->kf.reserve(d.n * sizeof(float));
   NDI_HIP(hipMemcpy(h->kf.p, h->hx.data(), d.n * sizeof(float), hipMemcpyHostToDevice));
@@ -509,8 +421,8 @@ struct Interp2DHalfImpl final : Interp2DBase, HalfEngine<F> {
     std::unique_ptr<Interp2DHalfImpl<F>> c(new Interp2DHalfImpl<F>());
     {
       DeviceGuard dg(d);
-      c->dtype = dtype; c->device = d; c->lanes = lanes; c->nx = nx; c->ny = ny; c->hx = hx; c->hy = hy;
-      c->dev = d; c->elanes = lanes; c->emode = this->emode; c->bnd = this->bnd;
+      set_scalars(*c, dtype, d, this->emode, lanes);
+      c->nx = nx; c->ny = ny; c->hx = hx; c->hy = hy; c->bnd = this->bnd;
       c->kxf.reserve(kxf.bytes); c->kyf.reserve(kyf.bytes); c->grid.reserve(grid.bytes);
     }
     copy_across_devices(c->kxf.p, d, kxf.p, device, kxf.bytes);
@@ -526,24 +438,12 @@ static ndi_status create2d_half(const ndi_interp2d_desc& d, Interp2DBase** out) 
   DeviceGuard dg(d.device);
   Range rg("ndi_interp2d_create");
   std::unique_ptr<Interp2DHalfImpl<F>> h(new Interp2DHalfImpl<F>());
-  h->dtype = d.dtype;
-  h->device = h->dev = d.device;
-  h->emode = d.extrapolate ? EX_YES : EX_NO;
+  set_scalars(*h, d.dtype, d.device, d.extrapolate ? EX_YES : EX_NO, d.lanes);
   h->nx = d.nx;
   h->ny = d.ny;
-  h->lanes = h->elanes = d.lanes;
   h->hx = d.x ? half_images<F>(fetch_axis<uint16_t>(d.x, d.x_len, d.memspace)) : half_default_axis<F>(d.nx);
   h->hy = d.y ? half_images<F>(fetch_axis<uint16_t>(d.y, d.y_len, d.memspace)) : half_default_axis<F>(d.ny);
-  const uint64_t x_len = d.x ? d.x_len : d.nx, y_len = d.y ? d.y_len : d.ny;
-  if (d.validate) {
-    ndi_status st = check_axes_2d<float>(h->hx.data(), x_len, h->hy.data(), y_len, d.nx, d.ny);
-    if (st != NDI_OK) return st;
-  } else if (x_len != d.nx || y_len != d.ny || d.nx < 2 || d.ny < 2) {
-    return fail(NDI_BAD_ARG, "unvalidated create with inconsistent sizes");
-  }
-  if (d.lanes == 0) return fail(NDI_BAD_ARG, "lanes must be >= 1");
-  if (d.nx > MAX_KNOTS || d.ny > MAX_KNOTS) return fail(NDI_UNSUPPORTED, "too many knots");
-  if (!d.data) return fail(NDI_BAD_ARG, "null data pointer");
+  if (const ndi_status st = check_desc_2d(d, h->hx.data(), h->hy.data()); st != NDI_OK) return st;
   h->bnd = HalfBounds{h->hx[0], h->hx[d.nx - 1], h->hy[0], h->hy[d.ny - 1]};
   h->kxf.reserve(d.nx * sizeof(float));
   h->kyf.reserve(d.ny * sizeof(float));
@@ -595,96 +495,4 @@ static ndi_status create_half_locator(int device, const void* knots, uint64_t n,
   h->f32.reset(inner);
   *out = h.release();
   return NDI_OK;
-}
-
-// ---- sharded ----------------------------------------------------------------------------------------------------
-// One host thread per shard, twice: every shard finds its first failure (pre-pass on its handle's device and stream),
-// the minimum F is the serial loop's first failure, then every shard produces its rows below F -- into its output or
-// through its ring.
-template <int F, class Impl>
-static ndi_status sharded_half(const std::vector<Impl*>& H, const void* qx, const void* qy, uint64_t nq,
-                               const ndi_shard_io* io, uint64_t stride, const ndi_ring_desc* rings,
-                               ndi_ring_consumer consume, void* user, const ndi_eval_opts& o, ndi_oob_info* info) {
-  if (o.path == NDI_PATH_BUCKETED)
-    return fail(NDI_UNSUPPORTED, "NDI_PATH_BUCKETED is not available for f16 / bf16 (AUTO / GATHER)");
-  if (info) *info = ndi_oob_info{0, 0.0, 0, NDI_OK};
-  const uint32_t ns = (uint32_t)H.size();
-  std::vector<uint64_t> lo(ns), hi(ns), fi(ns, NO_FAIL);
-  std::vector<const void*> px(ns), py(ns);
-  std::vector<const uint16_t*> dx(ns), dy(ns);
-  for (uint32_t i = 0; i < ns; ++i) {
-    shard_range(nq, i, ns, &lo[i], &hi[i]);
-    const bool own = io && io[i].q;
-    px[i] = own ? io[i].q : static_cast<const uint16_t*>(qx) + lo[i];
-    py[i] = own ? io[i].qy : (qy ? static_cast<const uint16_t*>(qy) + lo[i] : nullptr);
-  }
-  std::vector<ndi_status> sst(ns, NDI_OK);
-  std::vector<std::string> serr(ns);
-  auto each = [&](const std::function<void(uint32_t)>& fn) {
-    std::vector<std::thread> th;
-    for (uint32_t i = 0; i < ns; ++i)
-      th.emplace_back([&, i] {
-        try {
-          fn(i);
-        } catch (const HipFailure& f) {
-          sst[i] = from_hip(f);
-          serr[i] = tls_error();
-        } catch (...) {
-          sst[i] = NDI_HIP_ERROR;
-          serr[i] = "unexpected C++ exception in a shard thread";
-        }
-      });
-    for (std::thread& t : th) t.join();
-    for (uint32_t i = 0; i < ns; ++i)
-      if (sst[i] != NDI_OK) {
-        tls_error() = serr[i];
-        return sst[i];
-      }
-    return NDI_OK;
-  };
-  ndi_status st = each([&](uint32_t i) {
-    if (hi[i] == lo[i]) return;
-    DeviceGuard dg(H[i]->dev);
-    std::lock_guard<std::mutex> lk(H[i]->mu);
-    fi[i] = H[i]->first_fail(px[i], py[i], hi[i] - lo[i], o.q_memspace, (hipStream_t)(io ? io[i].stream : nullptr),
-                             &dx[i], &dy[i]);
-  });
-  if (st != NDI_OK) return st;
-  uint64_t F_ = NO_FAIL;
-  for (uint32_t i = 0; i < ns; ++i)
-    if (fi[i] != NO_FAIL) F_ = std::min<uint64_t>(F_, lo[i] + fi[i]);
-  if (rings)
-    for (uint32_t i = 0; i < ns; ++i) {
-      uint64_t rs = 0;
-      if (const ndi_status rst = check_ring_desc(&rings[i], H[i]->elanes, &rs); rst != NDI_OK) return rst;
-    }
-  st = each([&](uint32_t i) {
-    const uint64_t end = std::min<uint64_t>(hi[i], F_);
-    if (end <= lo[i]) return;
-    DeviceGuard dg(H[i]->dev);
-    std::lock_guard<std::mutex> lk(H[i]->mu);
-    hipStream_t s = (hipStream_t)(io ? io[i].stream : nullptr);
-    const uint64_t rows = end - lo[i];
-    if (rings) {
-      uint64_t rs = 0;
-      check_ring_desc(&rings[i], H[i]->elanes, &rs);
-      H[i]->ring_rows(dx[i], dy[i], rows, &rings[i], rs, consume, user, s, lo[i], i);
-    } else if (o.out_memspace == NDI_MEM_DEVICE) {
-      H[i]->launch_eval(dx[i], dy[i], rows, static_cast<uint16_t*>(io[i].out), stride, s, false, nullptr, nullptr);
-      NDI_HIP(hipStreamSynchronize(s));
-    } else {
-      HalfScratch& W = H[i]->ws(s);
-      W.out.reserve(rows * H[i]->elanes * sizeof(uint16_t));
-      H[i]->launch_eval(dx[i], dy[i], rows, W.out.as<uint16_t>(), H[i]->elanes, s, false, nullptr, nullptr);
-      NDI_HIP(hipMemcpy2DAsync(io[i].out, stride * sizeof(uint16_t), W.out.p, H[i]->elanes * sizeof(uint16_t),
-                               H[i]->elanes * sizeof(uint16_t), rows, hipMemcpyDeviceToHost, s));
-      NDI_HIP(hipStreamSynchronize(s));
-    }
-  });
-  if (st != NDI_OK) return st;
-  if (F_ >= nq) return NDI_OK;
-  uint32_t owner = 0;
-  while (owner + 1 < ns && F_ >= hi[owner]) ++owner;
-  DeviceGuard dg(H[owner]->dev);
-  return H[owner]->diagnose(px[owner], py[owner], F_ - lo[owner], o.q_memspace, F_, info);
 }

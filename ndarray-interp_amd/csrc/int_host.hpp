@@ -1,15 +1,14 @@
 // csrc/int_host.hpp -- host side of the i32 / i64 Linear and Bilinear handles (included by ndinterp_api.hip inside
 // namespace ndi, after the float handles; kernels in int_kernels.hpp).
 //
-// One engine serves every entry point of an integer handle:
-//   first_fail   lowest failing query of a block (1-D: the query-only pre-pass; 2-D: the write-free check pass)
-//   eval_rows    rows that are known to be valid (no checks)
+// IntEngine is the NarrowEngine (narrow_host.hpp: staging, first_fail, eval_rows, the ring, trim, the sharded call) of
+// the integer handles.  Its own part:
 //   run          ndi_interp{1,2}d_eval: caller-owned buffers take first_fail + eval_rows over [0, F); fresh /
 //                unspecified-rows outputs take the fused pass
 //   diagnose     the failing query alone, on the host, in the reference's order (generic_host.calc_frac): which
 //                range test or which operation of which lane failed first
-// Calls on one handle are serialised by its mutex (the staging buffers are the handle's).  async_launch is accepted and
-// completes inside the call; ndi_interp{1,2}d_finish then reports that batch's status.
+// The staging buffers are the handle's (one scratch set, calls serialised by the engine's mutex).  async_launch is
+// accepted and completes inside the call; ndi_interp{1,2}d_finish then reports that batch's status.
 
 // Linear::calc_frac (linear.rs:29-36) in T, in the reference's order: the ndi_int_op of the first overflowing operation,
 // or -1 (result in res).
@@ -54,138 +53,75 @@ static bool int_wave_mapping(uint64_t lanes) {
   return lanes > 32;
 }
 
+static const char* const INT_OP_NAMES[4] = {"subtract", "multiply", "add", "divide"};   // indexed by ndi_int_op
+
 template <class T>
-struct IntEngine {
-  int dev = 0, emode = EX_NO;
-  uint64_t elanes = 0;
-  std::mutex mu;
-  DevBuf qx_buf, qy_buf, out_buf, word;
-  OwnedRing ring_own;
+struct IntEngine : NarrowEngine<T> {
+  NarrowScratch scratch;   // one set per handle
   std::map<void*, std::pair<ndi_status, ndi_oob_info>> pending;   // async_launch batches awaiting finish, per stream
   std::string pending_err;
 
-  virtual ~IntEngine() = default;
-  virtual void launch_check(const T* qx, const T* qy, uint64_t nq, hipStream_t s, unsigned long long* w) = 0;
   virtual void launch_eval(const T* qx, const T* qy, uint64_t nq, T* out, uint64_t stride, hipStream_t s,
                            bool check, unsigned long long* w) = 0;
   virtual ndi_status diagnose_at(T x, T y, ndi_oob_info* info) = 0;
 
-  const T* stage(const void* q, uint64_t nq, int memspace, DevBuf& buf, hipStream_t s) {
-    if (!q || memspace == NDI_MEM_DEVICE) return static_cast<const T*>(q);
-    buf.reserve(nq * sizeof(T));
-    NDI_HIP(hipMemcpyAsync(buf.p, q, nq * sizeof(T), hipMemcpyHostToDevice, s));
-    return buf.as<T>();
+  NarrowScratch& ws(hipStream_t) override { return scratch; }
+  void release_scratch() override { scratch.release(); }
+  const char* bucketed_refusal() const override {
+    return "NDI_PATH_BUCKETED is not available for integer element types (AUTO / GATHER)";
   }
-  unsigned long long* reset_word(hipStream_t s) {
-    word.reserve(sizeof(unsigned long long));
-    NDI_HIP(hipMemsetAsync(word.p, 0xff, sizeof(unsigned long long), s));
-    return word.as<unsigned long long>();
+  void launch_rows(const T* dx, const T* dy, uint64_t cnt, T* out, uint64_t stride, hipStream_t s) override {
+    launch_eval(dx, dy, cnt, out, stride, s, false, nullptr);
   }
-  uint64_t read_word(hipStream_t s) {
-    unsigned long long f = NO_FAIL;
-    NDI_HIP(hipMemcpyAsync(&f, word.p, sizeof(f), hipMemcpyDeviceToHost, s));
-    NDI_HIP(hipStreamSynchronize(s));
-    return f;
-  }
-
-  // Lowest failing query of [0, nq) (NO_FAIL if none); queries already on the device.
-  uint64_t first_fail_dev(const T* qx, const T* qy, uint64_t nq, hipStream_t s) {
-    unsigned long long* w = reset_word(s);
-    launch_check(qx, qy, nq, s, w);
-    NDI_HIP(hipGetLastError());
-    return read_word(s);
-  }
-  uint64_t first_fail(const void* qx, const void* qy, uint64_t nq, int qmem, hipStream_t s) {
-    const T* dx = stage(qx, nq, qmem, qx_buf, s);
-    const T* dy = stage(qy, nq, qmem, qy_buf, s);
-    return first_fail_dev(dx, dy, nq, s);
-  }
-
-  // Rows [0, rows) of out, every query valid; host outputs are staged and copied back row by row (stride kept).
-  void eval_rows(const void* qx, const void* qy, uint64_t rows, void* out, uint64_t stride, int qmem, int omem,
-                 hipStream_t s) {
-    if (rows == 0) return;
-    const T* dx = stage(qx, rows, qmem, qx_buf, s);
-    const T* dy = stage(qy, rows, qmem, qy_buf, s);
-    if (omem == NDI_MEM_DEVICE) {
-      launch_eval(dx, dy, rows, static_cast<T*>(out), stride, s, false, nullptr);
-      NDI_HIP(hipGetLastError());
-      return;
-    }
-    out_buf.reserve(rows * elanes * sizeof(T));
-    launch_eval(dx, dy, rows, out_buf.as<T>(), elanes, s, false, nullptr);
-    NDI_HIP(hipGetLastError());
-    NDI_HIP(hipMemcpy2DAsync(out, stride * sizeof(T), out_buf.p, elanes * sizeof(T), elanes * sizeof(T), rows,
-                             hipMemcpyDeviceToHost, s));
+  // serial, on the calling thread, in shard order; a HIP failure unwinds to the entry point
+  ndi_status each_shard(uint32_t ns, const std::function<void(uint32_t)>& fn) override {
+    for (uint32_t i = 0; i < ns; ++i) fn(i);
+    return NDI_OK;
   }
 
   // The failing query j alone: its x (and y) fetched, the reference's checks replayed in order.
-  ndi_status diagnose(const void* qx, const void* qy, uint64_t j, int qmem, uint64_t index, ndi_oob_info* info) {
+  ndi_status diagnose(const void* qx, const void* qy, uint64_t j, int qmem, uint64_t index,
+                      ndi_oob_info* info) override {
     T x = 0, y = 0;
-    if (qmem == NDI_MEM_DEVICE) {
-      NDI_HIP(hipMemcpy(&x, static_cast<const T*>(qx) + j, sizeof(T), hipMemcpyDeviceToHost));
-      if (qy) NDI_HIP(hipMemcpy(&y, static_cast<const T*>(qy) + j, sizeof(T), hipMemcpyDeviceToHost));
-    } else {
-      x = static_cast<const T*>(qx)[j];
-      if (qy) y = static_cast<const T*>(qy)[j];
-    }
+    this->fetch_query(qx, qy, j, qmem, &x, &y);
     ndi_oob_info tmp{};
     if (!info) info = &tmp;
     ndi_status st = diagnose_at(x, y, info);
     info->index = index;
     return st;
   }
+  ndi_status overflow(int op, ndi_oob_info* info) {
+    info->axis = op;
+    info->status = NDI_INT_OVERFLOW;
+    return fail(NDI_INT_OVERFLOW, "attempt to %s with overflow", INT_OP_NAMES[op]);
+  }
 
   ndi_status run(const void* qx, const void* qy, uint64_t nq, void* out, uint64_t stride, const ndi_eval_opts* opts,
                  ndi_oob_info* info) {
     ndi_eval_opts o{};
-    if (const ndi_status vs = take_opts(opts, o); vs != NDI_OK) return vs;
-    if (o.path == NDI_PATH_BUCKETED)
-      return fail(NDI_UNSUPPORTED, "NDI_PATH_BUCKETED is not available for integer element types (AUTO / GATHER)");
-    if (stride < elanes)
-      return fail(NDI_BAD_ARG, "out_row_stride (%llu) < lanes (%llu)", (unsigned long long)stride,
-                  (unsigned long long)elanes);
-    if (nq && (!qx || !out)) return fail(NDI_BAD_ARG, "null query or output pointer");
-    if (info) *info = ndi_oob_info{0, 0.0, 0, NDI_OK};
-    DeviceGuard dg(dev);
-    std::lock_guard<std::mutex> lk(mu);
+    if (const ndi_status hs = this->run_head(opts, o, qx, out, nq, stride, info); hs != NDI_OK) return hs;
+    DeviceGuard dg(this->dev);
+    std::lock_guard<std::mutex> lk(this->mu);
     hipStream_t s = (hipStream_t)o.stream;
     ndi_status st = NDI_OK;
     if (nq) {
-      const T* dx = stage(qx, nq, o.q_memspace, qx_buf, s);
-      const T* dy = stage(qy, nq, o.q_memspace, qy_buf, s);
+      NarrowScratch& W = scratch;
+      const uint64_t elanes = this->elanes;
+      const T* dx = this->stage(qx, nq, o.q_memspace, W.qx, s);
+      const T* dy = this->stage(qy, nq, o.q_memspace, W.qy, s);
       uint64_t F;
       if (o.flags & NDI_EVAL_FRESH_OUTPUT) {   // fused: rows at / after the failure may be written
-        T* od = static_cast<T*>(out);
-        uint64_t ost = stride;
-        if (o.out_memspace != NDI_MEM_DEVICE) {
-          out_buf.reserve(nq * elanes * sizeof(T));
-          od = out_buf.as<T>();
-          ost = elanes;
-        }
-        unsigned long long* w = reset_word(s);
-        launch_eval(dx, dy, nq, od, ost, s, true, w);
+        const bool dev_out = o.out_memspace == NDI_MEM_DEVICE;
+        if (!dev_out) W.out.reserve(nq * elanes * sizeof(T));
+        unsigned long long* w = this->reset_word(W, s);
+        launch_eval(dx, dy, nq, dev_out ? static_cast<T*>(out) : W.out.as<T>(), dev_out ? stride : elanes, s,
+                    true, w);
         NDI_HIP(hipGetLastError());
-        F = read_word(s);
-        const uint64_t rows = std::min<uint64_t>(F, nq);
-        if (o.out_memspace != NDI_MEM_DEVICE && rows)
-          NDI_HIP(hipMemcpy2DAsync(out, stride * sizeof(T), out_buf.p, elanes * sizeof(T), elanes * sizeof(T), rows,
-                                   hipMemcpyDeviceToHost, s));
-      } else {
-        F = first_fail_dev(dx, dy, nq, s);
-        const uint64_t rows = std::min<uint64_t>(F, nq);
-        if (rows) {
-          if (o.out_memspace == NDI_MEM_DEVICE) {
-            launch_eval(dx, dy, rows, static_cast<T*>(out), stride, s, false, nullptr);
-            NDI_HIP(hipGetLastError());
-          } else {
-            out_buf.reserve(rows * elanes * sizeof(T));
-            launch_eval(dx, dy, rows, out_buf.as<T>(), elanes, s, false, nullptr);
-            NDI_HIP(hipGetLastError());
-            NDI_HIP(hipMemcpy2DAsync(out, stride * sizeof(T), out_buf.p, elanes * sizeof(T), elanes * sizeof(T), rows,
-                                     hipMemcpyDeviceToHost, s));
-          }
-        }
+        F = this->read_word(W, s);
+        if (!dev_out) this->rows_to_host(out, stride, W.out, std::min<uint64_t>(F, nq), s);
+      } else {   // caller-owned rows: the check pass, the host reads F, then rows [0, F)
+        F = this->first_fail(dx, dy, nq, W, s);
+        this->eval_rows(dx, dy, std::min<uint64_t>(F, nq), out, stride, o.out_memspace, W, s);
       }
       NDI_HIP(hipStreamSynchronize(s));
       if (F < nq) st = diagnose(qx, qy, F, o.q_memspace, F, info);
@@ -200,7 +136,7 @@ struct IntEngine {
   }
 
   ndi_status finish_impl(void* stream, ndi_oob_info* info) {
-    std::lock_guard<std::mutex> lk(mu);
+    std::lock_guard<std::mutex> lk(this->mu);
     auto it = pending.find(stream);
     if (it == pending.end()) return NDI_OK;
     const ndi_status st = it->second.first;
@@ -208,58 +144,6 @@ struct IntEngine {
     pending.erase(it);
     if (st != NDI_OK) tls_error() = pending_err;
     return st;
-  }
-
-  // Rows [0, rows) through a device-output ring (rows already cut at the first failure).  q_begin: flat index of qx[0]
-  // in the caller's batch; shard: reported in every chunk.
-  void ring_rows(const T* dx, const T* dy, uint64_t rows, const ndi_ring_desc* ring, uint64_t stride,
-                 ndi_ring_consumer consume, void* user, hipStream_t s, uint64_t q_begin, uint32_t shard) {
-    const uint32_t ns = ring->n_slots;
-    std::vector<T*> slots(ns);
-    uint64_t rstride = stride;
-    std::unique_lock<std::mutex> rl(ring_own.mu, std::defer_lock);
-    if (ring->slots) {
-      for (uint32_t i = 0; i < ns; ++i) slots[i] = static_cast<T*>(ring->slots[i]);
-    } else {   // library-owned: one allocation, slots interleaved row by row (ndinterp.h)
-      rl.lock();
-      rstride = (uint64_t)ns * stride;
-      ring_own.ensure(1, ring->chunk_queries, rstride * sizeof(T));
-      for (uint32_t i = 0; i < ns; ++i) slots[i] = ring_own.buf.as<T>() + (uint64_t)i * stride;
-    }
-    std::vector<hipEvent_t> waits(ns, nullptr);
-    uint64_t k = 0;
-    for (uint64_t b = 0; b < rows; b += ring->chunk_queries, ++k) {
-      const uint64_t cnt = std::min<uint64_t>(ring->chunk_queries, rows - b);
-      const uint32_t slot = (uint32_t)(k % ns);
-      if (waits[slot]) NDI_HIP(hipStreamWaitEvent(s, waits[slot], 0));
-      waits[slot] = nullptr;
-      launch_eval(dx + b, dy ? dy + b : nullptr, cnt, slots[slot], rstride, s, false, nullptr);
-      NDI_HIP(hipGetLastError());
-      ndi_ring_chunk c{k, q_begin + b, cnt, slots[slot], rstride, slot, shard, (void*)s};
-      waits[slot] = consume ? (hipEvent_t)consume(user, &c) : nullptr;
-    }
-    NDI_HIP(hipStreamSynchronize(s));
-  }
-
-  ndi_status run_ring(const void* qx, const void* qy, uint64_t nq, const ndi_ring_desc* ring,
-                      ndi_ring_consumer consume, void* user, const ndi_eval_opts* opts, ndi_oob_info* info) {
-    ndi_eval_opts o{};
-    if (const ndi_status vs = take_opts(opts, o); vs != NDI_OK) return vs;
-    if (o.path == NDI_PATH_BUCKETED)
-      return fail(NDI_UNSUPPORTED, "NDI_PATH_BUCKETED is not available for integer element types (AUTO / GATHER)");
-    uint64_t stride = 0;
-    if (const ndi_status rs = check_ring_desc(ring, elanes, &stride); rs != NDI_OK) return rs;
-    if (nq && !qx) return fail(NDI_BAD_ARG, "null query pointer");
-    if (info) *info = ndi_oob_info{0, 0.0, 0, NDI_OK};
-    if (nq == 0) return NDI_OK;
-    DeviceGuard dg(dev);
-    std::lock_guard<std::mutex> lk(mu);
-    hipStream_t s = (hipStream_t)o.stream;
-    const T* dx = stage(qx, nq, o.q_memspace, qx_buf, s);
-    const T* dy = stage(qy, nq, o.q_memspace, qy_buf, s);
-    const uint64_t F = first_fail_dev(dx, dy, nq, s);
-    ring_rows(dx, dy, std::min<uint64_t>(F, nq), ring, stride, consume, user, s, 0, 0);
-    return F < nq ? diagnose(qx, qy, F, o.q_memspace, F, info) : NDI_OK;
   }
 };
 
@@ -315,12 +199,7 @@ struct Interp1DIntImpl final : Interp1DBase, IntEngine<T> {
     for (uint64_t l = 0; l < lanes; ++l) {
       T res;
       const int op = int_calc_frac_host<T>(hx[i], r[l].v, hx[i + 1], r[lanes + l].v, x, res);
-      if (op >= 0) {
-        static const char* const names[4] = {"subtract", "multiply", "add", "divide"};
-        info->axis = op;
-        info->status = NDI_INT_OVERFLOW;
-        return fail(NDI_INT_OVERFLOW, "attempt to %s with overflow", names[op]);
-      }
+      if (op >= 0) return this->overflow(op, info);
     }
     return fail(NDI_HIP_ERROR, "integer evaluation reported query %lld as failing, but it evaluates", (long long)x);
   }
@@ -347,17 +226,8 @@ struct Interp1DIntImpl final : Interp1DBase, IntEngine<T> {
                        const ndi_eval_opts* opts, ndi_oob_info* info) override {
     return this->run_ring(q, nullptr, nq, ring, consume, user, opts, info);
   }
-  ndi_status trim() override {
-    DeviceGuard dg(device);
-    std::lock_guard<std::mutex> lk(this->mu);
-    std::lock_guard<std::mutex> rl(this->ring_own.mu);
-    this->qx_buf.release();
-    this->qy_buf.release();
-    this->out_buf.release();
-    this->ring_own.clear();
-    return NDI_OK;
-  }
-  uint64_t scratch_sets() override { return this->out_buf.p || this->qx_buf.p ? 1 : 0; }
+  ndi_status trim() override { return this->trim_impl(); }
+  uint64_t scratch_sets() override { return this->scratch.out.p || this->scratch.qx.p ? 1 : 0; }
 
   // build from host knots and device-resident data
   void build(const T* data_dev) {
@@ -379,8 +249,8 @@ struct Interp1DIntImpl final : Interp1DBase, IntEngine<T> {
     std::unique_ptr<Interp1DIntImpl<T>> c(new Interp1DIntImpl<T>());
     {
       DeviceGuard dg(d);
-      c->dtype = dtype; c->device = d; c->lanes = lanes; c->n = n; c->hx = hx;
-      c->dev = d; c->elanes = lanes; c->emode = this->emode;
+      set_scalars(*c, dtype, d, this->emode, lanes);
+      c->n = n; c->hx = hx;
       c->knots.reserve(knots.bytes); c->rec.reserve(rec.bytes); c->iv.reserve(iv.bytes);
     }
     copy_across_devices(c->knots.p, d, knots.p, device, knots.bytes);
@@ -396,23 +266,10 @@ static ndi_status create1d_int(const ndi_interp1d_desc& d, Interp1DBase** out) {
   DeviceGuard dg(d.device);
   Range rg("ndi_interp1d_create");
   std::unique_ptr<Interp1DIntImpl<T>> h(new Interp1DIntImpl<T>());
-  h->dtype = d.dtype;
-  h->device = h->dev = d.device;
-  h->emode = d.extrapolate ? EX_YES : EX_NO;
+  set_scalars(*h, d.dtype, d.device, d.extrapolate ? EX_YES : EX_NO, d.lanes);
   h->n = d.n;
-  h->lanes = h->elanes = d.lanes;
   h->hx = d.x ? fetch_axis<T>(d.x, d.x_len, d.memspace) : default_axis<T>(d.n);
-  const uint64_t x_len = d.x ? d.x_len : d.n;
-  if (d.validate) {
-    ndi_status st = check_axis_1d<T>(h->hx.data(), x_len, d.n, d.strategy);
-    if (st != NDI_OK) return st;
-  } else if (x_len != d.n || d.n < 2) {
-    return fail(NDI_BAD_ARG, "unvalidated create with inconsistent sizes (x_len %llu, n %llu)",
-                (unsigned long long)x_len, (unsigned long long)d.n);
-  }
-  if (d.lanes == 0) return fail(NDI_BAD_ARG, "lanes must be >= 1");
-  if (d.n > MAX_KNOTS) return fail(NDI_UNSUPPORTED, "more than %llu knots", (unsigned long long)MAX_KNOTS);
-  if (!d.data) return fail(NDI_BAD_ARG, "null data pointer");
+  if (const ndi_status st = check_desc_1d(d, h->hx.data()); st != NDI_OK) return st;
   const size_t bytes = (size_t)d.n * d.lanes * sizeof(T);
   DevBuf tmp;
   const T* src = static_cast<const T*>(d.data);
@@ -488,12 +345,7 @@ struct Interp2DIntImpl final : Interp2DBase, IntEngine<T> {
       int op = int_calc_frac_host<T>(x1, a[l].v, x2, b[l].v, x, z1);
       if (op < 0) op = int_calc_frac_host<T>(x1, a[lanes + l].v, x2, b[lanes + l].v, x, z2);
       if (op < 0) op = int_calc_frac_host<T>(y1, z1, y2, z2, y, res);
-      if (op >= 0) {
-        static const char* const names[4] = {"subtract", "multiply", "add", "divide"};
-        info->axis = op;
-        info->status = NDI_INT_OVERFLOW;
-        return fail(NDI_INT_OVERFLOW, "attempt to %s with overflow", names[op]);
-      }
+      if (op >= 0) return this->overflow(op, info);
     }
     return fail(NDI_HIP_ERROR, "integer evaluation reported a query as failing, but it evaluates");
   }
@@ -509,16 +361,7 @@ struct Interp2DIntImpl final : Interp2DBase, IntEngine<T> {
     if (nq && !qy) return fail(NDI_BAD_ARG, "null query pointer");
     return this->run_ring(qx, qy, nq, ring, consume, user, opts, info);
   }
-  ndi_status trim() override {
-    DeviceGuard dg(device);
-    std::lock_guard<std::mutex> lk(this->mu);
-    std::lock_guard<std::mutex> rl(this->ring_own.mu);
-    this->qx_buf.release();
-    this->qy_buf.release();
-    this->out_buf.release();
-    this->ring_own.clear();
-    return NDI_OK;
-  }
+  ndi_status trim() override { return this->trim_impl(); }
   ndi_status probe_ceiling(uint64_t, void*, uint64_t, void*, int, double*) override {
     return fail(NDI_UNSUPPORTED, "probe_ceiling measures the float gather; not available for integer handles");
   }
@@ -556,8 +399,8 @@ struct Interp2DIntImpl final : Interp2DBase, IntEngine<T> {
     std::unique_ptr<Interp2DIntImpl<T>> c(new Interp2DIntImpl<T>());
     {
       DeviceGuard dg(d);
-      c->dtype = dtype; c->device = d; c->lanes = lanes; c->nx = nx; c->ny = ny; c->hx = hx; c->hy = hy;
-      c->dev = d; c->elanes = lanes; c->emode = this->emode;
+      set_scalars(*c, dtype, d, this->emode, lanes);
+      c->nx = nx; c->ny = ny; c->hx = hx; c->hy = hy;
       c->kx.reserve(kx.bytes); c->ky.reserve(ky.bytes); c->rec.reserve(rec.bytes);
       c->pbad.reserve(pbad.bytes); c->yiv.reserve(yiv.bytes);
     }
@@ -576,24 +419,12 @@ static ndi_status create2d_int(const ndi_interp2d_desc& d, Interp2DBase** out) {
   DeviceGuard dg(d.device);
   Range rg("ndi_interp2d_create");
   std::unique_ptr<Interp2DIntImpl<T>> h(new Interp2DIntImpl<T>());
-  h->dtype = d.dtype;
-  h->device = h->dev = d.device;
-  h->emode = d.extrapolate ? EX_YES : EX_NO;
+  set_scalars(*h, d.dtype, d.device, d.extrapolate ? EX_YES : EX_NO, d.lanes);
   h->nx = d.nx;
   h->ny = d.ny;
-  h->lanes = h->elanes = d.lanes;
   h->hx = d.x ? fetch_axis<T>(d.x, d.x_len, d.memspace) : default_axis<T>(d.nx);
   h->hy = d.y ? fetch_axis<T>(d.y, d.y_len, d.memspace) : default_axis<T>(d.ny);
-  const uint64_t x_len = d.x ? d.x_len : d.nx, y_len = d.y ? d.y_len : d.ny;
-  if (d.validate) {
-    ndi_status st = check_axes_2d<T>(h->hx.data(), x_len, h->hy.data(), y_len, d.nx, d.ny);
-    if (st != NDI_OK) return st;
-  } else if (x_len != d.nx || y_len != d.ny || d.nx < 2 || d.ny < 2) {
-    return fail(NDI_BAD_ARG, "unvalidated create with inconsistent sizes");
-  }
-  if (d.lanes == 0) return fail(NDI_BAD_ARG, "lanes must be >= 1");
-  if (d.nx > MAX_KNOTS || d.ny > MAX_KNOTS) return fail(NDI_UNSUPPORTED, "too many knots");
-  if (!d.data) return fail(NDI_BAD_ARG, "null data pointer");
+  if (const ndi_status st = check_desc_2d(d, h->hx.data(), h->hy.data()); st != NDI_OK) return st;
   const size_t bytes = (size_t)d.nx * d.ny * d.lanes * sizeof(T);
   DevBuf tmp;
   const T* src = static_cast<const T*>(d.data);
@@ -652,55 +483,4 @@ static ndi_status create_int_locator(int device, const void* knots, uint64_t n, 
   NDI_HIP(hipMemcpy(h->knots.p, x.data(), n * sizeof(T), hipMemcpyHostToDevice));
   *out = h.release();
   return NDI_OK;
-}
-
-// ---- sharded ----------------------------------------------------------------------------------------------------
-// The shards' first failures are found block by block (each on its handle's device and stream), the minimum F is the
-// serial loop's first failure, then every shard produces its rows below F -- into its output or through its ring.
-template <class T, class Impl>
-static ndi_status sharded_int(const std::vector<Impl*>& H, const void* qx, const void* qy, uint64_t nq,
-                              const ndi_shard_io* io, uint64_t stride, const ndi_ring_desc* rings,
-                              ndi_ring_consumer consume, void* user, const ndi_eval_opts& o, ndi_oob_info* info) {
-  if (o.path == NDI_PATH_BUCKETED)
-    return fail(NDI_UNSUPPORTED, "NDI_PATH_BUCKETED is not available for integer element types (AUTO / GATHER)");
-  if (info) *info = ndi_oob_info{0, 0.0, 0, NDI_OK};
-  const uint32_t ns = (uint32_t)H.size();
-  std::vector<uint64_t> lo(ns), hi(ns);
-  std::vector<const T*> px(ns), py(ns);
-  uint64_t F = NO_FAIL;
-  for (uint32_t i = 0; i < ns; ++i) {
-    shard_range(nq, i, ns, &lo[i], &hi[i]);
-    const bool own = io && io[i].q;
-    px[i] = own ? static_cast<const T*>(io[i].q) : static_cast<const T*>(qx) + lo[i];
-    py[i] = own ? static_cast<const T*>(io[i].qy) : (qy ? static_cast<const T*>(qy) + lo[i] : nullptr);
-  }
-  for (uint32_t i = 0; i < ns; ++i) {
-    if (hi[i] == lo[i]) continue;
-    DeviceGuard dg(H[i]->dev);
-    std::lock_guard<std::mutex> lk(H[i]->mu);
-    const uint64_t f = H[i]->first_fail(px[i], py[i], hi[i] - lo[i], o.q_memspace, (hipStream_t)(io ? io[i].stream : nullptr));
-    if (f != NO_FAIL) F = std::min<uint64_t>(F, lo[i] + f);
-  }
-  for (uint32_t i = 0; i < ns; ++i) {
-    const uint64_t end = std::min<uint64_t>(hi[i], F);
-    if (end <= lo[i]) continue;
-    DeviceGuard dg(H[i]->dev);
-    std::lock_guard<std::mutex> lk(H[i]->mu);
-    hipStream_t s = (hipStream_t)(io ? io[i].stream : nullptr);
-    if (rings) {
-      uint64_t rs = 0;
-      if (const ndi_status st = check_ring_desc(&rings[i], H[i]->elanes, &rs); st != NDI_OK) return st;
-      const T* dx = H[i]->stage(px[i], end - lo[i], o.q_memspace, H[i]->qx_buf, s);
-      const T* dy = H[i]->stage(py[i], end - lo[i], o.q_memspace, H[i]->qy_buf, s);
-      H[i]->ring_rows(dx, dy, end - lo[i], &rings[i], rs, consume, user, s, lo[i], i);
-    } else {
-      H[i]->eval_rows(px[i], py[i], end - lo[i], io[i].out, stride, o.q_memspace, o.out_memspace, s);
-      NDI_HIP(hipStreamSynchronize(s));
-    }
-  }
-  if (F >= nq) return NDI_OK;
-  uint32_t owner = 0;
-  while (owner + 1 < ns && F >= hi[owner]) ++owner;
-  DeviceGuard dg(H[owner]->dev);
-  return H[owner]->diagnose(px[owner], py[owner], F - lo[owner], o.q_memspace, F, info);
 }

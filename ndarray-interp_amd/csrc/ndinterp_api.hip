@@ -2535,6 +2535,40 @@ static std::vector<T> fetch_axis(const void* p, uint64_t len, int memspace) {
   return v;
 }
 
+// The descriptor checks every create makes once the axes are on the host, in the order of the reference's builders
+// (interp1d/mod.rs:449-471, interp2d/mod.rs): the float, the integer and the half handles alike.  A: the axis as the
+// family keeps it on the host (T, or the f32 images of f16 / bf16 knots).
+template <class A>
+static ndi_status check_desc_1d(const ndi_interp1d_desc& d, const A* x) {
+  const uint64_t x_len = d.x ? d.x_len : d.n;
+  if (d.validate) {
+    ndi_status st = check_axis_1d<A>(x, x_len, d.n, d.strategy);
+    if (st != NDI_OK) return st;
+  } else if (x_len != d.n || d.n < min_len_1d(d.strategy)) {
+    return fail(NDI_BAD_ARG, "unvalidated create with inconsistent sizes (x_len %llu, n %llu)",
+                (unsigned long long)x_len, (unsigned long long)d.n);
+  }
+  if (d.lanes == 0) return fail(NDI_BAD_ARG, "lanes must be >= 1");
+  if (d.n > MAX_KNOTS) return fail(NDI_UNSUPPORTED, "more than %llu knots", (unsigned long long)MAX_KNOTS);
+  if (!d.data) return fail(NDI_BAD_ARG, "null data pointer");
+  return NDI_OK;
+}
+
+template <class A>
+static ndi_status check_desc_2d(const ndi_interp2d_desc& d, const A* x, const A* y) {
+  const uint64_t x_len = d.x ? d.x_len : d.nx, y_len = d.y ? d.y_len : d.ny;
+  if (d.validate) {
+    ndi_status st = check_axes_2d<A>(x, x_len, y, y_len, d.nx, d.ny);
+    if (st != NDI_OK) return st;
+  } else if (x_len != d.nx || y_len != d.ny || d.nx < 2 || d.ny < 2) {
+    return fail(NDI_BAD_ARG, "unvalidated create with inconsistent sizes");
+  }
+  if (d.lanes == 0) return fail(NDI_BAD_ARG, "lanes must be >= 1");
+  if (d.nx > MAX_KNOTS || d.ny > MAX_KNOTS) return fail(NDI_UNSUPPORTED, "too many knots");
+  if (!d.data) return fail(NDI_BAD_ARG, "null data pointer");
+  return NDI_OK;
+}
+
 template <class T>
 static ndi_status create1d(const ndi_interp1d_desc& d, Interp1DBase** out, const void* dydx = nullptr) {
   DeviceGuard dg(d.device);
@@ -2552,17 +2586,7 @@ static ndi_status create1d(const ndi_interp1d_desc& d, Interp1DBase** out, const
   BuildClock clk;
   std::vector<T> x = d.x ? fetch_axis<T>(d.x, d.x_len, d.memspace) : default_axis<T>(d.n);
   clk.mark("fetch axis");
-  const uint64_t x_len = d.x ? d.x_len : d.n;
-  if (d.validate) {
-    ndi_status st = check_axis_1d<T>(x.data(), x_len, d.n, d.strategy);
-    if (st != NDI_OK) return st;
-  } else if (x_len != d.n || d.n < min_len_1d(d.strategy)) {
-    return fail(NDI_BAD_ARG, "unvalidated create with inconsistent sizes (x_len %llu, n %llu)",
-                (unsigned long long)x_len, (unsigned long long)d.n);
-  }
-  if (d.lanes == 0) return fail(NDI_BAD_ARG, "lanes must be >= 1");
-  if (d.n > MAX_KNOTS) return fail(NDI_UNSUPPORTED, "more than %llu knots", (unsigned long long)MAX_KNOTS);
-  if (!d.data) return fail(NDI_BAD_ARG, "null data pointer");
+  if (const ndi_status st = check_desc_1d(d, x.data()); st != NDI_OK) return st;
   clk.mark("validate");
   h->adopt_arena(cubic, cubic);
   h->pyr.upload(x.data(), d.n);
@@ -3893,16 +3917,7 @@ static ndi_status create2d(const ndi_interp2d_desc& d, Interp2DBase** out) {
   h->lanes = d.lanes;
   std::vector<T> x = d.x ? fetch_axis<T>(d.x, d.x_len, d.memspace) : default_axis<T>(d.nx);
   std::vector<T> y = d.y ? fetch_axis<T>(d.y, d.y_len, d.memspace) : default_axis<T>(d.ny);
-  const uint64_t x_len = d.x ? d.x_len : d.nx, y_len = d.y ? d.y_len : d.ny;
-  if (d.validate) {
-    ndi_status st = check_axes_2d<T>(x.data(), x_len, y.data(), y_len, d.nx, d.ny);
-    if (st != NDI_OK) return st;
-  } else if (x_len != d.nx || y_len != d.ny || d.nx < 2 || d.ny < 2) {
-    return fail(NDI_BAD_ARG, "unvalidated create with inconsistent sizes");
-  }
-  if (d.lanes == 0) return fail(NDI_BAD_ARG, "lanes must be >= 1");
-  if (d.nx > MAX_KNOTS || d.ny > MAX_KNOTS) return fail(NDI_UNSUPPORTED, "too many knots");
-  if (!d.data) return fail(NDI_BAD_ARG, "null data pointer");
+  if (const ndi_status st = check_desc_2d(d, x.data(), y.data()); st != NDI_OK) return st;
   h->px.upload(x.data(), d.nx);
   h->py.upload(y.data(), d.ny);
   const size_t bytes = (size_t)d.nx * d.ny * d.lanes * sizeof(T);
@@ -4235,10 +4250,10 @@ struct ShardedCallScope {
   }
 };
 
-template <class T>
-struct Job1 {
-  std::vector<Interp1DImpl<T>*> H;
-  const void* q;
+// The arguments of a sharded entry point (qy: 2-D only; out_stride or rings / consume / user).
+struct ShardCall {
+  const void* qx;
+  const void* qy;
   uint64_t nq;
   const ndi_shard_io* io;
   uint64_t out_stride;
@@ -4246,8 +4261,14 @@ struct Job1 {
   ndi_ring_consumer consume;
   void* user;
   ndi_eval_opts o;
+};
+
+template <class T>
+struct Job1 : ShardCall {
+  std::vector<Interp1DImpl<T>*> H;
+  explicit Job1(const ShardCall& c) : ShardCall(c) {}
   const void* q_src(uint32_t i, uint32_t n) const {
-    return (io && io[i].q) ? io[i].q : (const void*)((const T*)q + shard_lo(nq, i, n));
+    return (io && io[i].q) ? io[i].q : (const void*)((const T*)qx + shard_lo(nq, i, n));
   }
 };
 
@@ -4295,17 +4316,9 @@ struct Shard1 {
 };
 
 template <class T>
-struct Job2 {
+struct Job2 : ShardCall {
   std::vector<Interp2DImpl<T>*> H;
-  const void* qx;
-  const void* qy;
-  uint64_t nq;
-  const ndi_shard_io* io;
-  uint64_t out_stride;
-  const ndi_ring_desc* rings;
-  ndi_ring_consumer consume;
-  void* user;
-  ndi_eval_opts o;
+  explicit Job2(const ShardCall& c) : ShardCall(c) {}
   const void* qx_src(uint32_t i, uint32_t n) const {
     return (io && io[i].q) ? io[i].q : (const void*)((const T*)qx + shard_lo(nq, i, n));
   }
@@ -4414,6 +4427,11 @@ static ndi_status sharded2d(Job2<T>& J, ndi_oob_info* info) {
   const unsigned long long lx = F[0] == NO_FAIL ? NO_FAIL : F[0] - lo, ly = F[1] == NO_FAIL ? NO_FAIL : F[1] - lo;
   return J.H[w]->report(J.qx_src(w, n), J.qy_src(w, n), J.o.q_memspace, lx, ly, lo, info);
 }
+
+// ---------------------------------------------------------------------------------------------
+// the host engine the narrow element types share (integer and half handles below)
+// ---------------------------------------------------------------------------------------------
+#include "narrow_host.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // integer element types (i32 / i64): Linear and Bilinear
@@ -4773,6 +4791,55 @@ static ndi_status check_sharded_args(const Handle* const* handles, uint32_t n, c
   return NDI_OK;
 }
 
+// One sharded call of handles whose implementation is Impl, a NarrowEngine (integer and half handles).
+template <class Impl, class Handle>
+static ndi_status sharded_narrow_call(const Handle* const* handles, uint32_t n, const ndi::ShardCall& c,
+                                      ndi_oob_info* info) {
+  std::vector<Impl*> H;
+  const ndi_status st = gather_handles(handles, n, handles[0]->impl->dtype, H);
+  if (st != NDI_OK) return st;
+  return ndi::sharded_narrow(std::vector<ndi::NarrowEngine<typename Impl::Elem>*>(H.begin(), H.end()), c, info);
+}
+
+// The element type of a sharded call is the first handle's (gather_handles holds the others to it).
+static ndi_status sharded_call(const ndi_interp1d* const* handles, uint32_t n, const ndi::ShardCall& c,
+                               ndi_oob_info* info) {
+  const int dtype = handles[0]->impl->dtype;
+  switch (dtype) {
+    case NDI_I32: return sharded_narrow_call<ndi::Interp1DIntImpl<int32_t>>(handles, n, c, info);
+    case NDI_I64: return sharded_narrow_call<ndi::Interp1DIntImpl<int64_t>>(handles, n, c, info);
+    case NDI_F16: return sharded_narrow_call<ndi::Interp1DHalfImpl<ndi::HF_F16>>(handles, n, c, info);
+    case NDI_BF16: return sharded_narrow_call<ndi::Interp1DHalfImpl<ndi::HF_BF16>>(handles, n, c, info);
+    case NDI_F32: {
+      ndi::Job1<float> J(c);
+      const ndi_status st = gather_handles(handles, n, dtype, J.H);
+      return st != NDI_OK ? st : ndi::sharded1d<float>(J, info);
+    }
+  }
+  ndi::Job1<double> J(c);
+  const ndi_status st = gather_handles(handles, n, dtype, J.H);
+  return st != NDI_OK ? st : ndi::sharded1d<double>(J, info);
+}
+
+static ndi_status sharded_call(const ndi_interp2d* const* handles, uint32_t n, const ndi::ShardCall& c,
+                               ndi_oob_info* info) {
+  const int dtype = handles[0]->impl->dtype;
+  switch (dtype) {
+    case NDI_I32: return sharded_narrow_call<ndi::Interp2DIntImpl<int32_t>>(handles, n, c, info);
+    case NDI_I64: return sharded_narrow_call<ndi::Interp2DIntImpl<int64_t>>(handles, n, c, info);
+    case NDI_F16: return sharded_narrow_call<ndi::Interp2DHalfImpl<ndi::HF_F16>>(handles, n, c, info);
+    case NDI_BF16: return sharded_narrow_call<ndi::Interp2DHalfImpl<ndi::HF_BF16>>(handles, n, c, info);
+    case NDI_F32: {
+      ndi::Job2<float> J(c);
+      const ndi_status st = gather_handles(handles, n, dtype, J.H);
+      return st != NDI_OK ? st : ndi::sharded2d<float>(J, info);
+    }
+  }
+  ndi::Job2<double> J(c);
+  const ndi_status st = gather_handles(handles, n, dtype, J.H);
+  return st != NDI_OK ? st : ndi::sharded2d<double>(J, info);
+}
+
 NDI_API ndi_status ndi_interp1d_eval_sharded(const ndi_interp1d* const* handles, uint32_t n_shards, const void* q,
                                              uint64_t nq, const ndi_shard_io* io, uint64_t out_row_stride,
                                              const ndi_eval_opts* opts, ndi_oob_info* info) {
@@ -4780,37 +4847,9 @@ NDI_API ndi_status ndi_interp1d_eval_sharded(const ndi_interp1d* const* handles,
   if (st != NDI_OK || nq == 0) return st;
   NDI_TRY
   ndi::Range rg("ndi_interp1d_eval_sharded");
-  const int dtype = handles[0]->impl->dtype;
-  ndi_eval_opts o{};
-  if (const ndi_status vs__ = ndi::take_opts(opts, o); vs__ != NDI_OK) return vs__;
-  if (dtype == NDI_I32) {
-    std::vector<ndi::Interp1DIntImpl<int32_t>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_int<int32_t>(H, q, nullptr, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
-  }
-  if (dtype == NDI_I64) {
-    std::vector<ndi::Interp1DIntImpl<int64_t>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_int<int64_t>(H, q, nullptr, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
-  }
-  if (dtype == NDI_F16) {
-    std::vector<ndi::Interp1DHalfImpl<ndi::HF_F16>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_F16>(H, q, nullptr, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
-  }
-  if (dtype == NDI_BF16) {
-    std::vector<ndi::Interp1DHalfImpl<ndi::HF_BF16>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_BF16>(H, q, nullptr, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
-  }
-  if (dtype == NDI_F32) {
-    ndi::Job1<float> J{{}, q, nq, io, out_row_stride, nullptr, nullptr, nullptr, o};
-    st = gather_handles(handles, n_shards, dtype, J.H);
-    return st != NDI_OK ? st : ndi::sharded1d<float>(J, info);
-  }
-  ndi::Job1<double> J{{}, q, nq, io, out_row_stride, nullptr, nullptr, nullptr, o};
-  st = gather_handles(handles, n_shards, dtype, J.H);
-  return st != NDI_OK ? st : ndi::sharded1d<double>(J, info);
+  ndi::ShardCall c{q, nullptr, nq, io, out_row_stride, nullptr, nullptr, nullptr, {}};
+  if (const ndi_status vs__ = ndi::take_opts(opts, c.o); vs__ != NDI_OK) return vs__;
+  return sharded_call(handles, n_shards, c, info);
   NDI_CATCH
 }
 
@@ -4822,37 +4861,9 @@ NDI_API ndi_status ndi_interp1d_eval_ring_sharded(const ndi_interp1d* const* han
   if (st != NDI_OK || nq == 0) return st;
   NDI_TRY
   ndi::Range rg("ndi_interp1d_eval_ring_sharded");
-  const int dtype = handles[0]->impl->dtype;
-  ndi_eval_opts o{};
-  if (const ndi_status vs__ = ndi::take_opts(opts, o); vs__ != NDI_OK) return vs__;
-  if (dtype == NDI_I32) {
-    std::vector<ndi::Interp1DIntImpl<int32_t>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_int<int32_t>(H, q, nullptr, nq, io, 0, rings, consume, user, o, info);
-  }
-  if (dtype == NDI_I64) {
-    std::vector<ndi::Interp1DIntImpl<int64_t>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_int<int64_t>(H, q, nullptr, nq, io, 0, rings, consume, user, o, info);
-  }
-  if (dtype == NDI_F16) {
-    std::vector<ndi::Interp1DHalfImpl<ndi::HF_F16>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_F16>(H, q, nullptr, nq, io, 0, rings, consume, user, o, info);
-  }
-  if (dtype == NDI_BF16) {
-    std::vector<ndi::Interp1DHalfImpl<ndi::HF_BF16>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_BF16>(H, q, nullptr, nq, io, 0, rings, consume, user, o, info);
-  }
-  if (dtype == NDI_F32) {
-    ndi::Job1<float> J{{}, q, nq, io, 0, rings, consume, user, o};
-    st = gather_handles(handles, n_shards, dtype, J.H);
-    return st != NDI_OK ? st : ndi::sharded1d<float>(J, info);
-  }
-  ndi::Job1<double> J{{}, q, nq, io, 0, rings, consume, user, o};
-  st = gather_handles(handles, n_shards, dtype, J.H);
-  return st != NDI_OK ? st : ndi::sharded1d<double>(J, info);
+  ndi::ShardCall c{q, nullptr, nq, io, 0, rings, consume, user, {}};
+  if (const ndi_status vs__ = ndi::take_opts(opts, c.o); vs__ != NDI_OK) return vs__;
+  return sharded_call(handles, n_shards, c, info);
   NDI_CATCH
 }
 
@@ -4864,37 +4875,9 @@ NDI_API ndi_status ndi_interp2d_eval_sharded(const ndi_interp2d* const* handles,
   if (st != NDI_OK || nq == 0) return st;
   NDI_TRY
   ndi::Range rg("ndi_interp2d_eval_sharded");
-  const int dtype = handles[0]->impl->dtype;
-  ndi_eval_opts o{};
-  if (const ndi_status vs__ = ndi::take_opts(opts, o); vs__ != NDI_OK) return vs__;
-  if (dtype == NDI_I32) {
-    std::vector<ndi::Interp2DIntImpl<int32_t>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_int<int32_t>(H, qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
-  }
-  if (dtype == NDI_I64) {
-    std::vector<ndi::Interp2DIntImpl<int64_t>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_int<int64_t>(H, qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
-  }
-  if (dtype == NDI_F16) {
-    std::vector<ndi::Interp2DHalfImpl<ndi::HF_F16>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_F16>(H, qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
-  }
-  if (dtype == NDI_BF16) {
-    std::vector<ndi::Interp2DHalfImpl<ndi::HF_BF16>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_BF16>(H, qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, o, info);
-  }
-  if (dtype == NDI_F32) {
-    ndi::Job2<float> J{{}, qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, o};
-    st = gather_handles(handles, n_shards, dtype, J.H);
-    return st != NDI_OK ? st : ndi::sharded2d<float>(J, info);
-  }
-  ndi::Job2<double> J{{}, qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, o};
-  st = gather_handles(handles, n_shards, dtype, J.H);
-  return st != NDI_OK ? st : ndi::sharded2d<double>(J, info);
+  ndi::ShardCall c{qx, qy, nq, io, out_row_stride, nullptr, nullptr, nullptr, {}};
+  if (const ndi_status vs__ = ndi::take_opts(opts, c.o); vs__ != NDI_OK) return vs__;
+  return sharded_call(handles, n_shards, c, info);
   NDI_CATCH
 }
 
@@ -4907,37 +4890,9 @@ NDI_API ndi_status ndi_interp2d_eval_ring_sharded(const ndi_interp2d* const* han
   if (st != NDI_OK || nq == 0) return st;
   NDI_TRY
   ndi::Range rg("ndi_interp2d_eval_ring_sharded");
-  const int dtype = handles[0]->impl->dtype;
-  ndi_eval_opts o{};
-  if (const ndi_status vs__ = ndi::take_opts(opts, o); vs__ != NDI_OK) return vs__;
-  if (dtype == NDI_I32) {
-    std::vector<ndi::Interp2DIntImpl<int32_t>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_int<int32_t>(H, qx, qy, nq, io, 0, rings, consume, user, o, info);
-  }
-  if (dtype == NDI_I64) {
-    std::vector<ndi::Interp2DIntImpl<int64_t>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_int<int64_t>(H, qx, qy, nq, io, 0, rings, consume, user, o, info);
-  }
-  if (dtype == NDI_F16) {
-    std::vector<ndi::Interp2DHalfImpl<ndi::HF_F16>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_F16>(H, qx, qy, nq, io, 0, rings, consume, user, o, info);
-  }
-  if (dtype == NDI_BF16) {
-    std::vector<ndi::Interp2DHalfImpl<ndi::HF_BF16>*> H;
-    st = gather_handles(handles, n_shards, dtype, H);
-    return st != NDI_OK ? st : ndi::sharded_half<ndi::HF_BF16>(H, qx, qy, nq, io, 0, rings, consume, user, o, info);
-  }
-  if (dtype == NDI_F32) {
-    ndi::Job2<float> J{{}, qx, qy, nq, io, 0, rings, consume, user, o};
-    st = gather_handles(handles, n_shards, dtype, J.H);
-    return st != NDI_OK ? st : ndi::sharded2d<float>(J, info);
-  }
-  ndi::Job2<double> J{{}, qx, qy, nq, io, 0, rings, consume, user, o};
-  st = gather_handles(handles, n_shards, dtype, J.H);
-  return st != NDI_OK ? st : ndi::sharded2d<double>(J, info);
+  ndi::ShardCall c{qx, qy, nq, io, 0, rings, consume, user, {}};
+  if (const ndi_status vs__ = ndi::take_opts(opts, c.o); vs__ != NDI_OK) return vs__;
+  return sharded_call(handles, n_shards, c, info);
   NDI_CATCH
 }
 
