@@ -3,7 +3,8 @@
  * Drop-in boundary for the batched `interp_array` hot path of the Rust crate
  * ndarray-interp v0.6.0 (1D Linear, 1D CubicSpline, 2D Bilinear), plus three 1D strategies the
  * reference leaves to user code: Pchip, Akima and CubicHermite (ndi_strategy1d), and first / second
- * derivatives of the four cubics as handles of their own (ndi_interp1d_derivative).  The reference
+ * derivatives of the four cubics as handles of their own (ndi_interp1d_derivative), and antiderivatives / definite
+ * integrals of every f32 / f64 1D interpolant (ndi_interp1d_antiderivative, ndi_interp1d_integrate).  The reference
  * has no FFI of its own: its boundary is the strategy trait pair plus the inherent
  * methods of Interp1D / Interp2D.  Each entry point below names the reference
  * interface it replaces (paths relative to the reference tree).  A Rust
@@ -317,14 +318,66 @@ ndi_status ndi_interp1d_data(const ndi_interp1d* h, void* data_out, int32_t mems
  * Where continuity holds only to rounding, an interior knot carries the value of the interval to its RIGHT: a query at
  * that knot returns Y[i] exactly, a query just left of it evaluates the left interval's polynomial, whose end value
  * (dy - b[i-1]) / dx of interval i-1 differs from Y[i] by rounding for a first derivative, and for a spline's second
- * derivative by the residual of the Thomas solve at that knot.
+ * derivative by the residual of the Thomas solve at that knot.  An antiderivative handle (ndi_interp1d_antiderivative)
+ * follows the same convention: a query at an interior knot x[i] returns P[i] exactly (interval i at t = 0); a query at the
+ * LAST knot evaluates interval n-2 at t = 1, and that result may differ from P[n-1] by rounding.
  * Y is always re-derived from y, a, b; a k table the source may have kept is never read, so the bits do not depend on
  * whether it kept one.  For NDI_CUBIC_HERMITE, Y[i] is therefore the caller's dydx[i] up to the rounding of
  * ((k dx - dy) + dy) / dx, not its bits.  A derivative handle keeps no k table of its own: the evaluation form that holds
  * {y, k} in LDS re-forms a / b from k and could not reproduce A == B bit for bit, so AUTO gives such handles the forms
  * that read a / b (scalar and short-row data: a measured cost).
- * Not provided: antiderivatives / integrals, second derivatives of the C1 strategies, third derivatives. */
+ * Not provided: second derivatives of the C1 strategies, third derivatives. */
 ndi_status ndi_interp1d_derivative(const ndi_interp1d* h, int32_t nu, ndi_interp1d** out);
+
+/* The antiderivative F of an interpolant as a NEW HANDLE (scipy: CubicSpline.antiderivative(), PchipInterpolator
+ * .antiderivative()), F(x[0]) = +0 for every lane.  It is built on h's device, `h` is only read and stays usable, the new
+ * handle keeps its own copies of what it reads and is destroyed independently; knots and `extrapolate` are h's.
+ * Sources: f32 / f64 handles of the cubic evaluation class (CubicSpline with every boundary kind and per-lane boundaries,
+ * Pchip, Akima, CubicHermite, and their derivative handles) and f32 / f64 Linear handles.  Refused with NDI_BAD_ARG, before
+ * any device work, with a message that names the strategy and the reason: integer handles, f16 / bf16 handles, an
+ * antiderivative handle, a handle whose extrapolation mode is Periodic, a null `h` or `out` (`*out` is cleared first).
+ * Numerical contract -- this project's own.  Every line is one IEEE operation in T, in this order, nothing fused.  Per
+ * interval i and lane, with yl = y[i], yr = y[i+1], a = a[i], b = b[i] and dx = x[i+1] - x[i]:
+ *     cubic class:   dy = yr - yl
+ *                    c1 = (dy + a) * 0.5
+ *                    c2 = (b - (a + a)) / 3
+ *                    c3 = (b - a) * 0.25
+ *                    G(t) = t * (yl + t * (c1 + t * (c2 - t * c3)))
+ *                    I[i] = dx * (yl + (c1 + (c2 - c3)))              (= dx * G(1))
+ *     Linear:        c1 = (yr - yl) * 0.5
+ *                    G(t) = t * (yl + t * c1)
+ *                    I[i] = dx * (yl + c1)
+ *     evaluation:    t = (xq - x[i]) / dx          (the cubic evaluation's t, interval by get_lower_index)
+ *                    F(xq) = P[i] + dx * G(t)
+ * (q(t) = yl + (dy + a) t + (b - 2a) t^2 - (b - a) t^3, and its integral over [0, 1] is (yl + yr) / 2 + (a + b) / 12.)
+ * `extrapolate` continues the end interval's quartic: t falls outside [0, 1].
+ * The prefix table P[n][lanes] is a FIXED blocked sum with B = 256 knots per block; its bits do not depend on the launch
+ * geometry:
+ *     local sums:    S[i] = +0 where i % B == 0, otherwise S[i] = S[i-1] + I[i-1]
+ *     block totals:  T[k] = S[kB + B - 1] + I[kB + B - 1]      the local running sum taken over the block's end
+ *     block offsets: O[0] = +0, O[k+1] = O[k] + T[k]           summed serially
+ *     table:         P[i] = O[i / B] + S[i]                    i = 0 .. n-1
+ * What an antiderivative handle takes: ndi_interp1d_eval in every form (sync, async_launch + ndi_interp1d_finish, host or
+ * device queries and outputs, strided rows; with a HOST output buffer async_launch is accepted and the call completes
+ * before it returns, as for every 1-D handle: the rows are copied out of a staging buffer) with the source's range, NaN and first-error semantics and messages (the
+ * lowest failing flat index is reported, rows before it are written, later rows are untouched; NDI_EVAL_FRESH_OUTPUT and
+ * NDI_EVAL_ROWS_AFTER_ERROR_UNSPECIFIED are accepted and ignored); ndi_interp1d_data (hands back P); ndi_interp1d_clone,
+ * ndi_interp1d_trim, ndi_interp1d_destroy.  ndi_interp1d_coefficients, ndi_interp1d_derivative and
+ * ndi_interp1d_antiderivative of it are NDI_BAD_ARG with a reason; ndi_interp1d_eval_ring, the sharded calls and
+ * NDI_PATH_BUCKETED are NDI_UNSUPPORTED with a message.  A function and its antiderivative are not replicas of each other
+ * (a sharded call that mixes them is refused as any non-replica set is).
+ * Not provided: the Periodic extrapolation mode, second antiderivatives, 2-D, integer and f16 / bf16 element types. */
+ndi_status ndi_interp1d_antiderivative(const ndi_interp1d* h, ndi_interp1d** out);
+
+/* Definite integrals through an antiderivative handle (scipy: .integrate(a, b)): out[j][l] = F(hi[j])[l] - F(lo[j])[l],
+ * one subtraction in T, for nq pairs; `lo`, `hi` are T[nq] in opts->q_memspace, `out` as for ndi_interp1d_eval.  `h` must
+ * be an antiderivative handle (anything else: NDI_BAD_ARG).  lo > hi is allowed and gives the negated integral; lo == hi
+ * gives F - F.  Both searches, both evaluations and the subtraction are ONE evaluation launch.  Errors: the lowest failing
+ * flat index is reported, lo[j] is tested before hi[j]; info->axis is 0 for lo and 1 for hi; rows before the failing index
+ * are written, later rows are untouched, as for ndi_interp1d_eval. */
+ndi_status ndi_interp1d_integrate(const ndi_interp1d* h, const void* lo, const void* hi, uint64_t nq,
+                                  void* out, uint64_t out_row_stride,
+                                  const ndi_eval_opts* opts, ndi_oob_info* info);
 
 /* ---- evaluate ----------------------------------------------------------------
  * Replaces Interp1D::interp_array_into for a flattened query array

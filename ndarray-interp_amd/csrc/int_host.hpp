@@ -216,6 +216,10 @@ struct Interp1DIntImpl final : Interp1DBase, IntEngine<T> {
     return fail(NDI_BAD_ARG, "derivative: an integer handle is a Linear interpolator: its slope jumps at the knots "
                 "(derivative takes f32 / f64 CubicSpline, Pchip, Akima and CubicHermite handles)");
   }
+  ndi_status antiderivative(Interp1DBase**) override {
+    return fail(NDI_BAD_ARG, "antiderivative: an integer handle is a Linear interpolator of a narrow element type: the prefix table would "
+                "round at every knot (antiderivative takes f32 / f64 Linear, CubicSpline, Pchip, Akima and CubicHermite handles)");
+  }
   ndi_status data_table(void* data_out, int memspace) override {   // the values of the slope records {v, m}
     DeviceGuard dg(device);
     NDI_HIP(hipMemcpy2D(data_out, sizeof(T), rec.p, sizeof(IntRec<T>), sizeof(T), n * lanes,

@@ -30,6 +30,7 @@
 #include "kernels.hpp"
 #include "hermite_kernels.hpp"
 #include "derivative_kernels.hpp"
+#include "antiderivative_kernels.hpp"
 
 #define NDI_API extern "C" __attribute__((visibility("default")))
 
@@ -896,6 +897,14 @@ struct Interp1DBase {
   virtual ndi_status derivative(int nu, Interp1DBase** out) = 0;
   // ndi_interp1d_data: the resident data table T[n * lanes]
   virtual ndi_status data_table(void* data_out, int memspace) = 0;
+  // ndi_interp1d_antiderivative: the refusals come before any device work
+  virtual ndi_status antiderivative(Interp1DBase** out) = 0;
+  virtual bool is_antiderivative() const { return false; }
+  // ndi_interp1d_integrate: antiderivative handles only
+  virtual ndi_status integrate(const void* lo, const void* hi, uint64_t nq, void* out, uint64_t out_stride,
+                               const ndi_eval_opts* opts, ndi_oob_info* info) {
+    return fail(NDI_BAD_ARG, "integrate takes an antiderivative handle (ndi_interp1d_antiderivative of this handle)");
+  }
 };
 
 static const char* hermite_rule_name(int rule) {
@@ -2515,7 +2524,11 @@ struct Interp1DImpl final : Interp1DBase {
     *out = h.release();
     return NDI_OK;
   }
+
+  ndi_status antiderivative(Interp1DBase** out) override;   // (defined behind AntiderivImpl)
 };
+
+#include "antiderivative_host.hpp"
 
 template <class T>
 static std::vector<T> default_axis(uint64_t n) {
@@ -4668,6 +4681,29 @@ NDI_API ndi_status ndi_interp1d_derivative(const ndi_interp1d* h, int32_t nu, nd
   NDI_CATCH
 }
 
+// Every refusal is decided before any device work: the argument checks here, the handle's own in its antiderivative().
+NDI_API ndi_status ndi_interp1d_antiderivative(const ndi_interp1d* h, ndi_interp1d** out) {
+  if (!out) return ndi::fail(NDI_BAD_ARG, "null out pointer");
+  *out = nullptr;
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  NDI_TRY
+  ndi::Interp1DBase* impl = nullptr;
+  ndi_status st = h->impl->antiderivative(&impl);
+  if (st != NDI_OK) return st;
+  *out = new ndi_interp1d{impl};
+  return ndi::bounds_verdict(NDI_OK, impl->device);
+  NDI_CATCH
+}
+
+NDI_API ndi_status ndi_interp1d_integrate(const ndi_interp1d* h, const void* lo, const void* hi, uint64_t nq, void* out,
+                                          uint64_t out_row_stride, const ndi_eval_opts* opts, ndi_oob_info* info) {
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  NDI_TRY
+  if (!h->impl->is_antiderivative()) return h->impl->integrate(lo, hi, nq, out, out_row_stride, opts, info);
+  return ndi::bounds_verdict(h->impl->integrate(lo, hi, nq, out, out_row_stride, opts, info), h->impl->device);
+  NDI_CATCH
+}
+
 NDI_API ndi_status ndi_interp1d_data(const ndi_interp1d* h, void* data_out, int32_t memspace) {
   if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
   if (!data_out) return ndi::fail(NDI_BAD_ARG, "null data_out pointer");
@@ -4805,6 +4841,17 @@ static ndi_status sharded_narrow_call(const Handle* const* handles, uint32_t n, 
 static ndi_status sharded_call(const ndi_interp1d* const* handles, uint32_t n, const ndi::ShardCall& c,
                                ndi_oob_info* info) {
   const int dtype = handles[0]->impl->dtype;
+  // antiderivative handles take no sharded call; a set that mixes a function with its antiderivative is no set of
+  // replicas at all (the signatures differ), which is the first thing to say about it
+  bool anti = false;
+  for (uint32_t i = 0; i < n; ++i) anti = anti || handles[i]->impl->is_antiderivative();
+  if (anti) {
+    std::vector<ndi::Interp1DBase*> H;
+    const ndi_status st = gather_handles(handles, n, dtype, H);
+    if (st != NDI_OK) return st;
+    return ndi::fail(NDI_UNSUPPORTED, "the sharded calls do not take antiderivative handles (ndi_interp1d_eval per device "
+                     "serves them)");
+  }
   switch (dtype) {
     case NDI_I32: return sharded_narrow_call<ndi::Interp1DIntImpl<int32_t>>(handles, n, c, info);
     case NDI_I64: return sharded_narrow_call<ndi::Interp1DIntImpl<int64_t>>(handles, n, c, info);

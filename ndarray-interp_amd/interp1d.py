@@ -1,7 +1,8 @@
 """Host-side mirror of the reference's 1-D surface (src/interp1d/mod.rs + strategies/):
 `Interp1DBuilder`, `Interp1D`, the strategy trait pair and the built-in `Linear` and `CubicSpline` -- plus
 `Pchip`, `Akima` and `CubicHermite`, which the reference leaves to user strategies and this build runs on the device,
-and `Interp1D.derivative(nu)` (scipy's name and meaning) for the four cubics.
+and `Interp1D.derivative(nu)` (scipy's name and meaning) for the four cubics, `Interp1D.antiderivative()` and
+`Interp1D.integrate(lo, hi)` for every f32 / f64 strategy.
 
 Names, argument meaning and error behaviour follow the reference so that the parity tests read like
 its own tests.  The built-in strategies override the *batched* hook (`interp_array_into`) and call the
@@ -166,6 +167,21 @@ class _DeviceStrategy1D(Interp1DStrategy):
         d.origin = getattr(self, "origin", type(self))
         return d
 
+    def antiderivative(self) -> "AntiderivativeStrategy":
+        """The antiderivative `F` (`F(x[0]) = 0`) as a finished strategy of its own (ndi_interp1d_antiderivative): a new
+        handle on this handle's device with a prefix table built there.  This strategy stays usable.  Sources the library
+        refuses (include/ndinterp.h lists them) raise `ValueError` with its message."""
+        h = C.c_void_p()
+        st = _capi.lib().ndi_interp1d_antiderivative(self._h, C.byref(h))
+        if st == _capi.BAD_ARG:
+            raise ValueError(_capi.last_error())
+        if st != _capi.OK:
+            raise_builder(st)
+        d = AntiderivativeStrategy()
+        d._h, d._device, d._np_dtype, d._lanes, d._n = h, self._device, self._np_dtype, self._lanes, self._n
+        d.origin = getattr(self, "origin", type(self))
+        return d
+
     # -- evaluate -----------------------------------------------------------------------------
     _takes_fresh = True   # interp_array() may tell this strategy that the output buffer is its own (ndi_eval_flags)
 
@@ -186,6 +202,15 @@ class _DeviceStrategy1D(Interp1DStrategy):
         # an async batch reads the query array until finish(): keep every (possibly converted) copy alive
         if async_launch:
             self._inflight.append(qb)
+        optr, stride = self._output(out2d, qb.memspace, opts)
+        info = _capi.OobInfo()
+        st = _capi.lib().ndi_interp1d_eval(self._h, qb.ptr, qb.size, optr, stride, C.byref(opts), C.byref(info))
+        if st != _capi.OK:
+            raise_eval(st, info, int_query(self._np_dtype, [qb], info))
+
+    def _output(self, out2d, q_memspace, opts):
+        """(pointer, row stride in elements) of a 2-D output buffer; sets `opts.out_memspace` and, where device memory is
+        involved, `opts.stream` to the current stream."""
         if is_torch(out2d):
             if not out2d.is_cuda:
                 raise TypeError("torch output buffers must live on the device; use numpy for host buffers")
@@ -197,13 +222,9 @@ class _DeviceStrategy1D(Interp1DStrategy):
             opts.out_memspace = _capi.MEM_HOST
             optr = out2d.ctypes.data
             stride = out2d.strides[0] // out2d.itemsize if out2d.ndim > 1 and out2d.shape[0] > 1 else self._lanes
-            if qb.memspace == _capi.MEM_DEVICE:
+            if q_memspace == _capi.MEM_DEVICE:
                 opts.stream = current_stream_ptr(self._device)
-        info = _capi.OobInfo()
-        st = _capi.lib().ndi_interp1d_eval(self._h, qb.ptr, qb.size, optr, max(stride, self._lanes),
-                                           C.byref(opts), C.byref(info))
-        if st != _capi.OK:
-            raise_eval(st, info, int_query(self._np_dtype, [qb], info))
+        return optr, max(stride, self._lanes)
 
     def finish(self):
         """Completes `async_launch` evaluations on the current stream and raises their error, if any."""
@@ -550,6 +571,54 @@ class DerivativeStrategy(CubicSplineStrategy):
     origin = None
 
 
+class AntiderivativeStrategy(_DeviceStrategy1D):
+    """The antiderivative of a Linear / CubicSpline / Pchip / Akima / CubicHermite strategy or of a derivative of one
+    (`strategy.antiderivative()`, `Interp1D.antiderivative()`): a handle with a prefix table `P` (`data_table()`) and
+    evaluation kernels of its own.  `interp_array_into`, `finish`, `clone`, `data_table`, `trim` and `release` are the
+    shared ones; `integrate_into` is the definite integral.  `origin`: the class of the strategy it started from.  The
+    ring, the sharded calls, `coefficients`, `derivative` and a second `antiderivative` are refused by the library."""
+
+    origin = None
+    path = _capi.PATH_GATHER   # the one form these handles take (NDI_PATH_BUCKETED is refused, AUTO means this)
+
+    def _refused(self, st):
+        if st in (_capi.BAD_ARG, _capi.UNSUPPORTED):
+            raise ValueError(_capi.last_error())
+        raise_builder(st)
+
+    def derivative(self, nu: int = 1):
+        h = C.c_void_p()
+        self._refused(_capi.lib().ndi_interp1d_derivative(self._h, int(nu), C.byref(h)))
+
+    def antiderivative(self):
+        h = C.c_void_p()
+        self._refused(_capi.lib().ndi_interp1d_antiderivative(self._h, C.byref(h)))
+
+    def coefficients(self, device: bool = False):
+        self._refused(_capi.lib().ndi_interp1d_coefficients(self._h, None, None, _capi.MEM_HOST))
+
+    def integrate_into(self, lo_flat, hi_flat, out2d):
+        """`out2d[j] = F(hi_flat[j]) - F(lo_flat[j])` (ndi_interp1d_integrate: both searches, both evaluations and the
+        subtraction in one evaluation launch).  Both query arrays live in the same memory space; errors name the lowest
+        failing flat index, `lo` before `hi`."""
+        lb, hb = Buf(lo_flat, self._np_dtype), Buf(hi_flat, self._np_dtype)
+        if lb.memspace != hb.memspace or lb.size != hb.size:
+            raise TypeError("integrate_into: lo and hi must have the same length and live in the same memory space")
+        _check_out_dtype(out2d, self._np_dtype)
+        opts = _capi.EvalOpts()
+        opts.q_memspace = lb.memspace
+        opts.path = self.path
+        optr, stride = self._output(out2d, lb.memspace, opts)
+        info = _capi.OobInfo()
+        st = _capi.lib().ndi_interp1d_integrate(self._h, lb.ptr, hb.ptr, lb.size, optr, stride, C.byref(opts), C.byref(info))
+        if st == _capi.OUT_OF_BOUNDS:   # both arrays are x coordinates: `axis` says which one (0: lo, 1: hi)
+            from .errors import _rust_float
+            raise InterpolateError.OutOfBounds(f"x = {_rust_float(info.value)} is not in range", index=int(info.index),
+                                               value=float(info.value), axis=int(info.axis))
+        if st != _capi.OK:
+            raise_eval(st, info)
+
+
 class _LocalCubic(Interp1DStrategyBuilder):
     """Shared builder body of Pchip / Akima / CubicHermite: `.extrapolate(b)` and `.device(d)` as `CubicSpline` has
     them (`extrapolate(True)` continues the first / last interval's polynomial); f32 / f64 only."""
@@ -810,6 +879,47 @@ class Interp1D:
         strat = self.strategy.derivative(nu)
         on_device = is_torch(self.data) and self.data.is_cuda
         return Interp1D(self.x, strat.data_table(device=on_device).reshape(tuple(self.data.shape)), strat)
+
+    def antiderivative(self) -> "Interp1D":
+        """The antiderivative of this interpolator as an interpolator of its own (scipy's `.antiderivative()`, with
+        `F(x[0]) = 0`): same `x`, `data` = the prefix table `P` in this data's shape (a host array for host-built
+        interpolators, a tensor on the strategy's device for device-built ones), strategy an `AntiderivativeStrategy`;
+        `interp`, `interp_array` and `interp_array_into` work on it unchanged.  Sources the library refuses (integer and
+        half element types, the periodic mode, an antiderivative) are a `ValueError` with its reason; strategies that are
+        not the built-in device ones raise `TypeError`."""
+        if not isinstance(self.strategy, _DeviceStrategy1D):
+            raise TypeError("antiderivative needs a built-in device strategy (Linear, CubicSpline, Pchip, Akima or "
+                            f"CubicHermite on f32 / f64 data), got {type(self.strategy).__name__}")
+        strat = self.strategy.antiderivative()
+        on_device = is_torch(self.data) and self.data.is_cuda
+        return Interp1D(self.x, strat.data_table(device=on_device).reshape(tuple(self.data.shape)), strat)
+
+    def integrate(self, lo, hi):
+        """Definite integrals (scipy's `.integrate(a, b)`, batched): `lo`, `hi` arrays of equal shape, host or device;
+        the result has the shape `lo.shape ++ data.shape[1:]` and lives where the queries live.  `lo > hi` gives the
+        negated integral.  On an interpolator that is no antiderivative, its antiderivative is built once, kept on the
+        instance and used."""
+        lo, hi = (v if is_torch(v) else np.asarray(v) for v in (lo, hi))      # (lists and scalars too)
+        if tuple(lo.shape) != tuple(hi.shape):
+            raise Panic(f"ShapeError/IncompatibleShape: incompatible shapes lo: {list(lo.shape)}, hi: {list(hi.shape)}")
+        if not isinstance(self.strategy, AntiderivativeStrategy):
+            if getattr(self, "_antiderivative", None) is None:
+                self._antiderivative = self.antiderivative()
+            return self._antiderivative.integrate(lo, hi)
+        shape = self.get_buffer_shape(tuple(lo.shape))
+        dt = np_dtype_of(self.data)
+        nq = int(np.prod(lo.shape, dtype=np.int64))
+        lanes = int(np.prod(self._lanes_shape(), dtype=np.int64))
+        if is_torch(lo) != is_torch(hi) or (is_torch(lo) and lo.is_cuda != hi.is_cuda):
+            raise TypeError("integrate: lo and hi must live in the same memory space")
+        if is_torch(lo) and lo.is_cuda:
+            import torch
+            out = torch.empty(shape, dtype=torch_dtype(dt), device=lo.device)
+            self.strategy.integrate_into(lo.reshape(-1), hi.reshape(-1), out.view(nq, lanes))
+            return out
+        out = np.zeros(shape, dtype=dt)
+        self.strategy.integrate_into(_host(lo).reshape(-1), _host(hi).reshape(-1), out.reshape(nq, lanes))
+        return out
 
     def interp_array_ring(self, xs, chunk_queries, consumer=None, *, slots=None, n_slots=2):
         """`interp_array` (interp1d/mod.rs:197-211) for outputs larger than device memory: the flattened

@@ -239,6 +239,19 @@ extern "C" {
     pub fn ndi_interp1d_data(h: *const ndi_interp1d, data_out: *mut c_void, memspace: i32) -> i32;
     /// The `nu`-th derivative (1, or 2 for CubicSpline) as a new handle; the header states the numerical contract
     pub fn ndi_interp1d_derivative(h: *const ndi_interp1d, nu: i32, out: *mut *mut ndi_interp1d) -> i32;
+    /// The antiderivative (F(x[0]) = +0) as a new handle; the header states the numerical contract
+    pub fn ndi_interp1d_antiderivative(h: *const ndi_interp1d, out: *mut *mut ndi_interp1d) -> i32;
+    /// `out[j] = F(hi[j]) - F(lo[j])` through an antiderivative handle, one evaluation launch
+    pub fn ndi_interp1d_integrate(
+        h: *const ndi_interp1d,
+        lo: *const c_void,
+        hi: *const c_void,
+        nq: u64,
+        out: *mut c_void,
+        out_row_stride: u64,
+        opts: *const ndi_eval_opts,
+        info: *mut ndi_oob_info,
+    ) -> i32;
     pub fn ndi_interp1d_eval(
         h: *const ndi_interp1d,
         q: *const c_void,
