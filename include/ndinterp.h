@@ -1,7 +1,8 @@
 /* include/ndinterp.h -- C ABI of libndinterp_hip.so (MI355X / gfx950).
  *
  * Drop-in boundary for the batched `interp_array` hot path of the Rust crate
- * ndarray-interp v0.6.0 (1D Linear, 1D CubicSpline, 2D Bilinear), plus three 1D strategies the
+ * ndarray-interp v0.6.0 (1D Linear, 1D CubicSpline, 2D Bilinear), plus a 2D Bicubic strategy
+ * (ndi_interp2d_create_bicubic) and three 1D strategies the
  * reference leaves to user code: Pchip, Akima and CubicHermite (ndi_strategy1d), and first / second
  * derivatives of the four cubics as handles of their own (ndi_interp1d_derivative), and antiderivatives / definite
  * integrals of every f32 / f64 1D interpolant (ndi_interp1d_antiderivative, ndi_interp1d_integrate).  The reference
@@ -211,6 +212,52 @@ typedef struct ndi_interp2d_desc {
   int32_t reserved;
 } ndi_interp2d_desc;
 
+/* Bicubic (ndi_interp2d_create_bicubic; f32 / f64): the tensor-product cubic spline on the grid, what scipy computes with
+ * RectBivariateSpline(x, y, z, kx=3, ky=3, s=0) for the default ends on any strictly rising axes -- C2 across every grid line where Bilinear is C0.  It
+ * is a bicubic Hermite patch per cell whose node derivatives zx, zy, zxy come from 1-D spline solves along each axis.
+ * The handle is an ndi_interp2d like any other: ndi_interp2d_eval (sync, async_launch + ndi_interp2d_finish), _trim,
+ * _clone (the node table is copied device to device, no rebuild), _eval_ring, _eval_sharded / _eval_ring_sharded (the
+ * replica signature includes the strategy: a set that mixes Bilinear and Bicubic handles is refused), _destroy.
+ * Numerical contract -- this project's own.  T in {f32, f64}, data z[nx][ny][C], axes x[nx], y[ny], one ndi_boundary of any
+ * ndi_bc_kind per end (x-left, x-right, y-left, y-right; default NotAKnot on all four).  Every line is one IEEE operation in
+ * T, in this order, nothing fused.
+ *  Node derivatives, three tables of z's shape:
+ *     x-pass  the CubicSpline coefficient build with knots x on z viewed as (nx, ny C), in the REFERENCE operation order (what
+ *             NDI_BUILD_REFERENCE_ORDER means; n == 3 with both ends NotAKnot takes the build's parabola branch), giving
+ *             a, b.  ONE entry differs from CubicSpline::build: for a NotAKnot right end the last row of the system has
+ *             x[n-2] - x[n-3] on the diagonal, which is what the not-a-knot condition gives, where the reference has
+ *             x[n-1] - x[n-2] (cubic_spline.rs:635).  So a pass is bit-identical to CubicSpline::build on those columns
+ *             whenever the right end is not NotAKnot or the last two intervals are equal, and differs in that entry alone
+ *             otherwise -- which is what makes the default ends scipy's spline on unevenly spaced axes as well
+ *             (ndi_interp1d handles keep the reference's row).  Then ndi_interp1d_derivative's rule per column, with
+ *             dz = z[i+1] - z[i], dx = x[i+1] - x[i]:
+ *                 zx[i]    = (dz + a[i]) / dx        i < nx-1
+ *                 zx[nx-1] = (dz - b[nx-2]) / dx     with i = nx-2
+ *     y-pass  the same with knots y on each z[i] viewed as (ny, C), giving zy
+ *     cross   the y-pass applied to zx with the y ends' kinds and end value 0 (the x-derivative of a constant end value),
+ *             giving zxy
+ *  Evaluation: i, j from get_lower_index on each axis; hx = x[i+1] - x[i], t = (qx - x[i]) / hx, likewise hy, u; with
+ *     H(pl, pr, kl, kr, h, s):  d = pr - pl;  a = kl h - d;  b = d - kr h;
+ *                               (1-s) pl + s pr + s (1-s) (a (1-s) + b s)        (the order of cubic_spline.rs:824-828)
+ *  per lane:
+ *     p0 = H(z[i][j],    z[i][j+1],    zy[i][j],    zy[i][j+1],    hy, u)
+ *     p1 = H(z[i+1][j],  z[i+1][j+1],  zy[i+1][j],  zy[i+1][j+1],  hy, u)
+ *     d0 = H(zx[i][j],   zx[i][j+1],   zxy[i][j],   zxy[i][j+1],   hy, u)
+ *     d1 = H(zx[i+1][j], zx[i+1][j+1], zxy[i+1][j], zxy[i+1][j+1], hy, u)
+ *     result = H(p0, p1, d0, d1, hx, t)
+ *  Range, errors, extrapolation are Bilinear's: inclusive range test, x before y for the same query, the lowest failing flat
+ *  index, NDI_NAN_QUERY by the same rule; after an error rows before the failing query are written and later rows untouched;
+ *  NDI_EVAL_FRESH_OUTPUT and NDI_EVAL_ROWS_AFTER_ERROR_UNSPECIFIED are honoured.  `extrapolate` != 0 uses the end cell's
+ *  patch with t / u outside [0, 1], as the 1-D spline does.
+ *  Refused before any device work, each with a message naming Bicubic and the reason: fewer than 3 points on an axis
+ *  (NDI_NOT_ENOUGH_DATA); with NDI_BAD_ARG integer and f16 / bf16 element types and any boundary kind outside ndi_bc_kind
+ *  (periodic ends and per-lane boundaries have no encoding here and are not provided).  NDI_PATH_AUTO and NDI_PATH_GATHER
+ *  take the one evaluation kernel; NDI_PATH_BUCKETED is NDI_BAD_ARG naming the strategy, and so is
+ *  ndi_interp2d_probe_ceiling.
+ *  Device memory: the node table {z, zx, zy, zxy} per grid node, T[nx][ny][4][C] = four times the grid, plus the two knot
+ *  axes; the plain grid is not kept.  The build's temporaries (about seven grids at the peak) are freed before create returns.
+ * Not provided: periodic and per-lane boundaries, Pchip / Akima node derivatives, partial-derivative and integral handles,
+ * a tile-grouped evaluation form, a blocked-sweep build for narrow grids, half and integer element types. */
 typedef struct ndi_interp1d ndi_interp1d; /* owns device copies of x, data (and a, b) */
 typedef struct ndi_interp2d ndi_interp2d;
 
@@ -272,6 +319,12 @@ ndi_status ndi_interp1d_create(const ndi_interp1d_desc* desc, ndi_interp1d** out
 ndi_status ndi_interp1d_create_hermite(const ndi_interp1d_desc* desc, const void* dydx, ndi_interp1d** out);
 void ndi_interp1d_destroy(ndi_interp1d* h);
 ndi_status ndi_interp2d_create(const ndi_interp2d_desc* desc, ndi_interp2d** out);
+/* The Bicubic strategy (contract above ndi_interp1d).  `bc`: four boundaries in the order x-left, x-right, y-left, y-right,
+ * or NULL for NotAKnot on all four.  A new symbol; ndi_interp2d_desc keeps its layout. */
+ndi_status ndi_interp2d_create_bicubic(const ndi_interp2d_desc* desc, const ndi_boundary* bc, ndi_interp2d** out);
+/* The node derivatives of a Bicubic handle as plain T[nx][ny][lanes] arrays, whatever the internal layout (any of the three
+ * may be NULL): the 2-D counterpart of ndi_interp1d_coefficients.  NDI_BAD_ARG for a Bilinear handle. */
+ndi_status ndi_interp2d_tables(const ndi_interp2d* h, void* zx, void* zy, void* zxy, int32_t memspace);
 void ndi_interp2d_destroy(ndi_interp2d* h);
 
 /* A replica of a built interpolator on `device` (any device, the handle's own included): the device-resident knots /

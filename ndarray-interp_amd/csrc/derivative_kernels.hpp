@@ -29,6 +29,9 @@ struct DerivArgs {
 };
 
 // One table entry: interval i, lanes [lv * VN, lv * VN + VN).
+// In-place use is relied on: the Bicubic axis passes (bicubic_host.hpp) run this with A == a and B == b.  That holds because
+// y, a and b of the entry are loaded into registers before anything is stored and an entry is read and written by one
+// thread only -- keep the loads ahead of the stores, and do not mark the DerivArgs pointers __restrict__.
 template <class T, int VN>
 __device__ __forceinline__ void derivative_entry(const DerivArgs<T>& D, uint64_t i, uint64_t lv) {
   using V = typename VecT<T, VN>::type;

@@ -213,9 +213,15 @@ SplinePlan<T> make_spline_plan_scalars(const T* x, uint64_t n, int lkind, double
   return P;
 }
 
+// Internal bit of ndi_interp1d_desc::build_flags (the public entry point clears it: callers have only
+// NDI_BUILD_REFERENCE_ORDER).  A not-a-knot right end takes dx_2 on the diagonal of the last row, which is what the
+// not-a-knot condition gives; the reference has dx_1 there (:635), the same number only when the last two intervals are
+// equal.  The Bicubic axis passes set it; everything else of the plan and of the build is unchanged.
+constexpr int BUILD_TRUE_NOT_A_KNOT = 1 << 30;
+
 template <class T>
 SplinePlan<T> make_spline_plan(const T* x, uint64_t n, bool periodic, int lkind, double lval,
-                               int rkind, double rval) {
+                               int rkind, double rval, bool true_not_a_knot = false) {
   SplinePlan<T> P;
   P.n = n;
   const T one = T(1), two = T(2);
@@ -291,7 +297,7 @@ SplinePlan<T> make_spline_plan(const T* x, uint64_t n, bool periodic, int lkind,
       up[0] = dx0; mid[0] = two * dx0;
     }
     if (rk == END_NOT_A_KNOT) {
-      mid[n - 1] = dxl;  // sic: the reference uses dx_1 here (:635)
+      mid[n - 1] = true_not_a_knot ? dxl2 : dxl;  // sic: the reference uses dx_1 here (:635)
       const T d = x[n - 1] - x[n - 3];
       low[n - 1] = d;
       P.nkR_d = d;

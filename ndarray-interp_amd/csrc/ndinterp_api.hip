@@ -31,6 +31,7 @@
 #include "hermite_kernels.hpp"
 #include "derivative_kernels.hpp"
 #include "antiderivative_kernels.hpp"
+#include "bicubic_kernels.hpp"
 
 #define NDI_API extern "C" __attribute__((visibility("default")))
 
@@ -1086,7 +1087,7 @@ struct Interp1DImpl final : Interp1DBase {
     SplinePlan<T> P = dev_elim ? make_spline_plan_scalars<T>(pyr.host_knots.data(), n, d.left.kind, d.left.value, d.right.kind,
                                                              d.right.value, ends)
                                : make_spline_plan<T>(pyr.host_knots.data(), n, periodic, d.left.kind, d.left.value,
-                                                     d.right.kind, d.right.value);
+                                                     d.right.kind, d.right.value, (d.build_flags & BUILD_TRUE_NOT_A_KNOT) != 0);
     clk.mark("  host plan");
     // Small systems (the reference's (100, 5); 1024 x 8; ...): ONE launch -- right-hand sides, elimination, back
     // substitution and the a / b epilogue in spline_build_general_kernel<FUSED>, dx / up formed from the resident knots;
@@ -2623,13 +2624,18 @@ static ndi_status create1d(const ndi_interp1d_desc& d, Interp1DBase** out, const
 }
 
 // ---------------------------------------------------------------------------------------------
-// Interp2D (Bilinear)
+// Interp2D (Bilinear; Bicubic: bicubic_host.hpp)
 // ---------------------------------------------------------------------------------------------
 struct Interp2DBase {
   virtual ~Interp2DBase() = default;
   virtual uint64_t signature() const = 0;
   int dtype = 0, device = 0;
   uint64_t lanes = 0;
+  bool bicubic = false;   // the strategy: Bilinear (every element type) or Bicubic (f32 / f64, ndi_interp2d_create_bicubic)
+  // ndi_interp2d_tables: Bicubic handles only
+  virtual ndi_status tables(void* zx, void* zy, void* zxy, int memspace) {
+    return fail(NDI_BAD_ARG, "ndi_interp2d_tables takes a Bicubic handle: Bilinear keeps no node derivatives");
+  }
   virtual ndi_status eval(const void* qx, const void* qy, uint64_t nq, void* out, uint64_t out_stride,
                           const ndi_eval_opts* opts, ndi_oob_info* info) = 0;
   virtual ndi_status finish(void* stream, ndi_oob_info* info) = 0;
@@ -2642,11 +2648,20 @@ struct Interp2DBase {
 };
 
 template <class T>
+struct Interp2DImpl;
+template <class T>
+static void bicubic_launch_eval(const Interp2DImpl<T>& h, hipStream_t s, StatusBlock* st, const T* qx, const T* qy,
+                                uint64_t nq, T* out, uint64_t out_stride, bool check);
+template <class T>
+static ndi_status bicubic_tables(const Interp2DImpl<T>& h, void* zx, void* zy, void* zxy, int memspace);
+
+template <class T>
 struct Interp2DImpl final : Interp2DBase {
   int mode = EX_NO;
   uint64_t nx = 0, ny = 0;
   DevicePyramid<T> px, py;
   DevBuf data;
+  DevBuf table;               // Bicubic: the node table T[nx][ny][4][lanes] ({z, zx, zy, zxy}); `data` is not kept
   bool pair_packed = false;   // data holds the pair-packed layout (pack_pairs_kernel)
   SpaceSet spaces;
   OwnedRing ring_own;
@@ -2735,14 +2750,18 @@ struct Interp2DImpl final : Interp2DBase {
   uint64_t signature() const override {
     uint64_t h = fnv1a(FNV_SEED, px.host_knots.data(), px.host_knots.size() * sizeof(T));
     h = fnv1a(h, py.host_knots.data(), py.host_knots.size() * sizeof(T));
-    const uint64_t f[3] = {nx, ny, (uint64_t)mode};
+    const uint64_t f[3] = {nx, ny, (uint64_t)mode | ((uint64_t)bicubic << 8)};   // (the strategy: no Bilinear / Bicubic mix)
     return fnv1a(h, f, sizeof(f));
+  }
+  ndi_status tables(void* zx, void* zy, void* zxy, int memspace) override {
+    if (!bicubic) return Interp2DBase::tables(zx, zy, zxy, memspace);
+    return bicubic_tables<T>(*this, zx, zy, zxy, memspace);
   }
 
   // Two stages as in Interp1DImpl: prep() = both searches (+ the optional tile grouping) into a scratch set,
   // launch_eval() = the bilinear kernel reading that set.
   struct Plan2 {
-    enum Kind { SMALL, GATHER, TILED, FUSED2, LANES2, SLOPES2 } kind = GATHER;
+    enum Kind { SMALL, GATHER, TILED, FUSED2, LANES2, SLOPES2, BICUBIC } kind = GATHER;
     int l_qpl = 1;          // LANES2, scalar grids: queries per lane (1, or one 16-byte vector)
     bool l_check = false;   // LANES2: no range pre-pass (NDI_EVAL_FRESH_OUTPUT)
     bool f_lds_wide = false;   // SLOPES2: f_lds includes the result strip of the 16-byte store path
@@ -2764,11 +2783,24 @@ struct Interp2DImpl final : Interp2DBase {
              int path, bool beside_eval = false, int flags = 0) {
     Plan2 P;
     P.qx = qx; P.qy = qy; P.nq = nq; P.out = out; P.out_stride = out_stride;
-    sc.idx.reserve(nq * sizeof(uint32_t));
-    sc.idx2.reserve(nq * sizeof(uint32_t));
     sc.status.reserve(sizeof(StatusBlock));
     reset_status(sc.status.p, s);
     StatusBlock* st = sc.status.as<StatusBlock>();
+    if (bicubic) {   // one kernel for AUTO and GATHER (eval_bicubic_kernel); BUCKETED was refused at the entry point
+      P.kind = Plan2::BICUBIC;
+      g_last_path.store(NDI_PATH_GATHER);
+      P.l_check = (flags & NDI_EVAL_FRESH_OUTPUT) != 0;   // fresh output: the kernel's own range test, no pre-pass
+      if (P.l_check) return P;
+      const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
+      ProfScope ps(s, PC_LOCATE);
+      hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, qx, qy, nq, px.host_knots.front(),
+                         px.host_knots.back(), py.host_knots.front(), py.host_knots.back(), mode, &st->first_fail[0]);
+      NDI_HIP(hipGetLastError());
+      ps.done();
+      return P;
+    }
+    sc.idx.reserve(nq * sizeof(uint32_t));
+    sc.idx2.reserve(nq * sizeof(uint32_t));
     const size_t both = ((px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15);
     // 1-2 values per grid point: one query per thread -- both searches and the evaluation in one launch, no (xi, yi)
     // round trip, two reciprocals per query instead of three divisions per value.  (NDI_SMALL2D_LANES extends it to
@@ -3179,6 +3211,10 @@ struct Interp2DImpl final : Interp2DBase {
   void launch_eval(hipStream_t s, Scratch& sc, const Plan2& P) {
     StatusBlock* st = sc.status.as<StatusBlock>();
     const uint64_t nq = P.nq;
+    if (P.kind == Plan2::BICUBIC) {
+      bicubic_launch_eval<T>(*this, s, st, P.qx, P.qy, nq, P.out, P.out_stride, P.l_check);
+      return;
+    }
     if (P.kind == Plan2::SMALL) {
       const size_t both = ((px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15);
       const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
@@ -3626,7 +3662,7 @@ struct Interp2DImpl final : Interp2DBase {
   // Zero-copy small batches, host arrays in and out (see Interp1DImpl::eval_small_zero_copy).
   static constexpr size_t ZERO_COPY_LIMIT = 1u << 20;
   bool zero_copy_fits(uint64_t nq, int q_space, int out_space) const {
-    return q_space == NDI_MEM_HOST && out_space == NDI_MEM_HOST && lanes <= (uint64_t)SMALL_LANES &&
+    return !bicubic && q_space == NDI_MEM_HOST && out_space == NDI_MEM_HOST && lanes <= (uint64_t)SMALL_LANES &&
            ((px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15) <= LDS_STAGE_LIMIT &&
            nq * (lanes + 2) * sizeof(T) <= ZERO_COPY_LIMIT;
   }
@@ -3688,7 +3724,7 @@ struct Interp2DImpl final : Interp2DBase {
       return collect(s, ws, 0, info);
     }
     const uint64_t row_bytes = lanes * sizeof(T);
-    if (lanes <= (uint64_t)SMALL_LANES && ((px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15) <= LDS_STAGE_LIMIT)
+    if (!bicubic && lanes <= (uint64_t)SMALL_LANES && ((px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15) <= LDS_STAGE_LIMIT)
       return eval_small_host(s, ws, qx, qy, (const T*)qx_orig, (const T*)qy_orig, q_space, nq, (T*)out_, out_stride,
                              info);
     const uint64_t chunk_q = std::max<uint64_t>(1, std::min<uint64_t>(nq, (256ull << 20) / row_bytes));
@@ -3848,6 +3884,7 @@ struct Interp2DImpl final : Interp2DBase {
     std::unique_ptr<Interp2DImpl<T>> h(new Interp2DImpl<T>());
     h->dtype = dtype; h->device = dev; h->lanes = lanes;
     h->mode = mode; h->nx = nx; h->ny = ny; h->pair_packed = pair_packed;
+    h->bicubic = bicubic;
     {
       DeviceGuard dg(device);
       NDI_HIP(hipDeviceSynchronize());
@@ -3855,14 +3892,20 @@ struct Interp2DImpl final : Interp2DBase {
     DeviceGuard dg(dev);
     h->px.upload(px.host_knots.data(), nx);
     h->py.upload(py.host_knots.data(), ny);
-    h->data.reserve(data.bytes);
-    copy_across_devices(h->data.p, dev, data.p, device, data.bytes);
+    if (bicubic) {   // the node table as it is: no rebuild
+      h->table.reserve(table.bytes);
+      copy_across_devices(h->table.p, dev, table.p, device, table.bytes);
+    } else {
+      h->data.reserve(data.bytes);
+      copy_across_devices(h->data.p, dev, data.p, device, data.bytes);
+    }
     *out = h.release();
     return NDI_OK;
   }
 
   // Median time of `reps` launches of probe_gather_kernel over nq queries (see kernels.hpp).
   ndi_status probe_ceiling(uint64_t nq, void* out, uint64_t out_stride, void* stream, int reps, double* ms) override {
+    if (bicubic) return fail(NDI_BAD_ARG, "Bicubic: the probe runs Bilinear's access mix (four corner vectors of the plain grid)");
     DeviceGuard dg(device);
     constexpr int VN = Wide<T>::N;
     if (!out || !ms || nq == 0 || reps < 1) return fail(NDI_BAD_ARG, "probe needs an output buffer, nq >= 1, reps >= 1");
@@ -3975,6 +4018,11 @@ static ndi_status create2d(const ndi_interp2d_desc& d, Interp2DBase** out) {
   *out = h.release();
   return NDI_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Interp2D Bicubic: build, launch and table read-back
+// ---------------------------------------------------------------------------------------------
+#include "bicubic_host.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // Locator: VectorExtensions::get_lower_index with the knot pyramid resident on the device
@@ -4569,12 +4617,14 @@ static ndi_status create1d_checked(const ndi_interp1d_desc* desc, const void* dy
   if (ds != NDI_OK) return ds;
   NDI_TRY
   ndi::Interp1DBase* impl = nullptr;
-  ndi_status st = desc->dtype == NDI_F32   ? ndi::create1d<float>(*desc, &impl, dydx)
-                  : desc->dtype == NDI_F64 ? ndi::create1d<double>(*desc, &impl, dydx)
-                  : desc->dtype == NDI_I32 ? ndi::create1d_int<int32_t>(*desc, &impl)
-                  : desc->dtype == NDI_I64 ? ndi::create1d_int<int64_t>(*desc, &impl)
-                  : desc->dtype == NDI_F16 ? ndi::create1d_half<ndi::HF_F16>(*desc, &impl)
-                                           : ndi::create1d_half<ndi::HF_BF16>(*desc, &impl);
+  ndi_interp1d_desc dd = *desc;
+  dd.build_flags &= ~ndi::BUILD_TRUE_NOT_A_KNOT;   // internal to the Bicubic axis passes: as before, unknown bits do nothing
+  ndi_status st = desc->dtype == NDI_F32   ? ndi::create1d<float>(dd, &impl, dydx)
+                  : desc->dtype == NDI_F64 ? ndi::create1d<double>(dd, &impl, dydx)
+                  : desc->dtype == NDI_I32 ? ndi::create1d_int<int32_t>(dd, &impl)
+                  : desc->dtype == NDI_I64 ? ndi::create1d_int<int64_t>(dd, &impl)
+                  : desc->dtype == NDI_F16 ? ndi::create1d_half<ndi::HF_F16>(dd, &impl)
+                                           : ndi::create1d_half<ndi::HF_BF16>(dd, &impl);
   if (st != NDI_OK) return st;
   *out = new ndi_interp1d{impl};
   return NDI_OK;
@@ -4621,6 +4671,60 @@ NDI_API ndi_status ndi_interp2d_create(const ndi_interp2d_desc* desc, ndi_interp
   *out = new ndi_interp2d{impl};
   return NDI_OK;
   NDI_CATCH
+}
+
+// Every refusal is decided before any device work, so it behaves the same everywhere.
+NDI_API ndi_status ndi_interp2d_create_bicubic(const ndi_interp2d_desc* desc, const ndi_boundary* bc, ndi_interp2d** out) {
+  if (!desc || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
+  *out = nullptr;
+  if (desc->dtype < NDI_F32 || desc->dtype > NDI_BF16) return ndi::fail(NDI_BAD_ARG, "unknown dtype");
+  if (desc->dtype == NDI_I32 || desc->dtype == NDI_I64)
+    return ndi::fail(NDI_BAD_ARG, "Bicubic needs a float element type (f32 / f64): a spline divides; integer data takes Bilinear");
+  if (desc->dtype == NDI_F16 || desc->dtype == NDI_BF16)
+    return ndi::fail(NDI_BAD_ARG, "Bicubic needs f32 / f64: the spline build has no half-precision form; f16 / bf16 data takes "
+                     "Bilinear");
+  ndi_boundary b4[4] = {{NDI_BC_NOT_A_KNOT, 0.0}, {NDI_BC_NOT_A_KNOT, 0.0}, {NDI_BC_NOT_A_KNOT, 0.0}, {NDI_BC_NOT_A_KNOT, 0.0}};
+  static const char* const END[4] = {"x-left", "x-right", "y-left", "y-right"};
+  for (int k = 0; bc && k < 4; ++k) {
+    b4[k] = bc[k];
+    if (bc[k].kind < NDI_BC_NOT_A_KNOT || bc[k].kind > NDI_BC_SECOND_DERIV)
+      return ndi::fail(NDI_BAD_ARG, "Bicubic takes one non-periodic boundary kind with a scalar value per end (ndi_bc_kind); "
+                       "periodic and per-lane boundaries are not provided (%s end: kind %d)", END[k], (int)bc[k].kind);
+  }
+  if (desc->validate && desc->memspace == NDI_MEM_HOST && desc->x && desc->y) {
+    ndi_status st = ndi_validate2d(desc->dtype, desc->x, desc->x_len, desc->y, desc->y_len, desc->nx, desc->ny);
+    if (st != NDI_OK) return st;
+  }
+  if (desc->nx < 3 || desc->ny < 3)
+    return ndi::fail(NDI_NOT_ENOUGH_DATA, "Bicubic needs at least 3 data points on each axis (got %llu x %llu)",
+                     (unsigned long long)desc->nx, (unsigned long long)desc->ny);
+  ndi_status ds = need_device(desc->device);
+  if (ds != NDI_OK) return ds;
+  NDI_TRY
+  ndi::Interp2DBase* impl = nullptr;
+  ndi_status st = desc->dtype == NDI_F32 ? ndi::create2d_bicubic<float>(*desc, b4, &impl)
+                                         : ndi::create2d_bicubic<double>(*desc, b4, &impl);
+  if (st != NDI_OK) return st;
+  *out = new ndi_interp2d{impl};
+  return ndi::bounds_verdict(NDI_OK, impl->device);
+  NDI_CATCH
+}
+
+NDI_API ndi_status ndi_interp2d_tables(const ndi_interp2d* h, void* zx, void* zy, void* zxy, int32_t memspace) {
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  if (memspace != NDI_MEM_HOST && memspace != NDI_MEM_DEVICE) return ndi::fail(NDI_BAD_ARG, "unknown memspace");
+  NDI_TRY
+  if (!h->impl->bicubic) return h->impl->tables(zx, zy, zxy, memspace);
+  return ndi::bounds_verdict(h->impl->tables(zx, zy, zxy, memspace), h->impl->device);
+  NDI_CATCH
+}
+
+// Bicubic has one evaluation form: NDI_PATH_BUCKETED (the tile-grouped order) is Bilinear's.
+static ndi_status bicubic_path_check(const ndi_interp2d* h, const ndi_eval_opts* opts) {
+  if (h->impl->bicubic && opts && opts->path == NDI_PATH_BUCKETED)
+    return ndi::fail(NDI_BAD_ARG, "Bicubic has no tile-grouped evaluation form: NDI_PATH_BUCKETED is Bilinear's (AUTO and "
+                     "GATHER evaluate)");
+  return NDI_OK;
 }
 
 NDI_API void ndi_interp2d_destroy(ndi_interp2d* h) {
@@ -4732,6 +4836,7 @@ NDI_API ndi_status ndi_interp2d_eval(const ndi_interp2d* h, const void* qx, cons
                                      void* out, uint64_t out_row_stride, const ndi_eval_opts* opts,
                                      ndi_oob_info* info) {
   if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  if (const ndi_status ps = bicubic_path_check(h, opts); ps != NDI_OK) return ps;
   NDI_TRY
   return ndi::bounds_verdict(h->impl->eval(qx, qy, nq, out, out_row_stride, opts, info), h->impl->device);
   NDI_CATCH
@@ -4764,6 +4869,7 @@ NDI_API ndi_status ndi_interp2d_eval_ring(const ndi_interp2d* h, const void* qx,
                                           const ndi_ring_desc* ring, ndi_ring_consumer consume, void* user,
                                           const ndi_eval_opts* opts, ndi_oob_info* info) {
   if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  if (const ndi_status ps = bicubic_path_check(h, opts); ps != NDI_OK) return ps;
   NDI_TRY
   return ndi::bounds_verdict(h->impl->eval_ring(qx, qy, nq, ring, consume, user, opts, info), h->impl->device);
   NDI_CATCH
@@ -4871,6 +4977,8 @@ static ndi_status sharded_call(const ndi_interp1d* const* handles, uint32_t n, c
 static ndi_status sharded_call(const ndi_interp2d* const* handles, uint32_t n, const ndi::ShardCall& c,
                                ndi_oob_info* info) {
   const int dtype = handles[0]->impl->dtype;
+  for (uint32_t i = 0; i < n; ++i)
+    if (const ndi_status ps = bicubic_path_check(handles[i], &c.o); ps != NDI_OK) return ps;
   switch (dtype) {
     case NDI_I32: return sharded_narrow_call<ndi::Interp2DIntImpl<int32_t>>(handles, n, c, info);
     case NDI_I64: return sharded_narrow_call<ndi::Interp2DIntImpl<int64_t>>(handles, n, c, info);

@@ -1,5 +1,6 @@
 """Host-side mirror of the reference's 2-D surface (src/interp2d/mod.rs + strategies/):
-`Interp2DBuilder`, `Interp2D`, the strategy trait pair and the built-in `Bilinear`."""
+`Interp2DBuilder`, `Interp2D`, the strategy trait pair and the built-in `Bilinear`; plus `Bicubic`, which the
+reference does not have."""
 from __future__ import annotations
 
 import ctypes as C
@@ -10,7 +11,8 @@ from . import _capi
 from ._arrays import (DEVICE_HALF_DTYPES, DEVICE_INT_DTYPES, OUTPUT_OWNED_MIN_BYTES, Buf, current_stream_ptr, dtype_id,
                       int_query, is_bf16, is_torch, np_dtype_of, output_empty, torch_dtype)
 from .errors import BuilderError, InterpolateError, Panic, raise_builder, raise_eval
-from .interp1d import _check_out_dtype, _default_axis, _default_device, _host, _one_query, _to_device, _zeros
+from .interp1d import (BoundaryCondition, RowBoundary, _check_out_dtype, _default_axis, _default_device, _host, _one_query,
+                       _to_device, _zeros)
 from .vector_extensions import Monotonic, get_lower_index, monotonic_prop
 
 
@@ -40,12 +42,11 @@ class Interp2DStrategy:
         pass
 
 
-class Bilinear(Interp2DStrategyBuilder, Interp2DStrategy):
-    """Bilinear strategy (src/interp2d/strategies/bilinear.rs); builder and finished strategy in one,
-    as in the reference (`type FinishedStrat = Self`, :43)."""
+class _DeviceStrategy2D(Interp2DStrategy):
+    """What the built-in device strategies share: one `ndi_interp2d` handle and every evaluation entry point on it
+    (Bilinear and Bicubic differ in how the handle is created)."""
 
-    MINIMUM_DATA_LENGHT = 2  # bilinear.rs:41
-    path = _capi.PATH_AUTO   # evaluation formulation (ndi_path): BUCKETED = tile-grouped query order
+    path = _capi.PATH_AUTO   # evaluation formulation (ndi_path)
 
     def __init__(self):
         self._extrapolate = False
@@ -56,30 +57,19 @@ class Bilinear(Interp2DStrategyBuilder, Interp2DStrategy):
         self._lanes = 1
         self._inflight = []
 
-    @staticmethod
-    def new() -> "Bilinear":
-        return Bilinear()
-
-    def device(self, ordinal: int) -> "Bilinear":
+    def device(self, ordinal: int):
         """Build-side option of this mirror: the HIP device that holds the grid (default: the data tensor's
         device, else LOCAL_RANK / device 0)."""
         self._device_req = int(ordinal)
         return self
 
-    def extrapolate(self, yes: bool) -> "Bilinear":
+    def extrapolate(self, yes: bool):
         self._extrapolate = bool(yes)
         return self
 
-    def build(self, x, y, data, device=None):
+    def _create(self, x, y, data, device, create):
+        """Fill an ndi_interp2d_desc from the arrays and call `create(desc, out_handle)` -> ndi_status."""
         dt = np_dtype_of(data)
-        on_device = device is not None or self._device_req is not None or (is_torch(data) and data.is_cuda)
-        device_t = (dt in DEVICE_INT_DTYPES or dt in DEVICE_HALF_DTYPES) and (on_device or is_bf16(dt))
-        if dt not in (np.dtype(np.float32), np.dtype(np.float64)) and not device_t:
-            # i32 / i64 / f16 take the device when asked for (.device(d) or a GPU tensor); plain host arrays stay here
-            # (bf16 always takes the device: it has no host path)
-            # integer (and other non-f32/f64) element types: the reference's generic per-query path
-            from .generic_host import HostBilinear
-            return HostBilinear(_host(x), _host(y), _host(data), self._extrapolate)
         tid = dtype_id(dt)
         db = Buf(data)
 
@@ -107,10 +97,11 @@ class Bilinear(Interp2DStrategyBuilder, Interp2DStrategy):
         d.data = db.ptr
         d.validate = 0  # Interp2DBuilder.build() validated already (interp2d/mod.rs:477-511)
         h = C.c_void_p()
-        st = _capi.lib().ndi_interp2d_create(C.byref(d), C.byref(h))
+        st = create(d, h)
         if st != _capi.OK:
             raise_builder(st)
         self._h, self._device, self._np_dtype, self._lanes = h, device, dt, lanes
+        self._shape = (nx, ny) + tuple(db.shape[2:])
         return self
 
     def release(self):
@@ -185,17 +176,6 @@ class Bilinear(Interp2DStrategyBuilder, Interp2DStrategy):
     def trim(self):
         _capi.lib().ndi_interp2d_trim(self._h)
 
-    def probe_ceiling(self, out2d, reps=5) -> float:
-        """ms of the evaluation kernel's memory access mix alone on this handle's grid (ndi_interp2d_probe_ceiling);
-        `out2d`: a device tensor (nq, lanes) that is overwritten."""
-        ms = C.c_double()
-        st = _capi.lib().ndi_interp2d_probe_ceiling(self._h, out2d.shape[0], out2d.data_ptr(), out2d.stride(0),
-                                                    current_stream_ptr(self._device), int(reps), C.byref(ms))
-        if st != _capi.OK:
-            from .errors import DeviceError
-            raise DeviceError(_capi.last_error())
-        return ms.value
-
     def interp_array_ring(self, xs_flat, ys_flat, chunk_queries, consumer=None, *, slots=None, n_slots=2):
         """ndi_interp2d_eval_ring; see `_DeviceStrategy1D.interp_array_ring`."""
         qx, qy = Buf(xs_flat, self._np_dtype), Buf(ys_flat, self._np_dtype)
@@ -264,6 +244,112 @@ class Bilinear(Interp2DStrategyBuilder, Interp2DStrategy):
         self.interp_array_into(interpolator, np.array([x], dtype=self._np_dtype),
                                np.array([y], dtype=self._np_dtype), out)
         target[...] = out.reshape(target.shape)
+
+
+class Bilinear(Interp2DStrategyBuilder, _DeviceStrategy2D):
+    """Bilinear strategy (src/interp2d/strategies/bilinear.rs); builder and finished strategy in one,
+    as in the reference (`type FinishedStrat = Self`, :43).  `path`: BUCKETED = tile-grouped query order."""
+
+    MINIMUM_DATA_LENGHT = 2  # bilinear.rs:41
+
+    @staticmethod
+    def new() -> "Bilinear":
+        return Bilinear()
+
+    def build(self, x, y, data, device=None):
+        dt = np_dtype_of(data)
+        on_device = device is not None or self._device_req is not None or (is_torch(data) and data.is_cuda)
+        device_t = (dt in DEVICE_INT_DTYPES or dt in DEVICE_HALF_DTYPES) and (on_device or is_bf16(dt))
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)) and not device_t:
+            # i32 / i64 / f16 take the device when asked for (.device(d) or a GPU tensor); plain host arrays stay here
+            # (bf16 always takes the device: it has no host path)
+            # integer (and other non-f32/f64) element types: the reference's generic per-query path
+            from .generic_host import HostBilinear
+            return HostBilinear(_host(x), _host(y), _host(data), self._extrapolate)
+        return self._create(x, y, data, device,
+                            lambda d, h: _capi.lib().ndi_interp2d_create(C.byref(d), C.byref(h)))
+
+    def probe_ceiling(self, out2d, reps=5) -> float:
+        """ms of the evaluation kernel's memory access mix alone on this handle's grid (ndi_interp2d_probe_ceiling);
+        `out2d`: a device tensor (nq, lanes) that is overwritten."""
+        ms = C.c_double()
+        st = _capi.lib().ndi_interp2d_probe_ceiling(self._h, out2d.shape[0], out2d.data_ptr(), out2d.stride(0),
+                                                    current_stream_ptr(self._device), int(reps), C.byref(ms))
+        if st != _capi.OK:
+            from .errors import DeviceError
+            raise DeviceError(_capi.last_error())
+        return ms.value
+
+
+class Bicubic(Interp2DStrategyBuilder, _DeviceStrategy2D):
+    """Bicubic strategy: the tensor-product cubic spline on the grid (scipy: RectBivariateSpline(kx=3, ky=3, s=0) for the
+    default ends, on evenly and unevenly spaced axes alike: its not-a-knot right end is the true not-a-knot row, where a
+    1-D CubicSpline keeps the reference's), built and evaluated on the device (ndi_interp2d_create_bicubic;
+    include/ndinterp.h states the numerical contract).  The reference has no such strategy.  Builder and finished strategy in one, like `Bilinear`."""
+
+    MINIMUM_DATA_LENGHT = 3
+
+    def __init__(self):
+        super().__init__()
+        self._bc_x = self._bc_y = RowBoundary.NotAKnot
+
+    @staticmethod
+    def new() -> "Bicubic":
+        return Bicubic()
+
+    @staticmethod
+    def _ends(bc) -> RowBoundary:
+        """One axis' (left, right) pair from a BoundaryCondition (NotAKnot / Natural / Clamped) or a RowBoundary."""
+        if isinstance(bc, RowBoundary):
+            return bc
+        if isinstance(bc, BoundaryCondition) and bc.tag in ("NotAKnot", "Natural", "Clamped"):
+            return getattr(RowBoundary, bc.tag)
+        if isinstance(bc, BoundaryCondition) and bc.tag == "Periodic":
+            raise TypeError("Bicubic has no periodic ends: its boundaries are one non-periodic kind per end")
+        if isinstance(bc, BoundaryCondition) and bc.tag == "Individual":
+            raise TypeError("Bicubic takes no per-lane (Individual) boundaries: one kind and scalar value per end "
+                            "(RowBoundary.Mixed(left, right) gives an axis two different ends)")
+        raise TypeError(f"Bicubic boundaries are BoundaryCondition or RowBoundary objects, got {type(bc).__name__}")
+
+    def boundary(self, bc) -> "Bicubic":
+        """The same ends on both axes."""
+        self._bc_x = self._bc_y = self._ends(bc)
+        return self
+
+    def boundary_x(self, bc) -> "Bicubic":
+        self._bc_x = self._ends(bc)
+        return self
+
+    def boundary_y(self, bc) -> "Bicubic":
+        self._bc_y = self._ends(bc)
+        return self
+
+    def build(self, x, y, data, device=None):
+        dt = np_dtype_of(data)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            got = "bfloat16" if is_bf16(dt) else dt
+            raise TypeError(f"Bicubic covers float32/float64 only, got {got}: a spline divides (integer data takes "
+                            "Bilinear) and the spline build has no half-precision form")
+        ends = (self._bc_x.left, self._bc_x.right, self._bc_y.left, self._bc_y.right)
+        bc = (_capi.Boundary * 4)(*[_capi.Boundary(int(e.kind), float(e.value)) for e in ends])
+        return self._create(x, y, data, device,
+                            lambda d, h: _capi.lib().ndi_interp2d_create_bicubic(C.byref(d), bc, C.byref(h)))
+
+    def tables(self, on_device=False):
+        """(zx, zy, zxy): the node derivatives, each of the data's shape (ndi_interp2d_tables), as host arrays -- or, with
+        `on_device`, as tensors on the handle's device."""
+        if on_device:
+            import torch
+            out = [torch.empty(self._shape, dtype=torch_dtype(self._np_dtype), device=f"cuda:{self._device}") for _ in range(3)]
+            ptrs, space = [t.data_ptr() for t in out], _capi.MEM_DEVICE
+        else:
+            out = [np.empty(self._shape, dtype=self._np_dtype) for _ in range(3)]
+            ptrs, space = [a.ctypes.data for a in out], _capi.MEM_HOST
+        st = _capi.lib().ndi_interp2d_tables(self._h, ptrs[0], ptrs[1], ptrs[2], space)
+        if st != _capi.OK:
+            from .errors import DeviceError
+            raise DeviceError(_capi.last_error())
+        return tuple(out)
 
 
 class Interp2D:

@@ -226,6 +226,18 @@ extern "C" {
     ) -> i32;
     pub fn ndi_interp1d_destroy(h: *mut ndi_interp1d);
     pub fn ndi_interp2d_create(desc: *const ndi_interp2d_desc, out: *mut *mut ndi_interp2d) -> i32;
+    pub fn ndi_interp2d_create_bicubic(
+        desc: *const ndi_interp2d_desc,
+        bc: *const ndi_boundary,
+        out: *mut *mut ndi_interp2d,
+    ) -> i32;
+    pub fn ndi_interp2d_tables(
+        h: *const ndi_interp2d,
+        zx: *mut c_void,
+        zy: *mut c_void,
+        zxy: *mut c_void,
+        memspace: i32,
+    ) -> i32;
     pub fn ndi_interp2d_destroy(h: *mut ndi_interp2d);
     pub fn ndi_interp1d_clone(h: *const ndi_interp1d, device: i32, out: *mut *mut ndi_interp1d) -> i32;
     pub fn ndi_interp2d_clone(h: *const ndi_interp2d, device: i32, out: *mut *mut ndi_interp2d) -> i32;

@@ -1,0 +1,255 @@
+"""GPU: the Bicubic strategy against the numpy restatement of its contract (tests/bicubic_ref.py), bit for bit -- the node
+tables read through ndi_interp2d_tables, evaluated rows on the device's own tables, the error semantics against Bilinear's
+on the same queries, extrapolation, every other handle surface at one small shape, and one grid whose table passes 2^32
+elements."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import bicubic_ref
+import oracle
+from conftest import ROOT
+from hostile_inputs import check_bits
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(3, 3), (3, 4), (4, 3), (5, 7), (64, 48), (1000, 3)]
+LANES = [1, 2, 3, 4, 5, 64, 65]
+NQS = [1, 63, 64, 65, 10007]
+MIXED = ((oracle.BC_NATURAL, 0.0), (oracle.BC_FIRST_DERIV, 0.75), (oracle.BC_CLAMPED, 0.0), (oracle.BC_CLAMPED, 0.0))
+
+
+def make_grid(rng, nx, ny, C, dt):
+    x = np.cumsum(rng.uniform(0.5, 1.5, nx)).astype(dt)
+    y = np.cumsum(rng.uniform(0.5, 1.5, ny)).astype(dt)
+    return x, y, rng.normal(size=(nx, ny, C)).astype(dt)
+
+
+def strategy(pkg, bc=None):
+    s = pkg.Bicubic.new()
+    if bc is not None:
+        sb = pkg.SingleBoundary
+        s.boundary_x(pkg.RowBoundary.Mixed(sb(*bc[0]), sb(*bc[1]))).boundary_y(pkg.RowBoundary.Mixed(sb(*bc[2]), sb(*bc[3])))
+    return s
+
+
+def build(pkg, x, y, z, bc=None, device_inputs=False, extrapolate=False):
+    import torch
+    if device_inputs:
+        x, y, z = (torch.as_tensor(a, device="cuda:0") for a in (x, y, z))
+    return pkg.Interp2DBuilder.new(z).x(x).y(y).strategy(strategy(pkg, bc).extrapolate(extrapolate)).build()
+
+
+def queries(rng, x, y, nq):
+    """random in-range queries, then (as far as nq allows) the four corners, points on each edge and every node"""
+    dt = x.dtype
+    ii, jj = np.meshgrid(np.arange(len(x)), np.arange(len(y)), indexing="ij")
+    sx = np.concatenate([[x[0], x[0], x[-1], x[-1]], [x[0], x[-1]], rng.uniform(x[0], x[-1], 2), x[ii.ravel()]])
+    sy = np.concatenate([[y[0], y[-1], y[0], y[-1]], rng.uniform(y[0], y[-1], 2), [y[0], y[-1]], y[jj.ravel()]])
+    k = min(len(sx), nq)
+    qx = np.concatenate([sx[:k], rng.uniform(x[0], x[-1], nq - k)]).astype(dt)
+    qy = np.concatenate([sy[:k], rng.uniform(y[0], y[-1], nq - k)]).astype(dt)
+    return np.clip(qx, x[0], x[-1]), np.clip(qy, y[0], y[-1])
+
+
+@pytest.mark.parametrize("C", LANES)
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("dt", [np.float32, np.float64], ids=["f32", "f64"])
+def test_tables_and_rows_are_bit_exact(pkg, dt, shape, C):
+    import torch
+    rng = np.random.default_rng(hash((shape, C)) % 2**32)
+    x, y, z = make_grid(rng, shape[0], shape[1], C, dt)
+    for bc in (None, MIXED):
+        ref = bicubic_ref.tables(x, y, z, bc or bicubic_ref.DEFAULT_BC)
+        for device_inputs in (False, True):
+            it = build(pkg, x, y, z, bc, device_inputs)
+            got = it.strategy.tables()
+            for name, g, r in zip(("zx", "zy", "zxy"), got, ref):
+                check_bits(g, r, f"{name} bc={'mixed' if bc else 'default'} device_inputs={device_inputs}")
+        zx, zy, zxy = got                       # rows: the restatement's evaluation on the device's own tables
+        for nq in NQS:
+            qx, qy = queries(rng, x, y, nq)
+            want = bicubic_ref.evaluate(x, y, z, zx, zy, zxy, qx, qy)
+            for path in (pkg.PATH_AUTO, pkg.PATH_GATHER):
+                it.strategy.path = path
+                check_bits(it.interp_array(qx, qy), want, f"host queries nq={nq} path={path}")
+                rows = it.interp_array(torch.as_tensor(qx, device="cuda:0"), torch.as_tensor(qy, device="cuda:0"))
+                check_bits(rows.cpu().numpy(), want, f"device queries nq={nq} path={path}")
+
+
+def test_rows_under_the_bounds_checked_library():
+    lib = os.path.join(ROOT, "ndarray-interp_amd", "libndinterp_hip_dbg.so")
+    assert os.path.exists(lib), "build() makes the checked library"
+    code = (
+        "import sys, numpy as np, torch; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "from conftest import load_product_package; import bicubic_ref, test_gpu_bicubic as t\n"
+        "from hostile_inputs import check_bits\n"
+        "pkg = load_product_package(); rng = np.random.default_rng(5)\n"
+        "for dt in (np.float32, np.float64):\n"
+        "    for (nx, ny), C in (((3, 3), 1), ((5, 7), 3), ((64, 48), 4), ((64, 48), 65), ((1000, 3), 5)):\n"
+        "        x, y, z = t.make_grid(rng, nx, ny, C, dt)\n"
+        "        it = t.build(pkg, x, y, z, t.MIXED)\n"
+        "        zx, zy, zxy = it.strategy.tables()\n"
+        "        for a, b in zip((zx, zy, zxy), bicubic_ref.tables(x, y, z, t.MIXED)): check_bits(a, b, 'tables')\n"
+        "        for nq in (1, 65, 10007):\n"
+        "            qx, qy = t.queries(rng, x, y, nq)\n"
+        "            want = bicubic_ref.evaluate(x, y, z, zx, zy, zxy, qx, qy)\n"
+        "            check_bits(it.interp_array(qx, qy), want, 'host')\n"
+        "            d = it.interp_array(torch.as_tensor(qx, device='cuda:0'), torch.as_tensor(qy, device='cuda:0'))\n"
+        "            check_bits(d.cpu().numpy(), want, 'device')\n"
+        "print('checked OK')\n") % (ROOT, os.path.join(ROOT, "tests"))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, NDI_LIB=lib), timeout=600)
+    assert r.returncode == 0 and "checked OK" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+
+
+@pytest.fixture(scope="module")
+def small(pkg):
+    """64 x 48 x 5 f64, 10 007 in-range queries, the Bicubic and the Bilinear interpolator and the expected rows"""
+    rng = np.random.default_rng(11)
+    x, y, z = make_grid(rng, 64, 48, 5, np.float64)
+    qx, qy = queries(rng, x, y, 10007)
+    bic = build(pkg, x, y, z)
+    bil = pkg.Interp2DBuilder.new(z).x(x).y(y).build()
+    want = bicubic_ref.evaluate(x, y, z, *bic.strategy.tables(), qx, qy)
+    return dict(x=x, y=y, z=z, qx=qx, qy=qy, bic=bic, bil=bil, want=want)
+
+
+def failure(it, qx, qy, **kw):
+    with pytest.raises(Exception) as e:
+        if kw.get("into") is not None:
+            it.interp_array_into(qx, qy, kw["into"])
+        else:
+            it.interp_array(qx, qy)
+    v = e.value
+    return type(v).__name__, str(v), getattr(v, "index", None), getattr(v, "value", None), getattr(v, "axis", None)
+
+
+@pytest.mark.parametrize("where", ["first", "middle", "last"])
+@pytest.mark.parametrize("kind", ["x_low", "x_high", "y_low", "y_high", "both"])
+def test_out_of_range_is_bilinears(pkg, small, kind, where):
+    import torch
+    x, y, nq = small["x"], small["y"], len(small["qx"])
+    pos = {"first": 0, "middle": nq // 2, "last": nq - 1}[where]
+    qx, qy = small["qx"].copy(), small["qy"].copy()
+    if kind in ("x_low", "both"):
+        qx[pos] = x[0] - 0.25
+    if kind == "x_high":
+        qx[pos] = x[-1] + 0.25
+    if kind == "y_low":
+        qy[pos] = y[0] - 0.25
+    if kind in ("y_high", "both"):
+        qy[pos] = y[-1] + 0.5
+    if pos + 7 < nq:
+        qy[pos + 7] = np.nan                       # a later failure must not be the one reported
+    exp = failure(small["bil"], qx, qy)
+    assert exp[2] == pos and exp[4] == (1 if kind.startswith("y") else 0)
+    assert failure(small["bic"], qx, qy) == exp                                  # fresh output, host queries
+    dqx, dqy = torch.as_tensor(qx, device="cuda:0"), torch.as_tensor(qy, device="cuda:0")
+    assert failure(small["bic"], dqx, dqy) == exp                                # fresh=True on a device buffer
+    for mk in (lambda: np.full((nq, 5), -7.0), lambda: torch.full((nq, 5), -7.0, dtype=torch.float64, device="cuda:0")):
+        buf = mk()                                                               # a caller-owned buffer
+        q = (qx, qy) if isinstance(buf, np.ndarray) else (dqx, dqy)
+        assert failure(small["bic"], *q, into=buf) == exp
+        rows = buf if isinstance(buf, np.ndarray) else buf.cpu().numpy()
+        check_bits(rows[:pos], small["want"][:pos], "rows before the failure")
+        assert np.all(rows[pos:] == -7.0), "rows from the failure on keep the sentinel"
+
+
+def test_extrapolation_continues_the_end_patches(pkg):
+    import torch
+    rng = np.random.default_rng(3)
+    for dt in (np.float32, np.float64):
+        x, y, z = make_grid(rng, 9, 7, 3, dt)
+        it = build(pkg, x, y, z, extrapolate=True)
+        wx, wy = x[-1] - x[0], y[-1] - y[0]
+        qx = rng.uniform(x[0] - wx, x[-1] + wx, 4000).astype(dt)
+        qy = rng.uniform(y[0] - wy, y[-1] + wy, 4000).astype(dt)
+        qx[:8] = [x[0] - wx, x[0] - wx, x[-1] + wx, x[-1] + wx, x[0] - wx, x[-1] + wx, x[3], x[4]]      # corners, sides
+        qy[:8] = [y[0] - wy, y[-1] + wy, y[0] - wy, y[-1] + wy, y[2], y[3], y[0] - wy, y[-1] + wy]
+        want = bicubic_ref.evaluate(x, y, z, *it.strategy.tables(), qx, qy)
+        check_bits(it.interp_array(qx, qy), want, "host")
+        check_bits(it.interp_array(torch.as_tensor(qx, device="cuda:0"), torch.as_tensor(qy, device="cuda:0")).cpu().numpy(),
+                   want, "device")
+        with pytest.raises(pkg.Panic, match="NaN"):
+            it.interp_array(np.array([x[1], np.nan], dt), np.array([y[1], y[1]], dt))
+
+
+def test_async_clone_ring_sharded_single_and_bucketed(pkg, small):
+    import torch
+    bic, want, nq = small["bic"], small["want"], len(small["qx"])
+    dqx, dqy = torch.as_tensor(small["qx"], device="cuda:0"), torch.as_tensor(small["qy"], device="cuda:0")
+    out = torch.empty((nq, 5), dtype=torch.float64, device="cuda:0")
+    bic.interp_array_into(dqx, dqy, out, async_launch=True)                      # async_launch + finish
+    bic.strategy.finish()
+    check_bits(out.cpu().numpy(), want, "async_launch + finish")
+    devices = [0] + ([1] if pkg.device_count() >= 2 else [])                      # clone: same device, and a second one
+    for d in devices:
+        rep = bic.replicate([d])[0]
+        for a, b in zip(rep.strategy.tables(), bic.strategy.tables()):
+            check_bits(a, b, f"clone to {d}: tables")
+        check_bits(rep.interp_array(small["qx"], small["qy"]), want, f"clone to {d}: rows")
+    got = np.zeros_like(want)                                                    # ring: 2 slots, 1000 does not divide 10 007
+    ring = pkg.striped_ring(1000, 5, 2, np.float64, 0)
+    chunks = []
+
+    def consumer(c, rows):
+        chunks.append(c.q_count)
+        got[c.q_begin:c.q_begin + c.q_count] = rows.cpu().numpy()
+    bic.interp_array_ring(dqx, dqy, 1000, consumer, slots=ring)
+    assert chunks == [1000] * 10 + [7]
+    check_bits(got, want, "ring")
+    reps = [build(pkg, small["x"], small["y"], small["z"]) for _ in range(2)]     # sharded: two replicas
+    got = np.full_like(want, -1.0)
+    pkg.sharding.interp_array_sharded(reps, small["qx"], small["qy"], out=got)
+    check_bits(got, want, "sharded")
+    with pytest.raises(Exception, match="replicas of one interpolator"):
+        pkg.sharding.interp_array_sharded([reps[0], small["bil"]], small["qx"], small["qy"], out=got)
+    one = bic.interp(small["qx"][5], small["qy"][5])                             # Interp2D.interp / interp_scalar
+    check_bits(one, want[5], "interp")
+    sc = build(pkg, small["x"], small["y"], np.ascontiguousarray(small["z"][:, :, 0]))
+    assert sc.interp_scalar(small["qx"][5], small["qy"][5]) == want[5, 0]
+    bic.strategy.path = pkg.PATH_BUCKETED
+    try:
+        with pytest.raises(Exception, match="Bicubic has no tile-grouped evaluation form"):
+            bic.interp_array(small["qx"], small["qy"])
+    finally:
+        bic.strategy.path = pkg.PATH_AUTO
+    cap = pkg._capi                                                               # tables of a Bilinear handle: refused
+    assert cap.lib().ndi_interp2d_tables(small["bil"].strategy._h, None, None, None, cap.MEM_HOST) == cap.BAD_ARG
+    assert "takes a Bicubic handle" in cap.last_error()
+
+
+def test_table_beyond_2_to_32_elements(pkg):
+    """3 x 3 x 2^27 f32: the grid is 4.8 GB, the node table 19 GB -- record offsets pass 2^32 elements.  Lanes are
+    independent, so the restatement runs on a sample of lanes only."""
+    import torch
+    free, _ = torch.cuda.mem_get_info(0)
+    assert free > 90 * 2**30, "the test needs 90 GB of free device memory"
+    C = 1 << 27
+    x = np.array([0.0, 1.0, 2.5], np.float32)
+    y = np.array([-1.0, 0.5, 1.0], np.float32)
+    g = torch.Generator(device="cuda:0").manual_seed(7)
+    z = torch.rand((3, 3, C), dtype=torch.float32, device="cuda:0", generator=g)
+    m = (1 << 32) // 36
+    lanes = np.array([0, 1, 2, 3] + list(range(m - 2, m + 3)) + list(range(C - 4, C)))
+    sel = torch.as_tensor(lanes, device="cuda:0")
+    it = pkg.Interp2DBuilder.new(z).x(torch.as_tensor(x, device="cuda:0")).y(torch.as_tensor(y, device="cuda:0")) \
+        .strategy(pkg.Bicubic.new()).build()
+    zs = z[:, :, sel].cpu().numpy()
+    del z
+    tabs = it.strategy.tables(on_device=True)
+    got = [t[:, :, sel].cpu().numpy() for t in tabs]
+    del tabs
+    ref = bicubic_ref.tables(x, y, zs)
+    for name, a, b in zip(("zx", "zy", "zxy"), got, ref):
+        check_bits(a, b, name)
+    rng = np.random.default_rng(2)
+    qx, qy = queries(rng, x, y, 16)
+    rows = it.interp_array(torch.as_tensor(qx, device="cuda:0"), torch.as_tensor(qy, device="cuda:0"))
+    check_bits(rows[:, sel].cpu().numpy(), bicubic_ref.evaluate(x, y, zs, *ref, qx, qy), "rows")
+    del rows
+    it.strategy.release()
+    torch.cuda.empty_cache()

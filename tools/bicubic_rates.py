@@ -1,0 +1,157 @@
+"""Rates of the Bicubic strategy against Bilinear on the same shapes (output committed as
+profiles/bicubic_rates.json).  Needs an MI355X; there is no CPU fallback.
+
+    python tools/bicubic_rates.py --out profiles/bicubic_rates.json
+        one process, device-resident inputs, median of 7 after a warm-up: `create` wall time (the call synchronises) and
+        one evaluation batch into a device buffer, for Bicubic and for Bilinear (the baseline, measured here).
+        Shapes: f32 and f64 at 100 x 100 x 1 and 100 x 100 x 5 (the reference's bench_interp2d grid), f32 2048 x 2048 x 64,
+        f32 4096 x 4096 x 16; 1e7 queries each (fewer where the output would pass 16 GiB: noted per shape).
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR/<key> -- python tools/bicubic_rates.py --profile-shape <dtype> <nx> <ny> <C>
+        one run per shape, a run of its own (tracing slows the host): REPS evaluations per strategy.
+    python tools/bicubic_rates.py --merge DIR --out profiles/bicubic_rates.json
+        adds the evaluation kernels' own times from those runs, the Bicubic / Bilinear ratio (expected from bytes: at most
+        17 / 5 = 3.4 beyond the caches, nearer 1 on cache-resident grids) and the fraction of 8 TB/s on the
+        17 Q C sizeof(T) compulsory bytes.
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+SHAPES = [("f32", 100, 100, 1), ("f64", 100, 100, 1), ("f32", 100, 100, 5), ("f64", 100, 100, 5),
+          ("f32", 2048, 2048, 64), ("f32", 4096, 4096, 16)]
+DTYPES = {"f64": np.float64, "f32": np.float32}
+QUERIES = 10_000_000
+REPS = 3
+PEAK_BPS = 8.0e12    # HBM3E spec peak of the MI355X
+
+
+def package():
+    from __graft_entry__ import load_package
+    return load_package()
+
+
+def n_queries(dt, C):
+    return int(min(QUERIES, (16 << 30) // (C * np.dtype(dt).itemsize)))
+
+
+def inputs(name, nx, ny, C):
+    import torch
+    dt = DTYPES[name]
+    rng = np.random.default_rng(nx + ny + C)
+    x = np.cumsum(rng.uniform(0.5, 1.5, nx)).astype(dt)
+    y = np.cumsum(rng.uniform(0.5, 1.5, ny)).astype(dt)
+    tdt = torch.float32 if name == "f32" else torch.float64
+    z = torch.rand((nx, ny, C), dtype=tdt, device="cuda:0")
+    nq = n_queries(dt, C)
+    qx = torch.as_tensor(rng.uniform(x[0], x[-1], nq).astype(dt), device="cuda:0")
+    qy = torch.as_tensor(rng.uniform(y[0], y[-1], nq).astype(dt), device="cuda:0")
+    out = torch.empty((nq, C), dtype=tdt, device="cuda:0")
+    return torch.as_tensor(x, device="cuda:0"), torch.as_tensor(y, device="cuda:0"), z, qx, qy, out
+
+
+def strategies(pkg):
+    return {"Bilinear": pkg.Bilinear.new, "Bicubic": pkg.Bicubic.new}
+
+
+def median_ms(fn, reps=7):
+    import torch
+    fn()                                   # warm-up: code objects, allocations
+    torch.cuda.synchronize()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(t)), float(min(t)), float(max(t))
+
+
+def timing_pass(out_path):
+    import torch
+    pkg = package()
+    assert torch.cuda.is_available() and pkg.device_count() >= 1, "needs a GPU"
+    res = {"device": torch.cuda.get_device_name(0), "create_ms": {}, "eval_ms": {}}
+    for name, nx, ny, C in SHAPES:
+        key = f"{name}_{nx}x{ny}x{C}"
+        x, y, z, qx, qy, out = inputs(name, nx, ny, C)
+        res["create_ms"][key], res["eval_ms"][key] = {}, {"queries": int(qx.numel())}
+        handles = {}
+        for sname, new in strategies(pkg).items():
+            def create():
+                return pkg.Interp2DBuilder.new(z).x(x).y(y).strategy(new()).build()
+            med, lo, hi = median_ms(create)
+            res["create_ms"][key][sname] = {"median": med, "min": lo, "max": hi}
+            handles[sname] = create()
+        for rnd in range(2):               # alternate the two handles: other work shares the host
+            for sname, h in handles.items():
+                med, lo, hi = median_ms(lambda: h.interp_array_into(qx, qy, out))
+                res["eval_ms"][key][f"{sname}_round{rnd}"] = {"median": med, "min": lo, "max": hi}
+        print(key, json.dumps(res["create_ms"][key]), json.dumps(res["eval_ms"][key]), flush=True)
+        del handles, x, y, z, qx, qy, out
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    json.dump(res, open(out_path, "w"), indent=1)
+
+
+def profile_shape(name, nx, ny, C):
+    pkg = package()
+    x, y, z, qx, qy, out = inputs(name, nx, ny, C)
+    for sname, new in strategies(pkg).items():
+        h = pkg.Interp2DBuilder.new(z).x(x).y(y).strategy(new()).build()
+        for _ in range(REPS):
+            h.interp_array_into(qx, qy, out)
+    print("profiled", name, nx, ny, C, flush=True)
+
+
+def merge(prof_dir, out_path):
+    res = json.load(open(out_path)) if os.path.exists(out_path) else {}
+    res["eval_kernels"] = {}
+    for name, nx, ny, C in SHAPES:
+        key = f"{name}_{nx}x{ny}x{C}"
+        files = glob.glob(os.path.join(prof_dir, key, "**", "*kernel_stats.csv"), recursive=True)
+        if not files:
+            continue
+        per, names = {"Bilinear": 0.0, "Bicubic": 0.0}, {"Bilinear": [], "Bicubic": []}
+        for row in csv.DictReader(open(files[0])):
+            kn, total = row["Name"], float(row["TotalDurationNs"])
+            if "eval_bicubic_kernel" in kn:
+                who = "Bicubic"
+            elif "eval_" in kn and "2d" in kn or "eval_bilinear" in kn:
+                who = "Bilinear"
+            else:
+                who = None               # range pre-passes, builds, fills
+            if who:
+                per[who] += total / REPS
+                names[who].append(kn.split("(")[0])
+        nq, size = n_queries(DTYPES[name], C), np.dtype(DTYPES[name]).itemsize
+        entry = {"queries": nq, "compulsory_bytes_bicubic": 17 * nq * C * size}
+        for who, ns in per.items():
+            entry[who] = {"kernel_ms_per_batch": ns / 1e6, "kernels": sorted(set(names[who]))}
+        if per["Bilinear"] > 0 and per["Bicubic"] > 0:
+            entry["ratio_bicubic_over_bilinear"] = per["Bicubic"] / per["Bilinear"]
+            entry["bicubic_fraction_of_8TBps"] = entry["compulsory_bytes_bicubic"] / (per["Bicubic"] * 1e-9) / PEAK_BPS
+        res["eval_kernels"][key] = entry
+        print(key, json.dumps(entry), flush=True)
+    json.dump(res, open(out_path, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bicubic_rates.json"))
+    ap.add_argument("--profile-shape", nargs=4, metavar=("DTYPE", "NX", "NY", "C"))
+    ap.add_argument("--merge", metavar="DIR")
+    a = ap.parse_args()
+    if a.profile_shape:
+        profile_shape(a.profile_shape[0], *(int(v) for v in a.profile_shape[1:]))
+    elif a.merge:
+        merge(a.merge, a.out)
+    else:
+        timing_pass(a.out)
