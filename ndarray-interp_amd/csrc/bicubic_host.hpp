@@ -148,8 +148,9 @@ static void bicubic_launch_eval(const Interp2DImpl<T>& h, hipStream_t s, StatusB
   const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + TB - 1) / TB,
                                                                         std::max<uint64_t>(1, (uint64_t)cu_count() * wg_per_cu * 4 / gy)));
   if (std::getenv("NDI_TRACE_PLAN"))
-    std::fprintf(stderr, "[ndi plan] bicubic vec=%d lv=%llu klds=%d grid=%u x %u lds=%zu prepass=%d\n", (int)vec,
-                 (unsigned long long)A.lv, (int)klds, gx, gy, lds, check ? 0 : 1);
+    std::fprintf(stderr, "[ndi plan] bicubic vec=%d lv=%llu klds=%d grid=%u x %u lds=%zu prepass=%d guess=%d,%d levels=%d,%d\n",
+                 (int)vec, (unsigned long long)A.lv, (int)klds, gx, gy, lds, check ? 0 : 1, A.px.guess, A.py.guess,
+                 A.px.levels, A.py.levels);
 #define NDI_BC(VEC, KL)                                                                  \
   do {                                                                                   \
     auto kern = eval_bicubic_kernel<T, VEC, KL, TB>;                                     \

@@ -18,6 +18,8 @@ import oracle
 
 NOT_A_KNOT = (oracle.BC_NOT_A_KNOT, 0.0)
 DEFAULT_BC = (NOT_A_KNOT,) * 4
+# one end condition of every other kind, a nonzero value among them: the second end set of the Bicubic tests
+MIXED_BC = ((oracle.BC_NATURAL, 0.0), (oracle.BC_FIRST_DERIV, 0.75), (oracle.BC_CLAMPED, 0.0), (oracle.BC_CLAMPED, 0.0))
 
 
 def _specialize(end):
@@ -121,16 +123,17 @@ def hermite(pl, pr, kl, kr, h, s, variant=None):
     return c0 * pl + s * pr + (s * c0) * (a * c0 + b * s)
 
 
-def cells(x, y, qx, qy):
-    """get_lower_index on each axis: clamped to the end cells, so queries outside continue the end patch."""
-    i = np.clip(np.searchsorted(x, qx, side="right") - 1, 0, len(x) - 2)
-    j = np.clip(np.searchsorted(y, qy, side="right") - 1, 0, len(y) - 2)
+def cells(x, y, qx, qy, side="right"):
+    """get_lower_index on each axis: clamped to the end cells, so queries outside continue the end patch.  `side="left"` is
+    the wrong search (a query at a knot falls into the cell below), for the self-check of the hostile query sets."""
+    i = np.clip(np.searchsorted(x, qx, side=side) - 1, 0, len(x) - 2)
+    j = np.clip(np.searchsorted(y, qy, side=side) - 1, 0, len(y) - 2)
     return i, j
 
 
-def evaluate(x, y, z, zx, zy, zxy, qx, qy, variant=None):
+def evaluate(x, y, z, zx, zy, zxy, qx, qy, variant=None, side="right"):
     """Rows (Q, C) of the bicubic Hermite patches at (qx, qy)."""
-    i, j = cells(x, y, qx, qy)
+    i, j = cells(x, y, qx, qy, side)
     hx = (x[i + 1] - x[i])
     t = ((qx - x[i]) / hx)[:, None]
     hy = (y[j + 1] - y[j])

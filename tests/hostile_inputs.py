@@ -1,4 +1,5 @@
-"""Hostile inputs for the Pchip / Akima / CubicHermite build and the derivative build, and a bit-level comparer.
+"""Hostile inputs for the Pchip / Akima / CubicHermite build and the derivative build, and a bit-level comparer; at the
+end of the file the hostile grids, lanes and queries of the 2-D Bicubic strategy.
 
 The rules (include/ndinterp.h, ndi_strategy1d / ndi_interp1d_derivative) have data-dependent branches and rest on plain
 IEEE arithmetic: correctly rounded division, nothing fused, f32 subnormals kept.  The generators here plant every branch
@@ -435,3 +436,176 @@ def branch_table(rule, dtype, n, L):
     for _, x, y, k in cases(rule, dtype, n, L):
         total.update(classify(rule, x, y, k))
     return total
+
+
+# ---- Bicubic: hostile grids (tests/test_gpu_bicubic_hostile.py, self-check in tests/test_hostile_inputs.py) ---------------
+# The spline build squares the knot spacings, so the `huge` / `mixed` axes above (and subnormal spacings) leave no finite
+# table entry; these families stay inside the range where the restatement (tests/bicubic_ref.py) is finite on integer data.
+BICUBIC_FAMILIES = ("uneven", "adjacent", "big", "small", "mixed2")
+BICUBIC_GRIDS = ((6, 7), (65, 5))
+BICUBIC_LANES = (1, 4, 5, 9)
+BICUBIC_RECIPES = ("integers", "subnormal", "constant", "+0", "-0", "inf node", "nan node", "top scale", "-0 among integers")
+BICUBIC_NONFINITE = (5, 6)        # positions of the two non-finite recipes in BICUBIC_RECIPES
+_BICUBIC_EXP = {np.dtype(np.float32): dict(step=40, coarse=10, sub=-135), np.dtype(np.float64): dict(step=400, coarse=100, sub=-1050)}
+
+
+def bicubic_knots(family, dtype, n, seed=0):
+    """uneven / adjacent: knots() above.  big / small: steps of 2^40 / 2^-40 (f32), 2^400 / 2^-400 (f64), centred so that 0.0
+    is a knot.  mixed2: adjacent floats from 1.0 for the first half, then steps of 2^10 (f32) / 2^100 (f64)."""
+    T = np.dtype(dtype).type
+    e = _BICUBIC_EXP[np.dtype(dtype)]
+    if family in ("uneven", "adjacent"):
+        return knots(family, dtype, n, seed)
+    if family in ("big", "small"):
+        step = np.ldexp(T(1), e["step"] if family == "big" else -e["step"])
+        x = ((np.arange(n) - n // 2).astype(dtype) * step).astype(dtype)
+    else:
+        assert family == "mixed2", family
+        x = np.empty(n, dtype)
+        x[0] = 1.0
+        for i in range(1, n):
+            x[i] = np.nextafter(x[i - 1], T(np.inf)) if i < (n + 1) // 2 else x[i - 1] + np.ldexp(T(1), e["coarse"])
+    assert np.all(np.isfinite(x)) and np.all(x[1:] > x[:-1])
+    return x
+
+
+def bicubic_ends():
+    """The two end-condition sets of the Bicubic tests: the default (None) and the MIXED ends of tests/test_gpu_bicubic.py."""
+    import bicubic_ref
+    return (None, bicubic_ref.MIXED_BC)
+
+
+def bicubic_grid(fx, fy, dtype, nx, ny):
+    return bicubic_knots(fx, dtype, nx, 0), bicubic_knots(fy, dtype, ny, 1)
+
+
+def bicubic_pairs(dtype):
+    """The (x family, y family) pairs the tests run.  f64 small x big is left out: its cross table zxy is a slope of the
+    order 2^400 divided once more by 2^-400, which overflows with the default ends (tests/test_hostile_inputs.py shows it)."""
+    return [(fx, fy) for fx in BICUBIC_FAMILIES for fy in BICUBIC_FAMILIES
+            if not (np.dtype(dtype) == np.float64 and (fx, fy) == ("small", "big"))]
+
+
+def bicubic_lane(recipe, dtype, nx, ny, rng, top_exp=0):
+    """One lane (nx, ny) of node data.  `rng` is consumed the same way by every recipe, so the integer background of two
+    arrays made with the same seed is the same lane by lane."""
+    T = np.dtype(dtype).type
+    ints = rng.integers(-3, 5, (nx, ny)).astype(dtype)
+    name = BICUBIC_RECIPES[recipe] if isinstance(recipe, int) else recipe
+    if name == "integers":
+        return ints
+    if name == "subnormal":       # the flush-to-zero detector: every node value is subnormal or zero
+        return (ints * np.ldexp(T(1), _BICUBIC_EXP[np.dtype(dtype)]["sub"])).astype(dtype)
+    if name == "constant":
+        return np.full((nx, ny), 2.5, dtype)
+    if name == "+0":
+        return np.zeros((nx, ny), dtype)
+    if name == "-0":
+        return np.full((nx, ny), -0.0, dtype)
+    if name in ("inf node", "nan node"):      # one interior node
+        ints[nx // 2, ny // 2] = np.inf if name == "inf node" else np.nan
+        return ints
+    if name == "top scale":
+        with np.errstate(over="ignore"):
+            return (ints * np.ldexp(T(1), top_exp)).astype(dtype)
+    assert name == "-0 among integers", name
+    ints[ints == 0] = -0.0
+    return ints
+
+
+def bicubic_nodes(dtype, nx, ny, C, part=0, top_exp=0, seed=0, finite_only=False):
+    """(z, names): z (nx, ny, C); lane l carries recipe (part * C + l) mod len(BICUBIC_RECIPES).  `finite_only` puts the
+    integer lane where the inf / NaN recipes would go and changes nothing else (the lane-independence check)."""
+    z = np.empty((nx, ny, C), dtype)
+    names = []
+    for l in range(C):
+        r = (part * C + l) % len(BICUBIC_RECIPES)
+        rng = np.random.default_rng([seed, nx, ny, r])
+        if finite_only and r in BICUBIC_NONFINITE:
+            r = 0
+        names.append(BICUBIC_RECIPES[r])
+        z[:, :, l] = bicubic_lane(r, dtype, nx, ny, rng, top_exp)
+    return z, names
+
+
+def bicubic_parts(C):
+    return -(-len(BICUBIC_RECIPES) // C)
+
+
+def bicubic_axis_queries(k, extrapolate=False):
+    """One axis: every knot, the float just above and just below each knot (clipped into range), every midpoint, both
+    zeros where 0.0 is a knot; with `extrapolate` points up to a full axis width outside, points 2^20 widths outside and
+    +-inf."""
+    T = k.dtype.type
+    q = [k, np.nextafter(k, T(np.inf)), np.nextafter(k, T(-np.inf)), k[:-1] + (k[1:] - k[:-1]) / T(2)]
+    if np.any(k == 0):
+        q.append(np.array([-0.0, 0.0], k.dtype))
+    q = np.clip(np.concatenate(q).astype(k.dtype), k[0], k[-1])      # (np.clip keeps the sign of a zero)
+    if extrapolate:
+        w = k[-1] - k[0]
+        far = np.ldexp(w, 20)
+        q = np.concatenate([q, np.array([k[0] - w, k[0] - w / T(3), np.nextafter(k[0], T(-np.inf)), np.nextafter(k[-1], T(np.inf)),
+                                         k[-1] + w / T(3), k[-1] + w, k[0] - far, k[-1] + far, -np.inf, np.inf], k.dtype)])
+    return q
+
+
+def bicubic_queries(x, y, extrapolate=False, seed=0, n_random=2000):
+    """(qx, qy): the cross product of the two axes' sets, then `n_random` points spread over the cells (a random cell and a
+    random position inside it on each axis, so the wide cells of a mixed axis do not take them all)."""
+    ax, ay = bicubic_axis_queries(x, extrapolate), bicubic_axis_queries(y, extrapolate)
+    gx, gy = np.meshgrid(ax, ay, indexing="ij")
+    rng = np.random.default_rng([seed, len(x), len(y)])
+
+    def spread(k):
+        i = rng.integers(0, len(k) - 1, n_random)
+        return np.clip(k[i] + (k[i + 1] - k[i]) * rng.uniform(0, 1, n_random).astype(k.dtype), k[0], k[-1]).astype(k.dtype)
+    return np.concatenate([gx.ravel(), spread(x)]), np.concatenate([gy.ravel(), spread(y)])
+
+
+def bicubic_reference(x, y, z, bc=None, qx=None, qy=None, tabs=None, side="right"):
+    """(tables, rows) of the restatement with numpy's floating-point warnings off.  `tabs`: evaluate on these tables (the
+    device's own) instead of the restatement's; `side="left"`: the wrong cell search, for the self-check."""
+    import bicubic_ref
+    with np.errstate(all="ignore"):
+        if tabs is None:
+            tabs = bicubic_ref.tables(x, y, z, bc or bicubic_ref.DEFAULT_BC)
+        if qx is None:
+            return tabs, None
+        return tabs, bicubic_ref.evaluate(x, y, z, *tabs, qx, qy, side=side)
+
+
+def finite_share(*arrays):
+    return float(np.mean(np.concatenate([np.isfinite(a).ravel() for a in arrays])))
+
+
+_TOP = {}
+
+
+def bicubic_top_exponent(dtype, fx="uneven", fy="uneven"):
+    """The largest e for which integer nodes times 2^e keep tables and rows of the restatement at least 90 % finite on this
+    pair of knot families, on every grid of BICUBIC_GRIDS and both end sets -- found, not guessed.  The divisions by the knot
+    spacings move it a long way: 2^118 / 2^1014 on uneven x uneven, far less on adjacent or small axes, so one exponent for
+    all pairs would leave the lane all inf and NaN on most of them.  Bisection: tables and rows are linear in the nodes and a
+    power of two scales them exactly, so what overflows at e overflows at e + 1 (tests/test_hostile_inputs.py holds the
+    result to ok(e) and not ok(e + 1) for every pair)."""
+    key = (np.dtype(dtype), fx, fy)
+    if key not in _TOP:
+        lo, hi = 0, np.finfo(dtype).maxexp      # ok(lo): the integer lane itself; 2^maxexp is inf
+        assert bicubic_top_ok(dtype, fx, fy, lo), key
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if bicubic_top_ok(dtype, fx, fy, mid) else (lo, mid)
+        _TOP[key] = lo
+    return _TOP[key]
+
+
+def bicubic_top_ok(dtype, fx, fy, e):
+    return all(_top_ok(dtype, fx, fy, e, nx, ny, bc) for nx, ny in BICUBIC_GRIDS for bc in bicubic_ends())
+
+
+def _top_ok(dtype, fx, fy, e, nx, ny, bc):
+    x, y = bicubic_grid(fx, fy, dtype, nx, ny)
+    z = bicubic_lane("top scale", dtype, nx, ny, np.random.default_rng([0, nx, ny, 7]), e)[:, :, None]
+    qx, qy = bicubic_queries(x, y)
+    tabs, rows = bicubic_reference(x, y, z, bc, qx, qy)
+    return finite_share(*tabs) >= 0.9 and finite_share(rows) >= 0.9

@@ -10,7 +10,6 @@ import numpy as np
 import pytest
 
 import bicubic_ref
-import oracle
 from conftest import ROOT
 from hostile_inputs import check_bits
 
@@ -19,7 +18,7 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(3, 3), (3, 4), (4, 3), (5, 7), (64, 48), (1000, 3)]
 LANES = [1, 2, 3, 4, 5, 64, 65]
 NQS = [1, 63, 64, 65, 10007]
-MIXED = ((oracle.BC_NATURAL, 0.0), (oracle.BC_FIRST_DERIV, 0.75), (oracle.BC_CLAMPED, 0.0), (oracle.BC_CLAMPED, 0.0))
+MIXED = bicubic_ref.MIXED_BC
 
 
 def make_grid(rng, nx, ny, C, dt):

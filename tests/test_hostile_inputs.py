@@ -5,7 +5,9 @@
 * check_bits sees the sign of a zero and the position of a NaN;
 * sgn(NaN) = 0: the header's statement, the restatement's `sgn`, and what follows for Pchip's end formula;
 * the restatement on the finite hostile classes still agrees with scipy;
-* mutants of the restatement -- the subtle ways a kernel could be wrong -- are told apart by at least one hostile array.
+* mutants of the restatement -- the subtle ways a kernel could be wrong -- are told apart by at least one hostile array;
+* the hostile Bicubic grids (tests/test_gpu_bicubic_hostile.py): finite where they claim to be, subnormal where they claim to
+  be, non-finite in the planted lanes only, with queries that tell a left-sided cell search from the right-sided one.
 """
 import os
 
@@ -318,3 +320,132 @@ def test_derivative_restatement_keeps_its_order():
     x = np.array([0.0, 2.0, 3.0]); y = np.array([[1.0], [4.0], [2.0]]); a = np.array([[0.5], [-1.0]]); b = np.array([[2.0], [3.0]])
     Y, A, B = derivative_ref.derive(x, y, a, b)
     assert Y.ravel().tolist() == [1.75, -3.0, -5.0] and A.ravel().tolist() == [2.25, 12.0] and np.array_equal(A, B)
+
+
+# ---- the hostile Bicubic grids ----------------------------------------------------------------------------------------------
+BICUBIC_FINITE = [i for i, n in enumerate(hostile.BICUBIC_RECIPES) if n not in ("inf node", "nan node")]
+BICUBIC_CASES = [(dt, fx, fy) for dt in DTYPES for fx, fy in hostile.bicubic_pairs(dt)]
+
+
+def _bicubic_case(dt, fx, fy, nx, ny, bc, finite_only=False, side="right"):
+    x, y = hostile.bicubic_grid(fx, fy, dt, nx, ny)
+    z, names = hostile.bicubic_nodes(dt, nx, ny, len(hostile.BICUBIC_RECIPES), 0, hostile.bicubic_top_exponent(dt, fx, fy),
+                                    finite_only=finite_only)
+    qx, qy = hostile.bicubic_queries(x, y)
+    tabs, rows = hostile.bicubic_reference(x, y, z, bc, qx, qy, side=side)
+    return x, y, z, names, qx, qy, tabs, rows
+
+
+@pytest.mark.parametrize("dt,fx,fy", BICUBIC_CASES, ids=[f"{np.dtype(c[0]).name}-{c[1]}-{c[2]}" for c in BICUBIC_CASES])
+def test_bicubic_hostile_grids_are_what_they_claim(dt, fx, fy):
+    """Every (family pair, dtype) of the GPU tests, all recipes side by side in one array of nine lanes (lanes are independent,
+    and bicubic_nodes gives a recipe the same lane whatever the array it sits in -- the last test below), both grids, both end
+    sets, so that the device comparison is not NaN against NaN:
+    * tables and rows of the finite recipes are at least 90 % finite on every grid and end set;
+    * the subnormal lane's rows are at least 30 % subnormal with the default ends (MIXED prescribes an end slope of 0.75 on
+      x, which no scaling of the data makes subnormal: rows near that end are of the order 1).  The share is pooled over
+      the rows of both grids, one figure per (family pair, dtype).  Taken per grid it is printed below; its smallest values
+      are 23 % on mixed2 x mixed2 and 34 % on mixed2 x adjacent, both on 6 x 7 in either dtype, and about 40 % or more
+      everywhere else -- so every grid of every pair has subnormal rows for a flush to zero to show in: at least 20 % on
+      each grid is asserted as well, a floor under those figures that still leaves hundreds of rows for a flush to show in;
+    * the top-scale lane counts among the finite recipes: its exponent is found per family pair (the last test but one);
+    * the inf and the NaN lane have non-finite rows, and every other lane has the bits it has without them;
+    * evaluating with searchsorted(side="left") changes the bits of at least one row over the two grids: the queries at the
+      nodes see the difference (a Hermite patch gives the node value from either side, so only the sign of a zero result
+      can tell -- the "-0 among integers" lane is there for that)."""
+    tiny = np.finfo(dt).tiny
+    sub, total, left_differs, per_grid = 0, 0, 0, {}
+    for nx, ny in hostile.BICUBIC_GRIDS:
+        for bi, bc in enumerate(hostile.bicubic_ends()):
+            x, y, z, names, qx, qy, tabs, rows = _bicubic_case(dt, fx, fy, nx, ny, bc)
+            what = f"{np.dtype(dt).name} {fx} x {fy} {nx}x{ny} ends {bi}"
+            assert names == list(hostile.BICUBIC_RECIPES)
+            for l in BICUBIC_FINITE:
+                assert hostile.finite_share(*[t[:, :, l] for t in tabs]) >= 0.9, (what, names[l], "tables")
+                assert hostile.finite_share(rows[:, l]) >= 0.9, (what, names[l], "rows")
+            if bc is None:
+                l = names.index("subnormal")
+                here = int(np.count_nonzero((rows[:, l] != 0) & (np.abs(rows[:, l]) < tiny)))
+                per_grid[f"{nx}x{ny}"] = round(here / len(rows), 2)
+                assert here >= 0.2 * len(rows), (what, "subnormal rows on this grid", per_grid)
+                sub += here
+                total += len(rows)
+            _, _, _, _, _, _, ftabs, frows = _bicubic_case(dt, fx, fy, nx, ny, bc, finite_only=True)
+            for l, name in enumerate(names):
+                if l in hostile.BICUBIC_NONFINITE:
+                    assert not np.all(np.isfinite(rows[:, l])), (what, name)
+                    assert hostile.finite_share(frows[:, l]) >= 0.9, (what, name)
+                else:
+                    for a, b in zip(tabs + (rows,), ftabs + (frows,)):
+                        check_bits(a[..., l], b[..., l], f"{what}: lane {name} beside the non-finite lanes")
+            left = _bicubic_case(dt, fx, fy, nx, ny, bc, side="left")[-1]
+            same = ((rows == left) & (np.signbit(rows) == np.signbit(left))) | (np.isnan(rows) & np.isnan(left))
+            left_differs += int(np.count_nonzero(~same.all(axis=1)))
+    assert sub >= 0.3 * total, (sub, total)
+    assert left_differs >= 1
+    print(f"{np.dtype(dt).name} {fx} x {fy}: subnormal rows {sub / total:.2f} {per_grid}, rows a left-sided search changes {left_differs}")
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_bicubic_top_scale_is_the_largest(dt):
+    """The "top scale" lane: integers times 2^e with the largest e that keeps tables and rows 90 % finite on both grids and
+    both end sets, found for every family pair (the knot spacings divide into it); e + 1 does not.  That the lane, as it sits
+    in the arrays, is 90 % finite on every pair is part of test_bicubic_hostile_grids_are_what_they_claim."""
+    found = {}
+    for fx, fy in hostile.bicubic_pairs(dt):
+        e = found[fx, fy] = hostile.bicubic_top_exponent(dt, fx, fy)
+        assert hostile.bicubic_top_ok(dt, fx, fy, e) and not hostile.bicubic_top_ok(dt, fx, fy, e + 1), (fx, fy, e)
+    print(f"{np.dtype(dt).name}: top scales 2^e, e = {found}")
+
+
+def test_bicubic_generators_are_seeded_and_shaped():
+    for dt in DTYPES:
+        T = np.dtype(dt).type
+        for fam in hostile.BICUBIC_FAMILIES:
+            for n in (5, 6, 7, 65):
+                k = hostile.bicubic_knots(fam, dt, n)
+                assert k.dtype == np.dtype(dt) and k.shape == (n,) and np.all(np.isfinite(k)) and np.all(k[1:] > k[:-1])
+                assert (0.0 in k) == (fam in ("big", "small"))
+                assert hostile.has_adjacent(k) == (fam in ("adjacent", "mixed2"))
+                # the query set: every knot, and both neighbours of every knot that lie in range; both zeros where 0.0 is a knot
+                for ext in (False, True):
+                    q = hostile.bicubic_axis_queries(k, ext)
+                    assert q.dtype == np.dtype(dt) and not np.isnan(q).any()
+                    have = set(q.tolist())
+                    for v in k:
+                        assert v in have
+                        for nb in (np.nextafter(v, T(-np.inf)), np.nextafter(v, T(np.inf))):
+                            assert nb in have or not (k[0] <= nb <= k[-1])
+                    for a, b in zip(k[:-1], k[1:]):
+                        assert a + (b - a) / T(2) in have
+                    if 0.0 in k:
+                        z = q[q == 0]
+                        assert np.signbit(z).any() and not np.signbit(z).all()
+                    w = k[-1] - k[0]
+                    outside = q[(q < k[0]) | (q > k[-1])]
+                    assert len(outside) == (10 if ext else 0)
+                    if ext:
+                        assert np.isinf(outside).sum() == 2 and k[0] - np.ldexp(w, 20) in have and k[-1] + w in have
+        # a recipe's lane does not depend on the array it sits in: what the nine-lane self-check shows holds for every
+        # (lanes, part) of the GPU tests; and every recipe occurs for every lane count
+        nx, ny = hostile.BICUBIC_GRIDS[0]
+        top = hostile.bicubic_top_exponent(dt)
+        full, names = hostile.bicubic_nodes(dt, nx, ny, len(hostile.BICUBIC_RECIPES), 0, top)
+        assert full.shape == (nx, ny, 9) and np.isinf(full[..., 5]).sum() == 1 and np.isnan(full[..., 6]).sum() == 1
+        assert np.isinf(full[nx // 2, ny // 2, 5]) and np.isnan(full[nx // 2, ny // 2, 6])
+        assert np.all(np.signbit(full[..., 4])) and not np.signbit(full[..., 3]).any() and np.signbit(full[..., 8][full[..., 8] == 0]).all()
+        for C in hostile.BICUBIC_LANES:
+            seen = []
+            for part in range(hostile.bicubic_parts(C)):
+                z, nm = hostile.bicubic_nodes(dt, nx, ny, C, part, top)
+                z2, _ = hostile.bicubic_nodes(dt, nx, ny, C, part, top)
+                check_bits(z, z2, "seeded")
+                for l, name in enumerate(nm):
+                    check_bits(z[..., l], full[..., names.index(name)], f"C={C} part={part} lane {l}")
+                seen += nm
+            assert set(seen) == set(hostile.BICUBIC_RECIPES), (C, seen)
+        x, y = hostile.bicubic_grid("big", "uneven", dt, nx, ny)
+        qx, qy = hostile.bicubic_queries(x, y)
+        ax, ay = hostile.bicubic_axis_queries(x), hostile.bicubic_axis_queries(y)
+        assert len(qx) == len(qy) == len(ax) * len(ay) + 2000 and qx.dtype == qy.dtype == np.dtype(dt)
+        assert x[0] <= qx.min() and qx.max() <= x[-1] and y[0] <= qy.min() and qy.max() <= y[-1]
