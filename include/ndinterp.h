@@ -256,8 +256,27 @@ typedef struct ndi_interp2d_desc {
  *  ndi_interp2d_probe_ceiling.
  *  Device memory: the node table {z, zx, zy, zxy} per grid node, T[nx][ny][4][C] = four times the grid, plus the two knot
  *  axes; the plain grid is not kept.  The build's temporaries (about seven grids at the peak) are freed before create returns.
- * Not provided: periodic and per-lane boundaries, Pchip / Akima node derivatives, partial-derivative and integral handles,
- * a tile-grouped evaluation form, a blocked-sweep build for narrow grids, half and integer element types. */
+ * Partial derivatives (ndi_interp2d_partial): a handle that evaluates d^(nu_x + nu_y) / dx^nu_x dy^nu_y of the surface,
+ * nu_x, nu_y in {0, 1, 2}, not both 0 -- the orders scipy's RectBivariateSpline.ev(x, y, dx, dy) offers.  The node table
+ * {z, zx, zy, zxy} determines all of them; the handle SHARES its source's table (no copy: three gradient handles cost three
+ * pairs of knot axes, not three tables), and the table is freed with the last handle that holds it, whatever the order of
+ * the ndi_interp2d_destroy calls.  Every line is one IEEE operation in T, in this order, nothing fused; d, a, b as in H:
+ *     c1 = d + a          c2 = b - (a + a)          c3 = b - a
+ *     H0(pl, pr, kl, kr, h, s) = H(pl, pr, kl, kr, h, s)
+ *     H1(pl, pr, kl, kr, h, s) = (c1 + s * ((c2 + c2) - (3 * c3) * s)) / h
+ *     H2(pl, pr, kl, kr, h, s) = ((c2 + c2) - (6 * c3) * s) / (h * h)
+ *  (the form is q(s) = pl + (d + a) s + (b - 2a) s^2 - (b - a) s^3, the expansion of the 1-D antiderivative contract), and
+ *  the evaluation is the one above with the forms swapped: p0, p1, d0, d1 = H_{nu_y}(..., hy, u) on the same sixteen
+ *  operands, result = H_{nu_x}(p0, p1, d0, d1, hx, t); cell, t, u, hx, hy exactly as above, and with `extrapolate` the end
+ *  cell's patch continued with t / u outside [0, 1].  The spline is C2 in each variable, so all eight orders are continuous
+ *  across grid lines up to rounding; a query on an interior grid line evaluates the cell to its right / above
+ *  (get_lower_index), the 1-D handles' convention.  Range, NaN, first-error and rows-before-the-error semantics, the eval
+ *  flags, the ring and sharded calls, _trim, _clone (the table is copied, the orders kept), _tables (the origin's zx, zy,
+ *  zxy) and the refusal of NDI_PATH_BUCKETED / _probe_ceiling are the Bicubic handle's, unchanged.  The orders are part of
+ *  the replica signature: a sharded set that mixes a surface with its partial, or two different partials, is refused.
+ * Not provided: periodic and per-lane boundaries, Pchip / Akima node derivatives, integral handles, third derivatives, a
+ * fused value-and-gradient call, a tile-grouped evaluation form, a blocked-sweep build for narrow grids, half and integer
+ * element types. */
 typedef struct ndi_interp1d ndi_interp1d; /* owns device copies of x, data (and a, b) */
 typedef struct ndi_interp2d ndi_interp2d;
 
@@ -325,6 +344,13 @@ ndi_status ndi_interp2d_create_bicubic(const ndi_interp2d_desc* desc, const ndi_
 /* The node derivatives of a Bicubic handle as plain T[nx][ny][lanes] arrays, whatever the internal layout (any of the three
  * may be NULL): the 2-D counterpart of ndi_interp1d_coefficients.  NDI_BAD_ARG for a Bilinear handle. */
 ndi_status ndi_interp2d_tables(const ndi_interp2d* h, void* zx, void* zy, void* zxy, int32_t memspace);
+/* A new handle that evaluates the partial derivative of orders (nu_x, nu_y) of `h`'s surface (contract above ndi_interp1d):
+ * the 2-D counterpart of ndi_interp1d_derivative.  `h`: a Bicubic handle or a partial handle of one; orders add (a partial of
+ * a partial acts as if asked of the origin with the orders summed); after summing nu_x, nu_y in {0, 1, 2}.  NDI_BAD_ARG, with
+ * *out cleared first and a message naming the strategy and the reason, decided before any device work: a Bilinear handle,
+ * an order below 0 or summing above 2, (0, 0), a null `h` or `out`.  The new handle shares `h`'s node table and has its
+ * knots, `extrapolate` and device; either may be destroyed first.  A new symbol: no new enumerator, no struct change. */
+ndi_status ndi_interp2d_partial(const ndi_interp2d* h, int32_t nu_x, int32_t nu_y, ndi_interp2d** out);
 void ndi_interp2d_destroy(ndi_interp2d* h);
 
 /* A replica of a built interpolator on `device` (any device, the handle's own included): the device-resident knots /

@@ -104,6 +104,7 @@ SYMBOLS = {
     "ndi_interp2d_create": (C.c_int, [C.POINTER(Interp2DDesc), C.POINTER(_P)]),
     "ndi_interp2d_create_bicubic": (C.c_int, [C.POINTER(Interp2DDesc), C.POINTER(Boundary), C.POINTER(_P)]),
     "ndi_interp2d_tables": (C.c_int, [_P, _P, _P, _P, C.c_int32]),
+    "ndi_interp2d_partial": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(_P)]),
     "ndi_interp2d_destroy": (None, [_P]),
     "ndi_interp1d_clone": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),
     "ndi_interp2d_clone": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),

@@ -2,7 +2,9 @@
 //
 // A Bicubic handle IS an Interp2DImpl (bicubic == true, `table` instead of `data`): eval, async_launch / finish, the ring,
 // the sharded calls, trim and clone are the Bilinear code; only the plan (Plan2::BICUBIC: range pre-pass unless the output
-// is fresh, then eval_bicubic_kernel) and the build below are its own.
+// is fresh, then eval_bicubic_kernel) and the build below are its own.  A partial-derivative handle
+// (ndi_interp2d_partial, Interp2DImpl::partial) is the same again with the orders nu_x, nu_y set and the node table shared
+// with its source: bicubic_launch_eval picks the kernel instance of the orders, nothing else knows about them.
 //
 // Build: three 1-D CubicSpline builds in the reference operation order (NDI_BUILD_REFERENCE_ORDER: the serial kernels,
 // bit-identical to the reference for every shape) followed by the derivative rule (derivative_build_kernel):
@@ -106,9 +108,10 @@ static ndi_status create2d_bicubic(const ndi_interp2d_desc& d, const ndi_boundar
     st = bicubic_axis_pass<T>(d.dtype, d.device, h->py.view.lv0, ny, nx * L, tr.as<T>(), cl, cr, zxyT.as<T>());
     if (st != NDI_OK) return st;
   }
-  h->table.reserve(4 * bytes);
+  h->table = std::make_shared<DevBuf>();
+  h->table->reserve(4 * bytes);
   hipLaunchKernelGGL(pack_nodes_kernel<T>, dim3(g), dim3(BLOCK), 0, s0, z, (const T*)zx.as<T>(), (const T*)zyT.as<T>(),
-                     (const T*)zxyT.as<T>(), h->table.template as<T>(), nx, ny, L);
+                     (const T*)zxyT.as<T>(), h->table->template as<T>(), nx, ny, L);
   NDI_HIP(hipGetLastError());
   NDI_HIP(hipStreamSynchronize(s0));         // the table is complete when create returns: any stream may read it
   *out = h.release();
@@ -124,7 +127,7 @@ static void bicubic_launch_eval(const Interp2DImpl<T>& h, hipStream_t s, StatusB
   const bool vec = (h.lanes % VN == 0) && (out_stride % VN == 0) && aligned16(out);
   BicubicArgs<T> A{};
   A.px = h.px.view; A.py = h.py.view;
-  A.table = h.table.template as<T>();
+  A.table = h.table->template as<T>();
   A.qx = qx; A.qy = qy;
   A.out = out;
   A.nq = nq;
@@ -148,17 +151,34 @@ static void bicubic_launch_eval(const Interp2DImpl<T>& h, hipStream_t s, StatusB
   const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + TB - 1) / TB,
                                                                         std::max<uint64_t>(1, (uint64_t)cu_count() * wg_per_cu * 4 / gy)));
   if (std::getenv("NDI_TRACE_PLAN"))
-    std::fprintf(stderr, "[ndi plan] bicubic vec=%d lv=%llu klds=%d grid=%u x %u lds=%zu prepass=%d guess=%d,%d levels=%d,%d\n",
+    std::fprintf(stderr, "[ndi plan] bicubic vec=%d lv=%llu klds=%d grid=%u x %u lds=%zu prepass=%d guess=%d,%d levels=%d,%d "
+                 "nu=%d,%d\n",
                  (int)vec, (unsigned long long)A.lv, (int)klds, gx, gy, lds, check ? 0 : 1, A.px.guess, A.py.guess,
-                 A.px.levels, A.py.levels);
-#define NDI_BC(VEC, KL)                                                                  \
+                 A.px.levels, A.py.levels, h.nu_x, h.nu_y);
+#define NDI_BC(VEC, KL, NX, NY)                                                          \
   do {                                                                                   \
-    auto kern = eval_bicubic_kernel<T, VEC, KL, TB>;                                     \
+    auto kern = eval_bicubic_kernel<T, VEC, KL, TB, NX, NY>;                             \
     allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)LDS_STAGE_LIMIT);        \
     launch1<T>(s, PC_EVAL, dim3(gx, gy), dim3(TB), lds, kern, A);                        \
   } while (0)
-  if (vec) { if (klds) NDI_BC(VN, true); else NDI_BC(VN, false); }
-  else { if (klds) NDI_BC(1, true); else NDI_BC(1, false); }
+#define NDI_BC_FORM(NX, NY)                                                              \
+  do {                                                                                   \
+    if (vec) { if (klds) NDI_BC(VN, true, NX, NY); else NDI_BC(VN, false, NX, NY); }     \
+    else { if (klds) NDI_BC(1, true, NX, NY); else NDI_BC(1, false, NX, NY); }           \
+  } while (0)
+  switch (h.nu_x * 3 + h.nu_y) {   // the orders were checked when the handle was made (Interp2DImpl::partial): 0 .. 2 each
+    case 0: NDI_BC_FORM(0, 0); break;
+    case 1: NDI_BC_FORM(0, 1); break;
+    case 2: NDI_BC_FORM(0, 2); break;
+    case 3: NDI_BC_FORM(1, 0); break;
+    case 4: NDI_BC_FORM(1, 1); break;
+    case 5: NDI_BC_FORM(1, 2); break;
+    case 6: NDI_BC_FORM(2, 0); break;
+    case 7: NDI_BC_FORM(2, 1); break;
+    case 8: NDI_BC_FORM(2, 2); break;
+    default: throw HipFailure{hipErrorInvalidValue, "bicubic_launch_eval: partial orders outside 0 .. 2", __LINE__};
+  }
+#undef NDI_BC_FORM
 #undef NDI_BC
 }
 
@@ -181,7 +201,7 @@ static ndi_status bicubic_tables(const Interp2DImpl<T>& h, void* zx, void* zy, v
     }
   }
   hipLaunchKernelGGL(unpack_nodes_kernel<T>, dim3(bicubic_copy_grid(total)), dim3(BLOCK), 0, (hipStream_t) nullptr,
-                     (const T*)h.table.template as<T>(), dev[0], dev[1], dev[2], nodes, h.lanes);
+                     (const T*)h.table->template as<T>(), dev[0], dev[1], dev[2], nodes, h.lanes);
   NDI_HIP(hipGetLastError());
   NDI_HIP(hipStreamSynchronize(nullptr));
   if (memspace != NDI_MEM_DEVICE)

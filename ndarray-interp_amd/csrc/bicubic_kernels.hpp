@@ -8,7 +8,7 @@
 //                               spline build along the first (lanes are independent: the bits do not change)
 //   pack_nodes_kernel<T>        z, zx (grid order) and zy, zxy (transposed order) -> the node table
 //   unpack_nodes_kernel<T>      the node table -> three plain [nx][ny][L] arrays (ndi_interp2d_tables)
-//   eval_bicubic_kernel<T, VEC, KLDS, TB>
+//   eval_bicubic_kernel<T, VEC, KLDS, TB, NUX, NUY>
 //                               QUERY ORDER with both searches fused in, as eval_fused2d_kernel: a wave takes 64
 //                               consecutive queries, one per lane (search on each axis, the cell's record offset, t, u and
 //                               the two knot spacings parked in a wave-private LDS strip), then walks the batch's output
@@ -16,7 +16,10 @@
 //                               streaming store.  Rows shorter than 64 vectors share a trip among several queries; longer
 //                               rows are cut into chunks of `vchunk` vectors along blockIdx.y, so a batch of few queries
 //                               on a very wide trailing axis still fills the chip.  KLDS: knot pyramids staged in LDS
-//                               (else read from global memory: axes that do not fit).
+//                               (else read from global memory: axes that do not fit).  NUX, NUY: the orders of the
+//                               partial derivative the kernel evaluates (ndi_interp2d_partial): the four forms along y
+//                               are H_NUY, the one along x is H_NUX (hermite_nu); (0, 0) is the surface itself and
+//                               compiles to the code it was before the orders existed.  Nothing else differs.
 //
 // Numerical contract (include/ndinterp.h, ndi_interp2d_create_bicubic): every line one IEEE operation in T, in the stated
 // order, nothing fused (-ffp-contract=off), so rows are bit-identical to the numpy restatement (tests/bicubic_ref.py).
@@ -93,7 +96,30 @@ __device__ __forceinline__ V hermite_form(V pl, V pr, V kl, V kr, T h, T s, T c0
   return c0 * pl + s * pr + c2 * (a * c0 + b * s);
 }
 
-template <class T, int VEC, bool KLDS, int TB>
+// H_NU of the header (ndi_interp2d_partial): the NU-th derivative of that form with respect to the coordinate s lives on.
+//   c1 = d + a;  c2 = b - (a + a);  c3 = b - a
+//   H1 = (c1 + s ((c2 + c2) - (3 c3) s)) / h          H2 = ((c2 + c2) - (6 c3) s) / (h h)
+template <int NU, class T, class V>
+__device__ __forceinline__ V hermite_nu(V pl, V pr, V kl, V kr, T h, T s, T c0, T c2) {
+  static_assert(NU >= 0 && NU <= 2, "orders 0, 1 and 2");
+  if constexpr (NU == 0) {
+    return hermite_form<T, V>(pl, pr, kl, kr, h, s, c0, c2);
+  } else {
+    const V d = pr - pl;
+    const V a = kl * h - d;
+    const V b = d - kr * h;
+    const V q2 = b - (a + a);
+    const V q3 = b - a;
+    if constexpr (NU == 1) {
+      const V q1 = d + a;
+      return (q1 + s * ((q2 + q2) - (T(3) * q3) * s)) / h;
+    } else {
+      return ((q2 + q2) - (T(6) * q3) * s) / (h * h);
+    }
+  }
+}
+
+template <class T, int VEC, bool KLDS, int TB, int NUX = 0, int NUY = 0>
 __global__ __launch_bounds__(TB) void eval_bicubic_kernel(BicubicArgs<T> A) {
   using V = typename VecT<T, VEC>::type;
   using PTR = typename std::conditional<KLDS, lds_ptr<T>, const T*>::type;
@@ -164,11 +190,11 @@ __global__ __launch_bounds__(TB) void eval_bicubic_kernel(BicubicArgs<T> A) {
       const V z10 = g1[0], zx10 = g1[LV], zy10 = g1[2 * LV], zxy10 = g1[3 * LV];
       const V z11 = g1[4 * LV], zx11 = g1[5 * LV], zy11 = g1[6 * LV], zxy11 = g1[7 * LV];
       const T cu = one - u, cu2 = u * cu, ct = one - t, ct2 = t * ct;
-      const V p0 = hermite_form<T, V>(z00, z01, zy00, zy01, hy, u, cu, cu2);
-      const V p1 = hermite_form<T, V>(z10, z11, zy10, zy11, hy, u, cu, cu2);
-      const V d0 = hermite_form<T, V>(zx00, zx01, zxy00, zxy01, hy, u, cu, cu2);
-      const V d1 = hermite_form<T, V>(zx10, zx11, zxy10, zxy11, hy, u, cu, cu2);
-      const V r = hermite_form<T, V>(p0, p1, d0, d1, hx, t, ct, ct2);
+      const V p0 = hermite_nu<NUY, T, V>(z00, z01, zy00, zy01, hy, u, cu, cu2);
+      const V p1 = hermite_nu<NUY, T, V>(z10, z11, zy10, zy11, hy, u, cu, cu2);
+      const V d0 = hermite_nu<NUY, T, V>(zx00, zx01, zxy00, zxy01, hy, u, cu, cu2);
+      const V d1 = hermite_nu<NUY, T, V>(zx10, zx11, zxy10, zxy11, hy, u, cu, cu2);
+      const V r = hermite_nu<NUX, T, V>(p0, p1, d0, d1, hx, t, ct, ct2);
       store_stream<true>(reinterpret_cast<V*>(A.out + (base + ql) * A.out_stride) + v, r);
     };
     if (LV < 64u) {                         // several queries per trip (one chunk: W == LV)

@@ -2645,6 +2645,11 @@ struct Interp2DBase {
   virtual ndi_status trim() = 0;
   virtual ndi_status probe_ceiling(uint64_t nq, void* out, uint64_t out_stride, void* stream, int reps, double* ms) = 0;
   virtual ndi_status clone_to(int dev, Interp2DBase** out) = 0;
+  // ndi_interp2d_partial: Bicubic handles and their partials only (Interp2DImpl::partial); every other handle is Bilinear
+  virtual ndi_status partial(int nu_x, int nu_y, Interp2DBase** out) {
+    return fail(NDI_BAD_ARG, "Bilinear has no partial-derivative handle: its slope jumps at every grid line and it keeps no "
+                "node derivatives (ndi_interp2d_partial takes a Bicubic handle or a partial handle of one)");
+  }
 };
 
 template <class T>
@@ -2661,7 +2666,10 @@ struct Interp2DImpl final : Interp2DBase {
   uint64_t nx = 0, ny = 0;
   DevicePyramid<T> px, py;
   DevBuf data;
-  DevBuf table;               // Bicubic: the node table T[nx][ny][4][lanes] ({z, zx, zy, zxy}); `data` is not kept
+  // Bicubic: the node table T[nx][ny][4][lanes] ({z, zx, zy, zxy}); `data` is not kept.  Shared between a handle and its
+  // partial-derivative handles (ndi_interp2d_partial), which only read it: freed with the last of them, in any order.
+  std::shared_ptr<DevBuf> table;
+  int nu_x = 0, nu_y = 0;     // Bicubic: the orders of the partial derivative this handle evaluates ((0, 0): the surface)
   bool pair_packed = false;   // data holds the pair-packed layout (pack_pairs_kernel)
   SpaceSet spaces;
   OwnedRing ring_own;
@@ -2750,7 +2758,8 @@ struct Interp2DImpl final : Interp2DBase {
   uint64_t signature() const override {
     uint64_t h = fnv1a(FNV_SEED, px.host_knots.data(), px.host_knots.size() * sizeof(T));
     h = fnv1a(h, py.host_knots.data(), py.host_knots.size() * sizeof(T));
-    const uint64_t f[3] = {nx, ny, (uint64_t)mode | ((uint64_t)bicubic << 8)};   // (the strategy: no Bilinear / Bicubic mix)
+    // (the strategy and the partial orders: no Bilinear / Bicubic mix, no surface beside its partial, no two partials)
+    const uint64_t f[3] = {nx, ny, (uint64_t)mode | ((uint64_t)bicubic << 8) | ((uint64_t)nu_x << 16) | ((uint64_t)nu_y << 24)};
     return fnv1a(h, f, sizeof(f));
   }
   ndi_status tables(void* zx, void* zy, void* zxy, int memspace) override {
@@ -3892,13 +3901,44 @@ struct Interp2DImpl final : Interp2DBase {
     DeviceGuard dg(dev);
     h->px.upload(px.host_knots.data(), nx);
     h->py.upload(py.host_knots.data(), ny);
-    if (bicubic) {   // the node table as it is: no rebuild
-      h->table.reserve(table.bytes);
-      copy_across_devices(h->table.p, dev, table.p, device, table.bytes);
+    if (bicubic) {   // the node table as it is: no rebuild; a replica owns its copy and keeps the partial orders
+      h->nu_x = nu_x; h->nu_y = nu_y;
+      h->table = std::make_shared<DevBuf>();
+      h->table->reserve(table->bytes);
+      copy_across_devices(h->table->p, dev, table->p, device, table->bytes);
     } else {
       h->data.reserve(data.bytes);
       copy_across_devices(h->data.p, dev, data.p, device, data.bytes);
     }
+    *out = h.release();
+    return NDI_OK;
+  }
+
+  // ndi_interp2d_partial: a handle on this handle's device that evaluates the partial derivative of the summed orders on
+  // the SAME node table (shared ownership, no copy, no device work but the upload of the two knot axes).  Every refusal is
+  // decided before that.
+  ndi_status partial(int nux, int nuy, Interp2DBase** out) override {
+    if (!bicubic) return Interp2DBase::partial(nux, nuy, out);
+    if (nux < 0 || nuy < 0)
+      return fail(NDI_BAD_ARG, "Bicubic: a partial-derivative order below 0 (asked for (%d, %d)); orders are 0, 1 or 2 per "
+                  "variable", nux, nuy);
+    if (nux == 0 && nuy == 0)
+      return fail(NDI_BAD_ARG, "Bicubic: the partial derivative of orders (0, 0) is the handle itself; ask for an order of 1 "
+                  "or 2 in at least one variable (ndi_interp2d_clone makes a copy)");
+    const long long tx = (long long)nu_x + nux, ty = (long long)nu_y + nuy;
+    if (tx > 2 || ty > 2)
+      return fail(NDI_BAD_ARG, "Bicubic: the third derivative of a cubic spline jumps at the grid lines, and the node table "
+                  "determines orders 0 to 2 per variable (asked for (%d, %d) of a handle of orders (%d, %d): (%lld, %lld))",
+                  nux, nuy, nu_x, nu_y, tx, ty);
+    DeviceGuard dg(device);
+    std::unique_ptr<Interp2DImpl<T>> h(new Interp2DImpl<T>());
+    h->dtype = dtype; h->device = device; h->lanes = lanes;
+    h->mode = mode; h->nx = nx; h->ny = ny;
+    h->bicubic = true;
+    h->nu_x = (int)tx; h->nu_y = (int)ty;
+    h->px.upload(px.host_knots.data(), nx);
+    h->py.upload(py.host_knots.data(), ny);
+    h->table = table;
     *out = h.release();
     return NDI_OK;
   }
@@ -4716,6 +4756,21 @@ NDI_API ndi_status ndi_interp2d_tables(const ndi_interp2d* h, void* zx, void* zy
   NDI_TRY
   if (!h->impl->bicubic) return h->impl->tables(zx, zy, zxy, memspace);
   return ndi::bounds_verdict(h->impl->tables(zx, zy, zxy, memspace), h->impl->device);
+  NDI_CATCH
+}
+
+// Every refusal is decided before any device work: the null checks here, the handle's own in Interp2DImpl::partial.
+NDI_API ndi_status ndi_interp2d_partial(const ndi_interp2d* h, int32_t nu_x, int32_t nu_y, ndi_interp2d** out) {
+  if (!out) return ndi::fail(NDI_BAD_ARG, "null out pointer");
+  *out = nullptr;
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  NDI_TRY
+  ndi::Range rg("ndi_interp2d_partial");
+  ndi::Interp2DBase* impl = nullptr;
+  ndi_status st = h->impl->partial(nu_x, nu_y, &impl);
+  if (st != NDI_OK) return st;
+  *out = new ndi_interp2d{impl};
+  return NDI_OK;
   NDI_CATCH
 }
 

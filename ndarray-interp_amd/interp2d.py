@@ -269,6 +269,10 @@ class Bilinear(Interp2DStrategyBuilder, _DeviceStrategy2D):
         return self._create(x, y, data, device,
                             lambda d, h: _capi.lib().ndi_interp2d_create(C.byref(d), C.byref(h)))
 
+    def partial(self, nu_x=0, nu_y=0):
+        raise TypeError("Bilinear has no partial derivatives: its slope jumps at every grid line and it keeps no node "
+                        "derivatives (Bicubic.partial gives them)")
+
     def probe_ceiling(self, out2d, reps=5) -> float:
         """ms of the evaluation kernel's memory access mix alone on this handle's grid (ndi_interp2d_probe_ceiling);
         `out2d`: a device tensor (nq, lanes) that is overwritten."""
@@ -334,6 +338,47 @@ class Bicubic(Interp2DStrategyBuilder, _DeviceStrategy2D):
         bc = (_capi.Boundary * 4)(*[_capi.Boundary(int(e.kind), float(e.value)) for e in ends])
         return self._create(x, y, data, device,
                             lambda d, h: _capi.lib().ndi_interp2d_create_bicubic(C.byref(d), bc, C.byref(h)))
+
+    orders = (0, 0)    # (nu_x, nu_y) of the partial derivative this strategy evaluates; (0, 0): the surface
+    origin = None      # a partial's source strategy (kept for documentation's sake: the library owns the shared table)
+
+    def partial(self, nu_x=0, nu_y=0) -> "Bicubic":
+        """The partial derivative d^(nu_x + nu_y) / dx^nu_x dy^nu_y of this built strategy's surface as a built strategy of
+        its own (ndi_interp2d_partial; scipy: `RectBivariateSpline.ev(x, y, dx=nu_x, dy=nu_y)`).  Orders are 0, 1 or 2 per
+        variable, not both 0, and add up over repeated calls.  The new handle shares this one's node table on the device --
+        no copy -- and either may be released first.  This strategy stays usable."""
+        import operator
+        try:
+            nu_x, nu_y = operator.index(nu_x), operator.index(nu_y)
+        except TypeError:
+            raise TypeError(f"Bicubic.partial: the orders are integers, got ({type(nu_x).__name__}, "
+                            f"{type(nu_y).__name__})") from None
+        if nu_x < 0 or nu_y < 0:
+            raise ValueError(f"Bicubic.partial: an order below 0 (asked for ({nu_x}, {nu_y})); orders are 0, 1 or 2 per "
+                             "variable")
+        if nu_x == 0 and nu_y == 0:
+            raise ValueError("Bicubic.partial: orders (0, 0) are the strategy itself; ask for an order of 1 or 2 in at least "
+                             "one variable")
+        tx, ty = self.orders[0] + nu_x, self.orders[1] + nu_y
+        if tx > 2 or ty > 2:
+            raise ValueError(f"Bicubic.partial: the third derivative of a cubic spline jumps at the grid lines; orders are 0 "
+                             f"to 2 per variable (asked for ({nu_x}, {nu_y}) of a strategy of orders {self.orders}: "
+                             f"({tx}, {ty}))")
+        if self._h is None:
+            from .errors import DeviceError
+            raise DeviceError("Bicubic.partial needs a built strategy: the node table lives on the device and partial "
+                              "derivatives are evaluated there; there is no CPU fallback")
+        import copy
+        h = C.c_void_p()
+        st = _capi.lib().ndi_interp2d_partial(self._h, nu_x, nu_y, C.byref(h))
+        if st == _capi.BAD_ARG:
+            raise ValueError(_capi.last_error())
+        if st != _capi.OK:
+            raise_builder(st)
+        other = copy.copy(self)
+        other._h, other._inflight = h, []
+        other.orders, other.origin = (tx, ty), self
+        return other
 
     def tables(self, on_device=False):
         """(zx, zy, zxy): the node derivatives, each of the data's shape (ndi_interp2d_tables), as host arrays -- or, with
@@ -476,6 +521,15 @@ class Interp2D:
             elif done:
                 where = np.unravel_index(np.arange(done), tuple(xs.shape))
                 buffer[where] = tmp[:done].reshape((done,) + self._lanes_shape())
+
+    def partial(self, nu_x=0, nu_y=0) -> "Interp2D":
+        """The partial derivative d^(nu_x + nu_y) / dx^nu_x dy^nu_y of this interpolator's surface as an interpolator over
+        the same axes (`Bicubic.partial`): orders 0, 1 or 2 per variable, not both 0; they add up over repeated calls.
+        `data` stays the surface's node values (the derivative shares the source's node table on the device)."""
+        if not hasattr(self.strategy, "partial"):
+            raise TypeError("partial needs a built Bicubic strategy (f32 / f64 data), got "
+                            f"{type(self.strategy).__name__}")
+        return Interp2D(self.x, self.y, self.data, self.strategy.partial(nu_x, nu_y))
 
     def replicate(self, devices):
         """Replicas of this interpolator on the given devices (see Interp1D.replicate)."""

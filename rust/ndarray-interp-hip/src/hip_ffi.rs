@@ -238,6 +238,7 @@ extern "C" {
         zxy: *mut c_void,
         memspace: i32,
     ) -> i32;
+    pub fn ndi_interp2d_partial(h: *const ndi_interp2d, nu_x: i32, nu_y: i32, out: *mut *mut ndi_interp2d) -> i32;
     pub fn ndi_interp2d_destroy(h: *mut ndi_interp2d);
     pub fn ndi_interp1d_clone(h: *const ndi_interp1d, device: i32, out: *mut *mut ndi_interp1d) -> i32;
     pub fn ndi_interp2d_clone(h: *const ndi_interp2d, device: i32, out: *mut *mut ndi_interp2d) -> i32;

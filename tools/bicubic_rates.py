@@ -12,6 +12,12 @@ profiles/bicubic_rates.json).  Needs an MI355X; there is no CPU fallback.
         adds the evaluation kernels' own times from those runs, the Bicubic / Bilinear ratio (expected from bytes: at most
         17 / 5 = 3.4 beyond the caches, nearer 1 on cache-resident grids) and the fraction of 8 TB/s on the
         17 Q C sizeof(T) compulsory bytes.
+
+Partial-derivative handles (output committed as profiles/bicubic_partial_rates.json): the same three steps
+with `--partial NUX,NUY` in each.  The timing pass then times the value handle and its partial handle of those orders side
+by side (two alternating rounds each: their spread is the margin), the profiled run evaluates both, and the merge pairs the
+two instances of eval_bicubic_kernel by their template arguments.  A partial reads the same sixteen operands and writes the
+same row, so by bytes the ratio is 1.
 """
 import argparse
 import csv
@@ -101,6 +107,78 @@ def timing_pass(out_path):
     json.dump(res, open(out_path, "w"), indent=1)
 
 
+def orders_of(text):
+    nux, nuy = (int(v) for v in text.split(","))
+    assert 0 <= nux <= 2 and 0 <= nuy <= 2 and (nux, nuy) != (0, 0), "orders are 0, 1 or 2 per variable, not both 0"
+    return nux, nuy
+
+
+def partial_timing_pass(out_path, orders):
+    import torch
+    pkg = package()
+    assert torch.cuda.is_available() and pkg.device_count() >= 1, "needs a GPU"
+    res = {"device": torch.cuda.get_device_name(0), "orders": list(orders), "partial_create_ms": {}, "eval_ms": {}}
+    for name, nx, ny, C in SHAPES:
+        key = f"{name}_{nx}x{ny}x{C}"
+        x, y, z, qx, qy, out = inputs(name, nx, ny, C)
+        value = pkg.Interp2DBuilder.new(z).x(x).y(y).strategy(pkg.Bicubic.new()).build()
+        med, lo, hi = median_ms(lambda: value.partial(*orders))
+        res["partial_create_ms"][key] = {"median": med, "min": lo, "max": hi}
+        handles = {"value": value, "partial": value.partial(*orders)}
+        res["eval_ms"][key] = {"queries": int(qx.numel())}
+        for rnd in range(2):               # alternate the two handles: the value handle's two rounds give the spread
+            for sname, h in handles.items():
+                med, lo, hi = median_ms(lambda: h.interp_array_into(qx, qy, out))
+                res["eval_ms"][key][f"{sname}_round{rnd}"] = {"median": med, "min": lo, "max": hi}
+        print(key, json.dumps(res["partial_create_ms"][key]), json.dumps(res["eval_ms"][key]), flush=True)
+        del handles, value, x, y, z, qx, qy, out
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    json.dump(res, open(out_path, "w"), indent=1)
+
+
+def partial_profile_shape(name, nx, ny, C, orders):
+    pkg = package()
+    x, y, z, qx, qy, out = inputs(name, nx, ny, C)
+    value = pkg.Interp2DBuilder.new(z).x(x).y(y).strategy(pkg.Bicubic.new()).build()
+    for h in (value, value.partial(*orders)):
+        for _ in range(REPS):
+            h.interp_array_into(qx, qy, out)
+    print("profiled", name, nx, ny, C, "partial", orders, flush=True)
+
+
+def partial_merge(prof_dir, out_path, orders):
+    """value / partial pairs of eval_bicubic_kernel<T, VEC, KLDS, TB, NUX, NUY> by the last two template arguments"""
+    res = json.load(open(out_path)) if os.path.exists(out_path) else {}
+    res["orders"] = list(orders)
+    res["eval_kernels"] = {}
+    tails = {"value": ", 0, 0>", "partial": f", {orders[0]}, {orders[1]}>"}
+    for name, nx, ny, C in SHAPES:
+        key = f"{name}_{nx}x{ny}x{C}"
+        files = glob.glob(os.path.join(prof_dir, key, "**", "*kernel_stats.csv"), recursive=True)
+        if not files:
+            continue
+        per, names = {"value": 0.0, "partial": 0.0}, {"value": [], "partial": []}
+        for row in csv.DictReader(open(files[0])):
+            kn = row["Name"].split("(")[0].strip()
+            if "eval_bicubic_kernel" not in kn:
+                continue
+            for who, tail in tails.items():
+                if kn.endswith(tail):
+                    per[who] += float(row["TotalDurationNs"]) / REPS
+                    names[who].append(kn)
+        nq, size = n_queries(DTYPES[name], C), np.dtype(DTYPES[name]).itemsize
+        entry = {"queries": nq, "compulsory_bytes": 17 * nq * C * size}
+        for who, ns in per.items():
+            entry[who] = {"kernel_ms_per_batch": ns / 1e6, "kernels": sorted(set(names[who]))}
+        if per["value"] > 0 and per["partial"] > 0:
+            entry["ratio_partial_over_value"] = per["partial"] / per["value"]
+            entry["partial_fraction_of_8TBps"] = entry["compulsory_bytes"] / (per["partial"] * 1e-9) / PEAK_BPS
+        res["eval_kernels"][key] = entry
+        print(key, json.dumps(entry), flush=True)
+    json.dump(res, open(out_path, "w"), indent=1)
+
+
 def profile_shape(name, nx, ny, C):
     pkg = package()
     x, y, z, qx, qy, out = inputs(name, nx, ny, C)
@@ -145,11 +223,21 @@ def merge(prof_dir, out_path):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bicubic_rates.json"))
+    ap.add_argument("--out")
+    ap.add_argument("--partial", metavar="NUX,NUY", type=orders_of,
+                    help="time a partial-derivative handle of these orders beside the value handle")
     ap.add_argument("--profile-shape", nargs=4, metavar=("DTYPE", "NX", "NY", "C"))
     ap.add_argument("--merge", metavar="DIR")
     a = ap.parse_args()
-    if a.profile_shape:
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "bicubic_partial_rates.json" if a.partial else "bicubic_rates.json")
+    if a.partial and a.profile_shape:
+        partial_profile_shape(a.profile_shape[0], *(int(v) for v in a.profile_shape[1:]), a.partial)
+    elif a.partial and a.merge:
+        partial_merge(a.merge, a.out, a.partial)
+    elif a.partial:
+        partial_timing_pass(a.out, a.partial)
+    elif a.profile_shape:
         profile_shape(a.profile_shape[0], *(int(v) for v in a.profile_shape[1:]))
     elif a.merge:
         merge(a.merge, a.out)
