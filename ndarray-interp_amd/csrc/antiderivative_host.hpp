@@ -82,6 +82,9 @@ struct AntiderivImpl final : Interp1DBase {
     const hipStream_t s0 = nullptr;
     const bool vec = lanes % VN == 0 && aligned16(A.y) && aligned16(A.a) && aligned16(A.b) && aligned16(A.P) && aligned16(A.tot);
     const bool staged = lanes <= AD_STAGED_LANES;
+    const bool fuse = A.nblk <= AD_FUSE_BLOCKS;
+    bool vec_local = false;
+    unsigned local_grid = 0;
     if (staged) {
       // chains per workgroup: as many blocks as AD_STAGED_CHAINS allows, halved while the grid would leave the chip's
       // 2048 resident workgroups unused (phase 2 takes the same time for one chain as for 32)
@@ -89,21 +92,24 @@ struct AntiderivImpl final : Interp1DBase {
       while (kb > 1 && (A.nblk + kb - 1) / kb < 2048) kb /= 2;
       A.kb = kb;
       const size_t lds = (size_t)kb * (AD_B * lanes + lanes) * sizeof(T);
-      const unsigned grid = (unsigned)std::min<uint64_t>((A.nblk + kb - 1) / kb, 1u << 16);
+      const unsigned grid = local_grid = (unsigned)std::min<uint64_t>((A.nblk + kb - 1) / kb, 1u << 16);
       allow_dynamic_lds(reinterpret_cast<const void*>(&antideriv_local_staged_kernel<T, LINEAR>), 96 * 1024);
       hipLaunchKernelGGL((antideriv_local_staged_kernel<T, LINEAR>), dim3(grid), dim3(BLOCK), lds, s0, A);
     } else {
       // every thread is a 256-step chain, so the threads are what hides the latency: 16-byte vectors only where they
       // still leave the chip a full set of waves (4096 x 4096 has 65536 chains: one lane each, 4-8 byte coalesced loads)
-      const bool vec_local = vec && A.nblk * (lanes / VN) >= (uint64_t)cu_count() * 8 * 64;
+      vec_local = vec && A.nblk * (lanes / VN) >= (uint64_t)cu_count() * 8 * 64;
       const uint64_t total = A.nblk * (vec_local ? lanes / VN : lanes);
-      const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + BLOCK - 1) / BLOCK, 1u << 20));
+      const unsigned grid = local_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + BLOCK - 1) / BLOCK, 1u << 20));
       if (vec_local) hipLaunchKernelGGL((antideriv_local_lanes_kernel<T, VN, LINEAR>), dim3(grid), dim3(BLOCK), 0, s0, A);
       else hipLaunchKernelGGL((antideriv_local_lanes_kernel<T, 1, LINEAR>), dim3(grid), dim3(BLOCK), 0, s0, A);
     }
     NDI_HIP(hipGetLastError());
+    if (std::getenv("NDI_TRACE_PLAN"))   // grid: the local kernel's; kb / vec_local: 0 on the local kernel that has no such field
+      std::fprintf(stderr, "[ndi plan] antiderivative build linear=%d staged=%d kb=%u vec=%d vec_local=%d nblk=%llu single=%d fuse=%d "
+                   "grid=%u\n", (int)LINEAR, (int)staged, A.kb, (int)vec, (int)vec_local, (unsigned long long)A.nblk, (int)A.single,
+                   (int)(!A.single && fuse), local_grid);
     if (!A.single) {
-      const bool fuse = A.nblk <= AD_FUSE_BLOCKS;
       if (!fuse) {
         if (staged) {
           const unsigned grid = (unsigned)((lanes * 64 + BLOCK - 1) / BLOCK);
@@ -167,6 +173,9 @@ struct AntiderivImpl final : Interp1DBase {
     if (vec_ok && LV >= (uint64_t)BLOCK) {   // long rows
       const uint64_t segs = (LV + BLOCK - 1) / BLOCK;
       const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nq, 65536)), (unsigned)std::min<uint64_t>(segs, 64));
+      if (std::getenv("NDI_TRACE_PLAN"))
+        std::fprintf(stderr, "[ndi plan] antiderivative eval form=rows linear=%d pair=%d vec=1 lv=%llu tile_q=0 grid=%u x %u\n",
+                     (int)linear, (int)pair, (unsigned long long)LV, grid.x, grid.y);
       if (linear) {
         if (pair) launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, antideriv_eval_rows_kernel<T, true, true>, A);
         else launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, antideriv_eval_rows_kernel<T, true, false>, A);
@@ -179,6 +188,9 @@ struct AntiderivImpl final : Interp1DBase {
     const uint32_t tile_q = (uint32_t)std::max<uint64_t>(1, 1024 / std::max<uint64_t>(LV, 1));
     const uint64_t ntiles = (nq + tile_q - 1) / tile_q;
     const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ntiles, 16384));
+    if (std::getenv("NDI_TRACE_PLAN"))
+      std::fprintf(stderr, "[ndi plan] antiderivative eval form=flat linear=%d pair=%d vec=%d lv=%llu tile_q=%u grid=%u x 1\n",
+                   (int)linear, (int)pair, (int)vec_ok, (unsigned long long)LV, tile_q, gx);
     ProfScope ps(s, PC_EVAL);
 #define NDI_AF(LIN, PAIR)                                                                                          \
   do {                                                                                                             \

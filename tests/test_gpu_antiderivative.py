@@ -327,7 +327,8 @@ def test_hostile_inputs_through_the_build(pkg, dt, rule):
 # ---- the bounds-checked build -------------------------------------------------------------------------------------------
 def test_checked_build_runs_the_new_kernels_clean(pkg):
     """One pass of the table and row checks under the bounds-checked build of the library (make debug), in a child process:
-    a violation would turn the call into NDI_HIP_ERROR."""
+    a violation would turn the call into NDI_HIP_ERROR.  The shapes of this file, and those of
+    test_gpu_antiderivative_plans.py whose kernels or index forms no shape here reaches."""
     import subprocess
     import sys
     from conftest import ROOT
@@ -337,8 +338,13 @@ def test_checked_build_runs_the_new_kernels_clean(pkg):
         "import sys, numpy as np; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
         "from conftest import load_product_package; import antiderivative_ref as ar, oracle\n"
         "pkg = load_product_package(); rng = np.random.default_rng(1)\n"
-        "for n, L in ((2, 3), (3, 5), (100, 5), (257, 130), (258, 3), (1000, 6), (64, 4096), (100000, 8), (300000, 1)):\n"
-        "    x = np.cumsum(rng.uniform(0.5, 2.0, n)); y = rng.normal(size=(n, L)); q = rng.uniform(x[0], x[-1], 2000)\n"
+        "shapes = [(n, L, 2000) for n, L in ((2, 3), (3, 5), (100, 5), (257, 130), (258, 3), (1000, 6), (64, 4096), (100000, 8), (300000, 1))]\n"
+        "# test_gpu_antiderivative_plans.py's plans: two and five chains per workgroup, the per-lane offsets kernel (scalar and\n"
+        "# 16-byte add), one full block; evaluation: a ragged last segment of long rows (257 vectors), scalar rows of 513 lanes\n"
+        "shapes += [(4095 * 256, 1, 2000), (10236 * 256 + 100, 3, 2000), (4353, 33, 2000), (4353, 36, 2000), (256, 5, 2000),\n"
+        "           (5, 514, 300), (7, 513, 300)]\n"
+        "for n, L, nq in shapes:\n"
+        "    x = np.cumsum(rng.uniform(0.5, 2.0, n)); y = rng.normal(size=(n, L)); q = rng.uniform(x[0], x[-1], nq)\n"
         "    for s in (pkg.Pchip.new(), pkg.Linear.new()):\n"
         "        it = pkg.Interp1D.builder(y).x(x).strategy(s).build()\n"
         "        t = (it.strategy.data_table(),) + (tuple(it.strategy.coefficients()) if isinstance(s, pkg.Pchip) else (None, None))\n"
