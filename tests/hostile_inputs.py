@@ -1,5 +1,5 @@
 """Hostile inputs for the Pchip / Akima / CubicHermite build and the derivative build, and a bit-level comparer; at the
-end of the file the hostile grids, lanes and queries of the 2-D Bicubic strategy.
+end of the file the hostile grids, lanes and queries of the 2-D Bicubic strategy and of its partial derivatives.
 
 The rules (include/ndinterp.h, ndi_strategy1d / ndi_interp1d_derivative) have data-dependent branches and rest on plain
 IEEE arithmetic: correctly rounded division, nothing fused, f32 subnormals kept.  The generators here plant every branch
@@ -451,7 +451,8 @@ _BICUBIC_EXP = {np.dtype(np.float32): dict(step=40, coarse=10, sub=-135), np.dty
 
 def bicubic_knots(family, dtype, n, seed=0):
     """uneven / adjacent: knots() above.  big / small: steps of 2^40 / 2^-40 (f32), 2^400 / 2^-400 (f64), centred so that 0.0
-    is a knot.  mixed2: adjacent floats from 1.0 for the first half, then steps of 2^10 (f32) / 2^100 (f64)."""
+    is a knot.  mixed2: adjacent floats from 1.0 for the first half, then steps of 2^10 (f32) / 2^100 (f64).  triple (the
+    partial-derivative tests only, bicubic_partial_pairs): every third float from 1.0 up."""
     T = np.dtype(dtype).type
     e = _BICUBIC_EXP[np.dtype(dtype)]
     if family in ("uneven", "adjacent"):
@@ -459,6 +460,8 @@ def bicubic_knots(family, dtype, n, seed=0):
     if family in ("big", "small"):
         step = np.ldexp(T(1), e["step"] if family == "big" else -e["step"])
         x = ((np.arange(n) - n // 2).astype(dtype) * step).astype(dtype)
+    elif family == "triple":      # three floats apart from 1.0 up: as close as `adjacent`, but no spacing is a power of two
+        x = (T(1) + T(3) * np.finfo(dtype).eps * np.arange(n).astype(dtype)).astype(dtype)
     else:
         assert family == "mixed2", family
         x = np.empty(n, dtype)
@@ -486,16 +489,32 @@ def bicubic_pairs(dtype):
             if not (np.dtype(dtype) == np.float64 and (fx, fy) == ("small", "big"))]
 
 
-def bicubic_lane(recipe, dtype, nx, ny, rng, top_exp=0):
+# Every spacing of adjacent, big, small and mixed2 is a power of two, on which a product or quotient with h is exact: a
+# reciprocal for a division, x / h / h for x / (h * h) or a fused kl * h - d are the same function there, whatever the nodes
+# (tests/test_hostile_inputs.py, mutant_can_show).  The partial-derivative tests, whose forms H1 and H2 have those divisions,
+# therefore run three pairs more, on an axis as fine as `adjacent` whose spacing of 3 ulps is not.
+BICUBIC_PARTIAL_EXTRA = (("triple", "triple"), ("triple", "uneven"), ("uneven", "triple"))
+
+
+def bicubic_partial_pairs(dtype):
+    return bicubic_pairs(dtype) + list(BICUBIC_PARTIAL_EXTRA)
+
+
+def bicubic_lane(recipe, dtype, nx, ny, rng, top_exp=0, order=(0, 0), pair=None):
     """One lane (nx, ny) of node data.  `rng` is consumed the same way by every recipe, so the integer background of two
-    arrays made with the same seed is the same lane by lane."""
+    arrays made with the same seed is the same lane by lane.  The two scaled recipes ("subnormal", "top scale") take the
+    partial-derivative order whose rows they are for: with the default (0, 0) the fixed subnormal exponent and `top_exp`, with
+    any other order the exponents found for it on the knot families `pair` (bicubic_sub_exponent, bicubic_top_exponent)."""
     T = np.dtype(dtype).type
     ints = rng.integers(-3, 5, (nx, ny)).astype(dtype)
     name = BICUBIC_RECIPES[recipe] if isinstance(recipe, int) else recipe
+    order = tuple(order)
     if name == "integers":
         return ints
     if name == "subnormal":       # the flush-to-zero detector: every node value is subnormal or zero
-        return (ints * np.ldexp(T(1), _BICUBIC_EXP[np.dtype(dtype)]["sub"])).astype(dtype)
+        e = _BICUBIC_EXP[np.dtype(dtype)]["sub"] if order == (0, 0) else bicubic_sub_exponent(dtype, pair[0], pair[1], order)
+        with np.errstate(over="ignore"):
+            return (ints * np.ldexp(T(1), e)).astype(dtype)
     if name == "constant":
         return np.full((nx, ny), 2.5, dtype)
     if name == "+0":
@@ -506,6 +525,8 @@ def bicubic_lane(recipe, dtype, nx, ny, rng, top_exp=0):
         ints[nx // 2, ny // 2] = np.inf if name == "inf node" else np.nan
         return ints
     if name == "top scale":
+        if order != (0, 0):
+            top_exp = bicubic_top_exponent(dtype, pair[0], pair[1], order)
         with np.errstate(over="ignore"):
             return (ints * np.ldexp(T(1), top_exp)).astype(dtype)
     assert name == "-0 among integers", name
@@ -532,6 +553,36 @@ def bicubic_parts(C):
     return -(-len(BICUBIC_RECIPES) // C)
 
 
+BICUBIC_PARTIAL_LANES = (25, 28)     # every lane once, scalar form (odd); the same and three more, 16-byte vectors in f32 and f64
+
+
+def bicubic_partial_recipes():
+    """The lanes of the partial-derivative arrays: the nine recipes, then for each of the eight orders a top-scale and a
+    subnormal lane scaled for the rows of that order: (recipe name, order) for each of 25 lanes."""
+    import bicubic_partial_ref
+    return [(r, (0, 0)) for r in BICUBIC_RECIPES] + [(r, o) for o in bicubic_partial_ref.ORDERS for r in ("top scale", "subnormal")]
+
+
+def bicubic_partial_nodes(dtype, nx, ny, fx, fy, C=25, seed=0, finite_only=False):
+    """(z, lanes): z (nx, ny, C); lane l carries entry l mod 25 of bicubic_partial_recipes().  One array per grid serves the
+    handles of all eight orders: a lane scaled for another order is mostly inf or 0 there, which still compares bit for bit.
+    `finite_only` as in bicubic_nodes.  The integer background of a recipe is the one it has in bicubic_nodes, whatever the
+    order (the exponents were searched on it)."""
+    rec = bicubic_partial_recipes()
+    top = bicubic_top_exponent(dtype, fx, fy)
+    z = np.empty((nx, ny, C), dtype)
+    lanes = []
+    for l in range(C):
+        name, order = rec[l % len(rec)]
+        r = BICUBIC_RECIPES.index(name)
+        rng = np.random.default_rng([seed, nx, ny, r])
+        if finite_only and r in BICUBIC_NONFINITE:
+            name = BICUBIC_RECIPES[0]
+        lanes.append((name, order))
+        z[:, :, l] = bicubic_lane(name, dtype, nx, ny, rng, top, order, (fx, fy))
+    return z, lanes
+
+
 def bicubic_axis_queries(k, extrapolate=False):
     """One axis: every knot, the float just above and just below each knot (clipped into range), every midpoint, both
     zeros where 0.0 is a knot; with `extrapolate` points up to a full axis width outside, points 2^20 widths outside and
@@ -549,11 +600,15 @@ def bicubic_axis_queries(k, extrapolate=False):
     return q
 
 
-def bicubic_queries(x, y, extrapolate=False, seed=0, n_random=2000):
+def bicubic_queries(x, y, extrapolate=False, seed=0, n_random=2000, thin=1):
     """(qx, qy): the cross product of the two axes' sets, then `n_random` points spread over the cells (a random cell and a
-    random position inside it on each axis, so the wide cells of a mixed axis do not take them all)."""
+    random position inside it on each axis, so the wide cells of a mixed axis do not take them all).  `thin`: every thin-th
+    pair of the cross product only; with `thin` prime to the length of the y set every point of either axis' set still occurs."""
     ax, ay = bicubic_axis_queries(x, extrapolate), bicubic_axis_queries(y, extrapolate)
     gx, gy = np.meshgrid(ax, ay, indexing="ij")
+    if thin > 1:
+        assert np.gcd(thin, len(ay)) == 1 and len(ax) >= thin, (thin, len(ax), len(ay))
+        gx, gy = gx.ravel()[::thin], gy.ravel()[::thin]
     rng = np.random.default_rng([seed, len(x), len(y)])
 
     def spread(k):
@@ -562,16 +617,21 @@ def bicubic_queries(x, y, extrapolate=False, seed=0, n_random=2000):
     return np.concatenate([gx.ravel(), spread(x)]), np.concatenate([gy.ravel(), spread(y)])
 
 
-def bicubic_reference(x, y, z, bc=None, qx=None, qy=None, tabs=None, side="right"):
+def bicubic_reference(x, y, z, bc=None, qx=None, qy=None, tabs=None, side="right", order=(0, 0), variant=None):
     """(tables, rows) of the restatement with numpy's floating-point warnings off.  `tabs`: evaluate on these tables (the
-    device's own) instead of the restatement's; `side="left"`: the wrong cell search, for the self-check."""
+    device's own) instead of the restatement's; `side="left"`: the wrong cell search, for the self-check.  `order`: rows of
+    that partial derivative (tests/bicubic_partial_ref.py), `variant` one of its deliberately wrong forms."""
     import bicubic_ref
     with np.errstate(all="ignore"):
         if tabs is None:
             tabs = bicubic_ref.tables(x, y, z, bc or bicubic_ref.DEFAULT_BC)
         if qx is None:
             return tabs, None
-        return tabs, bicubic_ref.evaluate(x, y, z, *tabs, qx, qy, side=side)
+        if tuple(order) == (0, 0) and variant is None:
+            return tabs, bicubic_ref.evaluate(x, y, z, *tabs, qx, qy, side=side)
+        import bicubic_partial_ref
+        assert side == "right"
+        return tabs, bicubic_partial_ref.evaluate(x, y, z, *tabs, qx, qy, order[0], order[1], variant)
 
 
 def finite_share(*arrays):
@@ -579,33 +639,156 @@ def finite_share(*arrays):
 
 
 _TOP = {}
+_SUB = {}
+_SEARCH = {}
 
 
-def bicubic_top_exponent(dtype, fx="uneven", fy="uneven"):
+def bicubic_recorded_exponents(dtype, fx, fy, order):
+    """(top, sub) of tests/golden/bicubic_partial_exponents.json: what the two searches below found for the orders other than
+    (0, 0), recorded so that the device tests do not search again (880 searches); tests/test_hostile_inputs.py runs every
+    search and holds the file to the results."""
+    import json
+    import os
+    if "recorded" not in _SEARCH:
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bicubic_partial_exponents.json")) as f:
+            _SEARCH["recorded"] = json.load(f)
+    return _SEARCH["recorded"].get(np.dtype(dtype).name, {}).get(f"{fx} {fy}", {}).get(f"{order[0]},{order[1]}")
+
+
+def bicubic_top_exponent(dtype, fx="uneven", fy="uneven", order=(0, 0), recorded=True):
     """The largest e for which integer nodes times 2^e keep tables and rows of the restatement at least 90 % finite on this
     pair of knot families, on every grid of BICUBIC_GRIDS and both end sets -- found, not guessed.  The divisions by the knot
     spacings move it a long way: 2^118 / 2^1014 on uneven x uneven, far less on adjacent or small axes, so one exponent for
     all pairs would leave the lane all inf and NaN on most of them.  Bisection: tables and rows are linear in the nodes and a
     power of two scales them exactly, so what overflows at e overflows at e + 1 (tests/test_hostile_inputs.py holds the
-    result to ok(e) and not ok(e + 1) for every pair)."""
-    key = (np.dtype(dtype), fx, fy)
+    result to ok(e) and not ok(e + 1) for every pair).  `recorded=False` searches whatever the recorded file says.  `order`: the rows are those of that partial derivative (the tables do
+    not depend on it).  Where the integer lane itself is not 90 % finite in the rows of an order -- a slope divided once or
+    twice more by a spacing of 2^-40 / 2^-400, bicubic_integer_overflows -- there is no such e: the answer is 0, the lane
+    repeats the integers and claims nothing."""
+    order = tuple(order)
+    key = (np.dtype(dtype), fx, fy, order)
+    if recorded and order != (0, 0) and bicubic_recorded_exponents(dtype, fx, fy, order):
+        return bicubic_recorded_exponents(dtype, fx, fy, order)[0]
     if key not in _TOP:
         lo, hi = 0, np.finfo(dtype).maxexp      # ok(lo): the integer lane itself; 2^maxexp is inf
-        assert bicubic_top_ok(dtype, fx, fy, lo), key
+        if order == (0, 0):
+            assert bicubic_top_ok(dtype, fx, fy, lo), key
+        elif not bicubic_top_ok(dtype, fx, fy, lo, order):
+            hi = 1
         while hi - lo > 1:
             mid = (lo + hi) // 2
-            lo, hi = (mid, hi) if bicubic_top_ok(dtype, fx, fy, mid) else (lo, mid)
+            lo, hi = (mid, hi) if bicubic_top_ok(dtype, fx, fy, mid, order) else (lo, mid)
         _TOP[key] = lo
     return _TOP[key]
 
 
-def bicubic_top_ok(dtype, fx, fy, e):
-    return all(_top_ok(dtype, fx, fy, e, nx, ny, bc) for nx, ny in BICUBIC_GRIDS for bc in bicubic_ends())
+def bicubic_top_ok(dtype, fx, fy, e, order=(0, 0)):
+    return all(_top_ok(dtype, fx, fy, e, nx, ny, bc, order) for nx, ny in BICUBIC_GRIDS for bc in bicubic_ends())
 
 
-def _top_ok(dtype, fx, fy, e, nx, ny, bc):
+def _top_ok(dtype, fx, fy, e, nx, ny, bc, order=(0, 0)):
     x, y = bicubic_grid(fx, fy, dtype, nx, ny)
     z = bicubic_lane("top scale", dtype, nx, ny, np.random.default_rng([0, nx, ny, 7]), e)[:, :, None]
     qx, qy = bicubic_queries(x, y)
-    tabs, rows = bicubic_reference(x, y, z, bc, qx, qy)
+    tabs, rows = bicubic_reference(x, y, z, bc, qx, qy, order=order)
     return finite_share(*tabs) >= 0.9 and finite_share(rows) >= 0.9
+
+
+def bicubic_integer_share(dtype, fx, fy, order, bc=None):
+    """the smallest finite share, over the grids, of the integer lane's rows of `order` with the ends `bc`"""
+    shares = []
+    for nx, ny in BICUBIC_GRIDS:
+        x, y = bicubic_grid(fx, fy, dtype, nx, ny)
+        z = bicubic_lane("integers", dtype, nx, ny, np.random.default_rng([0, nx, ny, 0]))[:, :, None]
+        shares.append(finite_share(bicubic_reference(x, y, z, bc, *bicubic_queries(x, y), order=order)[1]))
+    return min(shares)
+
+
+def bicubic_integer_overflows(dtype, bc=None):
+    """{(fx, fy, order): share}: the cases in which the integer lane's rows of a partial derivative are less than 90 % finite
+    on a grid, with the smallest share.  Genuine overflows of the contract's arithmetic, not defects."""
+    import bicubic_partial_ref
+    out = {}
+    for fx, fy in bicubic_partial_pairs(dtype):
+        for order in bicubic_partial_ref.ORDERS:
+            share = bicubic_integer_share(dtype, fx, fy, order, bc)
+            if share < 0.9:
+                out[fx, fy, order] = round(share, 2)
+    return out
+
+
+def subnormal_count(a):
+    return int(np.count_nonzero((a != 0) & (np.abs(a) < np.finfo(a.dtype).tiny)))
+
+
+def changed_rows(a, b):
+    """the number of rows (first axis) in which a and b differ in what check_bits compares"""
+    same = ((a == b) & (np.signbit(a) == np.signbit(b))) | (np.isnan(a) & np.isnan(b))
+    return int(np.count_nonzero(~same.reshape(len(a), -1).all(axis=1)))
+
+
+def bicubic_sub_scan(dtype, fx, fy, order, exps, grids=BICUBIC_GRIDS, thin=1):
+    """For every exponent e of `exps`: (subnormal non-zero rows of `order`, rows a flush to zero changes), each with one
+    column per grid of `grids`, for the subnormal recipe's integers times 2^e as one lane, default ends.  All exponents go
+    through the restatement at once, as lanes of one array.  `thin`: every thin-th query only (the search)."""
+    import bicubic_partial_ref
+    T = np.dtype(dtype).type
+    exps = np.asarray(exps)
+    sub, changed = [], []
+    for nx, ny in grids:
+        x, y = bicubic_grid(fx, fy, dtype, nx, ny)
+        ints = bicubic_lane("integers", dtype, nx, ny, np.random.default_rng([0, nx, ny, 1]))
+        with np.errstate(over="ignore"):
+            z = (ints[:, :, None] * np.ldexp(T(1), exps)[None, None, :]).astype(dtype)
+        qx, qy = bicubic_queries(x, y, n_random=300)
+        qx, qy = qx[::thin], qy[::thin]
+        tabs, rows = bicubic_reference(x, y, z, None, qx, qy, order=order)
+        _, flushed = bicubic_reference(x, y, z, None, qx, qy, tabs=tabs, order=order, variant=bicubic_partial_ref.FLUSHED)
+        sub.append(np.count_nonzero((rows != 0) & (np.abs(rows) < np.finfo(dtype).tiny), axis=0))
+        same = ((rows == flushed) & (np.signbit(rows) == np.signbit(flushed))) | (np.isnan(rows) & np.isnan(flushed))
+        changed.append(np.count_nonzero(~same, axis=0))
+    return np.stack(sub, 1), np.stack(changed, 1)
+
+
+def bicubic_sub_range(dtype):
+    """the exponents at which integers 1 .. 4 times 2^e are non-zero and finite"""
+    f = np.finfo(dtype)
+    return f.minexp - f.nmant, f.maxexp - 3
+
+
+SUB_STEP = 4
+
+
+def bicubic_sub_exponent(dtype, fx, fy, order, recorded=True):
+    """The exponent e for which integers times 2^e give the most subnormal, non-zero rows of the partial derivative `order`,
+    pooled over both grids with the default ends -- found by search, not guessed.  The count is not monotone in e (rows
+    underflow to zero below a window, are normal above it, and the build's products underflow before its quotients do), so
+    the whole range in which the scaled integers are non-zero is scanned: every 4th exponent on a third of the queries of
+    the small grid and a ninth of the large one's, then every exponent within 4 of the best.  The rows of a derivative are
+    node differences divided by spacings, so the best e moves with the knot families by hundreds; it may make the nodes
+    themselves subnormal, which puts subnormal operands into kl * h and pr - pl.  An exponent at which a flush to zero
+    (bicubic_partial_ref.FLUSHED) changes a row on every grid goes before one at which it does not; ties in the count go to
+    the exponent at which the flush changes more rows, then to the smaller one: where no exponent gives a subnormal row (the
+    rows would need nodes below the smallest subnormal) the lane is the one whose operands a flush changes most.  Where the
+    two stages find no exponent at which the flush changes a row on every grid, every exponent of the range is tried."""
+    key = (np.dtype(dtype), fx, fy, tuple(order))
+    if recorded and bicubic_recorded_exponents(dtype, fx, fy, order):
+        return bicubic_recorded_exponents(dtype, fx, fy, order)[1]
+    if key not in _SUB:
+        lo, hi = bicubic_sub_range(dtype)
+
+        def scan(exps):
+            best = None
+            for thin, grids in ((3, BICUBIC_GRIDS[:1]), (9, BICUBIC_GRIDS[1:])):
+                r = bicubic_sub_scan(dtype, fx, fy, order, exps, grids, thin)
+                sub, changed = (r[0], r[1]) if thin == 3 else (np.concatenate([sub, r[0]], 1), np.concatenate([changed, r[1]], 1))
+            for k, e in enumerate(exps):
+                cand = (bool(np.all(changed[k] > 0)), int(sub[k].sum()), int(changed[k].sum()), -int(e))
+                best = cand if best is None or cand > best else best
+            return best
+        best = scan(np.arange(lo, hi + 1, SUB_STEP))
+        best = scan(np.arange(max(lo, -best[3] - SUB_STEP), min(hi, -best[3] + SUB_STEP) + 1))
+        if not best[0]:
+            best = scan(np.arange(lo, hi + 1))
+        _SUB[key] = -best[3]
+    return _SUB[key]

@@ -7,7 +7,10 @@
 * the restatement on the finite hostile classes still agrees with scipy;
 * mutants of the restatement -- the subtle ways a kernel could be wrong -- are told apart by at least one hostile array;
 * the hostile Bicubic grids (tests/test_gpu_bicubic_hostile.py): finite where they claim to be, subnormal where they claim to
-  be, non-finite in the planted lanes only, with queries that tell a left-sided cell search from the right-sided one.
+  be, non-finite in the planted lanes only, with queries that tell a left-sided cell search from the right-sided one;
+* the same grids under the eight partial derivatives (tests/test_gpu_bicubic_partial_hostile.py): a top-scale and a subnormal
+  lane per order, each exponent found by search and recorded, the subnormal lane judged by a flush-to-zero mutant, six
+  mutants of H1 / H2 told apart, and the cases that claim nothing named in literals.
 """
 import os
 
@@ -449,3 +452,203 @@ def test_bicubic_generators_are_seeded_and_shaped():
         ax, ay = hostile.bicubic_axis_queries(x), hostile.bicubic_axis_queries(y)
         assert len(qx) == len(qy) == len(ax) * len(ay) + 2000 and qx.dtype == qy.dtype == np.dtype(dt)
         assert x[0] <= qx.min() and qx.max() <= x[-1] and y[0] <= qy.min() and qy.max() <= y[-1]
+
+
+# ---- the hostile Bicubic grids under partial derivatives (tests/test_gpu_bicubic_partial_hostile.py) ------------------------------
+import hashlib                                     # noqa: E402
+import bicubic_partial_ref as partial_ref          # noqa: E402
+
+ORDERS = partial_ref.ORDERS
+ALL_MUTANTS = partial_ref.MUTANTS + partial_ref.ROUNDING_MUTANTS
+# The integer lane's rows of these orders are less than 90 % finite on a grid (the smallest share beside each): a slope of the
+# order 2^40 / 2^400 divided twice more by 2^-40 / 2^-400 -- genuine overflows of the contract's arithmetic.  These cases run
+# on the device like every other; they make no finiteness claim, and their top-scale lane repeats the integers (exponent 0).
+INTEGERS_OVERFLOW = {
+    np.float32: {("adjacent", "small", (2, 2)): 0.08, ("small", "adjacent", (2, 2)): 0.08, ("small", "small", (2, 2)): 0.0,
+                 ("small", "mixed2", (2, 2)): 0.6, ("mixed2", "small", (2, 2)): 0.55},
+    np.float64: {("small", "small", (0, 2)): 0.0, ("small", "small", (1, 2)): 0.0, ("small", "small", (2, 1)): 0.0,
+                 ("small", "small", (2, 2)): 0.0},
+}
+# ... and those the MIXED ends add (an end slope of 0.75 prescribed on x, which no scaling of the data changes)
+INTEGERS_OVERFLOW_MIXED_ENDS = {np.float32: {}, np.float64: {}}
+# No exponent in the whole range at which a flush to zero changes a row of that order on every grid: none.
+NO_FLUSH_SHOWS = {np.float32: [], np.float64: []}
+# On the pairs drawn from {uneven, big}^2 at least 20 % of the subnormal lane's rows of every order are subnormal on each
+# grid, but for: f64 big x big (2, 2), whose rows are nodes times 2^-1600 while the tables overflow from nodes of 2^219 on
+# (bicubic_top_exponent: 218) -- every such row is below the smallest subnormal, 2^-1074, whatever the exponent.
+NO_SUBNORMAL_ROW_POSSIBLE = {np.float32: [], np.float64: [("big", "big", (2, 2))]}
+_PARTIAL = {}
+
+
+def _spacings(family, dt):
+    return np.concatenate([np.diff(hostile.bicubic_knots(family, dt, n, seed)) for n in (5, 6, 7, 65) for seed in (0, 1)])
+
+
+def mutant_can_show(variant, dt, fx, fy, order):
+    """False where the mutant is the restatement itself, as a function, on every axis on which it changes the form that
+    `order` uses: no node data can tell the two apart on those knots.  That is so for the three mutants that are about the
+    rounding of a product or quotient with h, on an axis whose every spacing is a power of two (computed from the knots:
+    adjacent, big, small, and mixed2, whose coarse steps round to 2^10 / 2^100 exactly): kl * h is exact, so rounding
+    kl * h - d once is rounding it twice; 1 / h is exact, so x * (1 / h) is x / h; and x / h / h has an exact first quotient.
+    (Exact but for a product or quotient that lands in the subnormal range, where the arithmetic is fixed-point and the
+    second rounding changes a result only on a tie; nothing is claimed there.)  Such an axis cannot tell these mutants
+    whatever lanes it carries: the pairs with an `uneven` axis under the mutated form are the ones that can.
+    "contracted" is defined for f32 alone."""
+    fams = [f for nu, f in zip(order, (fx, fy)) if nu in partial_ref.mutant_orders(variant)]
+    if not fams:
+        return False
+    if variant in ("reciprocal", "h2_two_divisions", "contracted"):
+        if variant == "contracted" and np.dtype(dt) != np.float32:
+            return False
+        return not all(bool(np.all(np.frexp(_spacings(f, dt))[0] == 0.5)) for f in fams)
+    return True
+
+
+def _partial_arrays(dt, fx, fy, bc):
+    for nx, ny in hostile.BICUBIC_GRIDS:
+        x, y = hostile.bicubic_grid(fx, fy, dt, nx, ny)
+        z, lanes = hostile.bicubic_partial_nodes(dt, nx, ny, fx, fy)
+        qx, qy = hostile.bicubic_queries(x, y, True, n_random=300)       # the outside points included: s beyond [0, 1]
+        yield x, y, z, lanes, qx, qy, hostile.bicubic_reference(x, y, z, bc)[0]
+
+
+def partial_table(dt, fx, fy):
+    """Everything the self-check says about one (dtype, pair), per order: computed once, asserted below."""
+    key = (np.dtype(dt), fx, fy)
+    if key in _PARTIAL:
+        return _PARTIAL[key]
+    out = {}
+    arrays = {bi: list(_partial_arrays(dt, fx, fy, bc)) for bi, bc in enumerate(hostile.bicubic_ends())}
+    for order in ORDERS:
+        r = out[order] = {}
+        r["integer share"] = [hostile.bicubic_integer_share(dt, fx, fy, order, bc) for bc in hostile.bicubic_ends()]
+        e = r["top"] = hostile.bicubic_top_exponent(dt, fx, fy, order, recorded=False)
+        r["top ok"] = (hostile.bicubic_top_ok(dt, fx, fy, e, order), hostile.bicubic_top_ok(dt, fx, fy, e + 1, order))
+        s = r["sub"] = hostile.bicubic_sub_exponent(dt, fx, fy, order, recorded=False)
+        r["recorded"] = hostile.bicubic_recorded_exponents(dt, fx, fy, order)
+        sub, changed = hostile.bicubic_sub_scan(dt, fx, fy, order, [s])
+        r["sub rows"], r["flush changes"] = sub[0].tolist(), changed[0].tolist()
+        r["rows"] = [len(a[4]) for a in arrays[0]]
+        # the mutants, on the arrays of the device test: the small grid first, the large one and the MIXED ends only if needed
+        caught = {}
+        for bi in arrays:
+            for x, y, z, lanes, qx, qy, tabs in arrays[bi]:
+                todo = [m for m in ALL_MUTANTS if m not in caught and mutant_can_show(m, dt, fx, fy, order)]
+                if not todo:
+                    break
+                _, want = hostile.bicubic_reference(x, y, z, None, qx, qy, tabs=tabs, order=order)
+                for m in todo:
+                    _, got = hostile.bicubic_reference(x, y, z, None, qx, qy, tabs=tabs, order=order, variant=m)
+                    n = hostile.changed_rows(got, want)
+                    if n:
+                        caught[m] = n
+        r["caught"] = caught
+        r["expected"] = [m for m in ALL_MUTANTS if mutant_can_show(m, dt, fx, fy, order)]
+    _PARTIAL[key] = out
+    return out
+
+
+BICUBIC_PARTIAL_CASES = [(dt, fx, fy) for dt in DTYPES for fx, fy in hostile.bicubic_partial_pairs(dt)]
+
+
+@pytest.mark.parametrize("dt,fx,fy", BICUBIC_PARTIAL_CASES, ids=[f"{np.dtype(c[0]).name}-{c[1]}-{c[2]}" for c in BICUBIC_PARTIAL_CASES])
+def test_bicubic_partial_lanes_are_what_they_claim(dt, fx, fy):
+    """Every (family pair, dtype) of tests/test_gpu_bicubic_partial_hostile.py and every order, so that the device comparison
+    is not NaN against NaN or 0 against 0 in the lanes that matter.  Printed per order (-s): the top exponent, the subnormal
+    exponent, the subnormal rows and the rows a flush to zero changes on each grid, the rows each mutant changes.
+    * Finite share: the integer lane and the order's top-scale lane are at least 90 % finite in the rows of the order on both
+      grids and both end sets, and one exponent more is not -- but for the cases of INTEGERS_OVERFLOW (9 of 440).
+    * The subnormal lane is judged by a flush-to-zero mutant of the restatement (operands, tables, t, u and the result of
+      every operation of H flushed): it changes at least one row of the order on each grid, in every case -- the search over
+      the whole exponent range found no case without such an exponent (0 of 440; NO_FLUSH_SHOWS).  In 84 of 224 f32 cases and
+      89 of 216 f64 cases no exponent gives a subnormal row on either grid -- rows of a derivative on adjacent, small or
+      mixed2 axes would need nodes below the smallest subnormal -- and the lane found is the one whose subnormal operands
+      (nodes, kl * h, pr - pl) a flush changes in the most rows.  On the pairs from {uneven, big}^2 every grid has at least
+      20 % subnormal rows (a floor under measured figures of 94 % and more), but for the one case of NO_SUBNORMAL_ROW_POSSIBLE.
+    * Mutants of H1 / H2 (bicubic_partial_ref.MUTANTS and ROUNDING_MUTANTS): each is told from the restatement on at least
+      one row of some hostile array of the pair, for every order it can affect.  It cannot where it is the restatement (mutant_can_show):
+      "reciprocal", "h2_two_divisions" and "contracted" on axes whose spacings are powers of two, which is every hostile
+      family of the value tests; the `triple` axis of the three further pairs is there for them."""
+    T = partial_table(dt, fx, fy)
+    name = np.dtype(dt).name
+    for (nx, ny) in hostile.BICUBIC_GRIDS:          # the lanes in the arrays are the lanes the searches ran on
+        z, lanes = hostile.bicubic_partial_nodes(dt, nx, ny, fx, fy, 28)
+        assert lanes[:9] == [(r, (0, 0)) for r in hostile.BICUBIC_RECIPES] and lanes[25:] == lanes[:3] and len(lanes) == 28
+        check_bits(z[..., :9], hostile.bicubic_nodes(dt, nx, ny, 9, 0, hostile.bicubic_top_exponent(dt, fx, fy))[0], "the nine recipes")
+        check_bits(z[..., 25:], z[..., :3], "lanes past 25 repeat")
+        for k, order in enumerate(ORDERS):
+            assert lanes[9 + 2 * k:11 + 2 * k] == [("top scale", order), ("subnormal", order)]
+            ints = [hostile.bicubic_lane("integers", dt, nx, ny, np.random.default_rng([0, nx, ny, r])) for r in (7, 1)]
+            with np.errstate(over="ignore"):
+                check_bits(z[..., 9 + 2 * k], (ints[0] * np.ldexp(dt(1), T[order]["top"])).astype(dt), f"top lane {order}")
+                check_bits(z[..., 10 + 2 * k], (ints[1] * np.ldexp(dt(1), T[order]["sub"])).astype(dt), f"subnormal lane {order}")
+        zf, lf = hostile.bicubic_partial_nodes(dt, nx, ny, fx, fy, 28, finite_only=True)
+        for l in range(28):
+            if l in hostile.BICUBIC_NONFINITE:
+                assert lf[l] == ("integers", (0, 0)) and np.all(np.isfinite(zf[..., l])) and not np.all(np.isfinite(z[..., l]))
+            else:
+                check_bits(zf[..., l], z[..., l], f"finite_only, lane {l}")
+    for order in ORDERS:
+        r = T[order]
+        what = f"{name} {fx} x {fy} {order}"
+        print(f"{what}: top 2^{r['top']}, subnormal lane 2^{r['sub']}: subnormal rows {r['sub rows']} and rows a flush changes "
+              f"{r['flush changes']} of {r['rows']}, integer lane finite {[round(v, 2) for v in r['integer share']]}, mutants {r['caught']}")
+        assert r["recorded"] == [r["top"], r["sub"]], (what, "the recorded exponents are not what the searches find", r["recorded"])
+        listed = (fx, fy, order) in INTEGERS_OVERFLOW[dt] or (fx, fy, order) in INTEGERS_OVERFLOW_MIXED_ENDS[dt]
+        if listed:
+            assert r["top"] == 0, what
+        else:
+            assert min(r["integer share"]) >= 0.9, (what, r["integer share"])
+            assert r["top ok"] == (True, False), (what, r["top"], r["top ok"])
+        if (fx, fy, order) not in NO_FLUSH_SHOWS[dt]:
+            assert all(c >= 1 for c in r["flush changes"]), (what, "a flush to zero changes no row on a grid", r["flush changes"])
+        if fx in ("uneven", "big") and fy in ("uneven", "big") and (fx, fy, order) not in NO_SUBNORMAL_ROW_POSSIBLE[dt]:
+            assert all(s >= 0.2 * n for s, n in zip(r["sub rows"], r["rows"])), (what, r["sub rows"], r["rows"])
+        missed = [m for m in r["expected"] if m not in r["caught"]]
+        assert not missed, f"{what}: no hostile array notices {missed}"
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_bicubic_partial_exclusions_are_the_listed_ones(dt):
+    """The cases that make no finiteness claim, no flush claim or no subnormal-row claim are computed, and are the literal
+    lists above: nothing is left out of a claim by a rule nobody can read."""
+    default, mixed = hostile.bicubic_integer_overflows(dt, None), hostile.bicubic_integer_overflows(dt, hostile.bicubic_ends()[1])
+    assert default == INTEGERS_OVERFLOW[dt], default
+    assert {k: v for k, v in mixed.items() if k not in default} == INTEGERS_OVERFLOW_MIXED_ENDS[dt], mixed
+    no_flush, no_sub = [], []
+    for fx, fy in hostile.bicubic_partial_pairs(dt):
+        T = partial_table(dt, fx, fy)
+        for order in ORDERS:
+            if not all(c >= 1 for c in T[order]["flush changes"]):
+                no_flush.append((fx, fy, order))
+            if fx in ("uneven", "big") and fy in ("uneven", "big") and sum(T[order]["sub rows"]) == 0:
+                no_sub.append((fx, fy, order))
+    assert no_flush == NO_FLUSH_SHOWS[dt] and no_sub == NO_SUBNORMAL_ROW_POSSIBLE[dt], (no_flush, no_sub)
+    none = sum(1 for fx, fy in hostile.bicubic_partial_pairs(dt) for o in ORDERS if sum(partial_table(dt, fx, fy)[o]["sub rows"]) == 0)
+    print(f"{np.dtype(dt).name}: {none} of {len(hostile.bicubic_partial_pairs(dt)) * len(ORDERS)} cases have no subnormal row at any exponent")
+
+
+# sha256 of the nine-recipe array (6 x 7 x 9, top exponent 5) made with the default arguments, before the order argument
+DEFAULT_BITS = {np.float32: "420ed827be92a8ec7103ed0ee8e01dbba435f5a9ce233b16810205ffb26e6ab8",
+                np.float64: "6ec54fbda447ba55934ecca634a7f2540f6f5fc2915266a4fde5550b6170a10b"}
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_default_arguments_give_the_bits_they_gave(dt):
+    """order=(0, 0) is the default and changes nothing: every recipe has the bits it had before the scaled recipes took an
+    order (a digest of them, recorded then), and naming the default explicitly is the same lane."""
+    z, _ = hostile.bicubic_nodes(dt, 6, 7, 9, 0, 5)
+    assert hashlib.sha256(np.ascontiguousarray(z).tobytes()).hexdigest() == DEFAULT_BITS[dt]
+    for r in range(len(hostile.BICUBIC_RECIPES)):
+        a = hostile.bicubic_lane(r, dt, 6, 7, np.random.default_rng([0, 6, 7, r]), 5)
+        b = hostile.bicubic_lane(r, dt, 6, 7, np.random.default_rng([0, 6, 7, r]), 5, order=(0, 0), pair=("small", "small"))
+        check_bits(a, z[..., r], f"recipe {r}"); check_bits(b, a, f"recipe {r}, the default named")
+    x, y = hostile.bicubic_grid("uneven", "mixed2", dt, 6, 7)
+    qx, qy = hostile.bicubic_queries(x, y)
+    tabs, rows = hostile.bicubic_reference(x, y, z, None, qx, qy)
+    check_bits(hostile.bicubic_reference(x, y, z, None, qx, qy, tabs=tabs, order=(0, 0))[1], rows, "order (0, 0) is the surface")
+    with np.errstate(all="ignore"):
+        check_bits(partial_ref.evaluate(x, y, z, *tabs, qx, qy, 0, 0), rows, "the partial restatement at (0, 0)")
+        for o in ORDERS:
+            check_bits(hostile.bicubic_reference(x, y, z, None, qx, qy, tabs=tabs, order=o)[1],
+                       partial_ref.evaluate(x, y, z, *tabs, qx, qy, *o), f"order {o}")
