@@ -6,9 +6,10 @@
 // evaluates in the two-kernel form only: locate_kernel writes idx[] / t[] and the first failing index, then ONE
 // evaluation launch reads them (antiderivative_kernels.hpp).  integrate() runs the search twice (lo into scratch set 0
 // and first_fail[0], hi into set 1 and first_fail[1]) and the same single evaluation launch with the pair flag.
+// Staging, the first-error report, the host-output chunk loop and finish are the float host engine's (float_host.hpp).
 
 template <class T>
-struct AntiderivImpl final : Interp1DBase {
+struct AntiderivImpl final : Interp1DBase, FloatEngine<T, AntiderivImpl<T>> {
   bool linear = false;     // the source's evaluation class
   int rule = HR_SPLINE;    // the source's rule and derivative order (names in messages, the replica signature)
   int deriv = 0;
@@ -148,7 +149,10 @@ struct AntiderivImpl final : Interp1DBase {
   }
 
   // One batch on device pointers: status reset, the search(es), ONE evaluation launch.  hi == nullptr: F(q); else F(hi) - F(q).
-  void enqueue(hipStream_t s, Workspace& ws, const T* q, const T* hi, uint64_t nq, T* out, uint64_t out_stride) {
+  // (path and flags: the engine's; this family has one form and always its range test)
+  void enqueue(hipStream_t s, Workspace& ws, Queries<T> qs, uint64_t nq, T* out, uint64_t out_stride, int, int) {
+    const T* q = qs.a;
+    const T* hi = qs.b;
     g_last_path.store(NDI_PATH_GATHER);
     ws.sc[0].status.reserve(sizeof(StatusBlock));
     reset_status(ws.sc[0].status.p, s);
@@ -204,42 +208,10 @@ struct AntiderivImpl final : Interp1DBase {
     ps.done();
   }
 
-  // The source's error for the lowest failing flat index of a batch; lo is tested before hi at the same index.
-  ndi_status report(const void* q, const void* hi, int q_space, unsigned long long f0, unsigned long long f1,
-                    uint64_t index_offset, ndi_oob_info* info) {
-    const int axis = f0 <= f1 ? 0 : 1;
-    const unsigned long long ff = axis ? f1 : f0;
-    const void* src = axis ? hi : q;
-    T v;
-    if (q_space == NDI_MEM_DEVICE) NDI_HIP(hipMemcpy(&v, (const T*)src + ff, sizeof(T), hipMemcpyDeviceToHost));
-    else v = ((const T*)src)[ff];
-    const ndi_status st = (mode != EX_NO) ? NDI_NAN_QUERY : NDI_OUT_OF_BOUNDS;
-    if (info) {
-      info->index = index_offset + ff;
-      info->value = (double)v;
-      info->axis = axis;
-      info->status = st;
-    }
-    if (st == NDI_NAN_QUERY) return fail(st, "failed to convert NaN to usize (query %llu)", index_offset + ff);
-    return fail(st, "x = %.17g is not in range", (double)v);
-  }
-
-  ndi_status collect(hipStream_t s, Workspace& ws, uint64_t index_offset, ndi_oob_info* info) {
-    ws.ensure_status();
-    NDI_HIP(hipMemcpyAsync(ws.host_status, ws.sc[0].status.p, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
-    NDI_HIP(hipStreamSynchronize(s));
-    ws.pending = false;
-    const unsigned long long f0 = ws.host_status->first_fail[0], f1 = ws.host_status->first_fail[1];
-    if (f0 == NO_FAIL && f1 == NO_FAIL) return NDI_OK;
-    return report(ws.last_q, ws.last_q2, ws.last_q_space, f0, f1, index_offset, info);
-  }
-
-  const T* stage_queries(hipStream_t s, DevBuf& buf, const void* q_, uint64_t nq, int q_space) {
-    if (!q_ || q_space != NDI_MEM_HOST) return (const T*)q_;
-    buf.reserve(nq * sizeof(T));
-    NDI_HIP(hipMemcpyAsync(buf.p, q_, nq * sizeof(T), hipMemcpyHostToDevice, s));
-    return buf.as<T>();
-  }
+  // ---- what the host engine (float_host.hpp) takes from this family: no small-row paths, no ring -----------------------
+  static constexpr bool small_rows = false, ring = false;
+  // lo is tested before hi at the same index, and both are the source's "x"
+  static const char* axis_name(int) { return "x"; }
 
   // eval (hi_ == nullptr) and integrate share one body.
   ndi_status run(const void* q_, const void* hi_, bool pair, uint64_t nq, void* out_, uint64_t out_stride,
@@ -259,39 +231,9 @@ struct AntiderivImpl final : Interp1DBase {
     hipStream_t s = (hipStream_t)o.stream;
     SpaceLease lease(spaces, s);
     Workspace& ws = lease.ws;
-    const T* q = stage_queries(s, ws.qdev, q_, nq, o.q_memspace);
-    const T* hi = pair ? stage_queries(s, ws.qdev2, hi_, nq, o.q_memspace) : nullptr;
-    ws.last_q = q_;
-    ws.last_q2 = hi_;
-    ws.last_q_space = o.q_memspace;
-    ws.last_nq = nq;
-    if (o.out_memspace == NDI_MEM_DEVICE) {
-      enqueue(s, ws, q, hi, nq, (T*)out_, out_stride);
-      ws.pending = true;
-      if (o.async_launch) return NDI_OK;
-      return collect(s, ws, 0, info);
-    }
-    // host output: the batch goes through a device staging buffer in query chunks; only rows before the first failure
-    // are copied into the caller's buffer
-    const uint64_t row_bytes = lanes * sizeof(T);
-    const uint64_t chunk_q = std::max<uint64_t>(1, std::min<uint64_t>(nq, (256ull << 20) / row_bytes));
-    ws.stage.reserve(chunk_q * row_bytes);
-    ws.ensure_status();
-    for (uint64_t off = 0; off < nq; off += chunk_q) {
-      const uint64_t cq = std::min<uint64_t>(chunk_q, nq - off);
-      enqueue(s, ws, q + off, hi ? hi + off : nullptr, cq, ws.stage.as<T>(), lanes);
-      NDI_HIP(hipMemcpyAsync(ws.host_status, ws.sc[0].status.p, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
-      NDI_HIP(hipStreamSynchronize(s));
-      const unsigned long long f0 = ws.host_status->first_fail[0], f1 = ws.host_status->first_fail[1];
-      const unsigned long long ff = std::min(f0, f1);
-      const uint64_t good = (ff == NO_FAIL) ? cq : (uint64_t)ff;
-      if (good)
-        NDI_HIP(hipMemcpy2D((T*)out_ + off * out_stride, out_stride * sizeof(T), ws.stage.p, row_bytes, row_bytes, good,
-                            hipMemcpyDeviceToHost));
-      if (ff != NO_FAIL)
-        return report((const T*)q_ + off, hi_ ? (const T*)hi_ + off : nullptr, o.q_memspace, f0, f1, off, info);
-    }
-    return NDI_OK;
+    const Queries<T> orig{(const T*)q_, pair ? (const T*)hi_ : nullptr};
+    return this->eval_body(s, ws, this->stage_queries(s, ws, orig, nq, o.q_memspace), orig, o.q_memspace, nq, out_,
+                           out_stride, o, info);
   }
 
   ndi_status eval(const void* q_, uint64_t nq, void* out_, uint64_t out_stride, const ndi_eval_opts* opts,
@@ -304,17 +246,7 @@ struct AntiderivImpl final : Interp1DBase {
     return run(lo, hi, true, nq, out_, out_stride, opts, info);
   }
 
-  ndi_status finish(void* stream, ndi_oob_info* info) override {
-    DeviceGuard dg(device);
-    hipStream_t s = (hipStream_t)stream;
-    SpaceLease lease(spaces, s);
-    Workspace& ws = lease.ws;
-    if (!ws.pending) {
-      NDI_HIP(hipStreamSynchronize(s));
-      return NDI_OK;
-    }
-    return collect(s, ws, 0, info);
-  }
+  ndi_status finish(void* stream, ndi_oob_info* info) override { return this->run_finish(stream, info); }
 
   ndi_status eval_ring(const void*, uint64_t, const ndi_ring_desc*, ndi_ring_consumer, void*, const ndi_eval_opts*,
                        ndi_oob_info*) override {
@@ -324,7 +256,7 @@ struct AntiderivImpl final : Interp1DBase {
 
   ndi_status trim() override {
     DeviceGuard dg(device);
-    spaces.trim();
+    this->trim_front();
     return NDI_OK;
   }
   uint64_t scratch_sets() override { return spaces.size(); }

@@ -818,6 +818,11 @@ static ndi_status check_ring_desc(const ndi_ring_desc* ring, uint64_t lanes, uin
 }
 
 // ---------------------------------------------------------------------------------------------
+// the host engine the f32 / f64 handles share (Interp1DImpl, AntiderivImpl, Interp2DImpl below)
+// ---------------------------------------------------------------------------------------------
+#include "float_host.hpp"
+
+// ---------------------------------------------------------------------------------------------
 // Interp1D
 // ---------------------------------------------------------------------------------------------
 // NDI_BUILD_TIMING=1: wall-clock milestones of create() on stderr (where a build's milliseconds go: tools/build_probe.py)
@@ -919,7 +924,7 @@ static const char* hermite_rule_name(int rule) {
 }
 
 template <class T>
-struct Interp1DImpl final : Interp1DBase {
+struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
   int strategy = NDI_LINEAR;   // the evaluation class: NDI_CUBIC_SPLINE = "has a / b tables" (Pchip, Akima, CubicHermite too)
   int rule = HR_SPLINE;        // ... and which rule chose the knot derivatives behind those tables (HermiteRule)
   int deriv = 0;               // derivative order: 0 = the interpolant; 1, 2 = ndi_interp1d_derivative of a handle of `rule`
@@ -2070,162 +2075,43 @@ struct Interp1DImpl final : Interp1DBase {
 #undef NDI_FU
   }
 
-  void enqueue(hipStream_t s, Workspace& ws, const T* q, uint64_t nq, T* out, uint64_t out_stride, int path, int flags = 0) {
-    launch_eval(s, ws.sc[0], prep(s, ws.sc[0], q, nq, out, out_stride, path, false, flags));
+  // ---- what the host engine (float_host.hpp) takes from this family ------------------------------------------------
+  using Elem = T;
+  using Plan = Plan1;
+  static constexpr int query_arrays = 1;
+  static constexpr bool small_rows = true, ring = true;
+  static const char* axis_name(int) { return "x"; }
+  void range_limits(T lim[4]) const {
+    lim[0] = lim[2] = pyr.host_knots.front();
+    lim[1] = lim[3] = pyr.host_knots.back();
   }
-
-  // Reads the status block of the batch enqueued with scratch set 0 (stream must be idle afterwards) and converts
-  // it to the reference's error.
-  ndi_status collect(hipStream_t s, Workspace& ws, uint64_t index_offset, ndi_oob_info* info) {
-    ws.ensure_status();
-    NDI_HIP(hipMemcpyAsync(ws.host_status, ws.sc[0].status.p, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
-    NDI_HIP(hipStreamSynchronize(s));
-    ws.pending = false;
-    const unsigned long long ff = ws.host_status->first_fail[0];
-    if (ff == NO_FAIL) return NDI_OK;
-    return report(ws.last_q, ws.last_q_space, ff, index_offset, info);
+  Plan1 prep(hipStream_t s, Scratch& sc, Queries<T> q, uint64_t nq, T* out, uint64_t out_stride, int path,
+             bool beside_eval = false, int flags = 0) {
+    return prep(s, sc, q.a, nq, out, out_stride, path, beside_eval, flags);
   }
-
-  // The reference's error for the batch whose lowest failing query is q[ff] (reported as index_offset + ff).
-  ndi_status report(const void* q, int q_space, unsigned long long ff, uint64_t index_offset, ndi_oob_info* info) {
-    T v;
-    if (q_space == NDI_MEM_DEVICE)
-      NDI_HIP(hipMemcpy(&v, (const T*)q + ff, sizeof(T), hipMemcpyDeviceToHost));
-    else
-      v = ((const T*)q)[ff];
-    // without extrapolation every failure is a range failure (NaN included: "x = NaN is not in range");
-    // with it the only failure is the search meeting a NaN -- the query itself or an infinite query that the
-    // periodic wrap turned into NaN (the reference panics: vector_extensions.rs:83-84)
-    const ndi_status st = (mode != EX_NO) ? NDI_NAN_QUERY : NDI_OUT_OF_BOUNDS;
-    if (info) {
-      info->index = index_offset + ff;
-      info->value = (double)v;
-      info->axis = 0;
-      info->status = st;
-    }
-    if (st == NDI_NAN_QUERY) return fail(st, "failed to convert NaN to usize (query %llu)", index_offset + ff);
-    return fail(st, "x = %.17g is not in range", (double)v);
+  void enqueue(hipStream_t s, Workspace& ws, Queries<T> q, uint64_t nq, T* out, uint64_t out_stride, int path, int flags) {
+    launch_eval(s, ws.sc[0], prep(s, ws.sc[0], q.a, nq, out, out_stride, path, false, flags));
   }
-
-  // Host queries are uploaded once per call into the workspace.
-  const T* stage_queries(hipStream_t s, Workspace& ws, const void* q_, uint64_t nq, int q_space) {
-    if (q_space != NDI_MEM_HOST) return (const T*)q_;
-    ws.qdev.reserve(nq * sizeof(T));
-    NDI_HIP(hipMemcpyAsync(ws.qdev.p, q_, nq * sizeof(T), hipMemcpyHostToDevice, s));
-    return ws.qdev.as<T>();
-  }
-
-  // Range pre-pass over a whole batch (8 B per query): the lowest failing index lands in ws.host_status once the
-  // stream has been synchronised.  The ring and the sharded evaluations need it before any row is produced.
-  void enqueue_prepass(hipStream_t s, Workspace& ws, const T* q, uint64_t nq) {
-    ws.ensure_status();
-    reset_status(ws.status.p, s);
-    StatusBlock* st = ws.status.as<StatusBlock>();
-    const T k0 = pyr.host_knots.front(), kn = pyr.host_knots.back();
-    const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-    {
-      ProfScope ps(s, PC_LOCATE);
-      hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, q, (const T*)nullptr, nq, k0, kn, k0, kn,
-                         mode, &st->first_fail[0]);
-      NDI_HIP(hipGetLastError());
-      ps.done();
-    }
-    NDI_HIP(hipMemcpyAsync(ws.host_status, ws.status.p, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
-  }
-
-  // Host output with short trailing axes (the reference's own bench shapes: scalar data, a few lanes):
-  // one fused search+evaluate launch per chunk into a staging buffer the library owns, results and status
-  // brought back with one synchronisation (small chunks bounce through pinned memory), and only the rows
-  // before the first failing query are copied into the caller's buffer.
-  ndi_status eval_small_host(hipStream_t s, Workspace& ws, const T* q_dev, const T* q_orig, int q_space,
-                             uint64_t nq, T* out, uint64_t out_stride, ndi_oob_info* info) {
-    const uint64_t row_bytes = lanes * sizeof(T);
-    const uint64_t chunk_q = std::max<uint64_t>(1, std::min<uint64_t>(nq, (64ull << 20) / row_bytes));
-    constexpr size_t BOUNCE = 8ull << 20;
-    ws.stage.reserve(chunk_q * row_bytes);
-    ws.ensure_status();
-    g_last_path.store(NDI_PATH_GATHER);
-    allow_dynamic_lds(reinterpret_cast<const void*>(&eval_small_kernel<T, ST_CUBIC>), (int)LDS_STAGE_LIMIT);
-    allow_dynamic_lds(reinterpret_cast<const void*>(&eval_small_kernel<T, ST_LINEAR>), (int)LDS_STAGE_LIMIT);
-    StatusBlock* st = ws.sc[0].status.as<StatusBlock>();
-    for (uint64_t off = 0; off < nq; off += chunk_q) {
-      const uint64_t cq = std::min<uint64_t>(chunk_q, nq - off);
-      const size_t bytes = cq * row_bytes;
-      NDI_HIP(hipMemsetAsync(st, 0xFF, 2 * sizeof(unsigned long long), s));
-      EvalSmallArgs<T> A{};
-      A.pyr = pyr.view;
-      A.data = data.as<T>();
-      A.ca = ca.as<T>();
-      A.cb = cb.as<T>();
-      A.q = q_dev + off;
-      A.out = ws.stage.as<T>();
-      A.nq = cq;
-      A.out_stride = lanes;
-      A.lanes = (uint32_t)lanes;
-      A.mode = mode;
-      A.first_fail = &st->first_fail[0];
-      A.prechecked = 0;
-      const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((cq + BLOCK - 1) / BLOCK, 4096));
-      const size_t shmem = (pyr.lds_bytes + 15) & ~(size_t)15;
-      if (strategy == NDI_CUBIC_SPLINE) launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), shmem, eval_small_kernel<T, ST_CUBIC>, A);
-      else launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), shmem, eval_small_kernel<T, ST_LINEAR>, A);
-      const bool bounce = bytes <= BOUNCE;
-      if (bounce) {
-        ws.ensure_pin(BOUNCE);
-        NDI_HIP(hipMemcpyAsync(ws.pin, ws.stage.p, bytes, hipMemcpyDeviceToHost, s));
-      }
-      NDI_HIP(hipMemcpyAsync(ws.host_status, st, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
-      NDI_HIP(hipStreamSynchronize(s));
-      const unsigned long long ff = ws.host_status->first_fail[0];
-      const uint64_t good = (ff == NO_FAIL) ? cq : (uint64_t)ff;
-      T* dst = out + off * out_stride;
-      if (good) {
-        if (bounce) {
-          if (out_stride == lanes) std::memcpy(dst, ws.pin, good * row_bytes);
-          else
-            for (uint64_t r = 0; r < good; ++r)
-              std::memcpy(dst + r * out_stride, (const char*)ws.pin + r * row_bytes, row_bytes);
-        } else {
-          NDI_HIP(hipMemcpy2D(dst, out_stride * sizeof(T), ws.stage.p, row_bytes, row_bytes, good,
-                              hipMemcpyDeviceToHost));
-        }
-      }
-      if (ff != NO_FAIL) return report(q_orig + off, q_space, ff, off, info);
-    }
-    return NDI_OK;
-  }
-
-  // Host arrays in and out, short trailing axes, small batch (the reference's own bench shapes: 1e4 queries on scalar
-  // data): ZERO-COPY.  The queries are copied into the workspace's pinned buffer with a plain memcpy, the fused
-  // search + evaluation kernel reads them and writes the rows straight through the host mapping of that buffer (a
-  // hipHostMalloc allocation is device-accessible), and one synchronisation later the rows are memcpy'd to the
-  // caller -- no H2D / D2H copy commands at all, only the 32-byte status read-back.  Saves two DMA round trips per
-  // call (C1: 48.7 -> see DESIGN.md 4.2).  Rows at / after the first failing query are not copied out.
-  static constexpr size_t ZERO_COPY_LIMIT = 1u << 20;   // queries + rows
+  // the small-row paths: the knot pyramid in LDS
+  bool small_rows_fit() const { return lanes <= (uint64_t)SMALL_LANES && pyr.lds_bytes <= LDS_STAGE_LIMIT; }
   bool zero_copy_fits(uint64_t nq, int q_space, int out_space) const {
-    return q_space == NDI_MEM_HOST && out_space == NDI_MEM_HOST && lanes <= (uint64_t)SMALL_LANES &&
-           pyr.lds_bytes <= LDS_STAGE_LIMIT && nq * (lanes + 1) * sizeof(T) <= ZERO_COPY_LIMIT;
+    return q_space == NDI_MEM_HOST && out_space == NDI_MEM_HOST && small_rows_fit() &&
+           nq * (lanes + 1) * sizeof(T) <= ZERO_COPY_LIMIT;
   }
-  ndi_status eval_small_zero_copy(hipStream_t s, Workspace& ws, const T* q_host, uint64_t nq, T* out,
-                                  uint64_t out_stride, ndi_oob_info* info) {
-    const size_t q_bytes = ((nq * sizeof(T)) + 255) & ~(size_t)255, row_bytes = lanes * sizeof(T);
-    ws.ensure_pin(std::max<size_t>(q_bytes + nq * row_bytes, 8ull << 20));
-    ws.ensure_status();
-    T* pq = reinterpret_cast<T*>(ws.pin);
-    T* po = reinterpret_cast<T*>((char*)ws.pin + q_bytes);
-    std::memcpy(pq, q_host, nq * sizeof(T));
+  void small_begin() {
     g_last_path.store(NDI_PATH_GATHER);
     allow_dynamic_lds(reinterpret_cast<const void*>(&eval_small_kernel<T, ST_CUBIC>), (int)LDS_STAGE_LIMIT);
     allow_dynamic_lds(reinterpret_cast<const void*>(&eval_small_kernel<T, ST_LINEAR>), (int)LDS_STAGE_LIMIT);
-    StatusBlock* st = ws.sc[0].status.as<StatusBlock>();
-    NDI_HIP(hipMemsetAsync(st, 0xFF, 2 * sizeof(unsigned long long), s));
+  }
+  // The fused search + evaluation launch of the small-row paths: nq packed rows into out, the kernel's own range test.
+  void launch_small(hipStream_t s, StatusBlock* st, Queries<T> q, T* out, uint64_t nq) {
     EvalSmallArgs<T> A{};
     A.pyr = pyr.view;
     A.data = data.as<T>();
     A.ca = ca.as<T>();
     A.cb = cb.as<T>();
-    A.q = ws.pin_device<const T>(pq);
-    A.out = ws.pin_device<T>(po);
+    A.q = q.a;
+    A.out = out;
     A.nq = nq;
     A.out_stride = lanes;
     A.lanes = (uint32_t)lanes;
@@ -2236,193 +2122,22 @@ struct Interp1DImpl final : Interp1DBase {
     const size_t shmem = (pyr.lds_bytes + 15) & ~(size_t)15;
     if (strategy == NDI_CUBIC_SPLINE) launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), shmem, eval_small_kernel<T, ST_CUBIC>, A);
     else launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), shmem, eval_small_kernel<T, ST_LINEAR>, A);
-    NDI_HIP(hipMemcpyAsync(ws.host_status, st, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
-    NDI_HIP(hipStreamSynchronize(s));
-    const unsigned long long ff = ws.host_status->first_fail[0];
-    const uint64_t good = (ff == NO_FAIL) ? nq : (uint64_t)ff;
-    if (good) {
-      if (out_stride == lanes) std::memcpy(out, po, good * row_bytes);
-      else
-        for (uint64_t r = 0; r < good; ++r) std::memcpy(out + r * out_stride, (const char*)po + r * row_bytes, row_bytes);
-    }
-    if (ff != NO_FAIL) return report(q_host, NDI_MEM_HOST, ff, 0, info);
-    return NDI_OK;
-  }
-
-  // interp_array_into on staged (device) queries; q_orig / q_space name the caller's array for error reports.
-  ndi_status eval_body(hipStream_t s, Workspace& ws, const T* q, const void* q_orig, int q_space, uint64_t nq,
-                       void* out_, uint64_t out_stride, const ndi_eval_opts& o, ndi_oob_info* info) {
-    ws.last_q = q_orig;
-    ws.last_q_space = q_space;
-    ws.last_nq = nq;
-    if (o.out_memspace == NDI_MEM_DEVICE) {
-      enqueue(s, ws, q, nq, (T*)out_, out_stride, o.path, o.flags);
-      ws.pending = true;
-      if (o.async_launch) return NDI_OK;
-      return collect(s, ws, 0, info);
-    }
-    // host output: stream the batch through a device staging buffer in query chunks
-    const uint64_t row_bytes = lanes * sizeof(T);
-    if (lanes <= (uint64_t)SMALL_LANES && pyr.lds_bytes <= LDS_STAGE_LIMIT)
-      return eval_small_host(s, ws, q, (const T*)q_orig, q_space, nq, (T*)out_, out_stride, info);
-    const uint64_t chunk_q = std::max<uint64_t>(1, std::min<uint64_t>(nq, (256ull << 20) / row_bytes));
-    ws.stage.reserve(chunk_q * row_bytes);
-    ws.ensure_status();
-    for (uint64_t off = 0; off < nq; off += chunk_q) {
-      const uint64_t cq = std::min<uint64_t>(chunk_q, nq - off);
-      enqueue(s, ws, q + off, cq, ws.stage.as<T>(), lanes, o.path);
-      NDI_HIP(hipMemcpyAsync(ws.host_status, ws.sc[0].status.p, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
-      NDI_HIP(hipStreamSynchronize(s));
-      unsigned long long ff = ws.host_status->first_fail[0];
-      const uint64_t good = (ff == NO_FAIL) ? cq : (uint64_t)ff;
-      if (good)
-        NDI_HIP(hipMemcpy2D((T*)out_ + off * out_stride, out_stride * sizeof(T), ws.stage.p, row_bytes,
-                            row_bytes, good, hipMemcpyDeviceToHost));
-      if (ff != NO_FAIL) return report((const T*)q_orig + off, q_space, ff, off, info);
-    }
-    return NDI_OK;
   }
 
   ndi_status eval(const void* q_, uint64_t nq, void* out_, uint64_t out_stride,
                   const ndi_eval_opts* opts, ndi_oob_info* info) override {
-    DeviceGuard dg(device);
-    Range rg("ndi_interp1d_eval");
-    ndi_eval_opts o{};
-    if (const ndi_status vs__ = take_opts(opts, o); vs__ != NDI_OK) return vs__;
-    hipStream_t s = (hipStream_t)o.stream;  // NULL = the HIP default stream
-    if (out_stride < lanes) return fail(NDI_BAD_ARG, "out_row_stride (%llu) < lanes (%llu)",
-                                        (unsigned long long)out_stride, (unsigned long long)lanes);
-    if (nq == 0) return NDI_OK;
-    if (!q_ || !out_) return fail(NDI_BAD_ARG, "null query / output pointer");
-    SpaceLease lease(spaces, s);
-    Workspace& ws = lease.ws;
-    if (zero_copy_fits(nq, o.q_memspace, o.out_memspace))
-      return eval_small_zero_copy(s, ws, (const T*)q_, nq, (T*)out_, out_stride, info);
-    const T* q = stage_queries(s, ws, q_, nq, o.q_memspace);
-    return eval_body(s, ws, q, q_, o.q_memspace, nq, out_, out_stride, o, info);
+    return this->run_eval("ndi_interp1d_eval", {(const T*)q_, nullptr}, nq, out_, out_stride, opts, info);
   }
-
-  ndi_status finish(void* stream, ndi_oob_info* info) override {
-    DeviceGuard dg(device);
-    hipStream_t s = (hipStream_t)stream;
-    SpaceLease lease(spaces, s);
-    Workspace& ws = lease.ws;
-    if (!ws.pending) {
-      NDI_HIP(hipStreamSynchronize(s));
-      return NDI_OK;
-    }
-    return collect(s, ws, 0, info);
-  }
-
-  // ---- ring evaluation ----------------------------------------------------------------------
-  // Interp1D::interp_array for outputs that do not fit / need not stay in device memory: chunks through a ring.
-  // The producer is a two-stream pipeline: locate + group of chunk k+1 run on the workspace's side stream into the
-  // other scratch set while chunk k is evaluated on the caller's stream; events order the two.
-  struct RingRun {
-    std::unique_lock<std::mutex> own;
-    std::vector<void*> slots;
-    uint64_t pitch = 0, chunk = 0, cq0 = 0;
-    uint32_t n_slots = 0;
-    Plan1 plan0;
-    hipStream_t side = nullptr;
-  };
-
-  // Resolves the ring and starts locate + group of chunk 0 on the side stream -- before the first failing index
-  // of the batch is known on the host (it does not depend on it: the evaluation kernels skip rows at / after the
-  // chunk's own first failure), so the range pre-pass and its synchronisation are hidden behind it.
-  void ring_begin(hipStream_t s, Workspace& ws, const T* q, uint64_t nq, const ndi_ring_desc* ring, uint64_t stride,
-                  const ndi_eval_opts& o, RingRun& R) {
-    R.n_slots = ring->n_slots;
-    R.chunk = ring->chunk_queries;
-    R.slots.resize(ring->n_slots);
-    R.pitch = stride;          // row pitch of a chunk, in elements
-    if (ring->slots) {
-      for (uint32_t i = 0; i < ring->n_slots; ++i) R.slots[i] = ring->slots[i];
-    } else {
-      R.own = std::unique_lock<std::mutex>(ring_own.mu);   // library-owned ring: one allocation, slots
-      ring_own.ensure(ring->n_slots, ring->chunk_queries, stride * sizeof(T));   // interleaved row by row (OwnedRing)
-      for (uint32_t i = 0; i < ring->n_slots; ++i) R.slots[i] = (char*)ring_own.buf.p + (size_t)i * stride * sizeof(T);
-      R.pitch = (uint64_t)ring->n_slots * stride;
-    }
-    R.side = ring_overlap() ? ws.side_stream() : s;
-    for (Scratch& sc : ws.sc) sc.ensure_events();
-    // the side stream starts after everything already enqueued on s (the query upload)
-    NDI_HIP(hipEventRecord(ws.order_event(), s));
-    NDI_HIP(hipStreamWaitEvent(R.side, ws.order_event(), 0));
-    R.cq0 = std::min<uint64_t>(R.chunk, nq);
-    R.plan0 = prep(R.side, ws.sc[0], q, R.cq0, (T*)R.slots[0], R.pitch, o.path);
-    NDI_HIP(hipEventRecord(ws.sc[0].prep_done, R.side));
-  }
-
-  // Produces the rows [0, limit) of the batch chunk by chunk.  q_offset / shard: position of this batch in a
-  // sharded evaluation (the consumer sees global query indices).
-  void ring_produce(hipStream_t s, Workspace& ws, const T* q, uint64_t limit, RingRun& R, ndi_ring_consumer consume,
-                    void* user, const ndi_eval_opts& o, uint64_t q_offset, uint32_t shard) {
-    std::vector<hipEvent_t> busy(R.n_slots, nullptr);
-    uint64_t k = 0;
-    for (uint64_t off = 0; off < limit; off += R.chunk, ++k) {
-      const uint64_t cq = std::min<uint64_t>(R.chunk, limit - off);
-      const uint32_t slot = (uint32_t)(k % R.n_slots);
-      Scratch& sc = ws.sc[k & 1];
-      Plan1 P = R.plan0;
-      if (k > 0) {
-        if (k >= 2) NDI_HIP(hipStreamWaitEvent(R.side, sc.eval_done, 0));   // chunk k-2 has released the set
-        P = prep(R.side, sc, q + off, cq, (T*)R.slots[slot], R.pitch, o.path, R.side != s);
-        NDI_HIP(hipEventRecord(sc.prep_done, R.side));
-      }
-      NDI_HIP(hipStreamWaitEvent(s, sc.prep_done, 0));
-      if (busy[slot]) {   // the consumer reads this slot on another stream: wait for it there
-        NDI_HIP(hipStreamWaitEvent(s, busy[slot], 0));
-        busy[slot] = nullptr;
-      }
-      launch_eval(s, sc, P);
-      NDI_HIP(hipEventRecord(sc.eval_done, s));
-      if (consume) {
-        ndi_ring_chunk c{};
-        c.index = k; c.q_begin = q_offset + off; c.q_count = cq; c.out = R.slots[slot]; c.row_stride = R.pitch;
-        c.slot = slot; c.shard = shard; c.stream = (void*)s;
-        busy[slot] = (hipEvent_t)consume(user, &c);
-      }
-    }
-    NDI_HIP(hipStreamSynchronize(s));
-    NDI_HIP(hipStreamSynchronize(R.side));   // (a speculative chunk 0 that was never evaluated)
-    for (hipEvent_t e : busy)
-      if (e) NDI_HIP(hipEventSynchronize(e));
-    ws.pending = false;
-  }
-
+  ndi_status finish(void* stream, ndi_oob_info* info) override { return this->run_finish(stream, info); }
+  // Interp1D::interp_array through a device-output ring.
   ndi_status eval_ring(const void* q_, uint64_t nq, const ndi_ring_desc* ring, ndi_ring_consumer consume,
                        void* user, const ndi_eval_opts* opts, ndi_oob_info* info) override {
-    DeviceGuard dg(device);
-    ndi_eval_opts o{};
-    if (const ndi_status vs__ = take_opts(opts, o); vs__ != NDI_OK) return vs__;
-    hipStream_t s = (hipStream_t)o.stream;
-    uint64_t stride = 0;
-    ndi_status rs = check_ring_desc(ring, lanes, &stride);
-    if (rs != NDI_OK) return rs;
-    if (nq == 0) return NDI_OK;
-    if (!q_) return fail(NDI_BAD_ARG, "null query pointer");
-    Range rg("ndi_interp1d_eval_ring");
-    SpaceLease lease(spaces, s);
-    Workspace& ws = lease.ws;
-    const T* q = stage_queries(s, ws, q_, nq, o.q_memspace);
-    // range pre-pass over the whole batch: the first failing index is known before any chunk is handed out
-    enqueue_prepass(s, ws, q, nq);
-    RingRun R;
-    ring_begin(s, ws, q, nq, ring, stride, o, R);
-    NDI_HIP(hipStreamSynchronize(s));
-    const unsigned long long ff = ws.host_status->first_fail[0];
-    const uint64_t limit = ff == NO_FAIL ? nq : std::min<uint64_t>(nq, ff);
-    ring_produce(s, ws, q, limit, R, consume, user, o, 0, 0);
-    if (ff == NO_FAIL) return NDI_OK;
-    return report(q_, o.q_memspace, ff, 0, info);
+    return this->run_ring("ndi_interp1d_eval_ring", {(const T*)q_, nullptr}, nq, ring, consume, user, opts, info);
   }
 
   ndi_status trim() override {
     DeviceGuard dg(device);
-    spaces.trim();
-    std::lock_guard<std::mutex> g(ring_own.mu);
-    ring_own.clear();
+    this->trim_front();
     return NDI_OK;
   }
 
@@ -2661,7 +2376,7 @@ template <class T>
 static ndi_status bicubic_tables(const Interp2DImpl<T>& h, void* zx, void* zy, void* zxy, int memspace);
 
 template <class T>
-struct Interp2DImpl final : Interp2DBase {
+struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
   int mode = EX_NO;
   uint64_t nx = 0, ny = 0;
   DevicePyramid<T> px, py;
@@ -3539,161 +3254,41 @@ struct Interp2DImpl final : Interp2DBase {
     ps.done();
   }
 
-  void enqueue(hipStream_t s, Workspace& ws, const T* qx, const T* qy, uint64_t nq, T* out,
-               uint64_t out_stride, int path, int flags = 0) {
-    launch_eval(s, ws.sc[0], prep(s, ws.sc[0], qx, qy, nq, out, out_stride, path, false, flags));
+  // ---- what the host engine (float_host.hpp) takes from this family: x is array a, y is array b ---------------------
+  using Elem = T;
+  using Plan = Plan2;
+  static constexpr int query_arrays = 2;
+  static constexpr bool small_rows = true, ring = true;
+  static const char* axis_name(int axis) { return axis == 0 ? "x" : "y"; }
+  void range_limits(T lim[4]) const {
+    lim[0] = px.host_knots.front(); lim[1] = px.host_knots.back();
+    lim[2] = py.host_knots.front(); lim[3] = py.host_knots.back();
   }
-
-  ndi_status collect(hipStream_t s, Workspace& ws, uint64_t index_offset, ndi_oob_info* info) {
-    ws.ensure_status();
-    NDI_HIP(hipMemcpyAsync(ws.host_status, ws.sc[0].status.p, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
-    NDI_HIP(hipStreamSynchronize(s));
-    ws.pending = false;
-    const unsigned long long fx = ws.host_status->first_fail[0], fy = ws.host_status->first_fail[1];
-    if (fx == NO_FAIL && fy == NO_FAIL) return NDI_OK;
-    return report(ws.last_q, ws.last_q2, ws.last_q_space, fx, fy, index_offset, info);
+  Plan2 prep(hipStream_t s, Scratch& sc, Queries<T> q, uint64_t nq, T* out, uint64_t out_stride, int path,
+             bool beside_eval = false, int flags = 0) {
+    return prep(s, sc, q.a, q.b, nq, out, out_stride, path, beside_eval, flags);
   }
-
-  ndi_status report(const void* qx, const void* qy, int q_space, unsigned long long fx, unsigned long long fy,
-                    uint64_t index_offset, ndi_oob_info* info) {
-    // x is tested before y for the same query (bilinear.rs:71-80)
-    const int axis = (fx <= fy) ? 0 : 1;
-    const unsigned long long ff = axis == 0 ? fx : fy;
-    const void* src = axis == 0 ? qx : qy;
-    T v;
-    if (q_space == NDI_MEM_DEVICE)
-      NDI_HIP(hipMemcpy(&v, (const T*)src + ff, sizeof(T), hipMemcpyDeviceToHost));
-    else
-      v = ((const T*)src)[ff];
-    // without extrapolation every failure is a range failure (NaN included: "x = NaN is not in range");
-    // with it the only failure is the search meeting a NaN -- the query itself or an infinite query that the
-    // periodic wrap turned into NaN (the reference panics: vector_extensions.rs:83-84)
-    const ndi_status st = (mode != EX_NO) ? NDI_NAN_QUERY : NDI_OUT_OF_BOUNDS;
-    if (info) {
-      info->index = index_offset + ff;
-      info->value = (double)v;
-      info->axis = axis;
-      info->status = st;
-    }
-    if (st == NDI_NAN_QUERY) return fail(st, "failed to convert NaN to usize (query %llu)", index_offset + ff);
-    return fail(st, "%s = %.17g is not in range", axis == 0 ? "x" : "y", (double)v);
+  void enqueue(hipStream_t s, Workspace& ws, Queries<T> q, uint64_t nq, T* out, uint64_t out_stride, int path, int flags) {
+    launch_eval(s, ws.sc[0], prep(s, ws.sc[0], q.a, q.b, nq, out, out_stride, path, false, flags));
   }
-
-  void stage_queries(hipStream_t s, Workspace& ws, const void* qx_, const void* qy_, uint64_t nq, int q_space,
-                     const T** qx, const T** qy) {
-    *qx = (const T*)qx_;
-    *qy = (const T*)qy_;
-    if (q_space != NDI_MEM_HOST) return;
-    ws.qdev.reserve(nq * sizeof(T));
-    ws.qdev2.reserve(nq * sizeof(T));
-    NDI_HIP(hipMemcpyAsync(ws.qdev.p, qx_, nq * sizeof(T), hipMemcpyHostToDevice, s));
-    NDI_HIP(hipMemcpyAsync(ws.qdev2.p, qy_, nq * sizeof(T), hipMemcpyHostToDevice, s));
-    *qx = ws.qdev.as<T>();
-    *qy = ws.qdev2.as<T>();
-  }
-
-  // Range pre-pass over a whole batch (see Interp1DImpl::enqueue_prepass): first_fail[0] = x, [1] = y.
-  void enqueue_prepass(hipStream_t s, Workspace& ws, const T* qx, const T* qy, uint64_t nq) {
-    ws.ensure_status();
-    reset_status(ws.status.p, s);
-    StatusBlock* st = ws.status.as<StatusBlock>();
-    const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-    {
-      ProfScope ps(s, PC_LOCATE);
-      hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, qx, qy, nq, px.host_knots.front(),
-                         px.host_knots.back(), py.host_knots.front(), py.host_knots.back(), mode,
-                         &st->first_fail[0]);
-      NDI_HIP(hipGetLastError());
-      ps.done();
-    }
-    NDI_HIP(hipMemcpyAsync(ws.host_status, ws.status.p, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
-  }
-
-  // Host output with short trailing axes: one fused launch per chunk (see Interp1DImpl::eval_small_host).
-  ndi_status eval_small_host(hipStream_t s, Workspace& ws, const T* qx_dev, const T* qy_dev, const T* qx_orig,
-                             const T* qy_orig, int q_space, uint64_t nq, T* out, uint64_t out_stride,
-                             ndi_oob_info* info) {
-    const uint64_t row_bytes = lanes * sizeof(T);
-    const uint64_t chunk_q = std::max<uint64_t>(1, std::min<uint64_t>(nq, (64ull << 20) / row_bytes));
-    constexpr size_t BOUNCE = 8ull << 20;
-    ws.stage.reserve(chunk_q * row_bytes);
-    ws.ensure_status();
-    g_last_path.store(NDI_PATH_GATHER);
-    allow_dynamic_lds(reinterpret_cast<const void*>(&eval_small2d_kernel<T>), (int)LDS_STAGE_LIMIT);
-    StatusBlock* st = ws.sc[0].status.as<StatusBlock>();
-    const size_t shmem = (px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15;
-    for (uint64_t off = 0; off < nq; off += chunk_q) {
-      const uint64_t cq = std::min<uint64_t>(chunk_q, nq - off);
-      const size_t bytes = cq * row_bytes;
-      NDI_HIP(hipMemsetAsync(st, 0xFF, 2 * sizeof(unsigned long long), s));
-      EvalSmall2Args<T> A{};
-      A.px = px.view; A.py = py.view;
-      A.data = data.as<T>();
-      A.qx = qx_dev + off; A.qy = qy_dev + off;
-      A.out = ws.stage.as<T>();
-      A.nq = cq;
-      A.out_stride = lanes;
-      A.row_cells = pair_packed ? ny - 1 : ny;
-      A.cell_elems = pair_packed ? 2 * lanes : lanes;
-      A.lanes = (uint32_t)lanes;
-      A.mode = mode;
-      A.first_fail = &st->first_fail[0];
-      A.prechecked = 0;
-      const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((cq + BLOCK - 1) / BLOCK, 4096));
-      launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), shmem, eval_small2d_kernel<T>, A);
-      const bool bounce = bytes <= BOUNCE;
-      if (bounce) {
-        ws.ensure_pin(BOUNCE);
-        NDI_HIP(hipMemcpyAsync(ws.pin, ws.stage.p, bytes, hipMemcpyDeviceToHost, s));
-      }
-      NDI_HIP(hipMemcpyAsync(ws.host_status, st, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
-      NDI_HIP(hipStreamSynchronize(s));
-      const unsigned long long fx = ws.host_status->first_fail[0], fy = ws.host_status->first_fail[1];
-      const unsigned long long ff = std::min(fx, fy);
-      const uint64_t good = (ff == NO_FAIL) ? cq : (uint64_t)ff;
-      T* dst = out + off * out_stride;
-      if (good) {
-        if (bounce) {
-          if (out_stride == lanes) std::memcpy(dst, ws.pin, good * row_bytes);
-          else
-            for (uint64_t r = 0; r < good; ++r)
-              std::memcpy(dst + r * out_stride, (const char*)ws.pin + r * row_bytes, row_bytes);
-        } else {
-          NDI_HIP(hipMemcpy2D(dst, out_stride * sizeof(T), ws.stage.p, row_bytes, row_bytes, good,
-                              hipMemcpyDeviceToHost));
-        }
-      }
-      if (ff != NO_FAIL) return report(qx_orig + off, qy_orig + off, q_space, fx, fy, off, info);
-    }
-    return NDI_OK;
-  }
-
-  // Zero-copy small batches, host arrays in and out (see Interp1DImpl::eval_small_zero_copy).
-  static constexpr size_t ZERO_COPY_LIMIT = 1u << 20;
+  // the small-row paths (Bilinear only): both pyramids in LDS
+  size_t small_shmem() const { return (px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15; }
+  bool small_rows_fit() const { return !bicubic && lanes <= (uint64_t)SMALL_LANES && small_shmem() <= LDS_STAGE_LIMIT; }
   bool zero_copy_fits(uint64_t nq, int q_space, int out_space) const {
-    return !bicubic && q_space == NDI_MEM_HOST && out_space == NDI_MEM_HOST && lanes <= (uint64_t)SMALL_LANES &&
-           ((px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15) <= LDS_STAGE_LIMIT &&
+    return q_space == NDI_MEM_HOST && out_space == NDI_MEM_HOST && small_rows_fit() &&
            nq * (lanes + 2) * sizeof(T) <= ZERO_COPY_LIMIT;
   }
-  ndi_status eval_small_zero_copy(hipStream_t s, Workspace& ws, const T* qx_host, const T* qy_host, uint64_t nq,
-                                  T* out, uint64_t out_stride, ndi_oob_info* info) {
-    const size_t q_bytes = ((nq * sizeof(T)) + 255) & ~(size_t)255, row_bytes = lanes * sizeof(T);
-    ws.ensure_pin(std::max<size_t>(2 * q_bytes + nq * row_bytes, 8ull << 20));
-    ws.ensure_status();
-    T* pqx = reinterpret_cast<T*>(ws.pin);
-    T* pqy = reinterpret_cast<T*>((char*)ws.pin + q_bytes);
-    T* po = reinterpret_cast<T*>((char*)ws.pin + 2 * q_bytes);
-    std::memcpy(pqx, qx_host, nq * sizeof(T));
-    std::memcpy(pqy, qy_host, nq * sizeof(T));
+  void small_begin() {
     g_last_path.store(NDI_PATH_GATHER);
     allow_dynamic_lds(reinterpret_cast<const void*>(&eval_small2d_kernel<T>), (int)LDS_STAGE_LIMIT);
-    StatusBlock* st = ws.sc[0].status.as<StatusBlock>();
-    NDI_HIP(hipMemsetAsync(st, 0xFF, 2 * sizeof(unsigned long long), s));
+  }
+  // The fused search + evaluation launch of the small-row paths: nq packed rows into out, the kernel's own range test.
+  void launch_small(hipStream_t s, StatusBlock* st, Queries<T> q, T* out, uint64_t nq) {
     EvalSmall2Args<T> A{};
     A.px = px.view; A.py = py.view;
     A.data = data.as<T>();
-    A.qx = ws.pin_device<const T>(pqx); A.qy = ws.pin_device<const T>(pqy);
-    A.out = ws.pin_device<T>(po);
+    A.qx = q.a; A.qy = q.b;
+    A.out = out;
     A.nq = nq;
     A.out_stride = lanes;
     A.row_cells = pair_packed ? ny - 1 : ny;
@@ -3703,188 +3298,19 @@ struct Interp2DImpl final : Interp2DBase {
     A.first_fail = &st->first_fail[0];
     A.prechecked = 0;
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-    const size_t shmem = (px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15;
-    launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), shmem, eval_small2d_kernel<T>, A);
-    NDI_HIP(hipMemcpyAsync(ws.host_status, st, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
-    NDI_HIP(hipStreamSynchronize(s));
-    const unsigned long long fx = ws.host_status->first_fail[0], fy = ws.host_status->first_fail[1];
-    const unsigned long long ff = std::min(fx, fy);
-    const uint64_t good = (ff == NO_FAIL) ? nq : (uint64_t)ff;
-    if (good) {
-      if (out_stride == lanes) std::memcpy(out, po, good * row_bytes);
-      else
-        for (uint64_t r = 0; r < good; ++r) std::memcpy(out + r * out_stride, (const char*)po + r * row_bytes, row_bytes);
-    }
-    if (ff != NO_FAIL) return report(qx_host, qy_host, NDI_MEM_HOST, fx, fy, 0, info);
-    return NDI_OK;
-  }
-
-  ndi_status eval_body(hipStream_t s, Workspace& ws, const T* qx, const T* qy, const void* qx_orig,
-                       const void* qy_orig, int q_space, uint64_t nq, void* out_, uint64_t out_stride,
-                       const ndi_eval_opts& o, ndi_oob_info* info) {
-    ws.last_q = qx_orig;
-    ws.last_q2 = qy_orig;
-    ws.last_q_space = q_space;
-    ws.last_nq = nq;
-    if (o.out_memspace == NDI_MEM_DEVICE) {
-      enqueue(s, ws, qx, qy, nq, (T*)out_, out_stride, o.path, o.flags);
-      ws.pending = true;
-      if (o.async_launch) return NDI_OK;
-      return collect(s, ws, 0, info);
-    }
-    const uint64_t row_bytes = lanes * sizeof(T);
-    if (!bicubic && lanes <= (uint64_t)SMALL_LANES && ((px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15) <= LDS_STAGE_LIMIT)
-      return eval_small_host(s, ws, qx, qy, (const T*)qx_orig, (const T*)qy_orig, q_space, nq, (T*)out_, out_stride,
-                             info);
-    const uint64_t chunk_q = std::max<uint64_t>(1, std::min<uint64_t>(nq, (256ull << 20) / row_bytes));
-    ws.stage.reserve(chunk_q * row_bytes);
-    ws.ensure_status();
-    for (uint64_t off = 0; off < nq; off += chunk_q) {
-      const uint64_t cq = std::min<uint64_t>(chunk_q, nq - off);
-      enqueue(s, ws, qx + off, qy + off, cq, ws.stage.as<T>(), lanes, o.path);
-      NDI_HIP(hipMemcpyAsync(ws.host_status, ws.sc[0].status.p, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
-      NDI_HIP(hipStreamSynchronize(s));
-      const unsigned long long fx = ws.host_status->first_fail[0], fy = ws.host_status->first_fail[1];
-      const unsigned long long ff = std::min(fx, fy);
-      const uint64_t good = (ff == NO_FAIL) ? cq : (uint64_t)ff;
-      if (good)
-        NDI_HIP(hipMemcpy2D((T*)out_ + off * out_stride, out_stride * sizeof(T), ws.stage.p, row_bytes,
-                            row_bytes, good, hipMemcpyDeviceToHost));
-      if (ff != NO_FAIL)
-        return report((const T*)qx_orig + off, (const T*)qy_orig + off, q_space, fx, fy, off, info);
-    }
-    return NDI_OK;
+    launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), small_shmem(), eval_small2d_kernel<T>, A);
   }
 
   ndi_status eval(const void* qx_, const void* qy_, uint64_t nq, void* out_, uint64_t out_stride,
                   const ndi_eval_opts* opts, ndi_oob_info* info) override {
-    DeviceGuard dg(device);
-    Range rg("ndi_interp2d_eval");
-    ndi_eval_opts o{};
-    if (const ndi_status vs__ = take_opts(opts, o); vs__ != NDI_OK) return vs__;
-    hipStream_t s = (hipStream_t)o.stream;  // NULL = the HIP default stream
-    if (out_stride < lanes) return fail(NDI_BAD_ARG, "out_row_stride (%llu) < lanes (%llu)",
-                                        (unsigned long long)out_stride, (unsigned long long)lanes);
-    if (nq == 0) return NDI_OK;
-    if (!qx_ || !qy_ || !out_) return fail(NDI_BAD_ARG, "null query / output pointer");
-    SpaceLease lease(spaces, s);
-    Workspace& ws = lease.ws;
-    if (zero_copy_fits(nq, o.q_memspace, o.out_memspace))
-      return eval_small_zero_copy(s, ws, (const T*)qx_, (const T*)qy_, nq, (T*)out_, out_stride, info);
-    const T *qx, *qy;
-    stage_queries(s, ws, qx_, qy_, nq, o.q_memspace, &qx, &qy);
-    return eval_body(s, ws, qx, qy, qx_, qy_, o.q_memspace, nq, out_, out_stride, o, info);
+    return this->run_eval("ndi_interp2d_eval", {(const T*)qx_, (const T*)qy_}, nq, out_, out_stride, opts, info);
   }
-
-  ndi_status finish(void* stream, ndi_oob_info* info) override {
-    DeviceGuard dg(device);
-    hipStream_t s = (hipStream_t)stream;
-    SpaceLease lease(spaces, s);
-    Workspace& ws = lease.ws;
-    if (!ws.pending) {
-      NDI_HIP(hipStreamSynchronize(s));
-      return NDI_OK;
-    }
-    return collect(s, ws, 0, info);
-  }
-
-  // ---- ring evaluation (see Interp1DImpl) ---------------------------------------------------
-  struct RingRun {
-    std::unique_lock<std::mutex> own;
-    std::vector<void*> slots;
-    uint64_t pitch = 0, chunk = 0, cq0 = 0;
-    uint32_t n_slots = 0;
-    Plan2 plan0;
-    hipStream_t side = nullptr;
-  };
-
-  void ring_begin(hipStream_t s, Workspace& ws, const T* qx, const T* qy, uint64_t nq, const ndi_ring_desc* ring,
-                  uint64_t stride, const ndi_eval_opts& o, RingRun& R) {
-    R.n_slots = ring->n_slots;
-    R.chunk = ring->chunk_queries;
-    R.slots.resize(ring->n_slots);
-    R.pitch = stride;
-    if (ring->slots) {
-      for (uint32_t i = 0; i < ring->n_slots; ++i) R.slots[i] = ring->slots[i];
-    } else {
-      R.own = std::unique_lock<std::mutex>(ring_own.mu);
-      ring_own.ensure(ring->n_slots, ring->chunk_queries, stride * sizeof(T));
-      for (uint32_t i = 0; i < ring->n_slots; ++i) R.slots[i] = (char*)ring_own.buf.p + (size_t)i * stride * sizeof(T);
-      R.pitch = (uint64_t)ring->n_slots * stride;
-    }
-    R.side = ring_overlap() ? ws.side_stream() : s;
-    for (Scratch& sc : ws.sc) sc.ensure_events();
-    NDI_HIP(hipEventRecord(ws.order_event(), s));
-    NDI_HIP(hipStreamWaitEvent(R.side, ws.order_event(), 0));
-    R.cq0 = std::min<uint64_t>(R.chunk, nq);
-    R.plan0 = prep(R.side, ws.sc[0], qx, qy, R.cq0, (T*)R.slots[0], R.pitch, o.path);
-    NDI_HIP(hipEventRecord(ws.sc[0].prep_done, R.side));
-  }
-
-  void ring_produce(hipStream_t s, Workspace& ws, const T* qx, const T* qy, uint64_t limit, RingRun& R,
-                    ndi_ring_consumer consume, void* user, const ndi_eval_opts& o, uint64_t q_offset,
-                    uint32_t shard) {
-    std::vector<hipEvent_t> busy(R.n_slots, nullptr);
-    uint64_t k = 0;
-    for (uint64_t off = 0; off < limit; off += R.chunk, ++k) {
-      const uint64_t cq = std::min<uint64_t>(R.chunk, limit - off);
-      const uint32_t slot = (uint32_t)(k % R.n_slots);
-      Scratch& sc = ws.sc[k & 1];
-      Plan2 P = R.plan0;
-      if (k > 0) {
-        if (k >= 2) NDI_HIP(hipStreamWaitEvent(R.side, sc.eval_done, 0));
-        P = prep(R.side, sc, qx + off, qy + off, cq, (T*)R.slots[slot], R.pitch, o.path, R.side != s);
-        NDI_HIP(hipEventRecord(sc.prep_done, R.side));
-      }
-      NDI_HIP(hipStreamWaitEvent(s, sc.prep_done, 0));
-      if (busy[slot]) {
-        NDI_HIP(hipStreamWaitEvent(s, busy[slot], 0));
-        busy[slot] = nullptr;
-      }
-      launch_eval(s, sc, P);
-      NDI_HIP(hipEventRecord(sc.eval_done, s));
-      if (consume) {
-        ndi_ring_chunk c{};
-        c.index = k; c.q_begin = q_offset + off; c.q_count = cq; c.out = R.slots[slot]; c.row_stride = R.pitch;
-        c.slot = slot; c.shard = shard; c.stream = (void*)s;
-        busy[slot] = (hipEvent_t)consume(user, &c);
-      }
-    }
-    NDI_HIP(hipStreamSynchronize(s));
-    NDI_HIP(hipStreamSynchronize(R.side));
-    for (hipEvent_t e : busy)
-      if (e) NDI_HIP(hipEventSynchronize(e));
-    ws.pending = false;
-  }
-
-  // Interp2D::interp_array through a device-output ring (see Interp1DImpl::eval_ring).
+  ndi_status finish(void* stream, ndi_oob_info* info) override { return this->run_finish(stream, info); }
+  // Interp2D::interp_array through a device-output ring.
   ndi_status eval_ring(const void* qx_, const void* qy_, uint64_t nq, const ndi_ring_desc* ring,
                        ndi_ring_consumer consume, void* user, const ndi_eval_opts* opts,
                        ndi_oob_info* info) override {
-    DeviceGuard dg(device);
-    ndi_eval_opts o{};
-    if (const ndi_status vs__ = take_opts(opts, o); vs__ != NDI_OK) return vs__;
-    hipStream_t s = (hipStream_t)o.stream;
-    uint64_t stride = 0;
-    ndi_status rs = check_ring_desc(ring, lanes, &stride);
-    if (rs != NDI_OK) return rs;
-    if (nq == 0) return NDI_OK;
-    if (!qx_ || !qy_) return fail(NDI_BAD_ARG, "null query pointer");
-    Range rg("ndi_interp2d_eval_ring");
-    SpaceLease lease(spaces, s);
-    Workspace& ws = lease.ws;
-    const T *qx, *qy;
-    stage_queries(s, ws, qx_, qy_, nq, o.q_memspace, &qx, &qy);
-    enqueue_prepass(s, ws, qx, qy, nq);
-    RingRun R;
-    ring_begin(s, ws, qx, qy, nq, ring, stride, o, R);
-    NDI_HIP(hipStreamSynchronize(s));
-    const unsigned long long fx = ws.host_status->first_fail[0], fy = ws.host_status->first_fail[1];
-    const unsigned long long ff = std::min(fx, fy);
-    const uint64_t limit = ff == NO_FAIL ? nq : std::min<uint64_t>(nq, ff);
-    ring_produce(s, ws, qx, qy, limit, R, consume, user, o, 0, 0);
-    if (ff == NO_FAIL) return NDI_OK;
-    return report(qx_, qy_, o.q_memspace, fx, fy, 0, info);
+    return this->run_ring("ndi_interp2d_eval_ring", {(const T*)qx_, (const T*)qy_}, nq, ring, consume, user, opts, info);
   }
 
   // A replica on another (or the same) device (see Interp1DImpl::clone_to): the grid is copied device to device in
@@ -3980,11 +3406,7 @@ struct Interp2DImpl final : Interp2DBase {
 
   ndi_status trim() override {
     DeviceGuard dg(device);
-    spaces.trim();
-    {
-      std::lock_guard<std::mutex> g(ring_own.mu);
-      ring_own.clear();
-    }
+    this->trim_front();
     {   // the slope-record copy (up to 256 MiB) goes too when it is complete and idle; the next batch that wants it rebuilds it
       std::lock_guard<std::mutex> g(slopes_mu);
       int st = slopes_state.load(std::memory_order_acquire);
@@ -4364,34 +3786,39 @@ struct ShardCall {
   ndi_eval_opts o;
 };
 
-template <class T>
-struct Job1 : ShardCall {
-  std::vector<Interp1DImpl<T>*> H;
-  explicit Job1(const ShardCall& c) : ShardCall(c) {}
-  const void* q_src(uint32_t i, uint32_t n) const {
-    return (io && io[i].q) ? io[i].q : (const void*)((const T*)qx + shard_lo(nq, i, n));
+// The f32 / f64 handles (Impl: a FloatEngine, float_host.hpp): a shard's query arrays are the caller's per-shard
+// pointers, or its block of the whole batch.
+template <class Impl>
+struct Job : ShardCall {
+  using T = typename Impl::Elem;
+  std::vector<Impl*> H;
+  explicit Job(const ShardCall& c) : ShardCall(c) {}
+  Queries<T> q_src(uint32_t i, uint32_t n) const {
+    constexpr bool two = Impl::query_arrays == 2;
+    if (io && io[i].q) return {(const T*)io[i].q, two ? (const T*)io[i].qy : nullptr};
+    return Queries<T>{(const T*)qx, two ? (const T*)qy : nullptr} + shard_lo(nq, i, n);
   }
 };
 
-template <class T>
-struct Shard1 {
-  const Job1<T>& J;
+template <class Impl>
+struct Shard {
+  using T = typename Impl::Elem;
+  const Job<Impl>& J;
   uint32_t i;
-  Interp1DImpl<T>* h;
+  Impl* h;
   uint64_t lo, cnt;
   DeviceGuard dg;
   hipStream_t s;
   SpaceLease lease;
   Workspace& ws;
-  const void* q_src;
-  const T* q = nullptr;
+  Queries<T> q_src, q;
   uint64_t stride = 0;
-  typename Interp1DImpl<T>::RingRun R;
-  Shard1(const Job1<T>& j, uint32_t i_, uint32_t n)
+  RingRun<typename Impl::Plan> R;
+  Shard(const Job<Impl>& j, uint32_t i_, uint32_t n)
       : J(j), i(i_), h(j.H[i_]), lo(shard_lo(j.nq, i_, n)), cnt(shard_lo(j.nq, i_ + 1, n) - shard_lo(j.nq, i_, n)),
         dg(h->device), s((hipStream_t)(j.io ? j.io[i_].stream : nullptr)), lease(h->spaces, s), ws(lease.ws),
         q_src(j.q_src(i_, n)) {}
-  void pre(unsigned long long* fx, unsigned long long*) {
+  void pre(unsigned long long* fx, unsigned long long* fy) {
     if (!cnt) return;
     q = h->stage_queries(s, ws, q_src, cnt, J.o.q_memspace);
     h->enqueue_prepass(s, ws, q, cnt);
@@ -4400,7 +3827,9 @@ struct Shard1 {
       h->ring_begin(s, ws, q, cnt, &J.rings[i], stride, J.o, R);
     }
     NDI_HIP(hipStreamSynchronize(s));
-    *fx = ws.host_status->first_fail[0];
+    const FirstFail f = FirstFail::of(ws, q);
+    *fx = f.f0;
+    *fy = f.f1;
   }
   ndi_status run(uint64_t limit) {
     if (!cnt) return NDI_OK;
@@ -4413,64 +3842,6 @@ struct Shard1 {
     o.async_launch = 0;
     ndi_oob_info none{};
     return h->eval_body(s, ws, q, q_src, J.o.q_memspace, limit, J.io[i].out, J.out_stride, o, &none);
-  }
-};
-
-template <class T>
-struct Job2 : ShardCall {
-  std::vector<Interp2DImpl<T>*> H;
-  explicit Job2(const ShardCall& c) : ShardCall(c) {}
-  const void* qx_src(uint32_t i, uint32_t n) const {
-    return (io && io[i].q) ? io[i].q : (const void*)((const T*)qx + shard_lo(nq, i, n));
-  }
-  const void* qy_src(uint32_t i, uint32_t n) const {
-    return (io && io[i].q) ? io[i].qy : (const void*)((const T*)qy + shard_lo(nq, i, n));
-  }
-};
-
-template <class T>
-struct Shard2 {
-  const Job2<T>& J;
-  uint32_t i;
-  Interp2DImpl<T>* h;
-  uint64_t lo, cnt;
-  DeviceGuard dg;
-  hipStream_t s;
-  SpaceLease lease;
-  Workspace& ws;
-  const void* qx_src;
-  const void* qy_src;
-  const T* qx = nullptr;
-  const T* qy = nullptr;
-  uint64_t stride = 0;
-  typename Interp2DImpl<T>::RingRun R;
-  Shard2(const Job2<T>& j, uint32_t i_, uint32_t n)
-      : J(j), i(i_), h(j.H[i_]), lo(shard_lo(j.nq, i_, n)), cnt(shard_lo(j.nq, i_ + 1, n) - shard_lo(j.nq, i_, n)),
-        dg(h->device), s((hipStream_t)(j.io ? j.io[i_].stream : nullptr)), lease(h->spaces, s), ws(lease.ws),
-        qx_src(j.qx_src(i_, n)), qy_src(j.qy_src(i_, n)) {}
-  void pre(unsigned long long* fx, unsigned long long* fy) {
-    if (!cnt) return;
-    h->stage_queries(s, ws, qx_src, qy_src, cnt, J.o.q_memspace, &qx, &qy);
-    h->enqueue_prepass(s, ws, qx, qy, cnt);
-    if (J.rings) {
-      (void)check_ring_desc(&J.rings[i], h->lanes, &stride);
-      h->ring_begin(s, ws, qx, qy, cnt, &J.rings[i], stride, J.o, R);
-    }
-    NDI_HIP(hipStreamSynchronize(s));
-    *fx = ws.host_status->first_fail[0];
-    *fy = ws.host_status->first_fail[1];
-  }
-  ndi_status run(uint64_t limit) {
-    if (!cnt) return NDI_OK;
-    if (J.rings) {
-      h->ring_produce(s, ws, qx, qy, limit, R, J.consume, J.user, J.o, lo, i);
-      return NDI_OK;
-    }
-    if (!limit) return NDI_OK;
-    ndi_eval_opts o = J.o;
-    o.async_launch = 0;
-    ndi_oob_info none{};
-    return h->eval_body(s, ws, qx, qy, qx_src, qy_src, J.o.q_memspace, limit, J.io[i].out, J.out_stride, o, &none);
   }
 };
 
@@ -4490,8 +3861,8 @@ static uint32_t shard_owner(uint64_t nq, uint32_t n, uint64_t index) {
   return n - 1;
 }
 
-template <class T>
-static ndi_status sharded1d(Job1<T>& J, ndi_oob_info* info) {
+template <class Impl>
+static ndi_status sharded_float(Job<Impl>& J, ndi_oob_info* info) {
   ShardedCallScope scope;
   if (scope.nested)
     return fail(NDI_BAD_ARG, "nested sharded call: this host thread is inside a sharded evaluation (e.g. its ring "
@@ -4499,25 +3870,7 @@ static ndi_status sharded1d(Job1<T>& J, ndi_oob_info* info) {
   const uint32_t n = (uint32_t)J.H.size();
   std::vector<ShardOutcome> out(n);
   unsigned long long F[2];
-  run_shards<Shard1<T>>(J, n, out, F);
-  ndi_status st = shards_failed(out);
-  if (st != NDI_OK || F[0] == NO_FAIL) return st;
-  const uint32_t w = shard_owner(J.nq, n, F[0]);
-  const uint64_t lo = shard_lo(J.nq, w, n);
-  DeviceGuard dg(J.H[w]->device);
-  return J.H[w]->report(J.q_src(w, n), J.o.q_memspace, F[0] - lo, lo, info);
-}
-
-template <class T>
-static ndi_status sharded2d(Job2<T>& J, ndi_oob_info* info) {
-  ShardedCallScope scope;
-  if (scope.nested)
-    return fail(NDI_BAD_ARG, "nested sharded call: this host thread is inside a sharded evaluation (e.g. its ring "
-                "consumer); issue the inner call from another thread");
-  const uint32_t n = (uint32_t)J.H.size();
-  std::vector<ShardOutcome> out(n);
-  unsigned long long F[2];
-  run_shards<Shard2<T>>(J, n, out, F);
+  run_shards<Shard<Impl>>(J, n, out, F);
   ndi_status st = shards_failed(out);
   const unsigned long long f = std::min(F[0], F[1]);
   if (st != NDI_OK || f == NO_FAIL) return st;
@@ -4525,8 +3878,8 @@ static ndi_status sharded2d(Job2<T>& J, ndi_oob_info* info) {
   const uint64_t lo = shard_lo(J.nq, w, n);
   DeviceGuard dg(J.H[w]->device);
   // indices relative to the owner's block; an axis whose first failure lies in a later shard stays larger
-  const unsigned long long lx = F[0] == NO_FAIL ? NO_FAIL : F[0] - lo, ly = F[1] == NO_FAIL ? NO_FAIL : F[1] - lo;
-  return J.H[w]->report(J.qx_src(w, n), J.qy_src(w, n), J.o.q_memspace, lx, ly, lo, info);
+  const FirstFail rel{F[0] == NO_FAIL ? NO_FAIL : F[0] - lo, F[1] == NO_FAIL ? NO_FAIL : F[1] - lo};
+  return J.H[w]->report(J.q_src(w, n), J.o.q_memspace, rel, lo, info);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4998,6 +4351,14 @@ static ndi_status sharded_narrow_call(const Handle* const* handles, uint32_t n, 
   return ndi::sharded_narrow(std::vector<ndi::NarrowEngine<typename Impl::Elem>*>(H.begin(), H.end()), c, info);
 }
 
+// One sharded call of f32 / f64 handles whose implementation is Impl, a FloatEngine.
+template <class Impl, class Handle>
+static ndi_status sharded_float_call(const Handle* const* handles, uint32_t n, const ndi::ShardCall& c, ndi_oob_info* info) {
+  ndi::Job<Impl> J(c);
+  const ndi_status st = gather_handles(handles, n, handles[0]->impl->dtype, J.H);
+  return st != NDI_OK ? st : ndi::sharded_float(J, info);
+}
+
 // The element type of a sharded call is the first handle's (gather_handles holds the others to it).
 static ndi_status sharded_call(const ndi_interp1d* const* handles, uint32_t n, const ndi::ShardCall& c,
                                ndi_oob_info* info) {
@@ -5018,15 +4379,9 @@ static ndi_status sharded_call(const ndi_interp1d* const* handles, uint32_t n, c
     case NDI_I64: return sharded_narrow_call<ndi::Interp1DIntImpl<int64_t>>(handles, n, c, info);
     case NDI_F16: return sharded_narrow_call<ndi::Interp1DHalfImpl<ndi::HF_F16>>(handles, n, c, info);
     case NDI_BF16: return sharded_narrow_call<ndi::Interp1DHalfImpl<ndi::HF_BF16>>(handles, n, c, info);
-    case NDI_F32: {
-      ndi::Job1<float> J(c);
-      const ndi_status st = gather_handles(handles, n, dtype, J.H);
-      return st != NDI_OK ? st : ndi::sharded1d<float>(J, info);
-    }
+    case NDI_F32: return sharded_float_call<ndi::Interp1DImpl<float>>(handles, n, c, info);
   }
-  ndi::Job1<double> J(c);
-  const ndi_status st = gather_handles(handles, n, dtype, J.H);
-  return st != NDI_OK ? st : ndi::sharded1d<double>(J, info);
+  return sharded_float_call<ndi::Interp1DImpl<double>>(handles, n, c, info);
 }
 
 static ndi_status sharded_call(const ndi_interp2d* const* handles, uint32_t n, const ndi::ShardCall& c,
@@ -5039,15 +4394,9 @@ static ndi_status sharded_call(const ndi_interp2d* const* handles, uint32_t n, c
     case NDI_I64: return sharded_narrow_call<ndi::Interp2DIntImpl<int64_t>>(handles, n, c, info);
     case NDI_F16: return sharded_narrow_call<ndi::Interp2DHalfImpl<ndi::HF_F16>>(handles, n, c, info);
     case NDI_BF16: return sharded_narrow_call<ndi::Interp2DHalfImpl<ndi::HF_BF16>>(handles, n, c, info);
-    case NDI_F32: {
-      ndi::Job2<float> J(c);
-      const ndi_status st = gather_handles(handles, n, dtype, J.H);
-      return st != NDI_OK ? st : ndi::sharded2d<float>(J, info);
-    }
+    case NDI_F32: return sharded_float_call<ndi::Interp2DImpl<float>>(handles, n, c, info);
   }
-  ndi::Job2<double> J(c);
-  const ndi_status st = gather_handles(handles, n, dtype, J.H);
-  return st != NDI_OK ? st : ndi::sharded2d<double>(J, info);
+  return sharded_float_call<ndi::Interp2DImpl<double>>(handles, n, c, info);
 }
 
 NDI_API ndi_status ndi_interp1d_eval_sharded(const ndi_interp1d* const* handles, uint32_t n_shards, const void* q,
