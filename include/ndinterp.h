@@ -274,9 +274,43 @@ typedef struct ndi_interp2d_desc {
  *  flags, the ring and sharded calls, _trim, _clone (the table is copied, the orders kept), _tables (the origin's zx, zy,
  *  zxy) and the refusal of NDI_PATH_BUCKETED / _probe_ceiling are the Bicubic handle's, unchanged.  The orders are part of
  *  the replica signature: a sharded set that mixes a surface with its partial, or two different partials, is refused.
- * Not provided: periodic and per-lane boundaries, Pchip / Akima node derivatives, integral handles, third derivatives, a
- * fused value-and-gradient call, a tile-grouped evaluation form, a blocked-sweep build for narrow grids, half and integer
- * element types. */
+ * Integrals (ndi_interp2d_antiderivative, ndi_interp2d_integral): a handle that evaluates
+ *     F(qx, qy) = the integral of the surface over [x[0], qx] x [y[0], qy]
+ * and rectangle integrals through it -- scipy's RectBivariateSpline.integral(xa, xb, ya, yb).  The antiderivative of a
+ * tensor-product Hermite cubic is the tensor product of ndi_interp1d_antiderivative's rule with itself.  Every line is one
+ * IEEE operation in T, in this order, nothing fused.  G is that rule's cubic-class G in Hermite form; d, a, b are H's lines:
+ *     G(pl, pr, kl, kr, h, s):  d = pr - pl;  a = kl h - d;  b = d - kr h;
+ *                               c1 = (d + a) * 0.5;  c2 = (b - (a + a)) / 3;  c3 = (b - a) * 0.25
+ *                               s * (pl + s * (c1 + s * (c2 - s * c3)))
+ *     the integral over the whole interval:  I = h * (pl + (c1 + (c2 - c3)))
+ *  prefix_axis(knots, p, k): ndi_interp1d_antiderivative's FIXED blocked sum with B = 256 along one axis over the I of the
+ *  Hermite data (values p, slopes k) -- the same S / T / O / P recurrences, bits that do not depend on launch geometry.
+ *  Five prefix tables of the grid's shape, from the node table {z, zx, zy, zxy}:
+ *     Qz  = prefix along x of (values z,  slopes zx)        Pz  = prefix along y of (values z,  slopes zy)
+ *     Qzy = prefix along x of (values zy, slopes zxy)       Pzx = prefix along y of (values zx, slopes zxy)
+ *     PP  = prefix along x of (values Pz, slopes Pzx)
+ *  (PP along y of (Qz, Qzy) is the same number and other bits: the contract is x of (Pz, Pzx).)
+ *  Evaluation: cell i, j and t, u, hx, hy exactly Bicubic's; per lane
+ *     w0 = Pz [i]  [j] + hy * G(z [i]  [j], z [i]  [j+1], zy [i]  [j], zy [i]  [j+1], hy, u)
+ *     w1 = Pz [i+1][j] + hy * G(z [i+1][j], z [i+1][j+1], zy [i+1][j], zy [i+1][j+1], hy, u)
+ *     v0 = Pzx[i]  [j] + hy * G(zx[i]  [j], zx[i]  [j+1], zxy[i]  [j], zxy[i]  [j+1], hy, u)
+ *     v1 = Pzx[i+1][j] + hy * G(zx[i+1][j], zx[i+1][j+1], zxy[i+1][j], zxy[i+1][j+1], hy, u)
+ *     e  = PP [i]  [j] + hy * G(Qz[i][j], Qz[i][j+1], Qzy[i][j], Qzy[i][j+1], hy, u)
+ *     F  = e + hx * G(w0, w1, v0, v1, hx, t)
+ *  25 operands per output element.  `extrapolate` continues the end cell's form with t / u outside [0, 1]; a query on an
+ *  interior grid line takes the cell to its right / above.  The rectangle integral is, in ONE evaluation launch,
+ *     out = (F(xb, yb) - F(xa, yb)) - (F(xb, ya) - F(xa, ya))
+ *  in this association: xa == xb or ya == yb gives exactly 0; xa > xb or ya > yb negates, as scipy does.
+ *  The integral handle SHARES its source's node table (no copy; freed with the last handle that holds it, in any order of
+ *  the destroy calls) and owns the five prefix tables (five times the grid) and its two knot axes.  Through
+ *  ndi_interp2d_eval it is a Bicubic handle: range, NaN, first-error and rows-before-the-error semantics, the eval flags,
+ *  async_launch / _finish, the ring and sharded calls, _trim, _clone (the tables are copied, the flag kept), _tables (the
+ *  origin's zx, zy, zxy) and the refusal of NDI_PATH_BUCKETED / _probe_ceiling are unchanged.  The integral bit is part
+ *  of the replica signature: a sharded set that mixes a surface with its integral is refused.
+ * Not provided: periodic and per-lane boundaries, Pchip / Akima node derivatives, integrals of Bilinear or of partial
+ * handles, partials of an integral handle, a second antiderivative, a ring / sharded / async_launch form of the four-array
+ * rectangle call, third derivatives, a fused value-and-gradient call, a tile-grouped evaluation form, a blocked-sweep
+ * build for narrow grids, half and integer element types. */
 typedef struct ndi_interp1d ndi_interp1d; /* owns device copies of x, data (and a, b) */
 typedef struct ndi_interp2d ndi_interp2d;
 
@@ -351,6 +385,29 @@ ndi_status ndi_interp2d_tables(const ndi_interp2d* h, void* zx, void* zy, void* 
  * an order below 0 or summing above 2, (0, 0), a null `h` or `out`.  The new handle shares `h`'s node table and has its
  * knots, `extrapolate` and device; either may be destroyed first.  A new symbol: no new enumerator, no struct change. */
 ndi_status ndi_interp2d_partial(const ndi_interp2d* h, int32_t nu_x, int32_t nu_y, ndi_interp2d** out);
+/* A new handle that evaluates F, the integral of `h`'s surface from (x[0], y[0]) (contract above ndi_interp1d): the 2-D
+ * counterpart of ndi_interp1d_antiderivative.  `h`: a Bicubic surface handle.  NDI_BAD_ARG, with *out cleared first and a
+ * message naming the strategy and the reason, decided before any device work: a Bilinear handle, a partial handle, an
+ * integral handle, a null `h` or `out`.  The new handle shares `h`'s node table, owns its five prefix tables (built on the
+ * NULL stream, complete on return) and has `h`'s knots, `extrapolate` and device; either may be destroyed first.
+ * ndi_interp2d_partial of an integral handle is NDI_BAD_ARG (its x-derivative is a y-integral, which is not provided).
+ * New symbols: no new enumerator, no struct change. */
+ndi_status ndi_interp2d_antiderivative(const ndi_interp2d* h, ndi_interp2d** out);
+/* Rectangle integrals through an integral handle (scipy: .integral(xa, xb, ya, yb)): out[q][l] = the integral of lane l
+ * over [xa[q], xb[q]] x [ya[q], yb[q]], four searches, four F and three subtractions in ONE evaluation launch.  `h` must be
+ * an integral handle (anything else: NDI_BAD_ARG).  Host or device bounds and outputs (ndi_eval_opts), strided rows.
+ * Errors: the lowest failing flat index wins; within a query the order is xa, xb, ya, yb; info->axis is 0 for an x bound
+ * and 1 for a y bound, info->value the offending bound; rows before the failing index are written, later rows untouched
+ * (NDI_EVAL_FRESH_OUTPUT and NDI_EVAL_ROWS_AFTER_ERROR_UNSPECIFIED are honoured); NDI_NAN_QUERY by Bilinear's rule.
+ * NDI_PATH_BUCKETED is NDI_BAD_ARG.  async_launch != 0 is NDI_UNSUPPORTED: the call completes before it returns (the four
+ * bounds do not fit the two-array record ndi_interp2d_finish reports from). */
+ndi_status ndi_interp2d_integral(const ndi_interp2d* h, const void* xa, const void* xb, const void* ya, const void* yb,
+                                 uint64_t nq, void* out, uint64_t out_row_stride, const ndi_eval_opts* opts,
+                                 ndi_oob_info* info);
+/* The five prefix tables of an integral handle as plain T[nx][ny][lanes] arrays, whatever the internal layout (any of them
+ * may be NULL): the counterpart of ndi_interp2d_tables.  NDI_BAD_ARG for any handle that is not an integral handle. */
+ndi_status ndi_interp2d_integral_tables(const ndi_interp2d* h, void* pp, void* qz, void* qzy, void* pz, void* pzx,
+                                        int32_t memspace);
 void ndi_interp2d_destroy(ndi_interp2d* h);
 
 /* A replica of a built interpolator on `device` (any device, the handle's own included): the device-resident knots /

@@ -8,6 +8,77 @@
 // and first_fail[0], hi into set 1 and first_fail[1]) and the same single evaluation launch with the pair flag.
 // Staging, the first-error report, the host-output chunk loop and finish are the float host engine's (float_host.hpp).
 
+// ---- the prefix table P[n][lanes] of the tables y (a, b) on the device-resident knots x (NULL stream, complete on return).
+// The 2-D integral build (bicubic_integral_host.hpp) runs it on views of its grids.
+template <class T, bool LINEAR>
+static void antideriv_prefix_build(int device, uint64_t n, uint64_t lanes, const T* y, const T* a, const T* b, const T* x, T* P) {
+  AntiBuildArgs<T> A{};
+  A.y = y; A.a = a; A.b = b; A.x = x; A.P = P;
+  A.n = n; A.lanes = lanes;
+  A.nblk = (n + AD_B - 1) / AD_B;
+  A.single = A.nblk == 1 ? 1u : 0u;
+  DevBuf tmp;
+  if (!A.single) {   // the block totals: kept per host thread like the spline build's temporaries
+    const size_t tb = (size_t)A.nblk * lanes * sizeof(T);
+    if (tb <= ((size_t)64 << 20)) A.tot = static_cast<T*>(build_scratch().device_buf(device, tb));
+    else {
+      tmp.reserve(tb);
+      A.tot = tmp.as<T>();
+    }
+  }
+  constexpr int VN = Wide<T>::N;
+  const hipStream_t s0 = nullptr;
+  const bool vec = lanes % VN == 0 && aligned16(A.y) && aligned16(A.a) && aligned16(A.b) && aligned16(A.P) && aligned16(A.tot);
+  const bool staged = lanes <= AD_STAGED_LANES;
+  const bool fuse = A.nblk <= AD_FUSE_BLOCKS;
+  bool vec_local = false;
+  unsigned local_grid = 0;
+  if (staged) {
+    // chains per workgroup: as many blocks as AD_STAGED_CHAINS allows, halved while the grid would leave the chip's
+    // 2048 resident workgroups unused (phase 2 takes the same time for one chain as for 32)
+    uint32_t kb = std::max<uint32_t>(1, AD_STAGED_CHAINS / (uint32_t)lanes);
+    while (kb > 1 && (A.nblk + kb - 1) / kb < 2048) kb /= 2;
+    A.kb = kb;
+    const size_t lds = (size_t)kb * (AD_B * lanes + lanes) * sizeof(T);
+    const unsigned grid = local_grid = (unsigned)std::min<uint64_t>((A.nblk + kb - 1) / kb, 1u << 16);
+    allow_dynamic_lds(reinterpret_cast<const void*>(&antideriv_local_staged_kernel<T, LINEAR>), 96 * 1024);
+    hipLaunchKernelGGL((antideriv_local_staged_kernel<T, LINEAR>), dim3(grid), dim3(BLOCK), lds, s0, A);
+  } else {
+    // every thread is a 256-step chain, so the threads are what hides the latency: 16-byte vectors only where they
+    // still leave the chip a full set of waves (4096 x 4096 has 65536 chains: one lane each, 4-8 byte coalesced loads)
+    vec_local = vec && A.nblk * (lanes / VN) >= (uint64_t)cu_count() * 8 * 64;
+    const uint64_t total = A.nblk * (vec_local ? lanes / VN : lanes);
+    const unsigned grid = local_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + BLOCK - 1) / BLOCK, 1u << 20));
+    if (vec_local) hipLaunchKernelGGL((antideriv_local_lanes_kernel<T, VN, LINEAR>), dim3(grid), dim3(BLOCK), 0, s0, A);
+    else hipLaunchKernelGGL((antideriv_local_lanes_kernel<T, 1, LINEAR>), dim3(grid), dim3(BLOCK), 0, s0, A);
+  }
+  NDI_HIP(hipGetLastError());
+  if (std::getenv("NDI_TRACE_PLAN"))   // grid: the local kernel's; kb / vec_local: 0 on the local kernel that has no such field
+    std::fprintf(stderr, "[ndi plan] antiderivative build linear=%d staged=%d kb=%u vec=%d vec_local=%d nblk=%llu single=%d fuse=%d "
+                 "grid=%u\n", (int)LINEAR, (int)staged, A.kb, (int)vec, (int)vec_local, (unsigned long long)A.nblk, (int)A.single,
+                 (int)(!A.single && fuse), local_grid);
+  if (!A.single) {
+    if (!fuse) {
+      if (staged) {
+        const unsigned grid = (unsigned)((lanes * 64 + BLOCK - 1) / BLOCK);
+        hipLaunchKernelGGL((antideriv_offsets_kernel<T, true>), dim3(grid), dim3(BLOCK), 0, s0, A.tot, A.nblk, (n - 1) / AD_B, lanes);
+      } else {
+        const unsigned grid = (unsigned)((lanes + BLOCK - 1) / BLOCK);
+        hipLaunchKernelGGL((antideriv_offsets_kernel<T, false>), dim3(grid), dim3(BLOCK), 0, s0, A.tot, A.nblk, (n - 1) / AD_B, lanes);
+      }
+      NDI_HIP(hipGetLastError());
+    }
+    const uint64_t total = n * (vec ? lanes / VN : lanes);
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + BLOCK - 1) / BLOCK, 1u << 20));
+    if (vec && fuse) hipLaunchKernelGGL((antideriv_add_kernel<T, VN, true>), dim3(grid), dim3(BLOCK), 0, s0, A);
+    else if (vec) hipLaunchKernelGGL((antideriv_add_kernel<T, VN, false>), dim3(grid), dim3(BLOCK), 0, s0, A);
+    else if (fuse) hipLaunchKernelGGL((antideriv_add_kernel<T, 1, true>), dim3(grid), dim3(BLOCK), 0, s0, A);
+    else hipLaunchKernelGGL((antideriv_add_kernel<T, 1, false>), dim3(grid), dim3(BLOCK), 0, s0, A);
+    NDI_HIP(hipGetLastError());
+  }
+  NDI_HIP(hipStreamSynchronize(s0));   // the table is complete on return: any stream may read it (and tmp may go)
+}
+
 template <class T>
 struct AntiderivImpl final : Interp1DBase, FloatEngine<T, AntiderivImpl<T>> {
   bool linear = false;     // the source's evaluation class
@@ -65,71 +136,7 @@ struct AntiderivImpl final : Interp1DBase, FloatEngine<T, AntiderivImpl<T>> {
   // ---- build: the prefix table from this handle's own copies (NULL stream, complete on return) ----------------------
   template <bool LINEAR>
   void launch_build() {
-    AntiBuildArgs<T> A{};
-    A.y = y.as<T>(); A.a = a.as<T>(); A.b = b.as<T>(); A.x = pyr.view.lv0; A.P = P.as<T>();
-    A.n = n; A.lanes = lanes;
-    A.nblk = (n + AD_B - 1) / AD_B;
-    A.single = A.nblk == 1 ? 1u : 0u;
-    DevBuf tmp;
-    if (!A.single) {   // the block totals: kept per host thread like the spline build's temporaries
-      const size_t tb = (size_t)A.nblk * lanes * sizeof(T);
-      if (tb <= ((size_t)64 << 20)) A.tot = static_cast<T*>(build_scratch().device_buf(device, tb));
-      else {
-        tmp.reserve(tb);
-        A.tot = tmp.as<T>();
-      }
-    }
-    constexpr int VN = Wide<T>::N;
-    const hipStream_t s0 = nullptr;
-    const bool vec = lanes % VN == 0 && aligned16(A.y) && aligned16(A.a) && aligned16(A.b) && aligned16(A.P) && aligned16(A.tot);
-    const bool staged = lanes <= AD_STAGED_LANES;
-    const bool fuse = A.nblk <= AD_FUSE_BLOCKS;
-    bool vec_local = false;
-    unsigned local_grid = 0;
-    if (staged) {
-      // chains per workgroup: as many blocks as AD_STAGED_CHAINS allows, halved while the grid would leave the chip's
-      // 2048 resident workgroups unused (phase 2 takes the same time for one chain as for 32)
-      uint32_t kb = std::max<uint32_t>(1, AD_STAGED_CHAINS / (uint32_t)lanes);
-      while (kb > 1 && (A.nblk + kb - 1) / kb < 2048) kb /= 2;
-      A.kb = kb;
-      const size_t lds = (size_t)kb * (AD_B * lanes + lanes) * sizeof(T);
-      const unsigned grid = local_grid = (unsigned)std::min<uint64_t>((A.nblk + kb - 1) / kb, 1u << 16);
-      allow_dynamic_lds(reinterpret_cast<const void*>(&antideriv_local_staged_kernel<T, LINEAR>), 96 * 1024);
-      hipLaunchKernelGGL((antideriv_local_staged_kernel<T, LINEAR>), dim3(grid), dim3(BLOCK), lds, s0, A);
-    } else {
-      // every thread is a 256-step chain, so the threads are what hides the latency: 16-byte vectors only where they
-      // still leave the chip a full set of waves (4096 x 4096 has 65536 chains: one lane each, 4-8 byte coalesced loads)
-      vec_local = vec && A.nblk * (lanes / VN) >= (uint64_t)cu_count() * 8 * 64;
-      const uint64_t total = A.nblk * (vec_local ? lanes / VN : lanes);
-      const unsigned grid = local_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + BLOCK - 1) / BLOCK, 1u << 20));
-      if (vec_local) hipLaunchKernelGGL((antideriv_local_lanes_kernel<T, VN, LINEAR>), dim3(grid), dim3(BLOCK), 0, s0, A);
-      else hipLaunchKernelGGL((antideriv_local_lanes_kernel<T, 1, LINEAR>), dim3(grid), dim3(BLOCK), 0, s0, A);
-    }
-    NDI_HIP(hipGetLastError());
-    if (std::getenv("NDI_TRACE_PLAN"))   // grid: the local kernel's; kb / vec_local: 0 on the local kernel that has no such field
-      std::fprintf(stderr, "[ndi plan] antiderivative build linear=%d staged=%d kb=%u vec=%d vec_local=%d nblk=%llu single=%d fuse=%d "
-                   "grid=%u\n", (int)LINEAR, (int)staged, A.kb, (int)vec, (int)vec_local, (unsigned long long)A.nblk, (int)A.single,
-                   (int)(!A.single && fuse), local_grid);
-    if (!A.single) {
-      if (!fuse) {
-        if (staged) {
-          const unsigned grid = (unsigned)((lanes * 64 + BLOCK - 1) / BLOCK);
-          hipLaunchKernelGGL((antideriv_offsets_kernel<T, true>), dim3(grid), dim3(BLOCK), 0, s0, A.tot, A.nblk, (n - 1) / AD_B, lanes);
-        } else {
-          const unsigned grid = (unsigned)((lanes + BLOCK - 1) / BLOCK);
-          hipLaunchKernelGGL((antideriv_offsets_kernel<T, false>), dim3(grid), dim3(BLOCK), 0, s0, A.tot, A.nblk, (n - 1) / AD_B, lanes);
-        }
-        NDI_HIP(hipGetLastError());
-      }
-      const uint64_t total = n * (vec ? lanes / VN : lanes);
-      const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + BLOCK - 1) / BLOCK, 1u << 20));
-      if (vec && fuse) hipLaunchKernelGGL((antideriv_add_kernel<T, VN, true>), dim3(grid), dim3(BLOCK), 0, s0, A);
-      else if (vec) hipLaunchKernelGGL((antideriv_add_kernel<T, VN, false>), dim3(grid), dim3(BLOCK), 0, s0, A);
-      else if (fuse) hipLaunchKernelGGL((antideriv_add_kernel<T, 1, true>), dim3(grid), dim3(BLOCK), 0, s0, A);
-      else hipLaunchKernelGGL((antideriv_add_kernel<T, 1, false>), dim3(grid), dim3(BLOCK), 0, s0, A);
-      NDI_HIP(hipGetLastError());
-    }
-    NDI_HIP(hipStreamSynchronize(s0));   // the table is complete on return: any stream may read it (and tmp may go)
+    antideriv_prefix_build<T, LINEAR>(device, n, lanes, y.as<T>(), a.as<T>(), b.as<T>(), pyr.view.lv0, P.as<T>());
   }
 
   void build() {

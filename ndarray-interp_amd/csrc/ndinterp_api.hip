@@ -32,6 +32,7 @@
 #include "derivative_kernels.hpp"
 #include "antiderivative_kernels.hpp"
 #include "bicubic_kernels.hpp"
+#include "bicubic_integral_kernels.hpp"
 
 #define NDI_API extern "C" __attribute__((visibility("default")))
 
@@ -2347,6 +2348,7 @@ struct Interp2DBase {
   int dtype = 0, device = 0;
   uint64_t lanes = 0;
   bool bicubic = false;   // the strategy: Bilinear (every element type) or Bicubic (f32 / f64, ndi_interp2d_create_bicubic)
+  bool integral = false;  // Bicubic: a 2-D antiderivative handle (ndi_interp2d_antiderivative)
   // ndi_interp2d_tables: Bicubic handles only
   virtual ndi_status tables(void* zx, void* zy, void* zxy, int memspace) {
     return fail(NDI_BAD_ARG, "ndi_interp2d_tables takes a Bicubic handle: Bilinear keeps no node derivatives");
@@ -2365,6 +2367,20 @@ struct Interp2DBase {
     return fail(NDI_BAD_ARG, "Bilinear has no partial-derivative handle: its slope jumps at every grid line and it keeps no "
                 "node derivatives (ndi_interp2d_partial takes a Bicubic handle or a partial handle of one)");
   }
+  // ndi_interp2d_antiderivative / _integral / _integral_tables: Bicubic surface handles and their integral handles only
+  virtual ndi_status antiderivative(Interp2DBase** out) {
+    return fail(NDI_BAD_ARG, "Bilinear has no antiderivative handle: ndi_interp2d_antiderivative takes a Bicubic surface handle "
+                "(the integral of a Bilinear surface is not provided)");
+  }
+  virtual ndi_status integral_rect(const void* xa, const void* xb, const void* ya, const void* yb, uint64_t nq, void* out,
+                                   uint64_t out_stride, const ndi_eval_opts* opts, ndi_oob_info* info) {
+    return fail(NDI_BAD_ARG, "ndi_interp2d_integral takes an integral handle (ndi_interp2d_antiderivative of a Bicubic handle): "
+                "this is a Bilinear handle");
+  }
+  virtual ndi_status integral_tables(void* const dst[5], int memspace) {
+    return fail(NDI_BAD_ARG, "ndi_interp2d_integral_tables takes an integral handle (ndi_interp2d_antiderivative of a Bicubic "
+                "handle): this is a Bilinear handle");
+  }
 };
 
 template <class T>
@@ -2374,6 +2390,17 @@ static void bicubic_launch_eval(const Interp2DImpl<T>& h, hipStream_t s, StatusB
                                 uint64_t nq, T* out, uint64_t out_stride, bool check);
 template <class T>
 static ndi_status bicubic_tables(const Interp2DImpl<T>& h, void* zx, void* zy, void* zxy, int memspace);
+template <class T>
+static void bicubic_integral_build(const Interp2DImpl<T>& src, Interp2DImpl<T>& h);
+template <class T>
+static void bicubic_integral_launch_eval(const Interp2DImpl<T>& h, hipStream_t s, StatusBlock* st, const T* qx, const T* qy,
+                                         const T* qx_lo, const T* qy_lo, uint64_t nq, T* out, uint64_t out_stride, bool check);
+template <class T>
+static ndi_status bicubic_integral_tables(const Interp2DImpl<T>& h, void* const dst[5], int memspace);
+template <class T>
+static ndi_status bicubic_integral_rect(Interp2DImpl<T>& h, const void* xa, const void* xb, const void* ya, const void* yb,
+                                        uint64_t nq, void* out, uint64_t out_stride, const ndi_eval_opts* opts,
+                                        ndi_oob_info* info);
 
 template <class T>
 struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
@@ -2385,6 +2412,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
   // partial-derivative handles (ndi_interp2d_partial), which only read it: freed with the last of them, in any order.
   std::shared_ptr<DevBuf> table;
   int nu_x = 0, nu_y = 0;     // Bicubic: the orders of the partial derivative this handle evaluates ((0, 0): the surface)
+  DevBuf itable;              // integral handles: the prefix records T[nx][ny][5][lanes] ({PP, Qz, Qzy, Pz, Pzx}), owned
   bool pair_packed = false;   // data holds the pair-packed layout (pack_pairs_kernel)
   SpaceSet spaces;
   OwnedRing ring_own;
@@ -2473,8 +2501,10 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
   uint64_t signature() const override {
     uint64_t h = fnv1a(FNV_SEED, px.host_knots.data(), px.host_knots.size() * sizeof(T));
     h = fnv1a(h, py.host_knots.data(), py.host_knots.size() * sizeof(T));
-    // (the strategy and the partial orders: no Bilinear / Bicubic mix, no surface beside its partial, no two partials)
-    const uint64_t f[3] = {nx, ny, (uint64_t)mode | ((uint64_t)bicubic << 8) | ((uint64_t)nu_x << 16) | ((uint64_t)nu_y << 24)};
+    // (the strategy, the partial orders and the integral bit: no Bilinear / Bicubic mix, no surface beside its partial or
+    // its integral, no two partials)
+    const uint64_t f[3] = {nx, ny, (uint64_t)mode | ((uint64_t)bicubic << 8) | ((uint64_t)nu_x << 16) | ((uint64_t)nu_y << 24) |
+                                       ((uint64_t)integral << 32)};
     return fnv1a(h, f, sizeof(f));
   }
   ndi_status tables(void* zx, void* zy, void* zxy, int memspace) override {
@@ -2485,7 +2515,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
   // Two stages as in Interp1DImpl: prep() = both searches (+ the optional tile grouping) into a scratch set,
   // launch_eval() = the bilinear kernel reading that set.
   struct Plan2 {
-    enum Kind { SMALL, GATHER, TILED, FUSED2, LANES2, SLOPES2, BICUBIC } kind = GATHER;
+    enum Kind { SMALL, GATHER, TILED, FUSED2, LANES2, SLOPES2, BICUBIC, BICUBIC_INT } kind = GATHER;
     int l_qpl = 1;          // LANES2, scalar grids: queries per lane (1, or one 16-byte vector)
     bool l_check = false;   // LANES2: no range pre-pass (NDI_EVAL_FRESH_OUTPUT)
     bool f_lds_wide = false;   // SLOPES2: f_lds includes the result strip of the 16-byte store path
@@ -2511,7 +2541,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     reset_status(sc.status.p, s);
     StatusBlock* st = sc.status.as<StatusBlock>();
     if (bicubic) {   // one kernel for AUTO and GATHER (eval_bicubic_kernel); BUCKETED was refused at the entry point
-      P.kind = Plan2::BICUBIC;
+      P.kind = integral ? Plan2::BICUBIC_INT : Plan2::BICUBIC;   // (an integral handle: eval_bicubic_integral_kernel)
       g_last_path.store(NDI_PATH_GATHER);
       P.l_check = (flags & NDI_EVAL_FRESH_OUTPUT) != 0;   // fresh output: the kernel's own range test, no pre-pass
       if (P.l_check) return P;
@@ -2939,6 +2969,11 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
       bicubic_launch_eval<T>(*this, s, st, P.qx, P.qy, nq, P.out, P.out_stride, P.l_check);
       return;
     }
+    if (P.kind == Plan2::BICUBIC_INT) {
+      bicubic_integral_launch_eval<T>(*this, s, st, P.qx, P.qy, (const T*)nullptr, (const T*)nullptr, nq, P.out, P.out_stride,
+                                      P.l_check);
+      return;
+    }
     if (P.kind == Plan2::SMALL) {
       const size_t both = ((px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15);
       const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
@@ -3332,6 +3367,11 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
       h->table = std::make_shared<DevBuf>();
       h->table->reserve(table->bytes);
       copy_across_devices(h->table->p, dev, table->p, device, table->bytes);
+      if (integral) {   // ... and the integral flag with a copy of the prefix records
+        h->integral = true;
+        h->itable.reserve(itable.bytes);
+        copy_across_devices(h->itable.p, dev, itable.p, device, itable.bytes);
+      }
     } else {
       h->data.reserve(data.bytes);
       copy_across_devices(h->data.p, dev, data.p, device, data.bytes);
@@ -3345,6 +3385,9 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
   // decided before that.
   ndi_status partial(int nux, int nuy, Interp2DBase** out) override {
     if (!bicubic) return Interp2DBase::partial(nux, nuy, out);
+    if (integral)
+      return fail(NDI_BAD_ARG, "Bicubic: an integral handle has no partial-derivative handle: its x-derivative is a y-integral "
+                  "of the surface, which is not provided (the mixed (1, 1) partial is the handle it was made from)");
     if (nux < 0 || nuy < 0)
       return fail(NDI_BAD_ARG, "Bicubic: a partial-derivative order below 0 (asked for (%d, %d)); orders are 0, 1 or 2 per "
                   "variable", nux, nuy);
@@ -3367,6 +3410,45 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     h->table = table;
     *out = h.release();
     return NDI_OK;
+  }
+
+  // ndi_interp2d_antiderivative: a handle on this handle's device that evaluates F(qx, qy), the integral of the surface over
+  // [x[0], qx] x [y[0], qy].  It shares the node table (no copy) and owns the five prefix tables, built here on the NULL
+  // stream.  Every refusal is decided before any device work.
+  ndi_status antiderivative(Interp2DBase** out) override {
+    if (!bicubic) return Interp2DBase::antiderivative(out);
+    if (integral)
+      return fail(NDI_BAD_ARG, "Bicubic: this handle is already an integral handle; a second antiderivative is not provided");
+    if (nu_x != 0 || nu_y != 0)
+      return fail(NDI_BAD_ARG, "Bicubic: a partial-derivative handle (orders (%d, %d)) has no antiderivative handle: the "
+                  "integral of a partial is not provided (ndi_interp2d_antiderivative takes the surface handle)", nu_x, nu_y);
+    DeviceGuard dg(device);
+    std::unique_ptr<Interp2DImpl<T>> h(new Interp2DImpl<T>());
+    h->dtype = dtype; h->device = device; h->lanes = lanes;
+    h->mode = mode; h->nx = nx; h->ny = ny;
+    h->bicubic = true;
+    h->integral = true;
+    h->px.upload(px.host_knots.data(), nx);
+    h->py.upload(py.host_knots.data(), ny);
+    h->table = table;
+    bicubic_integral_build<T>(*this, *h);
+    *out = h.release();
+    return NDI_OK;
+  }
+  ndi_status integral_rect(const void* xa, const void* xb, const void* ya, const void* yb, uint64_t nq, void* out_,
+                           uint64_t out_stride, const ndi_eval_opts* opts, ndi_oob_info* info) override {
+    if (!integral)
+      return fail(NDI_BAD_ARG, "ndi_interp2d_integral takes an integral handle (ndi_interp2d_antiderivative of a Bicubic "
+                  "handle): this is a %s handle", !bicubic ? "Bilinear" : (nu_x || nu_y) ? "Bicubic partial-derivative"
+                                                                                         : "Bicubic surface");
+    return bicubic_integral_rect<T>(*this, xa, xb, ya, yb, nq, out_, out_stride, opts, info);
+  }
+  ndi_status integral_tables(void* const dst[5], int memspace) override {
+    if (!integral)
+      return fail(NDI_BAD_ARG, "ndi_interp2d_integral_tables takes an integral handle (ndi_interp2d_antiderivative of a Bicubic "
+                  "handle): this is a %s handle", !bicubic ? "Bilinear" : (nu_x || nu_y) ? "Bicubic partial-derivative"
+                                                                                         : "Bicubic surface");
+    return bicubic_integral_tables<T>(*this, dst, memspace);
   }
 
   // Median time of `reps` launches of probe_gather_kernel over nq queries (see kernels.hpp).
@@ -3485,6 +3567,7 @@ static ndi_status create2d(const ndi_interp2d_desc& d, Interp2DBase** out) {
 // Interp2D Bicubic: build, launch and table read-back
 // ---------------------------------------------------------------------------------------------
 #include "bicubic_host.hpp"
+#include "bicubic_integral_host.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // Locator: VectorExtensions::get_lower_index with the knot pyramid resident on the device
@@ -4124,6 +4207,42 @@ NDI_API ndi_status ndi_interp2d_partial(const ndi_interp2d* h, int32_t nu_x, int
   if (st != NDI_OK) return st;
   *out = new ndi_interp2d{impl};
   return NDI_OK;
+  NDI_CATCH
+}
+
+// Every refusal is decided before any device work: the null checks here, the handle's own in Interp2DImpl::antiderivative.
+NDI_API ndi_status ndi_interp2d_antiderivative(const ndi_interp2d* h, ndi_interp2d** out) {
+  if (!out) return ndi::fail(NDI_BAD_ARG, "null out pointer");
+  *out = nullptr;
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  NDI_TRY
+  ndi::Range rg("ndi_interp2d_antiderivative");
+  ndi::Interp2DBase* impl = nullptr;
+  ndi_status st = h->impl->antiderivative(&impl);
+  if (st != NDI_OK) return st;
+  *out = new ndi_interp2d{impl};
+  return ndi::bounds_verdict(NDI_OK, impl->device);
+  NDI_CATCH
+}
+
+NDI_API ndi_status ndi_interp2d_integral(const ndi_interp2d* h, const void* xa, const void* xb, const void* ya, const void* yb,
+                                         uint64_t nq, void* out, uint64_t out_row_stride, const ndi_eval_opts* opts,
+                                         ndi_oob_info* info) {
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  NDI_TRY
+  if (!h->impl->integral) return h->impl->integral_rect(xa, xb, ya, yb, nq, out, out_row_stride, opts, info);
+  return ndi::bounds_verdict(h->impl->integral_rect(xa, xb, ya, yb, nq, out, out_row_stride, opts, info), h->impl->device);
+  NDI_CATCH
+}
+
+NDI_API ndi_status ndi_interp2d_integral_tables(const ndi_interp2d* h, void* pp, void* qz, void* qzy, void* pz, void* pzx,
+                                                int32_t memspace) {
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  if (memspace != NDI_MEM_HOST && memspace != NDI_MEM_DEVICE) return ndi::fail(NDI_BAD_ARG, "unknown memspace");
+  NDI_TRY
+  void* const dst[5] = {pp, qz, qzy, pz, pzx};
+  if (!h->impl->integral) return h->impl->integral_tables(dst, memspace);
+  return ndi::bounds_verdict(h->impl->integral_tables(dst, memspace), h->impl->device);
   NDI_CATCH
 }
 

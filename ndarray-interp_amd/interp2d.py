@@ -273,6 +273,13 @@ class Bilinear(Interp2DStrategyBuilder, _DeviceStrategy2D):
         raise TypeError("Bilinear has no partial derivatives: its slope jumps at every grid line and it keeps no node "
                         "derivatives (Bicubic.partial gives them)")
 
+    def antiderivative(self):
+        raise TypeError("Bilinear has no antiderivative handle: 2-D integrals are Bicubic's (Bicubic.antiderivative)")
+
+    def integral(self, *a, **kw):
+        raise TypeError("Bilinear has no rectangle integral: 2-D integrals are Bicubic's (Bicubic.antiderivative, then "
+                        "integral)")
+
     def probe_ceiling(self, out2d, reps=5) -> float:
         """ms of the evaluation kernel's memory access mix alone on this handle's grid (ndi_interp2d_probe_ceiling);
         `out2d`: a device tensor (nq, lanes) that is overwritten."""
@@ -359,6 +366,9 @@ class Bicubic(Interp2DStrategyBuilder, _DeviceStrategy2D):
         if nu_x == 0 and nu_y == 0:
             raise ValueError("Bicubic.partial: orders (0, 0) are the strategy itself; ask for an order of 1 or 2 in at least "
                              "one variable")
+        if self.is_integral:
+            raise ValueError("Bicubic.partial: an integral strategy has no partial derivatives: its x-derivative is a "
+                             "y-integral of the surface, which is not provided")
         tx, ty = self.orders[0] + nu_x, self.orders[1] + nu_y
         if tx > 2 or ty > 2:
             raise ValueError(f"Bicubic.partial: the third derivative of a cubic spline jumps at the grid lines; orders are 0 "
@@ -379,6 +389,86 @@ class Bicubic(Interp2DStrategyBuilder, _DeviceStrategy2D):
         other._h, other._inflight = h, []
         other.orders, other.origin = (tx, ty), self
         return other
+
+    is_integral = False   # True on the strategy `antiderivative()` returns
+
+    def antiderivative(self) -> "Bicubic":
+        """F(x, y), the integral of this built strategy's surface over [x[0], x] x [y[0], y], as a built strategy of its own
+        (ndi_interp2d_antiderivative).  It evaluates like any Bicubic strategy and adds `integral(xa, xb, ya, yb)` (scipy:
+        `RectBivariateSpline.integral`).  The new handle shares this one's node table on the device and owns its five
+        prefix tables; either may be released first.  This strategy stays usable."""
+        if self.is_integral:
+            raise ValueError("Bicubic.antiderivative: this strategy is already an integral; a second antiderivative is not "
+                             "provided")
+        if self.orders != (0, 0):
+            raise ValueError(f"Bicubic.antiderivative: a partial-derivative strategy (orders {self.orders}) has no "
+                             "antiderivative; ask the surface's strategy")
+        if self._h is None:
+            from .errors import DeviceError
+            raise DeviceError("Bicubic.antiderivative needs a built strategy: the node table lives on the device and the "
+                              "prefix tables are built there; there is no CPU fallback")
+        import copy
+        h = C.c_void_p()
+        st = _capi.lib().ndi_interp2d_antiderivative(self._h, C.byref(h))
+        if st == _capi.BAD_ARG:
+            raise ValueError(_capi.last_error())
+        if st != _capi.OK:
+            raise_builder(st)
+        other = copy.copy(self)
+        other._h, other._inflight = h, []
+        other.is_integral, other.origin = True, self
+        return other
+
+    def integral(self, xa_flat, xb_flat, ya_flat, yb_flat, out2d, *, fresh=False):
+        """Rectangle integrals (ndi_interp2d_integral): row q of `out2d` (nq, lanes) is the integral over
+        [xa[q], xb[q]] x [ya[q], yb[q]].  Reversed bounds negate; equal bounds give exactly 0."""
+        if not self.is_integral:
+            raise TypeError("Bicubic.integral needs the integral strategy: call antiderivative() first "
+                            f"(this is a Bicubic strategy of orders {self.orders})")
+        q = [Buf(a, self._np_dtype) for a in (xa_flat, xb_flat, ya_flat, yb_flat)]
+        if len({b.memspace for b in q}) != 1:
+            raise TypeError("Bicubic.integral: the four bounds must live in the same memory space")
+        if len({b.size for b in q}) != 1:
+            raise ValueError(f"Bicubic.integral: the four bounds differ in length: {[b.size for b in q]}")
+        _check_out_dtype(out2d, self._np_dtype)
+        opts = _capi.EvalOpts()
+        opts.q_memspace = q[0].memspace
+        opts.path = self.path
+        opts.flags = _capi.EVAL_FRESH_OUTPUT if fresh else _capi.EVAL_DEFAULT
+        if is_torch(out2d):
+            if not out2d.is_cuda:
+                raise TypeError("torch output buffers must live on the device; use numpy for host buffers")
+            opts.out_memspace = _capi.MEM_DEVICE
+            optr = out2d.data_ptr()
+            stride = out2d.stride(0) if out2d.dim() > 1 and out2d.shape[0] > 1 else self._lanes
+            opts.stream = current_stream_ptr(self._device)
+        else:
+            opts.out_memspace = _capi.MEM_HOST
+            optr = out2d.ctypes.data
+            stride = out2d.strides[0] // out2d.itemsize if out2d.ndim > 1 and out2d.shape[0] > 1 else self._lanes
+            if q[0].memspace == _capi.MEM_DEVICE:
+                opts.stream = current_stream_ptr(self._device)
+        info = _capi.OobInfo()
+        st = _capi.lib().ndi_interp2d_integral(self._h, q[0].ptr, q[1].ptr, q[2].ptr, q[3].ptr, q[0].size, optr,
+                                               max(stride, self._lanes), C.byref(opts), C.byref(info))
+        if st != _capi.OK:
+            raise_eval(st, info, None)
+
+    def integral_tables(self, on_device=False):
+        """(PP, Qz, Qzy, Pz, Pzx): the five prefix tables of an integral strategy, each of the data's shape
+        (ndi_interp2d_integral_tables), as host arrays -- or, with `on_device`, as tensors on the handle's device."""
+        if on_device:
+            import torch
+            out = [torch.empty(self._shape, dtype=torch_dtype(self._np_dtype), device=f"cuda:{self._device}") for _ in range(5)]
+            ptrs, space = [t.data_ptr() for t in out], _capi.MEM_DEVICE
+        else:
+            out = [np.empty(self._shape, dtype=self._np_dtype) for _ in range(5)]
+            ptrs, space = [a.ctypes.data for a in out], _capi.MEM_HOST
+        st = _capi.lib().ndi_interp2d_integral_tables(self._h, *ptrs, space)
+        if st != _capi.OK:
+            from .errors import DeviceError
+            raise DeviceError(_capi.last_error())
+        return tuple(out)
 
     def tables(self, on_device=False):
         """(zx, zy, zxy): the node derivatives, each of the data's shape (ndi_interp2d_tables), as host arrays -- or, with
@@ -530,6 +620,53 @@ class Interp2D:
             raise TypeError("partial needs a built Bicubic strategy (f32 / f64 data), got "
                             f"{type(self.strategy).__name__}")
         return Interp2D(self.x, self.y, self.data, self.strategy.partial(nu_x, nu_y))
+
+    def antiderivative(self) -> "Interp2D":
+        """F(x, y), the integral of this interpolator's surface over [x[0], x] x [y[0], y], as an interpolator over the same
+        axes (`Bicubic.antiderivative`).  `data` stays the surface's node values.  The result also has `integral`."""
+        if not hasattr(self.strategy, "antiderivative"):
+            raise TypeError("antiderivative needs a built Bicubic strategy (f32 / f64 data), got "
+                            f"{type(self.strategy).__name__}")
+        return Interp2D(self.x, self.y, self.data, self.strategy.antiderivative())
+
+    def integral(self, xa, xb, ya, yb):
+        """Integrals of the surface over the rectangles [xa, xb] x [ya, yb] (scipy: `RectBivariateSpline.integral`), on the
+        interpolator `antiderivative()` returns.  The four bounds broadcast to one common shape; the result has that shape
+        followed by the trailing data shape.  Reversed bounds negate; equal bounds give exactly 0."""
+        strat = self.strategy
+        if not getattr(strat, "is_integral", False):
+            if isinstance(strat, Bicubic):
+                raise TypeError("Interp2D.integral: this is a Bicubic interpolator of the surface (or a partial); call "
+                                "antiderivative() first and integrate through the interpolator it returns")
+            raise TypeError(f"Interp2D.integral needs the antiderivative of a Bicubic interpolator, got "
+                            f"{type(strat).__name__}: {type(strat).__name__} has no 2-D integrals")
+        bounds = (xa, xb, ya, yb)
+        dt = np_dtype_of(self.data)
+        on_dev = [is_torch(b) and b.is_cuda for b in bounds]
+        if any(on_dev) and not all(on_dev):
+            raise TypeError("Bicubic integral: the four bounds must live in the same memory space")
+        try:
+            if all(on_dev):
+                import torch
+                flat = [b.to(torch_dtype(dt)) for b in bounds]
+                flat = [b.contiguous() for b in torch.broadcast_tensors(*flat)]
+            else:
+                flat = [np.ascontiguousarray(b) for b in np.broadcast_arrays(*[np.asarray(_host(b), dtype=dt) for b in bounds])]
+        except (ValueError, RuntimeError):
+            raise ValueError("Bicubic integral: the bound shapes do not broadcast to one shape: "
+                             f"{[tuple(np.shape(b)) for b in bounds]}") from None
+        qshape = tuple(flat[0].shape)
+        shape = self.get_buffer_shape(qshape)
+        nq = int(np.prod(qshape, dtype=np.int64))
+        lanes = int(np.prod(self._lanes_shape(), dtype=np.int64))
+        if all(on_dev):
+            import torch
+            zs = torch.empty(shape, dtype=torch_dtype(dt), device=flat[0].device)
+            strat.integral(*[b.reshape(-1) for b in flat], zs.view(nq, lanes), fresh=True)
+        else:
+            zs = np.zeros(shape, dtype=dt)
+            strat.integral(*[b.reshape(-1) for b in flat], zs.reshape(nq, lanes), fresh=True)
+        return zs
 
     def replicate(self, devices):
         """Replicas of this interpolator on the given devices (see Interp1D.replicate)."""

@@ -239,6 +239,28 @@ extern "C" {
         memspace: i32,
     ) -> i32;
     pub fn ndi_interp2d_partial(h: *const ndi_interp2d, nu_x: i32, nu_y: i32, out: *mut *mut ndi_interp2d) -> i32;
+    pub fn ndi_interp2d_antiderivative(h: *const ndi_interp2d, out: *mut *mut ndi_interp2d) -> i32;
+    pub fn ndi_interp2d_integral(
+        h: *const ndi_interp2d,
+        xa: *const c_void,
+        xb: *const c_void,
+        ya: *const c_void,
+        yb: *const c_void,
+        nq: u64,
+        out: *mut c_void,
+        out_row_stride: u64,
+        opts: *const ndi_eval_opts,
+        info: *mut ndi_oob_info,
+    ) -> i32;
+    pub fn ndi_interp2d_integral_tables(
+        h: *const ndi_interp2d,
+        pp: *mut c_void,
+        qz: *mut c_void,
+        qzy: *mut c_void,
+        pz: *mut c_void,
+        pzx: *mut c_void,
+        memspace: i32,
+    ) -> i32;
     pub fn ndi_interp2d_destroy(h: *mut ndi_interp2d);
     pub fn ndi_interp1d_clone(h: *const ndi_interp1d, device: i32, out: *mut *mut ndi_interp1d) -> i32;
     pub fn ndi_interp2d_clone(h: *const ndi_interp2d, device: i32, out: *mut *mut ndi_interp2d) -> i32;

@@ -18,6 +18,13 @@ with `--partial NUX,NUY` in each.  The timing pass then times the value handle a
 by side (two alternating rounds each: their spread is the margin), the profiled run evaluates both, and the merge pairs the
 two instances of eval_bicubic_kernel by their template arguments.  A partial reads the same sixteen operands and writes the
 same row, so by bytes the ratio is 1.
+
+Integral handles (output committed as profiles/bicubic_integral_rates.json): the same three steps with
+`--integral` in each.  The timing pass times ndi_interp2d_antiderivative beside ndi_interp2d_create_bicubic, then an F batch
+beside the value handle's and a rectangle batch beside the F batch (two alternating rounds each: the value handle's spread
+is the margin); the profiled run evaluates all three, and the merge tells eval_bicubic_kernel, the F instance and the
+rectangle instance of eval_bicubic_integral_kernel apart by their names.  By bytes F is 26 / 17 of the value (25 operands
+and a store against 16 and a store); a rectangle is at most four times F's reads for one store.
 """
 import argparse
 import csv
@@ -179,6 +186,86 @@ def partial_merge(prof_dir, out_path, orders):
     json.dump(res, open(out_path, "w"), indent=1)
 
 
+def integral_inputs(name, nx, ny, C):
+    """the value handle, its integral handle, the four bounds of the rectangle batch (the queries against a rolled copy)"""
+    import torch
+    pkg = package()
+    x, y, z, qx, qy, out = inputs(name, nx, ny, C)
+    value = pkg.Interp2DBuilder.new(z).x(x).y(y).strategy(pkg.Bicubic.new()).build()
+    return pkg, x, y, z, value, (qx, torch.roll(qx, 1), qy, torch.roll(qy, 1)), out
+
+
+def integral_timing_pass(out_path):
+    import torch
+    pkg = package()
+    assert torch.cuda.is_available() and pkg.device_count() >= 1, "needs a GPU"
+    res = {"device": torch.cuda.get_device_name(0), "create_ms": {}, "eval_ms": {}}
+    for name, nx, ny, C in SHAPES:
+        key = f"{name}_{nx}x{ny}x{C}"
+        pkg, x, y, z, value, r, out = integral_inputs(name, nx, ny, C)
+        res["create_ms"][key] = {}
+        for what, fn in (("create_bicubic", lambda: pkg.Interp2DBuilder.new(z).x(x).y(y).strategy(pkg.Bicubic.new()).build()),
+                         ("antiderivative", lambda: value.antiderivative())):
+            med, lo, hi = median_ms(fn, reps=5)
+            res["create_ms"][key][what] = {"median": med, "min": lo, "max": hi}
+        F = value.antiderivative()
+        calls = {"value": lambda: value.interp_array_into(r[0], r[2], out), "F": lambda: F.interp_array_into(r[0], r[2], out),
+                 "rectangle": lambda: F.strategy.integral(*r, out)}
+        res["eval_ms"][key] = {"queries": int(r[0].numel())}
+        for rnd in range(2):               # alternate the three: the value handle's two rounds give the spread
+            for what, fn in calls.items():
+                med, lo, hi = median_ms(fn)
+                res["eval_ms"][key][f"{what}_round{rnd}"] = {"median": med, "min": lo, "max": hi}
+        print(key, json.dumps(res["create_ms"][key]), json.dumps(res["eval_ms"][key]), flush=True)
+        del F, value, calls, x, y, z, r, out
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    json.dump(res, open(out_path, "w"), indent=1)
+
+
+def integral_profile_shape(name, nx, ny, C):
+    pkg, x, y, z, value, r, out = integral_inputs(name, nx, ny, C)
+    F = value.antiderivative()
+    for fn in (lambda: value.interp_array_into(r[0], r[2], out), lambda: F.interp_array_into(r[0], r[2], out),
+               lambda: F.strategy.integral(*r, out)):
+        for _ in range(REPS):
+            fn()
+    print("profiled", name, nx, ny, C, "integral", flush=True)
+
+
+def integral_merge(prof_dir, out_path):
+    """eval_bicubic_kernel<..., 0, 0> (value), eval_bicubic_integral_kernel<..., false> (F) and <..., true> (rectangle)"""
+    res = json.load(open(out_path)) if os.path.exists(out_path) else {}
+    res["eval_kernels"] = {}
+    for name, nx, ny, C in SHAPES:
+        key = f"{name}_{nx}x{ny}x{C}"
+        files = glob.glob(os.path.join(prof_dir, key, "**", "*kernel_stats.csv"), recursive=True)
+        if not files:
+            continue
+        per, names = {"value": 0.0, "F": 0.0, "rectangle": 0.0}, {"value": [], "F": [], "rectangle": []}
+        for row in csv.DictReader(open(files[0])):
+            kn = row["Name"].split("(")[0].strip()
+            if "eval_bicubic_integral_kernel" in kn:
+                who = "rectangle" if kn.endswith(", true>") else "F"
+            elif "eval_bicubic_kernel" in kn and kn.endswith(", 0, 0>"):
+                who = "value"
+            else:
+                continue                 # range pre-passes, builds, fills
+            per[who] += float(row["TotalDurationNs"]) / REPS
+            names[who].append(kn)
+        nq, size = n_queries(DTYPES[name], C), np.dtype(DTYPES[name]).itemsize
+        entry = {"queries": nq, "compulsory_bytes_value": 17 * nq * C * size, "compulsory_bytes_F": 26 * nq * C * size}
+        for who, ns in per.items():
+            entry[who] = {"kernel_ms_per_batch": ns / 1e6, "kernels": sorted(set(names[who]))}
+        if per["value"] > 0 and per["F"] > 0 and per["rectangle"] > 0:
+            entry["ratio_F_over_value"] = per["F"] / per["value"]
+            entry["ratio_rectangle_over_F"] = per["rectangle"] / per["F"]
+            entry["F_fraction_of_8TBps"] = entry["compulsory_bytes_F"] / (per["F"] * 1e-9) / PEAK_BPS
+        res["eval_kernels"][key] = entry
+        print(key, json.dumps(entry), flush=True)
+    json.dump(res, open(out_path, "w"), indent=1)
+
+
 def profile_shape(name, nx, ny, C):
     pkg = package()
     x, y, z, qx, qy, out = inputs(name, nx, ny, C)
@@ -226,12 +313,20 @@ if __name__ == "__main__":
     ap.add_argument("--out")
     ap.add_argument("--partial", metavar="NUX,NUY", type=orders_of,
                     help="time a partial-derivative handle of these orders beside the value handle")
+    ap.add_argument("--integral", action="store_true", help="time the integral handle beside the value handle")
     ap.add_argument("--profile-shape", nargs=4, metavar=("DTYPE", "NX", "NY", "C"))
     ap.add_argument("--merge", metavar="DIR")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "bicubic_partial_rates.json" if a.partial else "bicubic_rates.json")
-    if a.partial and a.profile_shape:
+        a.out = os.path.join(ROOT, "profiles", "bicubic_integral_rates.json" if a.integral else
+                             "bicubic_partial_rates.json" if a.partial else "bicubic_rates.json")
+    if a.integral and a.profile_shape:
+        integral_profile_shape(a.profile_shape[0], *(int(v) for v in a.profile_shape[1:]))
+    elif a.integral and a.merge:
+        integral_merge(a.merge, a.out)
+    elif a.integral:
+        integral_timing_pass(a.out)
+    elif a.partial and a.profile_shape:
         partial_profile_shape(a.profile_shape[0], *(int(v) for v in a.profile_shape[1:]), a.partial)
     elif a.partial and a.merge:
         partial_merge(a.merge, a.out, a.partial)
