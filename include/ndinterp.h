@@ -307,10 +307,20 @@ typedef struct ndi_interp2d_desc {
  *  async_launch / _finish, the ring and sharded calls, _trim, _clone (the tables are copied, the flag kept), _tables (the
  *  origin's zx, zy, zxy) and the refusal of NDI_PATH_BUCKETED / _probe_ceiling are unchanged.  The integral bit is part
  *  of the replica signature: a sharded set that mixes a surface with its integral is refused.
+ * Value and derivatives in one call (ndi_interp2d_eval_jet): the surface and its partials up to `order` (1: value and
+ * gradient, 2: with the three second derivatives) at the same queries, from ONE read of the sixteen operands -- per point
+ * 16 + K element reads and writes where K separate handle calls move 17 K.  There are no new formulas: part k is, bit for
+ * bit, what ndi_interp2d_eval of ndi_interp2d_partial(h, nu_x, nu_y) writes for the same queries (part 0: what
+ * ndi_interp2d_eval(h) writes), in the fixed order of (nu_x, nu_y)
+ *     order 1:  (0,0) (1,0) (0,1)                    order 2:  (0,0) (1,0) (0,1) (2,0) (1,1) (0,2)
+ *  with Pm = the four y-forms H_m(..., hy, u) of the sixteen operands:  (0,0) = H0(P0, hx, t)   (1,0) = H1(P0, hx, t)
+ *  (0,1) = H0(P1, hx, t)   (2,0) = H2(P0, hx, t)   (1,1) = H1(P1, hx, t)   (0,2) = H0(P2, hx, t).  Cell, t, u, hx, hy, the
+ *  range test, the NaN rule and `extrapolate` are the Bicubic handle's.
  * Not provided: periodic and per-lane boundaries, Pchip / Akima node derivatives, integrals of Bilinear or of partial
  * handles, partials of an integral handle, a second antiderivative, a ring / sharded / async_launch form of the four-array
- * rectangle call, third derivatives, a fused value-and-gradient call, a tile-grouped evaluation form, a blocked-sweep
- * build for narrow grids, half and integer element types. */
+ * rectangle call and of the jet call, a jet of a partial or of an integral handle, null entries in the jet's `outs` to skip
+ * parts, jet orders above 2, third derivatives, a tile-grouped evaluation form, a blocked-sweep build for narrow grids,
+ * half and integer element types. */
 typedef struct ndi_interp1d ndi_interp1d; /* owns device copies of x, data (and a, b) */
 typedef struct ndi_interp2d ndi_interp2d;
 
@@ -408,6 +418,31 @@ ndi_status ndi_interp2d_integral(const ndi_interp2d* h, const void* xa, const vo
  * may be NULL): the counterpart of ndi_interp2d_tables.  NDI_BAD_ARG for any handle that is not an integral handle. */
 ndi_status ndi_interp2d_integral_tables(const ndi_interp2d* h, void* pp, void* qz, void* qzy, void* pz, void* pzx,
                                         int32_t memspace);
+/* The surface and its partial derivatives up to `order` at the same queries, in ONE evaluation launch (contract above
+ * ndi_interp1d).  `order` is 1 or 2 and selects K = 3 or 6 parts in the fixed order of (nu_x, nu_y)
+ *     order 1: (0,0), (1,0), (0,1)        order 2: (0,0), (1,0), (0,1), (2,0), (1,1), (0,2)
+ * Part k is, bit for bit, what ndi_interp2d_eval of ndi_interp2d_partial(h, nu_x, nu_y) writes for the same queries; part 0
+ * is what ndi_interp2d_eval(h) writes.  `outs` is a HOST array of K pointers (whatever out_memspace says about what they
+ * point to); part k of query i, lane l goes to outs[k][i * out_row_stride + l]: ONE row stride in elements, >= lanes,
+ * common to all parts.  Both natural layouts are expressible: planar (K, nq, lanes) is stride = lanes with the bases
+ * nq * lanes apart, interleaved (nq, K, lanes) is stride = K * lanes with the bases lanes apart.  Parts must not overlap:
+ * two equal pointers in `outs` are refused, any other overlap is the caller's responsibility.  The 16-byte vector form is
+ * taken when lanes and the stride are multiples of a vector and ALL K bases are 16-byte aligned, else every part takes
+ * the scalar form (the same bits).
+ * `h` must be a Bicubic surface handle: a Bilinear handle, a partial handle (a jet of a partial would need third orders)
+ * and an integral handle are NDI_BAD_ARG with a message naming the strategy and the reason.  Also NDI_BAD_ARG, all decided
+ * before any device work: `order` outside {1, 2}; a null `h` or `outs`; with nq > 0 a null query pointer or a null
+ * outs[k]; two equal pointers in `outs`; out_row_stride < lanes; NDI_PATH_BUCKETED.  async_launch != 0 is NDI_UNSUPPORTED:
+ * the call completes before it returns (the partial handles have an async_launch form).  nq == 0 is NDI_OK and touches
+ * nothing.
+ * Errors are ndi_interp2d_eval's: the lowest failing flat index wins, x before y, `info` filled the same way; without
+ * NDI_EVAL_FRESH_OUTPUT rows before the failing index are written in EVERY part and rows from it on are untouched in EVERY
+ * part (a range pre-pass over the queries); with it there is no pre-pass and the kernel applies its own range test;
+ * NDI_EVAL_ROWS_AFTER_ERROR_UNSPECIFIED is honoured as elsewhere.  Thread-safety is ndi_interp2d_eval's.
+ * Not provided: ring, sharded and async_launch forms; a jet of a partial or of an integral handle; null entries in `outs`
+ * to skip parts; orders above 2.  A new symbol: no new enumerator, no struct change. */
+ndi_status ndi_interp2d_eval_jet(const ndi_interp2d* h, int32_t order, const void* qx, const void* qy, uint64_t nq,
+                                 void* const* outs, uint64_t out_row_stride, const ndi_eval_opts* opts, ndi_oob_info* info);
 void ndi_interp2d_destroy(ndi_interp2d* h);
 
 /* A replica of a built interpolator on `device` (any device, the handle's own included): the device-resident knots /

@@ -18,7 +18,8 @@ from .interp1d import (Akima, AkimaStrategy, AntiderivativeStrategy, BoundaryCon
                        CubicSplineStrategy, DerivativeStrategy, Interp1D, Interp1DBuilder, Interp1DStrategy,
                        Interp1DStrategyBuilder, Linear,
                        Pchip, PchipStrategy, RowBoundary, SingleBoundary)
-from .interp2d import Bicubic, Bilinear, Interp2D, Interp2DBuilder, Interp2DStrategy, Interp2DStrategyBuilder
+from .interp2d import (JET_PARTS, Bicubic, Bilinear, Interp2D, Interp2DBuilder, Interp2DStrategy,
+                       Interp2DStrategyBuilder)
 from .vector_extensions import Locator, Monotonic, get_lower_index, monotonic_prop
 from . import sharding
 
@@ -50,7 +51,7 @@ __all__ = [
     "CubicSplineStrategy", "BoundaryCondition", "RowBoundary", "SingleBoundary",
     "Pchip", "PchipStrategy", "Akima", "AkimaStrategy", "CubicHermite", "CubicHermiteStrategy",
     "DerivativeStrategy", "AntiderivativeStrategy",
-    "Interp2D", "Interp2DBuilder", "Interp2DStrategy", "Interp2DStrategyBuilder", "Bilinear", "Bicubic",
+    "Interp2D", "Interp2DBuilder", "Interp2DStrategy", "Interp2DStrategyBuilder", "Bilinear", "Bicubic", "JET_PARTS",
     "Monotonic", "monotonic_prop", "get_lower_index", "Locator", "sharding", "device_count", "striped_ring", "output_empty", "output_zeros", "output_trim",
     "profile_enable", "profile_read", "PATH_AUTO", "PATH_GATHER", "PATH_BUCKETED",
 ]

@@ -108,6 +108,8 @@ SYMBOLS = {
     "ndi_interp2d_antiderivative": (C.c_int, [_P, C.POINTER(_P)]),
     "ndi_interp2d_integral": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(EvalOpts), C.POINTER(OobInfo)]),
     "ndi_interp2d_integral_tables": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32]),
+    "ndi_interp2d_eval_jet": (C.c_int, [_P, C.c_int32, _P, _P, C.c_uint64, C.POINTER(_P), C.c_uint64, C.POINTER(EvalOpts),
+                                        C.POINTER(OobInfo)]),
     "ndi_interp2d_destroy": (None, [_P]),
     "ndi_interp1d_clone": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),
     "ndi_interp2d_clone": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),

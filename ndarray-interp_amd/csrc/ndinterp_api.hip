@@ -33,6 +33,7 @@
 #include "antiderivative_kernels.hpp"
 #include "bicubic_kernels.hpp"
 #include "bicubic_integral_kernels.hpp"
+#include "bicubic_jet_kernels.hpp"
 
 #define NDI_API extern "C" __attribute__((visibility("default")))
 
@@ -2381,6 +2382,12 @@ struct Interp2DBase {
     return fail(NDI_BAD_ARG, "ndi_interp2d_integral_tables takes an integral handle (ndi_interp2d_antiderivative of a Bicubic "
                 "handle): this is a Bilinear handle");
   }
+  // ndi_interp2d_eval_jet: Bicubic surface handles only
+  virtual ndi_status eval_jet(int order, const void* qx, const void* qy, uint64_t nq, void* const* outs, uint64_t out_stride,
+                              const ndi_eval_opts* opts, ndi_oob_info* info) {
+    return fail(NDI_BAD_ARG, "Bilinear has no value-and-gradient (jet) evaluation: its slope jumps at every grid line and it "
+                "keeps no node derivatives (ndi_interp2d_eval_jet takes a Bicubic surface handle)");
+  }
 };
 
 template <class T>
@@ -2401,6 +2408,9 @@ template <class T>
 static ndi_status bicubic_integral_rect(Interp2DImpl<T>& h, const void* xa, const void* xb, const void* ya, const void* yb,
                                         uint64_t nq, void* out, uint64_t out_stride, const ndi_eval_opts* opts,
                                         ndi_oob_info* info);
+template <class T>
+static ndi_status bicubic_jet_eval(Interp2DImpl<T>& h, int order, const void* qx, const void* qy, uint64_t nq,
+                                   void* const* outs, uint64_t out_stride, const ndi_eval_opts* opts, ndi_oob_info* info);
 
 template <class T>
 struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
@@ -3450,6 +3460,18 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
                                                                                          : "Bicubic surface");
     return bicubic_integral_tables<T>(*this, dst, memspace);
   }
+  ndi_status eval_jet(int order, const void* qx, const void* qy, uint64_t nq, void* const* outs, uint64_t out_stride,
+                      const ndi_eval_opts* opts, ndi_oob_info* info) override {
+    if (!bicubic) return Interp2DBase::eval_jet(order, qx, qy, nq, outs, out_stride, opts, info);
+    if (integral)
+      return fail(NDI_BAD_ARG, "Bicubic: an integral handle has no value-and-gradient (jet) evaluation: its x-derivative is a "
+                  "y-integral of the surface, which is not provided (ndi_interp2d_eval_jet takes the surface handle)");
+    if (nu_x != 0 || nu_y != 0)
+      return fail(NDI_BAD_ARG, "Bicubic: a partial-derivative handle (orders (%d, %d)) has no value-and-gradient (jet) "
+                  "evaluation: a jet of a partial would need third orders, which jump at the grid lines "
+                  "(ndi_interp2d_eval_jet takes the surface handle)", nu_x, nu_y);
+    return bicubic_jet_eval<T>(*this, order, qx, qy, nq, outs, out_stride, opts, info);
+  }
 
   // Median time of `reps` launches of probe_gather_kernel over nq queries (see kernels.hpp).
   ndi_status probe_ceiling(uint64_t nq, void* out, uint64_t out_stride, void* stream, int reps, double* ms) override {
@@ -3568,6 +3590,7 @@ static ndi_status create2d(const ndi_interp2d_desc& d, Interp2DBase** out) {
 // ---------------------------------------------------------------------------------------------
 #include "bicubic_host.hpp"
 #include "bicubic_integral_host.hpp"
+#include "bicubic_jet_host.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // Locator: VectorExtensions::get_lower_index with the knot pyramid resident on the device
@@ -4243,6 +4266,19 @@ NDI_API ndi_status ndi_interp2d_integral_tables(const ndi_interp2d* h, void* pp,
   void* const dst[5] = {pp, qz, qzy, pz, pzx};
   if (!h->impl->integral) return h->impl->integral_tables(dst, memspace);
   return ndi::bounds_verdict(h->impl->integral_tables(dst, memspace), h->impl->device);
+  NDI_CATCH
+}
+
+// Every refusal is decided before any device work: the null checks here, the handle's kind in Interp2DImpl::eval_jet, the
+// rest at the top of bicubic_jet_eval.
+NDI_API ndi_status ndi_interp2d_eval_jet(const ndi_interp2d* h, int32_t order, const void* qx, const void* qy, uint64_t nq,
+                                         void* const* outs, uint64_t out_row_stride, const ndi_eval_opts* opts,
+                                         ndi_oob_info* info) {
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  if (!outs) return ndi::fail(NDI_BAD_ARG, "null outs pointer (ndi_interp2d_eval_jet takes a host array of part pointers)");
+  NDI_TRY
+  if (!h->impl->bicubic) return h->impl->eval_jet(order, qx, qy, nq, outs, out_row_stride, opts, info);
+  return ndi::bounds_verdict(h->impl->eval_jet(order, qx, qy, nq, outs, out_row_stride, opts, info), h->impl->device);
   NDI_CATCH
 }
 

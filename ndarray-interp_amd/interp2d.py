@@ -15,6 +15,11 @@ from .interp1d import (BoundaryCondition, RowBoundary, _check_out_dtype, _defaul
                        _to_device, _zeros)
 from .vector_extensions import Monotonic, get_lower_index, monotonic_prop
 
+# The parts of a jet (ndi_interp2d_eval_jet) in their fixed order, as (nu_x, nu_y): order 1 is the value and the gradient,
+# order 2 adds the three second derivatives.
+JET_PARTS = {1: ((0, 0), (1, 0), (0, 1)),
+             2: ((0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2))}
+
 
 class Interp2DStrategyBuilder:
     """Trait `Interp2DStrategyBuilder` (src/interp2d/strategies/mod.rs:14-44)."""
@@ -280,6 +285,10 @@ class Bilinear(Interp2DStrategyBuilder, _DeviceStrategy2D):
         raise TypeError("Bilinear has no rectangle integral: 2-D integrals are Bicubic's (Bicubic.antiderivative, then "
                         "integral)")
 
+    def jet_into(self, *a, **kw):
+        raise TypeError("Bilinear has no value-and-gradient (jet) evaluation: its slope jumps at every grid line and it "
+                        "keeps no node derivatives (Bicubic.jet_into gives the value and the partials in one call)")
+
     def probe_ceiling(self, out2d, reps=5) -> float:
         """ms of the evaluation kernel's memory access mix alone on this handle's grid (ndi_interp2d_probe_ceiling);
         `out2d`: a device tensor (nq, lanes) that is overwritten."""
@@ -451,6 +460,84 @@ class Bicubic(Interp2DStrategyBuilder, _DeviceStrategy2D):
         info = _capi.OobInfo()
         st = _capi.lib().ndi_interp2d_integral(self._h, q[0].ptr, q[1].ptr, q[2].ptr, q[3].ptr, q[0].size, optr,
                                                max(stride, self._lanes), C.byref(opts), C.byref(info))
+        if st != _capi.OK:
+            raise_eval(st, info, None)
+
+    def _jet_parts(self, order, n_buffers=None) -> int:
+        """The refusals of a jet call that come before the library is reached; returns K, the number of parts."""
+        import operator
+        if self.is_integral:
+            raise ValueError("Bicubic.jet_into: an integral strategy has no value-and-gradient (jet) evaluation: its "
+                             "x-derivative is a y-integral of the surface, which is not provided; ask the surface's strategy")
+        if self.orders != (0, 0):
+            raise ValueError(f"Bicubic.jet_into: a partial-derivative strategy (orders {self.orders}) has no jet: a jet of a "
+                             "partial would need third orders, which jump at the grid lines; ask the surface's strategy")
+        if order is None and n_buffers is not None:
+            order = {len(p): o for o, p in JET_PARTS.items()}.get(n_buffers)
+            if order is None:
+                raise ValueError(f"Bicubic.jet_into: {n_buffers} output buffers select no order: order 1 writes "
+                                 f"{len(JET_PARTS[1])} parts, order 2 writes {len(JET_PARTS[2])}")
+        try:
+            order = operator.index(order)
+        except TypeError:
+            raise TypeError(f"Bicubic.jet_into: the order is an integer, got {type(order).__name__}") from None
+        if order not in JET_PARTS:
+            raise ValueError(f"Bicubic.jet_into: order {order}; a jet has order 1 (value and gradient) or 2 (with the three "
+                             "second derivatives): the third derivative of a cubic spline jumps at the grid lines")
+        if n_buffers is not None and n_buffers != len(JET_PARTS[order]):
+            raise ValueError(f"Bicubic.jet_into: order {order} writes {len(JET_PARTS[order])} parts, got {n_buffers} output "
+                             "buffers (parts cannot be skipped)")
+        if self._h is None:
+            from .errors import DeviceError
+            raise DeviceError("Bicubic.jet_into needs a built strategy: the node table lives on the device and the jet is "
+                              "evaluated there; there is no CPU fallback")
+        return order
+
+    def jet_into(self, xs_flat, ys_flat, outs, *, order=None, fresh=False):
+        """The surface and its partial derivatives up to `order` at the same queries in ONE evaluation
+        (ndi_interp2d_eval_jet): `outs` is a sequence of K = 3 (order 1) or 6 (order 2) buffers (nq, lanes), part k being
+        the partial of orders JET_PARTS[order][k] -- bit for bit the rows `partial(nu_x, nu_y)` evaluates.  `order` is
+        inferred from len(outs) when not given.  The buffers are numpy arrays (host) or torch tensors on the device, all
+        in one memory space and of the data's dtype; their rows need not be contiguous with each other, but all K buffers
+        share ONE row stride (planar and interleaved layouts both do)."""
+        outs = list(outs)
+        order = self._jet_parts(order, len(outs))
+        qx = Buf(xs_flat, self._np_dtype)
+        qy = Buf(ys_flat, self._np_dtype)
+        if qx.memspace != qy.memspace:
+            raise TypeError("xs and ys must live in the same memory space")
+        if len({is_torch(o) for o in outs}) != 1:
+            raise TypeError("Bicubic.jet_into: the output buffers must live in one memory space (all numpy host arrays or "
+                            "all torch device tensors)")
+        on_dev = is_torch(outs[0])
+        strides, ptrs = [], []
+        for k, o in enumerate(outs):
+            _check_out_dtype(o, self._np_dtype)
+            if on_dev and not o.is_cuda:
+                raise TypeError("torch output buffers must live on the device; use numpy for host buffers")
+            if len(o.shape) != 2 or tuple(o.shape) != (qx.size, self._lanes):
+                raise ValueError(f"Bicubic.jet_into: buffer {k} has shape {tuple(o.shape)}, expected "
+                                 f"{(qx.size, self._lanes)} (queries, lanes)")
+            st = o.stride() if on_dev else tuple(b // o.itemsize for b in o.strides)
+            if self._lanes > 1 and qx.size > 0 and st[1] != 1:
+                raise ValueError(f"Bicubic.jet_into: buffer {k} has element strides {tuple(st)}: the lanes of a row must be "
+                                 "contiguous")
+            strides.append(st[0] if qx.size > 1 else self._lanes)
+            ptrs.append(o.data_ptr() if on_dev else o.ctypes.data)
+        if len(set(strides)) != 1 or strides[0] < self._lanes:
+            raise ValueError(f"Bicubic.jet_into: the buffers must share one row stride >= lanes ({self._lanes}), got row "
+                             f"strides {strides}")
+        opts = _capi.EvalOpts()
+        opts.q_memspace = qx.memspace
+        opts.path = self.path
+        opts.flags = _capi.EVAL_FRESH_OUTPUT if fresh else _capi.EVAL_DEFAULT
+        opts.out_memspace = _capi.MEM_DEVICE if on_dev else _capi.MEM_HOST
+        if on_dev or qx.memspace == _capi.MEM_DEVICE:
+            opts.stream = current_stream_ptr(self._device)
+        arr = (C.c_void_p * len(ptrs))(*ptrs)
+        info = _capi.OobInfo()
+        st = _capi.lib().ndi_interp2d_eval_jet(self._h, order, qx.ptr, qy.ptr, qx.size, arr, strides[0], C.byref(opts),
+                                               C.byref(info))
         if st != _capi.OK:
             raise_eval(st, info, None)
 
@@ -667,6 +754,94 @@ class Interp2D:
             zs = np.zeros(shape, dtype=dt)
             strat.integral(*[b.reshape(-1) for b in flat], zs.reshape(nq, lanes), fresh=True)
         return zs
+
+    def _jet_strategy(self, what):
+        if not hasattr(self.strategy, "jet_into"):
+            raise TypeError(f"Interp2D.{what} needs a built Bicubic strategy (f32 / f64 data), got "
+                            f"{type(self.strategy).__name__}")
+        if not isinstance(self.strategy, Bicubic):
+            self.strategy.jet_into()      # Bilinear: the TypeError naming the strategy
+        return self.strategy
+
+    def jet(self, xs, ys, order=1):
+        """The surface and its partial derivatives up to `order` (1 or 2) at the queries, in ONE evaluation
+        (`Bicubic.jet_into`): a tuple of K = 3 or 6 arrays in the order of JET_PARTS[order], each of shape
+        `xs.shape ++ trailing data shape` and equal, bit for bit, to `partial(nu_x, nu_y).interp_array(xs, ys)` (part 0 to
+        `interp_array(xs, ys)`).  They are views of one allocation of shape (K, ...): a torch tensor on the queries' device
+        for device queries, a numpy array otherwise.  Panics when `xs.shape != ys.shape`."""
+        strat = self._jet_strategy("jet")
+        order = strat._jet_parts(order)
+        if tuple(xs.shape) != tuple(ys.shape):
+            raise Panic("`xs.shape()` and `ys.shape()` do not match")
+        K = len(JET_PARTS[order])
+        shape = self.get_buffer_shape(tuple(xs.shape))
+        dt = np_dtype_of(self.data)
+        nq = int(np.prod(xs.shape, dtype=np.int64))
+        lanes = int(np.prod(self._lanes_shape(), dtype=np.int64))
+        if is_torch(xs) and xs.is_cuda:
+            import torch
+            zs = torch.empty((K,) + shape, dtype=torch_dtype(dt), device=xs.device)
+            xf, yf, flat = xs.reshape(-1), ys.reshape(-1), zs.view(K, nq, lanes)
+        else:
+            zs = np.zeros((K,) + shape, dtype=dt)
+            xf, yf, flat = _host(xs).reshape(-1), _host(ys).reshape(-1), zs.reshape(K, nq, lanes)
+        strat.jet_into(xf, yf, [flat[k] for k in range(K)], order=order, fresh=True)
+        return tuple(zs[k] for k in range(K))
+
+    def value_and_gradient(self, xs, ys):
+        """(z, dz/dx, dz/dy) at the queries in one evaluation: `jet(xs, ys, 1)`."""
+        return self.jet(xs, ys, 1)
+
+    def jet_into(self, xs, ys, buffers):
+        """`jet` into K = 3 (order 1) or 6 (order 2) caller-owned buffers, each of the shape and dtype `interp_array_into`
+        takes, with its semantics: if a query fails, the rows before it are written in every buffer and the rows from it
+        on are left untouched in every buffer."""
+        strat = self._jet_strategy("jet_into")
+        buffers = list(buffers)
+        order = strat._jet_parts(None, len(buffers))
+        if tuple(xs.shape) != tuple(ys.shape):
+            raise Panic("`xs.shape()` and `ys.shape()` do not match")
+        expect = self.get_buffer_shape(tuple(xs.shape))
+        dt = np_dtype_of(self.data)
+        for b in buffers:
+            if tuple(b.shape) != expect:
+                raise Panic(f"ShapeError/IncompatibleShape: incompatible shapes expected: {list(expect)}, "
+                            f"got: {list(b.shape)}")
+            if np_dtype_of(b) != dt:
+                raise TypeError(f"buffer has element type {np_dtype_of(b)}, the data is {dt}")
+        if len({is_torch(b) for b in buffers}) != 1:
+            raise TypeError("Interp2D.jet_into: the buffers must live in one memory space (all numpy host arrays or all "
+                            "torch device tensors)")
+        nq = int(np.prod(xs.shape, dtype=np.int64))
+        lanes = int(np.prod(self._lanes_shape(), dtype=np.int64))
+        xf, yf = xs.reshape(-1), ys.reshape(-1)
+        if is_torch(buffers[0]):
+            if not all(b.is_contiguous() for b in buffers):
+                raise TypeError("device output buffers must be contiguous")
+            strat.jet_into(xf, yf, [b.view(nq, lanes) for b in buffers], order=order)
+            return
+        if not is_torch(xs):
+            xf, yf = _host(xf), _host(yf)
+        if all(b.flags.c_contiguous for b in buffers):
+            strat.jet_into(xf, yf, [b.reshape(nq, lanes) for b in buffers], order=order)
+            return
+        tmp = np.zeros((len(buffers), nq, lanes), dtype=dt)
+        done = nq
+        try:
+            strat.jet_into(xf, yf, list(tmp), order=order)
+        except (InterpolateError.OutOfBounds, Panic) as e:
+            done = e.index if getattr(e, "index", None) is not None else 0   # as interp_array_into: rows before the failure
+            raise
+        except BaseException:
+            done = 0
+            raise
+        finally:
+            for b, t in zip(buffers, tmp):
+                if done and len(xs.shape) == 0:
+                    b[...] = t[0].reshape(b.shape)
+                elif done:
+                    where = np.unravel_index(np.arange(done), tuple(xs.shape))
+                    b[where] = t[:done].reshape((done,) + self._lanes_shape())
 
     def replicate(self, devices):
         """Replicas of this interpolator on the given devices (see Interp1D.replicate)."""

@@ -261,6 +261,17 @@ extern "C" {
         pzx: *mut c_void,
         memspace: i32,
     ) -> i32;
+    pub fn ndi_interp2d_eval_jet(
+        h: *const ndi_interp2d,
+        order: i32,
+        qx: *const c_void,
+        qy: *const c_void,
+        nq: u64,
+        outs: *const *mut c_void,
+        out_row_stride: u64,
+        opts: *const ndi_eval_opts,
+        info: *mut ndi_oob_info,
+    ) -> i32;
     pub fn ndi_interp2d_destroy(h: *mut ndi_interp2d);
     pub fn ndi_interp1d_clone(h: *const ndi_interp1d, device: i32, out: *mut *mut ndi_interp1d) -> i32;
     pub fn ndi_interp2d_clone(h: *const ndi_interp2d, device: i32, out: *mut *mut ndi_interp2d) -> i32;

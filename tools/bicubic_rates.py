@@ -25,6 +25,15 @@ beside the value handle's and a rectangle batch beside the F batch (two alternat
 is the margin); the profiled run evaluates all three, and the merge tells eval_bicubic_kernel, the F instance and the
 rectangle instance of eval_bicubic_integral_kernel apart by their names.  By bytes F is 26 / 17 of the value (25 operands
 and a store against 16 and a store); a rectangle is at most four times F's reads for one store.
+
+The fused value-and-gradient call (output committed as profiles/bicubic_jet_rates.json): the same three steps
+with `--jet ORDER` in each, on 4.13's four shapes in f32 and f64.  The timing pass runs alternating rounds of (a) ONE jet call
+and (b) the K separate handle calls (the value handle and its K - 1 partial handles) into K buffers, all on device queries
+and fresh device outputs, checks that (a) and (b) wrote the same bits at the timed size, and records the two rounds of each
+(the ratio of (b)'s two rounds is the spread).  The profiled run does both again; the merge sums the K instances of
+eval_bicubic_kernel against the one of eval_bicubic_jet_kernel, and writes their ratio beside the byte-model ratio
+17 K / (16 + K), the jet's fraction of 8 TB/s on (16 + K) Q C sizeof(T) and whether the jet is below the separate calls by
+more than the spread.  Both orders share the output file (one entry per order).
 """
 import argparse
 import csv
@@ -266,6 +275,129 @@ def integral_merge(prof_dir, out_path):
     json.dump(res, open(out_path, "w"), indent=1)
 
 
+JET_SHAPES = [(name, nx, ny, C) for nx, ny, C in ((100, 100, 1), (100, 100, 5), (2048, 2048, 64), (4096, 4096, 16))
+              for name in ("f32", "f64")]
+JET_BEYOND_CACHE = ((2048, 2048, 64), (4096, 4096, 16))     # where 4.13 expects the operand loads to bound the kernel
+
+
+def jet_queries(dt, C):
+    """enough queries that one jet call moves about 24 GB by the byte model (3 ms at 8 TB/s), between 1e6 and 4e7"""
+    return int(min(40_000_000, max(1_000_000, 24e9 // (19 * C * np.dtype(dt).itemsize))))
+
+
+def jet_setup(name, nx, ny, C, order):
+    """the value handle and its partial handles in the order of JET_PARTS, device queries, a planar jet buffer (K, nq, C) and
+    K separate buffers"""
+    import torch
+    pkg = package()
+    dt = DTYPES[name]
+    tdt = torch.float32 if name == "f32" else torch.float64
+    rng = np.random.default_rng(nx + ny + C)
+    x = np.cumsum(rng.uniform(0.5, 1.5, nx)).astype(dt)
+    y = np.cumsum(rng.uniform(0.5, 1.5, ny)).astype(dt)
+    gen = torch.Generator(device="cuda:0").manual_seed(nx + ny + C)
+    z = torch.rand((nx, ny, C), dtype=tdt, device="cuda:0", generator=gen)
+    nq = jet_queries(dt, C)
+    span = lambda k: (float(k[0]) + (float(k[-1]) - float(k[0])) * torch.rand(nq, dtype=torch.float64, device="cuda:0",  # noqa: E731
+                                                                             generator=gen)).to(tdt).clamp(float(k[0]), float(k[-1]))
+    qx, qy = span(x), span(y)
+    value = pkg.Interp2DBuilder.new(z).x(torch.as_tensor(x, device="cuda:0")).y(torch.as_tensor(y, device="cuda:0")) \
+        .strategy(pkg.Bicubic.new()).build()
+    handles = [value if nu == (0, 0) else value.partial(*nu) for nu in pkg.JET_PARTS[order]]
+    K = len(handles)
+    jet = torch.empty((K, nq, C), dtype=tdt, device="cuda:0")
+    sep = [torch.empty((nq, C), dtype=tdt, device="cuda:0") for _ in range(K)]
+    parts = [jet[k] for k in range(K)]
+
+    def run_jet():
+        value.strategy.jet_into(qx, qy, parts, order=order, fresh=True)
+
+    def run_separate():
+        for h, buf in zip(handles, sep):
+            h.interp_array_into(qx, qy, buf, fresh=True)
+    return dict(nq=nq, K=K, jet=jet, sep=sep, run_jet=run_jet, run_separate=run_separate)
+
+
+def jet_timing_pass(out_path, order):
+    import torch
+    pkg = package()
+    assert torch.cuda.is_available() and pkg.device_count() >= 1, "needs a GPU"
+    res = json.load(open(out_path)) if os.path.exists(out_path) else {}
+    res["device"] = torch.cuda.get_device_name(0)
+    mine = res.setdefault(f"order_{order}", {})
+    mine["parts"] = [list(nu) for nu in pkg.JET_PARTS[order]]
+    mine["eval_ms"] = {}
+    for name, nx, ny, C in JET_SHAPES:
+        key = f"{name}_{nx}x{ny}x{C}"
+        s = jet_setup(name, nx, ny, C, order)
+        entry = {"queries": s["nq"]}
+        for rnd in range(2):               # alternate the two: the separate calls' two rounds give the spread
+            for what, fn in (("jet", s["run_jet"]), ("separate", s["run_separate"])):
+                med, lo, hi = median_ms(fn)
+                entry[f"{what}_round{rnd}"] = {"median": med, "min": lo, "max": hi}
+        bits = torch.int32 if name == "f32" else torch.int64
+        entry["bit_equal_parts"] = [bool(torch.equal(s["jet"][k].view(bits), s["sep"][k].view(bits))) for k in range(s["K"])]
+        entry["wall_ratio_separate_over_jet"] = entry["separate_round1"]["median"] / entry["jet_round1"]["median"]
+        entry["spread_of_separate_rounds"] = entry["separate_round0"]["median"] / entry["separate_round1"]["median"]
+        mine["eval_ms"][key] = entry
+        print(key, json.dumps(entry), flush=True)
+        del s
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    json.dump(res, open(out_path, "w"), indent=1)
+
+
+def jet_profile_shape(name, nx, ny, C, order):
+    import torch
+    assert torch.cuda.is_available(), "needs a GPU"
+    s = jet_setup(name, nx, ny, C, order)
+    for fn in (s["run_jet"], s["run_separate"]):
+        for _ in range(REPS):
+            fn()
+    torch.cuda.synchronize()
+    print("profiled", name, nx, ny, C, "jet", order, flush=True)
+
+
+def jet_merge(prof_dir, out_path, order):
+    """eval_bicubic_jet_kernel<..., ORDER> (one launch per batch) against the K instances eval_bicubic_kernel<..., NUX, NUY>"""
+    res = json.load(open(out_path)) if os.path.exists(out_path) else {}
+    mine = res.setdefault(f"order_{order}", {})
+    mine["eval_kernels"] = {}
+    K = 3 if order == 1 else 6
+    for name, nx, ny, C in JET_SHAPES:
+        key = f"{name}_{nx}x{ny}x{C}"
+        files = glob.glob(os.path.join(prof_dir, key, "**", "*kernel_stats.csv"), recursive=True)
+        if not files:
+            continue
+        per, names = {"jet": 0.0, "separate": 0.0}, {"jet": [], "separate": []}
+        for row in csv.DictReader(open(files[0])):
+            kn = row["Name"].split("(")[0].strip()
+            if "eval_bicubic_jet_kernel" in kn:
+                who = "jet"
+            elif "eval_bicubic_kernel" in kn:
+                who = "separate"
+            else:
+                continue                 # builds, fills
+            per[who] += float(row["TotalDurationNs"]) / REPS
+            names[who].append(kn)
+        nq, size = jet_queries(DTYPES[name], C), np.dtype(DTYPES[name]).itemsize
+        entry = {"queries": nq, "compulsory_bytes_jet": (16 + K) * nq * C * size, "byte_model_ratio": 17 * K / (16 + K),
+                 "beyond_cache": (nx, ny, C) in JET_BEYOND_CACHE}
+        for who, ns in per.items():
+            entry[who] = {"kernel_ms_per_batch": ns / 1e6, "kernels": sorted(set(names[who]))}
+        wall = mine.get("eval_ms", {}).get(key)
+        if per["jet"] > 0 and per["separate"] > 0:
+            entry["ratio_separate_over_jet"] = per["separate"] / per["jet"]
+            entry["jet_fraction_of_8TBps"] = entry["compulsory_bytes_jet"] / (per["jet"] * 1e-9) / PEAK_BPS
+            if wall:
+                spread = abs(wall["spread_of_separate_rounds"] - 1.0)
+                entry["spread_of_separate_rounds"] = wall["spread_of_separate_rounds"]
+                entry["jet_below_separate_by_more_than_the_spread"] = bool(per["jet"] < per["separate"] * (1.0 - spread))
+        mine["eval_kernels"][key] = entry
+        print(key, json.dumps(entry), flush=True)
+    json.dump(res, open(out_path, "w"), indent=1)
+
+
 def profile_shape(name, nx, ny, C):
     pkg = package()
     x, y, z, qx, qy, out = inputs(name, nx, ny, C)
@@ -314,13 +446,22 @@ if __name__ == "__main__":
     ap.add_argument("--partial", metavar="NUX,NUY", type=orders_of,
                     help="time a partial-derivative handle of these orders beside the value handle")
     ap.add_argument("--integral", action="store_true", help="time the integral handle beside the value handle")
+    ap.add_argument("--jet", metavar="ORDER", type=int, choices=(1, 2),
+                    help="time one fused jet call of this order beside the K separate handle calls")
     ap.add_argument("--profile-shape", nargs=4, metavar=("DTYPE", "NX", "NY", "C"))
     ap.add_argument("--merge", metavar="DIR")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "bicubic_integral_rates.json" if a.integral else
+        a.out = os.path.join(ROOT, "profiles", "bicubic_jet_rates.json" if a.jet else
+                             "bicubic_integral_rates.json" if a.integral else
                              "bicubic_partial_rates.json" if a.partial else "bicubic_rates.json")
-    if a.integral and a.profile_shape:
+    if a.jet and a.profile_shape:
+        jet_profile_shape(a.profile_shape[0], *(int(v) for v in a.profile_shape[1:]), a.jet)
+    elif a.jet and a.merge:
+        jet_merge(a.merge, a.out, a.jet)
+    elif a.jet:
+        jet_timing_pass(a.out, a.jet)
+    elif a.integral and a.profile_shape:
         integral_profile_shape(a.profile_shape[0], *(int(v) for v in a.profile_shape[1:]))
     elif a.integral and a.merge:
         integral_merge(a.merge, a.out)
