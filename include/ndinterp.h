@@ -2,7 +2,8 @@
  *
  * Drop-in boundary for the batched `interp_array` hot path of the Rust crate
  * ndarray-interp v0.6.0 (1D Linear, 1D CubicSpline, 2D Bilinear), plus a 2D Bicubic strategy
- * (ndi_interp2d_create_bicubic) and three 1D strategies the
+ * (ndi_interp2d_create_bicubic; with Pchip, Akima or caller-given node derivatives: ndi_interp2d_create_bicubic_local,
+ * ndi_interp2d_create_bicubic_hermite) and three 1D strategies the
  * reference leaves to user code: Pchip, Akima and CubicHermite (ndi_strategy1d), and first / second
  * derivatives of the four cubics as handles of their own (ndi_interp1d_derivative), and antiderivatives / definite
  * integrals of every f32 / f64 1D interpolant (ndi_interp1d_antiderivative, ndi_interp1d_integrate).  The reference
@@ -316,7 +317,34 @@ typedef struct ndi_interp2d_desc {
  *  with Pm = the four y-forms H_m(..., hy, u) of the sixteen operands:  (0,0) = H0(P0, hx, t)   (1,0) = H1(P0, hx, t)
  *  (0,1) = H0(P1, hx, t)   (2,0) = H2(P0, hx, t)   (1,1) = H1(P1, hx, t)   (0,2) = H0(P2, hx, t).  Cell, t, u, hx, hy, the
  *  range test, the NaN rule and `extrapolate` are the Bicubic handle's.
- * Not provided: periodic and per-lane boundaries, Pchip / Akima node derivatives, integrals of Bilinear or of partial
+ * Local rules and caller-given node derivatives (ndi_interp2d_create_bicubic_local, ndi_interp2d_create_bicubic_hermite):
+ * the same Bicubic handle with the node derivatives chosen differently, as NDI_PCHIP / NDI_AKIMA / NDI_CUBIC_HERMITE choose
+ * k differently in 1-D.  Numerical contract -- this project's own.  Let k = RULE(knots, columns) be the knot-derivative
+ * rule exactly as ndi_strategy1d states it for NDI_PCHIP / NDI_AKIMA: every line one IEEE operation in T, in that order,
+ * nothing fused, n == 2, the sgn rule, the +0 rule and the exact s == 0 included.  One rule serves both axes of a handle:
+ *     zx  = RULE(x, .) on z viewed as (nx, ny C)
+ *     zy  = RULE(y, .) on each z[i] viewed as (ny, C)
+ *     zxy = RULE(y, .) on each zx[i] viewed as (ny, C)        (the "cross" composition of the spline Bicubic)
+ *  For the hermite call zx, zy, zxy are the caller's arrays and no rule is applied; ndi_interp2d_tables hands them back bit
+ *  for bit.  Evaluation, partials, jet, F and rectangle integrals are the formulas above on that table, character for
+ *  character: there are no new evaluation formulas and no new evaluation kernels.
+ *  Grid-line property: on a grid line x = x[i] the surface is, bit for bit for finite tables, the 1-D strategy's interpolant
+ *  of the column z[i][:] (t == 0; t == 1 on the last line), and likewise along y.  Pchip therefore does not overshoot
+ *  ALONG GRID LINES.  Monotonicity INSIDE a cell is NOT promised: the tensor composition of a monotone rule is not monotone
+ *  in 2-D, and a cell's interior may leave the range of its four corners.
+ *  Smoothness and partials: these surfaces are C1, not C2.  Partial handles of order 2 in a variable are piecewise and JUMP at
+ *  the grid lines of that variable; a query on an interior line takes the cell to its right / above, as always.  The 1-D
+ *  derivative handles offer "Pchip, Akima, CubicHermite (C1)  nu = 1" only, for the reason ndi_interp1d_derivative states:
+ *  "a table holds one value per knot, so only a derivative that is continuous at the knots".  That reason does not bind here:
+ *  a 2-D partial handle keeps no derivative table, it evaluates H_nu on the shared node table per cell, so
+ *  ndi_interp2d_partial (every order of the spline handle), ndi_interp2d_eval_jet order 2 and the integral handles stay
+ *  allowed, and the jump is the documented behaviour.
+ *  Minimum points per axis: Pchip 2, Akima 3, caller-given 2.  Non-finite data is not refused; it flows through as IEEE
+ *  values, as in 1-D.  The handle is a Bicubic handle in every other respect: every entry point, the AUTO / GATHER rule and
+ *  the BUCKETED refusal, and the replica signature (the rule is not part of it, just as the boundary kinds are not).
+ *  Device memory: the node table and the two knot axes; the build is a stencil that writes the table directly and keeps no
+ *  grid-sized temporary beyond the uploaded z (host data), or the four uploaded arrays of the hermite call.
+ * Not provided: periodic and per-lane boundaries, a different rule per axis, integrals of Bilinear or of partial
  * handles, partials of an integral handle, a second antiderivative, a ring / sharded / async_launch form of the four-array
  * rectangle call and of the jet call, a jet of a partial or of an integral handle, null entries in the jet's `outs` to skip
  * parts, jet orders above 2, third derivatives, a tile-grouped evaluation form, a blocked-sweep build for narrow grids,
@@ -385,6 +413,18 @@ ndi_status ndi_interp2d_create(const ndi_interp2d_desc* desc, ndi_interp2d** out
 /* The Bicubic strategy (contract above ndi_interp1d).  `bc`: four boundaries in the order x-left, x-right, y-left, y-right,
  * or NULL for NotAKnot on all four.  A new symbol; ndi_interp2d_desc keeps its layout. */
 ndi_status ndi_interp2d_create_bicubic(const ndi_interp2d_desc* desc, const ndi_boundary* bc, ndi_interp2d** out);
+/* Bicubic with the node derivatives of a local rule (contract above ndi_interp1d).  rule: NDI_PCHIP or NDI_AKIMA
+ * (ndi_strategy1d), the same on both axes.  Refused before any device work, *out cleared first, the message naming the
+ * strategy and the reason: NDI_BAD_ARG for a null `desc` or `out`, any other rule, integer and f16 / bf16 dtypes;
+ * NDI_NOT_ENOUGH_DATA for fewer than 2 (Pchip) / 3 (Akima) points on an axis; `validate` as in
+ * ndi_interp2d_create_bicubic.  Built on the NULL stream, complete on return.  A new symbol: no new enumerator, no struct
+ * change. */
+ndi_status ndi_interp2d_create_bicubic_local(const ndi_interp2d_desc* desc, int32_t rule, ndi_interp2d** out);
+/* Bicubic with the caller's node derivatives: zx, zy, zxy are T[nx][ny][lanes] in desc->memspace, laid out like the data; no
+ * rule is applied (the 2-D counterpart of ndi_interp1d_create_hermite; ndi_interp2d_tables of another handle gives such
+ * arrays).  At least 2 points per axis.  Refusals as above, and NDI_BAD_ARG for a null table. */
+ndi_status ndi_interp2d_create_bicubic_hermite(const ndi_interp2d_desc* desc, const void* zx, const void* zy,
+                                               const void* zxy, ndi_interp2d** out);
 /* The node derivatives of a Bicubic handle as plain T[nx][ny][lanes] arrays, whatever the internal layout (any of the three
  * may be NULL): the 2-D counterpart of ndi_interp1d_coefficients.  NDI_BAD_ARG for a Bilinear handle. */
 ndi_status ndi_interp2d_tables(const ndi_interp2d* h, void* zx, void* zy, void* zxy, int32_t memspace);

@@ -74,6 +74,16 @@ __device__ __forceinline__ T akima_knot(T mm2, T mm1, T m0, T mp1) {
   return (w1 * mm1 + w2 * m0) / s;
 }
 
+// Akima's end extension for the window of interval i: m[w] = m_{i-2+w}, the data's slopes where 0 <= i-2+w <= n-2, else the
+// linear extension, formed outwards.  (Shared with the 2-D node build, bicubic_local_kernels.hpp.)
+template <class T>
+__device__ __forceinline__ void akima_extend(T (&m)[5], uint64_t i, uint64_t n) {
+  if (i + 1 < 2) m[1] = (m[2] + m[2]) - m[3];          // m_{-1}
+  if (i + 0 < 2) m[0] = (m[1] + m[1]) - m[2];          // m_{-1} (i == 1) or m_{-2} (i == 0)
+  if (i + 3 > n) m[3] = (m[2] + m[2]) - m[1];          // m_{n-1}
+  if (i + 4 > n) m[4] = (m[3] + m[3]) - m[2];          // m_{n-1} (i == n-3) or m_n (i == n-2)
+}
+
 // One table entry: interval i, lanes [lv * VN, lv * VN + VN).  Reads rows i - HALO .. i + 1 + HALO where they exist
 // (the neighbouring rows are other threads' own rows: they come from L2), forms k_i and k_{i+1}, writes a_i, b_i.
 template <class T, int RULE, int VN>
@@ -123,14 +133,10 @@ __device__ __forceinline__ void hermite_entry(const HermiteArgs<T>& A, uint64_t 
           r1 = i + 2 == n ? pchip_edge(h[1], h[0], d1, d0) : pchip_interior(h[1], h[2], d1, d2);
         }
       } else {
-        // m[w] = m_{i-2+w}: the data's slopes where 0 <= i-2+w <= n-2, else the linear extension, formed outwards
         T m[5];
 #pragma unroll
         for (int w = 0; w < 5; ++w) m[w] = hermite_get<T, VN>(dl[w], c);
-        if (i + 1 < 2) m[1] = (m[2] + m[2]) - m[3];          // m_{-1}
-        if (i + 0 < 2) m[0] = (m[1] + m[1]) - m[2];          // m_{-1} (i == 1) or m_{-2} (i == 0)
-        if (i + 3 > n) m[3] = (m[2] + m[2]) - m[1];          // m_{n-1}
-        if (i + 4 > n) m[4] = (m[3] + m[3]) - m[2];          // m_{n-1} (i == n-3) or m_n (i == n-2)
+        akima_extend(m, i, n);
         r0 = akima_knot(m[0], m[1], m[2], m[3]);
         r1 = akima_knot(m[1], m[2], m[3], m[4]);
       }

@@ -32,6 +32,7 @@
 #include "derivative_kernels.hpp"
 #include "antiderivative_kernels.hpp"
 #include "bicubic_kernels.hpp"
+#include "bicubic_local_kernels.hpp"
 #include "bicubic_integral_kernels.hpp"
 #include "bicubic_jet_kernels.hpp"
 
@@ -3589,6 +3590,7 @@ static ndi_status create2d(const ndi_interp2d_desc& d, Interp2DBase** out) {
 // Interp2D Bicubic: build, launch and table read-back
 // ---------------------------------------------------------------------------------------------
 #include "bicubic_host.hpp"
+#include "bicubic_local_host.hpp"
 #include "bicubic_integral_host.hpp"
 #include "bicubic_jet_host.hpp"
 
@@ -4207,6 +4209,58 @@ NDI_API ndi_status ndi_interp2d_create_bicubic(const ndi_interp2d_desc* desc, co
   *out = new ndi_interp2d{impl};
   return ndi::bounds_verdict(NDI_OK, impl->device);
   NDI_CATCH
+}
+
+// The Bicubic handles of a local rule (Pchip, Akima) and of caller-given node derivatives: bicubic_local_host.hpp.
+// Every refusal is decided before any device work.  `rule`: HR_PCHIP, HR_AKIMA or HR_GIVEN.
+static ndi_status create_bicubic_local(const char* name, const ndi_interp2d_desc* desc, int rule, const void* zx, const void* zy,
+                                       const void* zxy, ndi_interp2d** out) {
+  if (desc->dtype < NDI_F32 || desc->dtype > NDI_BF16) return ndi::fail(NDI_BAD_ARG, "unknown dtype");
+  if (desc->dtype == NDI_I32 || desc->dtype == NDI_I64)
+    return ndi::fail(NDI_BAD_ARG, "Bicubic (%s) needs a float element type (f32 / f64): the rule divides; integer data takes "
+                     "Bilinear", name);
+  if (desc->dtype == NDI_F16 || desc->dtype == NDI_BF16)
+    return ndi::fail(NDI_BAD_ARG, "Bicubic (%s) needs f32 / f64: the node build has no half-precision form; f16 / bf16 data "
+                     "takes Bilinear", name);
+  if (rule == ndi::HR_GIVEN && (!zx || !zy || !zxy))
+    return ndi::fail(NDI_BAD_ARG, "Bicubic (%s) needs all three node derivative tables: %s is null", name,
+                     !zx ? "zx" : !zy ? "zy" : "zxy");
+  if (desc->validate && desc->memspace == NDI_MEM_HOST && desc->x && desc->y) {
+    ndi_status st = ndi_validate2d(desc->dtype, desc->x, desc->x_len, desc->y, desc->y_len, desc->nx, desc->ny);
+    if (st != NDI_OK) return st;
+  }
+  const unsigned long long need = rule == ndi::HR_AKIMA ? 3 : 2;
+  if (desc->nx < need || desc->ny < need)
+    return ndi::fail(NDI_NOT_ENOUGH_DATA, "Bicubic (%s) needs at least %llu data points on each axis (got %llu x %llu)", name,
+                     need, (unsigned long long)desc->nx, (unsigned long long)desc->ny);
+  ndi_status ds = need_device(desc->device);
+  if (ds != NDI_OK) return ds;
+  NDI_TRY
+  ndi::Interp2DBase* impl = nullptr;
+  ndi_status st = desc->dtype == NDI_F32 ? ndi::create2d_bicubic_local<float>(*desc, rule, zx, zy, zxy, &impl)
+                                         : ndi::create2d_bicubic_local<double>(*desc, rule, zx, zy, zxy, &impl);
+  if (st != NDI_OK) return st;
+  *out = new ndi_interp2d{impl};
+  return ndi::bounds_verdict(NDI_OK, impl->device);
+  NDI_CATCH
+}
+
+NDI_API ndi_status ndi_interp2d_create_bicubic_local(const ndi_interp2d_desc* desc, int32_t rule, ndi_interp2d** out) {
+  if (!desc || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
+  *out = nullptr;
+  if (rule != NDI_PCHIP && rule != NDI_AKIMA)
+    return ndi::fail(NDI_BAD_ARG, "Bicubic (local rule) takes NDI_PCHIP or NDI_AKIMA as its rule (ndi_strategy1d), got %d: the "
+                     "spline is ndi_interp2d_create_bicubic, caller-given derivatives ndi_interp2d_create_bicubic_hermite",
+                     (int)rule);
+  return rule == NDI_PCHIP ? create_bicubic_local("Pchip", desc, ndi::HR_PCHIP, nullptr, nullptr, nullptr, out)
+                           : create_bicubic_local("Akima", desc, ndi::HR_AKIMA, nullptr, nullptr, nullptr, out);
+}
+
+NDI_API ndi_status ndi_interp2d_create_bicubic_hermite(const ndi_interp2d_desc* desc, const void* zx, const void* zy,
+                                                       const void* zxy, ndi_interp2d** out) {
+  if (!desc || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
+  *out = nullptr;
+  return create_bicubic_local("Hermite", desc, ndi::HR_GIVEN, zx, zy, zxy, out);
 }
 
 NDI_API ndi_status ndi_interp2d_tables(const ndi_interp2d* h, void* zx, void* zy, void* zxy, int32_t memspace) {

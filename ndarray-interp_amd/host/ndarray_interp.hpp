@@ -671,6 +671,55 @@ class Bilinear : public Interp2DStrategyBuilder<T> {  // src/interp2d/strategies
   }
 };
 
+// Bicubic with the node derivatives of a local rule or of the caller (ndi_interp2d_create_bicubic_local,
+// ndi_interp2d_create_bicubic_hermite; include/ndinterp.h states the contract): Bicubic<T>::pchip(), ::akima() and
+// ::hermite(zx, zy, zxy).  The reference has no such strategy.  There are no boundary conditions: ends are a spline notion.
+template <class T>
+class Bicubic : public Interp2DStrategyBuilder<T> {
+  int rule_ = NDI_PCHIP;   // NDI_PCHIP, NDI_AKIMA, or NDI_CUBIC_HERMITE for the caller's tables
+  Array<T> zx_, zy_, zxy_;
+  bool extrapolate_ = false;
+  int device_ = -1;   // -1: current_device() at build time
+  explicit Bicubic(int rule) : rule_(rule) {}
+ public:
+  static Bicubic pchip() { return Bicubic(NDI_PCHIP); }
+  static Bicubic akima() { return Bicubic(NDI_AKIMA); }
+  static Bicubic hermite(Array<T> zx, Array<T> zy, Array<T> zxy) {
+    Bicubic b(NDI_CUBIC_HERMITE);
+    b.zx_ = std::move(zx); b.zy_ = std::move(zy); b.zxy_ = std::move(zxy);
+    return b;
+  }
+  Bicubic extrapolate(bool yes) && { extrapolate_ = yes; return std::move(*this); }
+  Bicubic device(int ordinal) && { device_ = ordinal; return std::move(*this); }
+  size_t MINIMUM_DATA_LENGHT() const override { return rule_ == NDI_AKIMA ? 3 : 2; }
+  std::shared_ptr<Interp2DStrategy<T>> build(const std::vector<T>& x, const std::vector<T>& y,
+                                             const Array<T>& data) override {
+    static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>,
+                  "Bicubic covers float / double only: the rule divides (integer data takes Bilinear)");
+    if (rule_ == NDI_CUBIC_HERMITE) {
+      const Array<T>* t[3] = {&zx_, &zy_, &zxy_};
+      const char* name[3] = {"zx", "zy", "zxy"};
+      for (int k = 0; k < 3; ++k)
+        if (t[k]->shape != data.shape)
+          throw BuilderError(BuilderError::ShapeError, std::string(name[k]) + " has wrong shape. Expected: " +
+                                                           detail::shape_str(data.shape) + ", got: " +
+                                                           detail::shape_str(t[k]->shape));
+    }
+    auto s = std::make_shared<detail::Device2D<T>>();
+    ndi_interp2d_desc d{};
+    s->device = device_ >= 0 ? device_ : current_device();
+    d.dtype = detail::DType<T>::id; d.extrapolate = extrapolate_; d.device = s->device; d.memspace = NDI_MEM_HOST;
+    d.nx = data.shape[0]; d.ny = data.shape[1]; d.lanes = s->lanes = detail::prod(data.shape, 2);
+    d.x_len = x.size(); d.y_len = y.size(); d.x = x.data(); d.y = y.data(); d.data = data.data.data();
+    d.validate = 0;
+    int st = rule_ == NDI_CUBIC_HERMITE
+                 ? ndi_interp2d_create_bicubic_hermite(&d, zx_.data.data(), zy_.data.data(), zxy_.data.data(), &s->h)
+                 : ndi_interp2d_create_bicubic_local(&d, rule_, &s->h);
+    if (st != NDI_OK) detail::throw_builder(st);
+    return s;
+  }
+};
+
 template <class T>
 class Interp2D {  // interp2d/mod.rs:36-48
  public:

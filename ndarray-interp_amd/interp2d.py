@@ -305,17 +305,59 @@ class Bicubic(Interp2DStrategyBuilder, _DeviceStrategy2D):
     """Bicubic strategy: the tensor-product cubic spline on the grid (scipy: RectBivariateSpline(kx=3, ky=3, s=0) for the
     default ends, on evenly and unevenly spaced axes alike: its not-a-knot right end is the true not-a-knot row, where a
     1-D CubicSpline keeps the reference's), built and evaluated on the device (ndi_interp2d_create_bicubic;
-    include/ndinterp.h states the numerical contract).  The reference has no such strategy.  Builder and finished strategy in one, like `Bilinear`."""
+    include/ndinterp.h states the numerical contract).  The reference has no such strategy.  Builder and finished strategy in one, like `Bilinear`.
+    `Bicubic.pchip()`, `Bicubic.akima()` and `Bicubic.hermite(zx, zy, zxy)` build the same strategy with the node derivatives of a
+    local rule or of the caller instead of the spline's: `partial`, `antiderivative`, `integral`, `jet_into` and the rest
+    are shared."""
 
     MINIMUM_DATA_LENGHT = 3
+
+    # where the node derivatives come from: None -- the spline (`new()`); "pchip" / "akima" -- the 1-D rule of that name along
+    # each axis (`pchip()`, `akima()`: ndi_interp2d_create_bicubic_local); "hermite" -- the caller (`hermite(zx, zy, zxy)`:
+    # ndi_interp2d_create_bicubic_hermite).  Everything after the build is the same strategy.
+    rule = None
 
     def __init__(self):
         super().__init__()
         self._bc_x = self._bc_y = RowBoundary.NotAKnot
+        self._given = None
 
     @staticmethod
     def new() -> "Bicubic":
         return Bicubic()
+
+    @staticmethod
+    def _local(rule, minimum) -> "Bicubic":
+        b = Bicubic()
+        b.rule, b.MINIMUM_DATA_LENGHT = rule, minimum
+        return b
+
+    @staticmethod
+    def pchip() -> "Bicubic":
+        """Node derivatives by the 1-D Pchip rule along each axis (scipy / MATLAB: `pchip`; at least 2 points per axis).  On
+        every grid line the surface is the 1-D Pchip interpolant of that line, so it does not overshoot ALONG grid lines;
+        inside a cell monotonicity is not promised.  C1: second partials jump at the grid lines."""
+        return Bicubic._local("pchip", 2)
+
+    @staticmethod
+    def akima() -> "Bicubic":
+        """Node derivatives by the 1-D Akima rule along each axis (at least 3 points per axis): local, an outlier moves the
+        derivatives of its neighbours only.  C1: second partials jump at the grid lines."""
+        return Bicubic._local("akima", 3)
+
+    @staticmethod
+    def hermite(zx, zy, zxy) -> "Bicubic":
+        """The caller's node derivatives d/dx, d/dy and d2/dxdy, each of the data's shape and dtype (numpy arrays or
+        tensors; `tables()` of another Bicubic strategy gives such arrays).  No rule is applied; at least 2 points per
+        axis."""
+        b = Bicubic._local("hermite", 2)
+        b._given = (zx, zy, zxy)
+        return b
+
+    def _no_ends(self):
+        if self.rule is not None:
+            raise TypeError(f"Bicubic.{self.rule}() takes no boundary conditions: ends are a spline notion "
+                            "(the rule needs none; Bicubic.new() builds the spline)")
 
     @staticmethod
     def _ends(bc) -> RowBoundary:
@@ -333,14 +375,17 @@ class Bicubic(Interp2DStrategyBuilder, _DeviceStrategy2D):
 
     def boundary(self, bc) -> "Bicubic":
         """The same ends on both axes."""
+        self._no_ends()
         self._bc_x = self._bc_y = self._ends(bc)
         return self
 
     def boundary_x(self, bc) -> "Bicubic":
+        self._no_ends()
         self._bc_x = self._ends(bc)
         return self
 
     def boundary_y(self, bc) -> "Bicubic":
+        self._no_ends()
         self._bc_y = self._ends(bc)
         return self
 
@@ -350,10 +395,33 @@ class Bicubic(Interp2DStrategyBuilder, _DeviceStrategy2D):
             got = "bfloat16" if is_bf16(dt) else dt
             raise TypeError(f"Bicubic covers float32/float64 only, got {got}: a spline divides (integer data takes "
                             "Bilinear) and the spline build has no half-precision form")
+        if self.rule in ("pchip", "akima"):
+            code = _capi.PCHIP if self.rule == "pchip" else _capi.AKIMA
+            return self._create(x, y, data, device,
+                                lambda d, h: _capi.lib().ndi_interp2d_create_bicubic_local(C.byref(d), code, C.byref(h)))
+        if self.rule == "hermite":
+            return self._create_hermite(x, y, data, device)
         ends = (self._bc_x.left, self._bc_x.right, self._bc_y.left, self._bc_y.right)
         bc = (_capi.Boundary * 4)(*[_capi.Boundary(int(e.kind), float(e.value)) for e in ends])
         return self._create(x, y, data, device,
                             lambda d, h: _capi.lib().ndi_interp2d_create_bicubic(C.byref(d), bc, C.byref(h)))
+
+    def _create_hermite(self, x, y, data, device):
+        dt = np_dtype_of(data)
+        for name, t in zip(("zx", "zy", "zxy"), self._given):
+            if not hasattr(t, "shape") or not hasattr(t, "dtype"):
+                raise TypeError(f"Bicubic.hermite: {name} is a numpy array or a tensor, got {type(t).__name__}")
+            if tuple(t.shape) != tuple(data.shape):
+                raise BuilderError.ShapeError(
+                    f"{name} has wrong shape. Expected: {list(data.shape)}, got: {list(t.shape)}")
+            if np_dtype_of(t) != dt:
+                raise TypeError(f"Bicubic.hermite: {name} has element type {np_dtype_of(t)}, the data is {dt}")
+        on_dev = is_torch(data) and data.is_cuda
+        # the tables travel in the same memory space as the data
+        bufs = [Buf(_to_device(t, data.device), dt) if on_dev else Buf(_host(t), dt) for t in self._given]
+        return self._create(x, y, data, device,
+                            lambda d, h: _capi.lib().ndi_interp2d_create_bicubic_hermite(
+                                C.byref(d), bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, C.byref(h)))
 
     orders = (0, 0)    # (nu_x, nu_y) of the partial derivative this strategy evaluates; (0, 0): the surface
     origin = None      # a partial's source strategy (kept for documentation's sake: the library owns the shared table)
@@ -885,7 +953,7 @@ class Interp2DBuilder:
         shape = tuple(data.shape)
         if len(shape) < 2:
             raise BuilderError.ShapeError("data dimension needs to be at least 2")
-        need = type(strategy).MINIMUM_DATA_LENGHT
+        need = strategy.MINIMUM_DATA_LENGHT    # (a Bicubic strategy of a local rule carries its own)
         if shape[0] < need:
             raise BuilderError.NotEnoughData(
                 "The 0-dimension has not enough data for the chosen interpolation strategy. "

@@ -231,6 +231,14 @@ extern "C" {
         bc: *const ndi_boundary,
         out: *mut *mut ndi_interp2d,
     ) -> i32;
+    pub fn ndi_interp2d_create_bicubic_local(desc: *const ndi_interp2d_desc, rule: i32, out: *mut *mut ndi_interp2d) -> i32;
+    pub fn ndi_interp2d_create_bicubic_hermite(
+        desc: *const ndi_interp2d_desc,
+        zx: *const c_void,
+        zy: *const c_void,
+        zxy: *const c_void,
+        out: *mut *mut ndi_interp2d,
+    ) -> i32;
     pub fn ndi_interp2d_tables(
         h: *const ndi_interp2d,
         zx: *mut c_void,
