@@ -590,6 +590,64 @@ ndi_status ndi_interp1d_integrate(const ndi_interp1d* h, const void* lo, const v
                                   void* out, uint64_t out_row_stride,
                                   const ndi_eval_opts* opts, ndi_oob_info* info);
 
+/* The inverse of an interpolant as a NEW HANDLE (scipy: PPoly.solve / CubicSpline.solve, one root per lane): the new
+ * handle's queries are VALUES v and its rows are abscissae,
+ *     out[j * out_row_stride + l] = x   with   f_l(x) = v[j].
+ * It is built on h's device, `h` is only read and stays usable, the new handle keeps its own copies of what it reads (as an
+ * antiderivative handle does) and either handle may be destroyed first.
+ * Sources (f32 and f64 only): Linear; the cubic evaluation class (CubicSpline with every boundary kind, Pchip, Akima,
+ * CubicHermite, and derivative handles); antiderivative handles of either (a CDF: F^-1(u) is inverse-transform sampling).
+ * Refused with NDI_BAD_ARG, before any device work, with a message that names the strategy and the reason: integer and
+ * f16 / bf16 handles, a handle whose extrapolation mode is Periodic, an inverse handle, a null `h` or `out` (`*out` is
+ * cleared first).
+ * The node table N[n][lanes] is the data table y (Linear and cubic sources) or the prefix table P (antiderivative sources).
+ * Every lane of N must be monotone; ties are allowed (a density that is zero over an interval gives a flat run in P).  One
+ * device pass at creation checks it: a lane that both rises and falls, or holds a NaN, gives NDI_MONOTONIC, and the
+ * message names the lowest such lane.  Per lane, rising = N[n-1][l] >= N[0][l].  The handle keeps the value range common
+ * to all lanes, Lo = max_l min(N[0][l], N[n-1][l]) and Hi = min_l max(N[0][l], N[n-1][l]).
+ * Evaluation: ndi_interp1d_eval in every form (sync, async_launch + ndi_interp1d_finish, host or device queries and
+ * outputs, strided rows).  A row is defined only where v lies in every lane's range: v outside [Lo, Hi] (inclusive test)
+ * is NDI_OUT_OF_BOUNDS, a NaN is NDI_NAN_QUERY; the lowest failing flat index is reported with value = v and axis = 0, rows
+ * before it are written, later rows are untouched (NDI_EVAL_FRESH_OUTPUT and NDI_EVAL_ROWS_AFTER_ERROR_UNSPECIFIED are
+ * accepted and ignored).  `extrapolate` of the source is IGNORED: the inverse is defined on the node range only.
+ * Numerical contract -- this project's own.  Every line is one IEEE operation in T, in this order, nothing fused.  Per
+ * output element (query v, lane l, column c = N[:, l]):
+ *     search   lo = 0, hi = n-1;  while hi - lo > 1:  mid = (lo + hi) >> 1
+ *                  if (rising ? c[mid] <= v : c[mid] >= v) lo = mid else hi = mid
+ *              i = lo;  nl = c[i], nr = c[i+1];  xl = x[i], xr = x[i+1];  dx = xr - xl
+ *     start    if v == nl:  t = 0                         -> finish
+ *              t = (v - nl) / (nr - nl)                   Linear sources: -> finish (closed form)
+ *     solve    tl = 0, th = 1, dprev = 1;   repeat at most K times:
+ *                  f = p(t) - v;            if f == 0: stop
+ *                  if (rising ? f < 0 : f > 0) tl = t else th = t
+ *                  d = p'(t);  s = f / d;  tn = t - s
+ *                  if !(tn > tl && tn < th) or !(|s + s| <= |dprev|):  tn = tl + 0.5 * (th - tl)
+ *                  step = tn - t;  dprev = step;  t = tn
+ *                  if |step| <= eps_T: stop                eps_T = 2^-52 (f64) / 2^-23 (f32)
+ *     finish   w = xl + t * dx;  x = (t == 1) ? xr : min(w, xr)          min(w, xr) = (w < xr) ? w : xr
+ * p(t) is exactly the forward evaluation's expression of the class, with yl = y[i], yr = y[i+1], a = a[i], b = b[i]:
+ *     cubic class:                p(t)  = ((1-t) yl + t yr) + (t (1-t)) (a (1-t) + b t)
+ *                                 p'(t) = (dy + a) + t (((b - (a+a)) + (b - (a+a))) - (3 (b - a)) t)        dy = yr - yl
+ *     antiderivative, cubic:      p(t)  = P[i] + dx * (t (yl + t (c1 + t (c2 - t c3))))
+ *                                 p'(t) = dx * (yl + t ((c1 + c1) + t (3 c2 - (4 c3) t)))
+ *     antiderivative of Linear:   p(t)  = P[i] + dx * (t (yl + t c1))
+ *                                 p'(t) = dx * (yl + t (c1 + c1))
+ * with c1, c2, c3 as stated for ndi_interp1d_antiderivative.  K = 128 (f64) / 64 (f32) is a safety net, not part of the
+ * accuracy argument: the |step| <= eps_T stop ends the iteration long before it.
+ * Properties: (1) the returned x is in [xl, xr], so a forward evaluation of it is never out of bounds; (2) a comparison
+ * with NaN or an infinite Newton step falls into the bisection branch, so the loop terminates for any table contents;
+ * (3) t always lies in a bracket across which the COMPUTED residual changes sign: where the interpolant is monotone on
+ * the interval (Linear, Pchip, and CDFs always) that is THE root, for an overshooting spline it is A root of that
+ * interval; (4) for a value taken on a whole flat run the run's right end is returned (the search takes the last i with
+ * c[i] == v; a flat run that reaches the last node returns x[n-2], the left end of the last interval).
+ * Other entry points on an inverse handle: ndi_interp1d_data hands back N; ndi_interp1d_clone, ndi_interp1d_trim and
+ * ndi_interp1d_destroy work.  ndi_interp1d_coefficients, ndi_interp1d_derivative, ndi_interp1d_antiderivative,
+ * ndi_interp1d_integrate and ndi_interp1d_inverse of it are NDI_BAD_ARG with a reason; ndi_interp1d_eval_ring, the
+ * sharded calls and NDI_PATH_BUCKETED are NDI_UNSUPPORTED with a message.
+ * Not provided: all roots of a non-monotone interpolant, extrapolated inverses, per-lane query arrays, 2-D, integer and
+ * f16 / bf16 element types. */
+ndi_status ndi_interp1d_inverse(const ndi_interp1d* h, ndi_interp1d** out);
+
 /* ---- evaluate ----------------------------------------------------------------
  * Replaces Interp1D::interp_array_into for a flattened query array
  * (src/interp1d/mod.rs:272-343) with Linear::interp_into (linear.rs:73-98) or

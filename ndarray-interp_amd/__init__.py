@@ -14,7 +14,7 @@ The directory name carries a hyphen (fixed by the project layout); it is importe
 from . import _capi
 from ._arrays import OUTPUT_OWNED_MIN_BYTES, output_empty, output_trim, output_zeros, striped_ring
 from .errors import BuilderError, DeviceError, InterpolateError, Panic
-from .interp1d import (Akima, AkimaStrategy, AntiderivativeStrategy, BoundaryCondition, CubicHermite, CubicHermiteStrategy, CubicSpline,
+from .interp1d import (Akima, AkimaStrategy, AntiderivativeStrategy, InverseStrategy, BoundaryCondition, CubicHermite, CubicHermiteStrategy, CubicSpline,
                        CubicSplineStrategy, DerivativeStrategy, Interp1D, Interp1DBuilder, Interp1DStrategy,
                        Interp1DStrategyBuilder, Linear,
                        Pchip, PchipStrategy, RowBoundary, SingleBoundary)
@@ -50,7 +50,7 @@ __all__ = [
     "Interp1D", "Interp1DBuilder", "Interp1DStrategy", "Interp1DStrategyBuilder", "Linear", "CubicSpline",
     "CubicSplineStrategy", "BoundaryCondition", "RowBoundary", "SingleBoundary",
     "Pchip", "PchipStrategy", "Akima", "AkimaStrategy", "CubicHermite", "CubicHermiteStrategy",
-    "DerivativeStrategy", "AntiderivativeStrategy",
+    "DerivativeStrategy", "AntiderivativeStrategy", "InverseStrategy",
     "Interp2D", "Interp2DBuilder", "Interp2DStrategy", "Interp2DStrategyBuilder", "Bilinear", "Bicubic", "JET_PARTS",
     "Monotonic", "monotonic_prop", "get_lower_index", "Locator", "sharding", "device_count", "striped_ring", "output_empty", "output_zeros", "output_trim",
     "profile_enable", "profile_read", "PATH_AUTO", "PATH_GATHER", "PATH_BUCKETED",

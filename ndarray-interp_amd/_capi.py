@@ -120,6 +120,7 @@ SYMBOLS = {
     "ndi_interp1d_derivative": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),
     "ndi_interp1d_antiderivative": (C.c_int, [_P, C.POINTER(_P)]),
     "ndi_interp1d_integrate": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(EvalOpts), C.POINTER(OobInfo)]),
+    "ndi_interp1d_inverse": (C.c_int, [_P, C.POINTER(_P)]),
     "ndi_interp1d_eval": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(EvalOpts), C.POINTER(OobInfo)]),
     "ndi_interp2d_eval": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(EvalOpts), C.POINTER(OobInfo)]),
     "ndi_interp1d_finish": (C.c_int, [_P, _P, C.POINTER(OobInfo)]),

@@ -280,6 +280,7 @@ struct AntiderivImpl final : Interp1DBase, FloatEngine<T, AntiderivImpl<T>> {
     return fail(NDI_BAD_ARG, "antiderivative: this handle is already the antiderivative of %s; a second antiderivative "
                 "(a piecewise quintic) is not provided", source_name());
   }
+  ndi_status inverse(Interp1DBase** out) override;   // (defined behind InverseImpl)
 
   ndi_status data_table(void* data_out, int memspace) override {
     DeviceGuard dg(device);

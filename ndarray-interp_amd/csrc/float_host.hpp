@@ -65,10 +65,7 @@ struct FloatEngine {
     T v;
     if (q_space == NDI_MEM_DEVICE) NDI_HIP(hipMemcpy(&v, src + ff, sizeof(T), hipMemcpyDeviceToHost));
     else v = src[ff];
-    // without extrapolation every failure is a range failure (NaN included: "x = NaN is not in range");
-    // with it the only failure is the search meeting a NaN -- the query itself or an infinite query that the
-    // periodic wrap turned into NaN (the reference panics: vector_extensions.rs:83-84)
-    const ndi_status st = (self().mode != EX_NO) ? NDI_NAN_QUERY : NDI_OUT_OF_BOUNDS;
+    const ndi_status st = self().failure_status(v);
     if (info) {
       info->index = index_offset + ff;
       info->value = (double)v;
@@ -78,6 +75,11 @@ struct FloatEngine {
     if (st == NDI_NAN_QUERY) return fail(st, "failed to convert NaN to usize (query %llu)", index_offset + ff);
     return fail(st, "%s = %.17g is not in range", self().axis_name(axis), (double)v);
   }
+
+  // The status of a failing query v.  Without extrapolation every failure is a range failure (NaN included: "x = NaN is
+  // not in range"); with it the only failure is the search meeting a NaN -- the query itself or an infinite query that
+  // the periodic wrap turned into NaN (the reference panics: vector_extensions.rs:83-84).  (An inverse handle has its own.)
+  ndi_status failure_status(T) { return (self().mode != EX_NO) ? NDI_NAN_QUERY : NDI_OUT_OF_BOUNDS; }
 
   // Reads the status block of the batch enqueued with scratch set 0 (the stream is idle afterwards) and converts it to
   // the reference's error, with the query pointers the batch was issued with.

@@ -307,6 +307,11 @@ struct Interp1DHalfImpl final : Interp1DBase, HalfEngine<F> {
     return fail(NDI_BAD_ARG, "antiderivative: an f16 / bf16 handle is a Linear interpolator of a narrow element type: the prefix table would "
                 "round at every knot (antiderivative takes f32 / f64 Linear, CubicSpline, Pchip, Akima and CubicHermite handles)");
   }
+  ndi_status inverse(Interp1DBase**) override {
+    return fail(NDI_BAD_ARG, "inverse: an f16 / bf16 handle is a Linear interpolator of a narrow element type: the returned abscissae "
+                "would round to it (inverse takes f32 / f64 Linear, CubicSpline, Pchip, Akima, CubicHermite, derivative and "
+                "antiderivative handles)");
+  }
   ndi_status data_table(void* data_out, int memspace) override {
     DeviceGuard dg(device);
     NDI_HIP(hipMemcpy(data_out, data.p, n * lanes * sizeof(uint16_t),

@@ -220,6 +220,11 @@ struct Interp1DIntImpl final : Interp1DBase, IntEngine<T> {
     return fail(NDI_BAD_ARG, "antiderivative: an integer handle is a Linear interpolator of a narrow element type: the prefix table would "
                 "round at every knot (antiderivative takes f32 / f64 Linear, CubicSpline, Pchip, Akima and CubicHermite handles)");
   }
+  ndi_status inverse(Interp1DBase**) override {
+    return fail(NDI_BAD_ARG, "inverse: an integer handle is a Linear interpolator of a narrow element type: the returned abscissae "
+                "would round to it (inverse takes f32 / f64 Linear, CubicSpline, Pchip, Akima, CubicHermite, derivative and "
+                "antiderivative handles)");
+  }
   ndi_status data_table(void* data_out, int memspace) override {   // the values of the slope records {v, m}
     DeviceGuard dg(device);
     NDI_HIP(hipMemcpy2D(data_out, sizeof(T), rec.p, sizeof(IntRec<T>), sizeof(T), n * lanes,

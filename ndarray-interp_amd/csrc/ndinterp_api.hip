@@ -31,6 +31,7 @@
 #include "hermite_kernels.hpp"
 #include "derivative_kernels.hpp"
 #include "antiderivative_kernels.hpp"
+#include "inverse_kernels.hpp"
 #include "bicubic_kernels.hpp"
 #include "bicubic_local_kernels.hpp"
 #include "bicubic_integral_kernels.hpp"
@@ -914,6 +915,9 @@ struct Interp1DBase {
                                const ndi_eval_opts* opts, ndi_oob_info* info) {
     return fail(NDI_BAD_ARG, "integrate takes an antiderivative handle (ndi_interp1d_antiderivative of this handle)");
   }
+  // ndi_interp1d_inverse: the refusals come before any device work
+  virtual ndi_status inverse(Interp1DBase** out) = 0;
+  bool inverse_handle = false;   // an inverse handle (inverse_host.hpp): its queries are values, its rows abscissae
 };
 
 static const char* hermite_rule_name(int rule) {
@@ -2245,9 +2249,11 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
   }
 
   ndi_status antiderivative(Interp1DBase** out) override;   // (defined behind AntiderivImpl)
+  ndi_status inverse(Interp1DBase** out) override;          // (defined behind InverseImpl)
 };
 
 #include "antiderivative_host.hpp"
+#include "inverse_host.hpp"
 
 template <class T>
 static std::vector<T> default_axis(uint64_t n) {
@@ -4416,6 +4422,21 @@ NDI_API ndi_status ndi_interp1d_antiderivative(const ndi_interp1d* h, ndi_interp
   NDI_CATCH
 }
 
+// Every refusal is decided before any device work: the argument checks here, the handle's own in its inverse().
+NDI_API ndi_status ndi_interp1d_inverse(const ndi_interp1d* h, ndi_interp1d** out) {
+  if (!out) return ndi::fail(NDI_BAD_ARG, "null out pointer");
+  *out = nullptr;
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  NDI_TRY
+  ndi::Range rg("ndi_interp1d_inverse");
+  ndi::Interp1DBase* impl = nullptr;
+  ndi_status st = h->impl->inverse(&impl);
+  if (st != NDI_OK) return st;
+  *out = new ndi_interp1d{impl};
+  return ndi::bounds_verdict(NDI_OK, impl->device);
+  NDI_CATCH
+}
+
 NDI_API ndi_status ndi_interp1d_integrate(const ndi_interp1d* h, const void* lo, const void* hi, uint64_t nq, void* out,
                                           uint64_t out_row_stride, const ndi_eval_opts* opts, ndi_oob_info* info) {
   if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
@@ -4574,14 +4595,17 @@ static ndi_status sharded_call(const ndi_interp1d* const* handles, uint32_t n, c
   const int dtype = handles[0]->impl->dtype;
   // antiderivative handles take no sharded call; a set that mixes a function with its antiderivative is no set of
   // replicas at all (the signatures differ), which is the first thing to say about it
-  bool anti = false;
-  for (uint32_t i = 0; i < n; ++i) anti = anti || handles[i]->impl->is_antiderivative();
-  if (anti) {
+  bool anti = false, inv = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    anti = anti || handles[i]->impl->is_antiderivative();
+    inv = inv || handles[i]->impl->inverse_handle;
+  }
+  if (anti || inv) {
     std::vector<ndi::Interp1DBase*> H;
     const ndi_status st = gather_handles(handles, n, dtype, H);
     if (st != NDI_OK) return st;
-    return ndi::fail(NDI_UNSUPPORTED, "the sharded calls do not take antiderivative handles (ndi_interp1d_eval per device "
-                     "serves them)");
+    return ndi::fail(NDI_UNSUPPORTED, "the sharded calls do not take %s handles (ndi_interp1d_eval per device serves them)",
+                     inv ? "inverse" : "antiderivative");
   }
   switch (dtype) {
     case NDI_I32: return sharded_narrow_call<ndi::Interp1DIntImpl<int32_t>>(handles, n, c, info);

@@ -182,6 +182,23 @@ class _DeviceStrategy1D(Interp1DStrategy):
         d.origin = getattr(self, "origin", type(self))
         return d
 
+    def inverse(self) -> "InverseStrategy":
+        """The inverse `f^-1` as a finished strategy of its own (ndi_interp1d_inverse): a new handle on this handle's
+        device whose queries are values `v` and whose rows are the abscissae `x` with `f_l(x) = v`.  This strategy stays
+        usable.  Sources the library refuses (include/ndinterp.h lists them) raise `ValueError` with its message; a lane
+        that is not monotone raises `BuilderError.Monotonic`."""
+        h = C.c_void_p()
+        st = _capi.lib().ndi_interp1d_inverse(self._h, C.byref(h))
+        if st == _capi.BAD_ARG:
+            raise ValueError(_capi.last_error())
+        if st != _capi.OK:
+            raise_builder(st)
+        d = InverseStrategy()
+        d._h, d._device, d._np_dtype, d._lanes, d._n = h, self._device, self._np_dtype, self._lanes, self._n
+        d.origin = getattr(self, "origin", type(self))
+        d.source = type(self)
+        return d
+
     # -- evaluate -----------------------------------------------------------------------------
     _takes_fresh = True   # interp_array() may tell this strategy that the output buffer is its own (ndi_eval_flags)
 
@@ -576,7 +593,8 @@ class AntiderivativeStrategy(_DeviceStrategy1D):
     (`strategy.antiderivative()`, `Interp1D.antiderivative()`): a handle with a prefix table `P` (`data_table()`) and
     evaluation kernels of its own.  `interp_array_into`, `finish`, `clone`, `data_table`, `trim` and `release` are the
     shared ones; `integrate_into` is the definite integral.  `origin`: the class of the strategy it started from.  The
-    ring, the sharded calls, `coefficients`, `derivative` and a second `antiderivative` are refused by the library."""
+    ring, the sharded calls, `coefficients`, `derivative` and a second `antiderivative` are refused by the library;
+    `inverse()` (a CDF's quantile function) is the shared one."""
 
     origin = None
     path = _capi.PATH_GATHER   # the one form these handles take (NDI_PATH_BUCKETED is refused, AUTO means this)
@@ -617,6 +635,58 @@ class AntiderivativeStrategy(_DeviceStrategy1D):
                                                value=float(info.value), axis=int(info.axis))
         if st != _capi.OK:
             raise_eval(st, info)
+
+
+class InverseStrategy(_DeviceStrategy1D):
+    """The inverse of a Linear / CubicSpline / Pchip / Akima / CubicHermite strategy, of a derivative of one, or of an
+    antiderivative (`strategy.inverse()`, `Interp1D.inverse()`): queries are values `v`, rows are the abscissae `x` with
+    `f_l(x) = v`, defined for `v` in the value range common to all lanes.  `interp_array_into`, `finish`, `clone`,
+    `data_table` (the node table `N`), `trim` and `release` are the shared ones.  `origin`: the class of the strategy the
+    chain started from; `source`: the class of the strategy that was inverted.  The ring, the sharded calls,
+    `coefficients`, `derivative`, `antiderivative` and a second `inverse` are refused by the library."""
+
+    origin = None
+    source = None
+    path = _capi.PATH_GATHER   # the one form these handles take (NDI_PATH_BUCKETED is refused, AUTO means this)
+
+    def _refused(self, st):
+        if st in (_capi.BAD_ARG, _capi.UNSUPPORTED):
+            raise ValueError(_capi.last_error())
+        raise_builder(st)
+
+    def derivative(self, nu: int = 1):
+        h = C.c_void_p()
+        self._refused(_capi.lib().ndi_interp1d_derivative(self._h, int(nu), C.byref(h)))
+
+    def antiderivative(self):
+        h = C.c_void_p()
+        self._refused(_capi.lib().ndi_interp1d_antiderivative(self._h, C.byref(h)))
+
+    def inverse(self):
+        h = C.c_void_p()
+        self._refused(_capi.lib().ndi_interp1d_inverse(self._h, C.byref(h)))
+
+    def coefficients(self, device: bool = False):
+        self._refused(_capi.lib().ndi_interp1d_coefficients(self._h, None, None, _capi.MEM_HOST))
+
+    @staticmethod
+    def _as_value_error(e):
+        """the query of an inverse handle is a value `v`, not an `x`"""
+        from .errors import _rust_float
+        return InterpolateError.OutOfBounds(f"v = {_rust_float(e.value)} is not in range", index=e.index, value=e.value,
+                                            axis=0)
+
+    def interp_array_into(self, *args, **kw):
+        try:
+            super().interp_array_into(*args, **kw)
+        except InterpolateError.OutOfBounds as e:
+            raise self._as_value_error(e) from None
+
+    def finish(self):
+        try:
+            super().finish()
+        except InterpolateError.OutOfBounds as e:
+            raise self._as_value_error(e) from None
 
 
 class _LocalCubic(Interp1DStrategyBuilder):
@@ -891,6 +961,21 @@ class Interp1D:
             raise TypeError("antiderivative needs a built-in device strategy (Linear, CubicSpline, Pchip, Akima or "
                             f"CubicHermite on f32 / f64 data), got {type(self.strategy).__name__}")
         strat = self.strategy.antiderivative()
+        on_device = is_torch(self.data) and self.data.is_cuda
+        return Interp1D(self.x, strat.data_table(device=on_device).reshape(tuple(self.data.shape)), strat)
+
+    def inverse(self) -> "Interp1D":
+        """The inverse of this interpolator as an interpolator of its own (scipy's `PPoly.solve`, one root per lane and
+        batched): `inv.interp_array(vs)[j, l]` is the `x` with `f_l(x) = vs[j]`, of shape `vs.shape ++ data.shape[1:]`.
+        Same `x`, `data` = the node table (this data; the prefix table for an antiderivative), strategy an
+        `InverseStrategy`.  Every lane must be monotone (ties allowed), else `BuilderError.Monotonic`; a value outside
+        the range common to all lanes is `InterpolateError.OutOfBounds`, whatever `extrapolate` was.  Sources the library
+        refuses (integer and half element types, the periodic mode, an inverse) are a `ValueError` with its reason;
+        strategies that are not the built-in device ones raise `TypeError`."""
+        if not isinstance(self.strategy, _DeviceStrategy1D):
+            raise TypeError("inverse needs a built-in device strategy (Linear, CubicSpline, Pchip, Akima or CubicHermite "
+                            f"on f32 / f64 data, a derivative or an antiderivative), got {type(self.strategy).__name__}")
+        strat = self.strategy.inverse()
         on_device = is_torch(self.data) and self.data.is_cuda
         return Interp1D(self.x, strat.data_table(device=on_device).reshape(tuple(self.data.shape)), strat)
 

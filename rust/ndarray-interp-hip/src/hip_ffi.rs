@@ -295,6 +295,9 @@ extern "C" {
     pub fn ndi_interp1d_derivative(h: *const ndi_interp1d, nu: i32, out: *mut *mut ndi_interp1d) -> i32;
     /// The antiderivative (F(x[0]) = +0) as a new handle; the header states the numerical contract
     pub fn ndi_interp1d_antiderivative(h: *const ndi_interp1d, out: *mut *mut ndi_interp1d) -> i32;
+    /// The inverse (queries are values `v`, rows the `x` with `f(x) = v`) as a new handle; the header states the
+    /// numerical contract
+    pub fn ndi_interp1d_inverse(h: *const ndi_interp1d, out: *mut *mut ndi_interp1d) -> i32;
     /// `out[j] = F(hi[j]) - F(lo[j])` through an antiderivative handle, one evaluation launch
     pub fn ndi_interp1d_integrate(
         h: *const ndi_interp1d,
