@@ -644,8 +644,9 @@ ndi_status ndi_interp1d_integrate(const ndi_interp1d* h, const void* lo, const v
  * ndi_interp1d_destroy work.  ndi_interp1d_coefficients, ndi_interp1d_derivative, ndi_interp1d_antiderivative,
  * ndi_interp1d_integrate and ndi_interp1d_inverse of it are NDI_BAD_ARG with a reason; ndi_interp1d_eval_ring, the
  * sharded calls and NDI_PATH_BUCKETED are NDI_UNSUPPORTED with a message.
- * Not provided: all roots of a non-monotone interpolant, extrapolated inverses, per-lane query arrays, 2-D, integer and
- * f16 / bf16 element types. */
+ * A value per lane (independent quantiles: inverse-transform sampling from `lanes` densities) is ndi_interp1d_eval_lanewise.
+ * Not provided: all roots of a non-monotone interpolant, extrapolated inverses, 2-D, the ring, the sharded calls, integer
+ * and f16 / bf16 element types. */
 ndi_status ndi_interp1d_inverse(const ndi_interp1d* h, ndi_interp1d** out);
 
 /* ---- evaluate ----------------------------------------------------------------
@@ -659,6 +660,34 @@ ndi_status ndi_interp1d_inverse(const ndi_interp1d* h, ndi_interp1d** out);
 ndi_status ndi_interp1d_eval(const ndi_interp1d* h, const void* q, uint64_t nq, void* out,
                              uint64_t out_row_stride, const ndi_eval_opts* opts,
                              ndi_oob_info* info);
+
+/* Lane-wise evaluation, a query per lane (this project's own; the reference evaluates all lanes at one abscissa):
+ *     out[j * out_row_stride + l] = f_l(q[j * q_row_stride + l]),   j < nq, l < lanes.
+ * `q` is T[nq][q_row_stride] in opts->q_memspace, `out` is T[nq][out_row_stride] in opts->out_memspace; both strides are
+ * in elements and at least lanes.
+ * Value rule: out[j][l] is, bit for bit and zero signs included, element l of the row ndi_interp1d_eval(h) writes for the single query q[j][l].
+ * It holds for every handle kind the call accepts, every extrapolation mode (none, end-interval, periodic wrap) and
+ * whatever path, table layout or kernel form is taken.
+ * Handles accepted (f32 and f64 only): Linear; the cubic evaluation class (CubicSpline with every boundary kind, Pchip,
+ * Akima, CubicHermite, and derivative handles); antiderivative handles; inverse handles, where `q` holds values and `out`
+ * abscissae.  Integer and f16 / bf16 handles are NDI_BAD_ARG with a message that names the strategy.
+ * Failures: the lowest failing flat ELEMENT index j * lanes + l wins (computed with lanes, not with the strides);
+ * info->index is that index, info->value is q[j][l], info->axis is 0; status and message are those of ndi_interp1d_eval on
+ * the handle ("x = ... is not in range", NDI_NAN_QUERY for a NaN the search meets).  Forward and antiderivative handles
+ * test against the knot range with the extrapolation mode's rule; an inverse handle tests q[j][l] against lane l's OWN
+ * value range [min(N[0][l], N[n-1][l]), max(N[0][l], N[n-1][l])], not the range common to all lanes (a NaN is
+ * NDI_NAN_QUERY).  Rows j < index / lanes are written whole; the failing row and all later rows are untouched.
+ * NDI_EVAL_FRESH_OUTPUT and NDI_EVAL_ROWS_AFTER_ERROR_UNSPECIFIED drop the pre-pass over the queries that this needs: the
+ * report is the same, the rows at and after the failing row are then unspecified.
+ * Refused before any device work: a null `h`, with nq > 0 a null `q` or `out`, a stride below lanes, NDI_PATH_BUCKETED,
+ * unknown flag bits or a non-zero `reserved` (all NDI_BAD_ARG); async_launch != 0 is NDI_UNSUPPORTED (the finish record
+ * carries no element index).  nq == 0 is NDI_OK and touches nothing.
+ * Host arrays go through device staging in row chunks; only rows before the failing row are copied back.  Linear / cubic
+ * handles may keep an element-record copy of their tables for this call (built on the first lane-wise call, at most 1 GiB,
+ * released by ndi_interp1d_trim; a clone builds its own).
+ * Not provided: lane-wise 2-D evaluation, the ring, the sharded calls, async_launch, integer and f16 / bf16 element types. */
+ndi_status ndi_interp1d_eval_lanewise(const ndi_interp1d* h, const void* q, uint64_t nq, uint64_t q_row_stride,
+                                      void* out, uint64_t out_row_stride, const ndi_eval_opts* opts, ndi_oob_info* info);
 
 /* Replaces Interp2D::interp_array_into (src/interp2d/mod.rs:215-307) with
  * Bilinear::interp_into (bilinear.rs:64-99) as the per-query body. */

@@ -255,6 +255,12 @@ struct AntiderivImpl final : Interp1DBase, FloatEngine<T, AntiderivImpl<T>> {
 
   ndi_status finish(void* stream, ndi_oob_info* info) override { return this->run_finish(stream, info); }
 
+  // lane-wise evaluation (defined in lanewise_host.hpp)
+  void lanewise_enqueue(hipStream_t s, Workspace& ws, const T* q, uint64_t q_stride, uint64_t rows, T* out,
+                        uint64_t out_stride, bool check);
+  ndi_status eval_lanewise(const void* q, uint64_t nq, uint64_t q_stride, void* out, uint64_t out_stride,
+                           const ndi_eval_opts* opts, ndi_oob_info* info) override;
+
   ndi_status eval_ring(const void*, uint64_t, const ndi_ring_desc*, ndi_ring_consumer, void*, const ndi_eval_opts*,
                        ndi_oob_info*) override {
     return fail(NDI_UNSUPPORTED, "eval_ring: an antiderivative handle (of %s) has no ring evaluation; ndi_interp1d_eval "

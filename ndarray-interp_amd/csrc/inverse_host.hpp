@@ -20,6 +20,12 @@ struct InverseImpl final : Interp1DBase, FloatEngine<T, InverseImpl<T>> {
   DevicePyramid<T> pyr;    // (the knots; their host copy)
   DevBuf y, a, b, P;       // y: the source's data; a, b: the cubic class; P: antiderivative sources.  N is P or y.
   T Lo = T(0), Hi = T(0);  // the value range common to all lanes
+  std::vector<T> lane_limits;   // [2][lanes]: lane l's own range, min and max of N[0][l] and N[n-1][l] (the lane-wise evaluation)
+  DevBuf lane_dev;              // ... and its device copy, uploaded with the other tables at creation / clone
+  void upload_lane_limits() {
+    lane_dev.reserve((size_t)2 * lanes * sizeof(T));
+    NDI_HIP(hipMemcpy(lane_dev.p, lane_limits.data(), (size_t)2 * lanes * sizeof(T), hipMemcpyHostToDevice));
+  }
   SpaceSet spaces;
 
   bool anti() const { return cls == IC_ANTI_CUBIC || cls == IC_ANTI_LINEAR; }
@@ -70,6 +76,12 @@ struct InverseImpl final : Interp1DBase, FloatEngine<T, InverseImpl<T>> {
                     "(ties allowed) to be inverted", source_name().c_str(), (unsigned long long)l,
                     nan ? "holds a NaN" : "both rises and falls");
     }
+    lane_limits.resize((size_t)2 * lanes);
+    for (uint64_t l = 0; l < lanes; ++l) {
+      lane_limits[l] = std::min(ends[l], ends[lanes + l]);
+      lane_limits[lanes + l] = std::max(ends[l], ends[lanes + l]);
+    }
+    upload_lane_limits();
     Lo = std::min(ends[0], ends[lanes]);
     Hi = std::max(ends[0], ends[lanes]);
     for (uint64_t l = 1; l < lanes; ++l) {
@@ -144,6 +156,12 @@ struct InverseImpl final : Interp1DBase, FloatEngine<T, InverseImpl<T>> {
 
   ndi_status finish(void* stream, ndi_oob_info* info) override { return this->run_finish(stream, info); }
 
+  // lane-wise evaluation (defined in lanewise_host.hpp): values per lane, tested against the lane's own range
+  void lanewise_enqueue(hipStream_t s, Workspace& ws, const T* q, uint64_t q_stride, uint64_t rows, T* out,
+                        uint64_t out_stride, bool check);
+  ndi_status eval_lanewise(const void* q, uint64_t nq, uint64_t q_stride, void* out, uint64_t out_stride,
+                           const ndi_eval_opts* opts, ndi_oob_info* info) override;
+
   ndi_status eval_ring(const void*, uint64_t, const ndi_ring_desc*, ndi_ring_consumer, void*, const ndi_eval_opts*,
                        ndi_oob_info*) override {
     return fail(NDI_UNSUPPORTED, "eval_ring: an inverse handle (of %s) has no ring evaluation; ndi_interp1d_eval chunk by "
@@ -190,6 +208,7 @@ struct InverseImpl final : Interp1DBase, FloatEngine<T, InverseImpl<T>> {
     h->dtype = dtype; h->device = dev; h->lanes = lanes; h->inverse_handle = true;
     h->cls = cls; h->rule = rule; h->deriv = deriv; h->n = n;
     h->Lo = Lo; h->Hi = Hi;
+    h->lane_limits = lane_limits;
     return h;
   }
 
@@ -201,6 +220,7 @@ struct InverseImpl final : Interp1DBase, FloatEngine<T, InverseImpl<T>> {
     }
     DeviceGuard dg(dev);
     h->reserve_tables(pyr.host_knots.data());
+    h->upload_lane_limits();
     const size_t data_b = (size_t)n * lanes * sizeof(T), tab_b = (size_t)(n - 1) * lanes * sizeof(T);
     copy_across_devices(h->y.p, dev, y.p, device, data_b);
     if (anti()) copy_across_devices(h->P.p, dev, P.p, device, data_b);

@@ -107,6 +107,7 @@ enum BoundsCode : int {
   BC_CELL_X = 5, BC_CELL_Y = 6,   // 2-D cell indices, limits nx - 1 / ny - 1
   BC_TILE = 7,          // tile-local grid point offset, limit (2^ts + 1)^2
   BC_STRIP = 8,         // query slot of a wave's strip, limit 64
+  BC_LANE = 9,          // lane of a lane-wise element (lanewise_kernels.hpp), limit lanes
 };
 
 __global__ __launch_bounds__(64) void reset_status_kernel(StatusBlock* s) {

@@ -19,6 +19,7 @@
 #include <memory>
 #include <mutex>
 #include <set>
+#include <shared_mutex>
 #include <stdexcept>
 #include <thread>
 #include <unordered_map>
@@ -32,6 +33,7 @@
 #include "derivative_kernels.hpp"
 #include "antiderivative_kernels.hpp"
 #include "inverse_kernels.hpp"
+#include "lanewise_kernels.hpp"
 #include "bicubic_kernels.hpp"
 #include "bicubic_local_kernels.hpp"
 #include "bicubic_integral_kernels.hpp"
@@ -918,6 +920,35 @@ struct Interp1DBase {
   // ndi_interp1d_inverse: the refusals come before any device work
   virtual ndi_status inverse(Interp1DBase** out) = 0;
   bool inverse_handle = false;   // an inverse handle (inverse_host.hpp): its queries are values, its rows abscissae
+  // ndi_interp1d_eval_lanewise (lanewise_host.hpp): f32 / f64 handles only
+  virtual ndi_status eval_lanewise(const void* q, uint64_t nq, uint64_t q_stride, void* out, uint64_t out_stride,
+                                   const ndi_eval_opts* opts, ndi_oob_info* info) {
+    return fail(NDI_BAD_ARG, "eval_lanewise: %s handle is a Linear interpolator of a narrow element type; the lane-wise "
+                "evaluation takes f32 / f64 handles", (dtype == NDI_I32 || dtype == NDI_I64) ? "an integer" : "an f16 / bf16");
+  }
+};
+
+// The element-record copy of a Linear / cubic handle's tables for the lane-wise evaluation (lanewise_kernels.hpp), built on
+// first use; a replica builds its own, trim releases it.
+struct LanewiseRecords {
+  static constexpr size_t LIMIT = 1ull << 30;   // the copy's memory cap: above it the plain tables serve
+  DevBuf buf;
+  // 0 = not tried, 1 = ready and known complete, 2 = unavailable (above the cap / allocation failed), 3 = built by a kernel
+  // enqueued on `stream`, completion signalled by `ev`
+  std::atomic<int> state{0};
+  std::mutex build;            // the state machine
+  std::shared_mutex use;       // shared: a call between taking the pointer and its launch; exclusive: drop
+  hipEvent_t ev = nullptr;
+  hipStream_t stream = nullptr;
+  ~LanewiseRecords() {
+    if (ev) (void)hipEventDestroy(ev);
+  }
+  void drop() {   // (hipFree waits for the kernels that read the copy)
+    std::unique_lock<std::shared_mutex> u(use);
+    std::lock_guard<std::mutex> g(build);
+    buf.release();
+    state.store(0, std::memory_order_release);
+  }
 };
 
 static const char* hermite_rule_name(int rule) {
@@ -956,6 +987,13 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
   ~Interp1DImpl() override {
     if (packed_ev) (void)hipEventDestroy(packed_ev);
   }
+  // lane-wise evaluation (defined in lanewise_host.hpp)
+  LanewiseRecords records;
+  const void* lanewise_records(hipStream_t s);
+  void lanewise_enqueue(hipStream_t s, Workspace& ws, const T* q, uint64_t q_stride, uint64_t rows, T* out,
+                        uint64_t out_stride, bool check);
+  ndi_status eval_lanewise(const void* q, uint64_t nq, uint64_t q_stride, void* out, uint64_t out_stride,
+                           const ndi_eval_opts* opts, ndi_oob_info* info) override;
   // The copy is made by a kernel on the CALLER's stream (no NULL-stream launch, no device-wide synchronisation on the
   // evaluation path: the ring's side stream keeps running); calls on other streams are ordered behind it with an event
   // until it is known complete.  Never while the stream is being captured, and never fatal: a failed allocation leaves
@@ -2145,6 +2183,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
   ndi_status trim() override {
     DeviceGuard dg(device);
     this->trim_front();
+    records.drop();
     return NDI_OK;
   }
 
@@ -2254,6 +2293,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
 
 #include "antiderivative_host.hpp"
 #include "inverse_host.hpp"
+#include "lanewise_host.hpp"
 
 template <class T>
 static std::vector<T> default_axis(uint64_t n) {
@@ -4467,6 +4507,18 @@ NDI_API ndi_status ndi_interp1d_eval(const ndi_interp1d* h, const void* q, uint6
   if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
   NDI_TRY
   return ndi::bounds_verdict(h->impl->eval(q, nq, out, out_row_stride, opts, info), h->impl->device);
+  NDI_CATCH
+}
+
+// Every refusal is decided before any device work: the null handle here, the rest in the handle's eval_lanewise().
+NDI_API ndi_status ndi_interp1d_eval_lanewise(const ndi_interp1d* h, const void* q, uint64_t nq, uint64_t q_row_stride,
+                                              void* out, uint64_t out_row_stride, const ndi_eval_opts* opts,
+                                              ndi_oob_info* info) {
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  NDI_TRY
+  const ndi_status st = h->impl->eval_lanewise(q, nq, q_row_stride, out, out_row_stride, opts, info);
+  if (st == NDI_BAD_ARG || st == NDI_UNSUPPORTED) return st;   // a refusal: no device was touched
+  return ndi::bounds_verdict(st, h->impl->device);
   NDI_CATCH
 }
 

@@ -225,6 +225,27 @@ class _DeviceStrategy1D(Interp1DStrategy):
         if st != _capi.OK:
             raise_eval(st, info, int_query(self._np_dtype, [qb], info))
 
+    def interp_lanewise_into(self, interpolator, xs2d, out2d, *, fresh=False, rows_after_error_unspecified=False):
+        """`out2d[j, l] = f_l(xs2d[j, l])` (ndi_interp1d_eval_lanewise): a query per lane, `(Q, lanes)` in and out, host
+        or device.  Errors name the flat element index `j * lanes + l`.  Element types the library refuses (integers,
+        f16 / bf16) raise `ValueError` with its message."""
+        qb = Buf(xs2d, self._np_dtype)
+        _check_out_dtype(out2d, self._np_dtype)
+        opts = _capi.EvalOpts()
+        opts.q_memspace = qb.memspace
+        opts.path = _capi.PATH_AUTO if self.path == _capi.PATH_BUCKETED else self.path
+        opts.flags = (_capi.EVAL_FRESH_OUTPUT if fresh else _capi.EVAL_DEFAULT) | \
+            (_capi.EVAL_ROWS_AFTER_ERROR_UNSPECIFIED if rows_after_error_unspecified else 0)
+        optr, stride = self._output(out2d, qb.memspace, opts)
+        info = _capi.OobInfo()
+        nq = qb.size // self._lanes
+        st = _capi.lib().ndi_interp1d_eval_lanewise(self._h, qb.ptr, nq, self._lanes, optr, stride, C.byref(opts),
+                                                    C.byref(info))
+        if st in (_capi.BAD_ARG, _capi.UNSUPPORTED):
+            raise ValueError(_capi.last_error())
+        if st != _capi.OK:
+            raise_eval(st, info)
+
     def _output(self, out2d, q_memspace, opts):
         """(pointer, row stride in elements) of a 2-D output buffer; sets `opts.out_memspace` and, where device memory is
         involved, `opts.stream` to the current stream."""
@@ -688,6 +709,12 @@ class InverseStrategy(_DeviceStrategy1D):
         except InterpolateError.OutOfBounds as e:
             raise self._as_value_error(e) from None
 
+    def interp_lanewise_into(self, *args, **kw):
+        try:
+            super().interp_lanewise_into(*args, **kw)
+        except InterpolateError.OutOfBounds as e:
+            raise self._as_value_error(e) from None
+
 
 class _LocalCubic(Interp1DStrategyBuilder):
     """Shared builder body of Pchip / Akima / CubicHermite: `.extrapolate(b)` and `.device(d)` as `CubicSpline` has
@@ -928,6 +955,55 @@ class Interp1D:
             elif done:
                 where = np.unravel_index(np.arange(done), tuple(xs.shape))     # works for any strides
                 buffer[where] = tmp[:done].reshape((done,) + self._lanes_shape())
+
+    def interp_lanewise(self, xs):
+        """A query per lane: `xs.shape` ends with `data.shape[1:]` and `result[..., l] = f_l(xs[..., l])`, where
+        `interp_array` evaluates every lane at one abscissa.  The result has `xs.shape` and the data's element type; numpy
+        in -> numpy out, a device tensor in -> a tensor on its device.  On an inverse interpolator `xs` holds values, each
+        tested against its own lane's range.  `InterpolateError.OutOfBounds.index` is the flat element index."""
+        self._lanewise_check(xs)
+        dt = np_dtype_of(self.data)
+        if is_torch(xs) and xs.is_cuda:
+            import torch
+            ys = torch.empty(tuple(xs.shape), dtype=torch_dtype(dt), device=xs.device)
+        else:
+            ys = np.zeros(tuple(xs.shape), dtype=dt)
+        self.interp_lanewise_into(xs, ys, fresh=True)
+        return ys
+
+    def interp_lanewise_into(self, xs, buffer, *, fresh=False, rows_after_error_unspecified=False):
+        """`interp_lanewise` into a caller's buffer of `xs.shape`: rows (one per leading index) before the row of the
+        first failing element are written, that row and all later ones stay untouched -- unless `fresh` or
+        `rows_after_error_unspecified` give them up, which saves a pass over the queries."""
+        self._lanewise_check(xs)
+        if tuple(buffer.shape) != tuple(xs.shape):
+            raise Panic(f"ShapeError/IncompatibleShape: incompatible shapes expected: {list(xs.shape)}, "
+                        f"got: {list(buffer.shape)}")
+        if np_dtype_of(buffer) != np_dtype_of(self.data):
+            raise TypeError(f"buffer has element type {np_dtype_of(buffer)}, the data is {np_dtype_of(self.data)}")
+        lanes = int(np.prod(self._lanes_shape(), dtype=np.int64))
+        nq = int(np.prod(xs.shape, dtype=np.int64)) // max(lanes, 1)
+        kw = dict(fresh=fresh, rows_after_error_unspecified=rows_after_error_unspecified)
+        if is_torch(buffer):
+            if not buffer.is_contiguous():
+                raise TypeError("device output buffers must be contiguous")
+            self.strategy.interp_lanewise_into(self, xs.reshape(nq, lanes), buffer.view(nq, lanes), **kw)
+            return
+        if not buffer.flags.c_contiguous:
+            raise TypeError("interp_lanewise_into needs a C-contiguous host buffer")
+        self.strategy.interp_lanewise_into(self, xs.reshape(nq, lanes) if is_torch(xs) else _host(xs).reshape(nq, lanes),
+                                           buffer.reshape(nq, lanes), **kw)
+
+    def _lanewise_check(self, xs):
+        if not isinstance(self.strategy, _DeviceStrategy1D):
+            raise TypeError("interp_lanewise needs a built-in device strategy (Linear, CubicSpline, Pchip, Akima or "
+                            "CubicHermite on f32 / f64 data, a derivative, an antiderivative or an inverse), got "
+                            f"{type(self.strategy).__name__}")
+        lanes_shape = self._lanes_shape()
+        k = len(lanes_shape)
+        if len(xs.shape) < k or tuple(xs.shape)[len(xs.shape) - k:] != lanes_shape:
+            raise Panic(f"ShapeError/IncompatibleShape: incompatible shapes expected: [.., "
+                        f"{', '.join(str(d) for d in lanes_shape)}], got: {list(xs.shape)}")
 
     def replicate(self, devices):
         """Replicas of this interpolator on the given devices (tables copied device to device, nothing rebuilt):
