@@ -121,8 +121,9 @@ static void copy_across_devices(void* dst, int dst_dev, const void* src, int src
   }
 }
 
-// Test hook (tests/test_gpu_short_rows.py): NDI_TEST_FAIL_LAZY_ALLOC=1 makes the lazily built optional copies (bucket
-// indices, interval-packed tables) fail as an out-of-memory hipMalloc would -- the fallbacks must serve the batch.
+// Test hook (tests/test_gpu_lazy_tables.py): NDI_TEST_FAIL_LAZY_ALLOC=1 makes the lazily built optional copies (bucket
+// indices, interval-packed tables, slope and element records) fail as an out-of-memory hipMalloc would -- the fallbacks
+// must serve the batch.
 static void maybe_fail_lazy_alloc(int line) {
   const char* e = std::getenv("NDI_TEST_FAIL_LAZY_ALLOC");
   if (e && e[0] == '1') throw HipFailure{hipErrorOutOfMemory, "injected lazy-allocation failure", line};
