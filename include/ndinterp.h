@@ -717,9 +717,19 @@ ndi_status ndi_interp2d_finish(const ndi_interp2d* h, void* stream, ndi_oob_info
  * then NDI_OUT_OF_BOUNDS / NDI_NAN_QUERY is returned with info filled in.  The call returns after the last
  * chunk's kernels (and the consumer's stream-ordered work) have completed.
  *
- * Internally the producer is a two-stream pipeline: the search + grouping of chunk k+1 run on a side stream the
- * handle owns while chunk k is evaluated on opts->stream (event-ordered; two scratch sets).  Everything the
- * consumer can observe -- the chunk's rows and chunk->stream -- is on opts->stream. */
+ * Internally the producer is a two-stream pipeline: the search + grouping of the next chunks run on a side stream the
+ * handle owns while the previous ones are evaluated on opts->stream (event-ordered; a scratch set per chunk in
+ * flight).  Everything the consumer can observe -- the chunk's rows and chunk->stream -- is on opts->stream.
+ *
+ * Group launches (1-D, rows of 256 16-byte vectors and more on the bucketed path).  While every consumer call so far
+ * has returned NULL -- the slots are handed back stream-ordered, so all n_slots of them are free as far as
+ * opts->stream is concerned -- up to min(n_slots, 4) consecutive chunks are evaluated by ONE kernel launch.  `consume`
+ * is still called once per chunk, in order, after that chunk's kernels are enqueued (for a group: after the group's
+ * launch), and chunk->stream is still opts->stream; what changes is only that the rows of chunk k may be written
+ * together with those of the chunks that share its launch.  A consumer that works on another stream keeps its
+ * overlap (chunk k+1 evaluated while it drains chunk k): it signals itself by returning an event, and from the first
+ * non-NULL return on the rest of the call runs one chunk per launch, waiting for each slot's event as before.  A NULL
+ * `consume` pointer counts as stream-ordered.  NDI_RING_GROUP=0 in the environment forces one chunk per launch. */
 typedef struct ndi_ring_chunk {
   uint64_t index;      /* chunk number, 0, 1, ... */
   uint64_t q_begin;    /* flat index of the chunk's first query */

@@ -15,6 +15,7 @@
 //   range_limits(lim)                  {lo, hi} of either axis for the range pre-pass
 //   small_rows_fit() / zero_copy_fits(nq, q_space, out_space) / small_begin() / launch_small(s, st, q, out, nq)
 //   Plan, prep(s, sc, q, ...), launch_eval(s, sc, P)   the two stages of a ring chunk
+//   ring_groups = true, groupable(P), launch_eval_group(s, sets, plans, w)   one evaluation launch for w ring chunks
 // The sharded call of these handles (Job / Shard / sharded_float) is written once too, beside run_shards in
 // ndinterp_api.hip, whose worker pool it needs.  What the families do differently is listed in DESIGN.md 4.9b.  This is not NarrowEngine (narrow_host.hpp): that one
 // serialises a handle's calls on a mutex and owns one scratch set; this one takes a per-stream workspace lease with a
@@ -46,9 +47,13 @@ template <class Plan>
 struct RingRun {
   std::unique_lock<std::mutex> own;
   std::vector<void*> slots;
-  uint64_t pitch = 0, chunk = 0, cq0 = 0;
+  uint64_t pitch = 0, chunk = 0;
   uint32_t n_slots = 0;
-  Plan plan0;
+  uint32_t wmax = 1;         // chunks per evaluation launch, at most (1: the family or NDI_RING_GROUP has no groups)
+  bool narrow_first = false; // chunk 0 is launched alone (NDI_RING_GROUP=2)
+  uint32_t n_sets = 2;       // scratch sets in use: chunk k lives in set k % n_sets
+  uint64_t prepped = 0;      // chunks [0, prepped) were located + grouped by ring_begin
+  std::vector<Plan> plans;   // the plan of the chunk in every set
   hipStream_t side = nullptr;
 };
 
@@ -275,12 +280,34 @@ struct FloatEngine {
 
   // ---- ring evaluation ----------------------------------------------------------------------
   // interp_array for outputs that do not fit / need not stay in device memory: chunks through a ring.  The producer is a
-  // two-stream pipeline: locate + group of chunk k+1 run on the workspace's side stream into the other scratch set while
-  // chunk k is evaluated on the caller's stream; events order the two.
+  // two-stream pipeline: locate + group of the next chunks run on the workspace's side stream into scratch sets of their
+  // own while the previous ones are evaluated on the caller's stream; events order the two.
   //
+  // Groups (a family with ring_groups: the 1-D long-row bucketed plan).  Up to wmax = min(n_slots, RING_GROUP_MAX)
+  // consecutive chunks, each prepared on its own, are evaluated by ONE launch (launch_eval_group): the launch's fixed cost
+  // -- the table set read once beside the write stream, ramp and drain -- is paid once per group instead of once per
+  // chunk.  A chunk joins a group only while every consumer so far has released its slot stream-ordered (returned NULL):
+  // the slots a group writes are then free as soon as the caller's stream gets there.  A consumer that returns an event
+  // works on another stream and lives on the overlap of chunk k+1's evaluation with its own work on chunk k: from its
+  // first event on, the call runs one chunk per launch, as it always has.  consume() is still called once per chunk, in
+  // order, after the chunk's kernels (its group's launch) are enqueued.  Chunk k uses scratch set k mod 2 * wmax: a
+  // group being evaluated and the group being prepared never share a set.
+  static constexpr bool ring_groups = false;   // (shadowed by a family that has launch_eval_group / groupable)
+
+  template <class Plan>
+  void ring_prep(hipStream_t s, Workspace& ws, Queries<T> q, uint64_t k, uint64_t cq, RingRun<Plan>& R, int path,
+                 bool beside_eval) {
+    Scratch& sc = ws.sc[k % R.n_sets];
+    if (k >= R.n_sets) NDI_HIP(hipStreamWaitEvent(R.side, sc.eval_done, 0));   // chunk k - n_sets has released the set
+    R.plans[k % R.n_sets] = self().prep(R.side, sc, q + k * R.chunk, cq, (T*)R.slots[k % R.n_slots], R.pitch, path,
+                                        beside_eval);
+    NDI_HIP(hipEventRecord(sc.prep_done, R.side));
+  }
+
   // ring_begin resolves the ring and starts locate + group of chunk 0 on the side stream -- before the first failing
   // index of the batch is known on the host (it does not depend on it: the evaluation kernels skip rows at / after the
-  // chunk's own first failure), so the range pre-pass and its synchronisation are hidden behind it.
+  // chunk's own first failure), so the range pre-pass and its synchronisation are hidden behind it.  With full-width
+  // groups from the start, so are the other chunks of the first group.
   template <class Plan>
   void ring_begin(hipStream_t s, Workspace& ws, Queries<T> q, uint64_t nq, const ndi_ring_desc* ring, uint64_t stride,
                   const ndi_eval_opts& o, RingRun<Plan>& R) {
@@ -298,13 +325,24 @@ struct FloatEngine {
       R.pitch = (uint64_t)ring->n_slots * stride;
     }
     R.side = ring_overlap() ? ws.side_stream() : s;
-    for (Scratch& sc : ws.sc) sc.ensure_events();
+    const int mode = Impl::ring_groups ? ring_group_mode() : 0;
+    R.wmax = mode ? std::min<uint32_t>({R.n_slots, (uint32_t)RING_GROUP_MAX, Workspace::MAX_SETS / 2}) : 1u;
+    R.narrow_first = mode == 2;
+    R.n_sets = 2 * R.wmax;
+    R.plans.assign(R.n_sets, Plan{});
+    for (uint32_t i = 0; i < R.n_sets; ++i) ws.sc[i].ensure_events();
     // the side stream starts after everything already enqueued on s (the query upload)
     NDI_HIP(hipEventRecord(ws.order_event(), s));
     NDI_HIP(hipStreamWaitEvent(R.side, ws.order_event(), 0));
-    R.cq0 = std::min<uint64_t>(R.chunk, nq);
-    R.plan0 = self().prep(R.side, ws.sc[0], q, R.cq0, (T*)R.slots[0], R.pitch, o.path);
-    NDI_HIP(hipEventRecord(ws.sc[0].prep_done, R.side));
+    uint64_t first = 1;   // chunks of the first launch
+    if constexpr (Impl::ring_groups)
+      if (!R.narrow_first) first = std::min<uint64_t>(R.wmax, (nq + R.chunk - 1) / R.chunk);
+    for (R.prepped = 0; R.prepped < first;) {
+      const uint64_t k = R.prepped++;
+      ring_prep(s, ws, q, k, std::min<uint64_t>(R.chunk, nq - k * R.chunk), R, o.path, false);
+      if constexpr (Impl::ring_groups)
+        if (!self().groupable(R.plans[k])) break;   // no group starts here: nothing to prepare ahead
+    }
   }
 
   // Produces the rows [0, limit) of the batch chunk by chunk.  q_offset / shard: position of this batch in a
@@ -313,33 +351,56 @@ struct FloatEngine {
   void ring_produce(hipStream_t s, Workspace& ws, Queries<T> q, uint64_t limit, RingRun<Plan>& R,
                     ndi_ring_consumer consume, void* user, const ndi_eval_opts& o, uint64_t q_offset, uint32_t shard) {
     std::vector<hipEvent_t> busy(R.n_slots, nullptr);
-    uint64_t k = 0;
-    for (uint64_t off = 0; off < limit; off += R.chunk, ++k) {
-      const uint64_t cq = std::min<uint64_t>(R.chunk, limit - off);
-      const uint32_t slot = (uint32_t)(k % R.n_slots);
-      Scratch& sc = ws.sc[k & 1];
-      Plan P = R.plan0;
-      if (k > 0) {
-        if (k >= 2) NDI_HIP(hipStreamWaitEvent(R.side, sc.eval_done, 0));   // chunk k-2 has released the set
-        P = self().prep(R.side, sc, q + off, cq, (T*)R.slots[slot], R.pitch, o.path, R.side != s);
-        NDI_HIP(hipEventRecord(sc.prep_done, R.side));
+    const uint64_t nchunks = (limit + R.chunk - 1) / R.chunk;
+    auto count = [&](uint64_t k) { return std::min<uint64_t>(R.chunk, limit - k * R.chunk); };
+    bool solo = R.wmax == 1;      // one chunk per launch: no groups, or a consumer has returned an event
+    uint64_t prepped = R.prepped; // chunks [k, prepped) are located + grouped
+    for (uint64_t k = 0; k < nchunks;) {
+      uint32_t want = solo || (R.narrow_first && k == 0) ? 1u : (uint32_t)std::min<uint64_t>(R.wmax, nchunks - k);
+      uint32_t w = 0;
+      while (w < want) {
+        if (k + w >= prepped) {
+          ring_prep(s, ws, q, k + w, count(k + w), R, o.path, R.side != s);
+          prepped = k + w + 1;
+        }
+        bool joins = w == 0;     // the first chunk is evaluated whatever its plan; the others only by a group launch
+        if constexpr (Impl::ring_groups) joins = joins || (self().groupable(R.plans[k % R.n_sets]) &&
+                                                          self().groupable(R.plans[(k + w) % R.n_sets]));
+        if (!joins) break;       // (it stays prepared and opens the next launch)
+        ++w;
       }
-      NDI_HIP(hipStreamWaitEvent(s, sc.prep_done, 0));
-      if (busy[slot]) {   // the consumer reads this slot on another stream: wait for it there
-        NDI_HIP(hipStreamWaitEvent(s, busy[slot], 0));
-        busy[slot] = nullptr;
+      Scratch* sets[RING_GROUP_MAX];
+      Plan plans[RING_GROUP_MAX];
+      for (uint32_t i = 0; i < w; ++i) {
+        sets[i] = &ws.sc[(k + i) % R.n_sets];
+        plans[i] = R.plans[(k + i) % R.n_sets];
+        NDI_HIP(hipStreamWaitEvent(s, sets[i]->prep_done, 0));
+        const uint32_t slot = (uint32_t)((k + i) % R.n_slots);
+        if (busy[slot]) {   // the consumer reads this slot on another stream: wait for it there
+          NDI_HIP(hipStreamWaitEvent(s, busy[slot], 0));
+          busy[slot] = nullptr;
+        }
       }
-      self().launch_eval(s, sc, P);
-      NDI_HIP(hipEventRecord(sc.eval_done, s));
-      if (consume) {
+      bool grouped = false;
+      if constexpr (Impl::ring_groups)
+        if (self().groupable(plans[0])) {
+          self().launch_eval_group(s, sets, plans, w);
+          grouped = true;
+        }
+      if (!grouped) self().launch_eval(s, *sets[0], plans[0]);   // (w == 1)
+      for (uint32_t i = 0; i < w; ++i) NDI_HIP(hipEventRecord(sets[i]->eval_done, s));
+      for (uint32_t i = 0; i < w && consume; ++i) {
+        const uint32_t slot = (uint32_t)((k + i) % R.n_slots);
         ndi_ring_chunk c{};
-        c.index = k; c.q_begin = q_offset + off; c.q_count = cq; c.out = R.slots[slot]; c.row_stride = R.pitch;
-        c.slot = slot; c.shard = shard; c.stream = (void*)s;
+        c.index = k + i; c.q_begin = q_offset + (k + i) * R.chunk; c.q_count = count(k + i); c.out = R.slots[slot];
+        c.row_stride = R.pitch; c.slot = slot; c.shard = shard; c.stream = (void*)s;
         busy[slot] = (hipEvent_t)consume(user, &c);
+        if (busy[slot]) solo = true;   // a consumer on another stream: it keeps its overlap, one chunk per launch from here
       }
+      k += w;
     }
     NDI_HIP(hipStreamSynchronize(s));
-    NDI_HIP(hipStreamSynchronize(R.side));   // (a speculative chunk 0 that was never evaluated)
+    NDI_HIP(hipStreamSynchronize(R.side));   // (speculative chunks that were never evaluated)
     for (hipEvent_t e : busy)
       if (e) NDI_HIP(hipEventSynchronize(e));
     ws.pending = false;

@@ -2367,6 +2367,129 @@ __global__ __launch_bounds__(BLOCK) void eval_bucketed_kernel(Eval1Args<T> A) {
   }
 }
 
+// eval_bucketed_kernel over a GROUP of up to RING_GROUP_MAX chunks of a ring evaluation in one launch: every chunk was
+// located and grouped on its own (own record array, query count, output base and status block), the tables and the row
+// pitch are shared.  What one launch saves over `width` launches is the once-per-launch read of the table set
+// interleaved into the write stream, and the launch's ramp and drain (profiles/ring_groups.md).  For the tables to be
+// fetched once, the pieces (CQ grouped queries) of the same interval from different chunks must run side by side on one
+// XCD: the workgroup index space is nmax rounds x width chunks, round-major, nmax = pieces of the longest chunk, walked
+// in the XCD-aware order of eval_bucketed_kernel; in round r chunk c contributes its piece floor(r * n_c / nmax) -- the
+// piece at the same relative position of its interval-sorted sequence -- in the last round that maps to it, so a shorter
+// (ragged last) chunk leaves nmax - n_c workgroup passes empty.  (Placement is a speed heuristic only.)
+// One piece per workgroup pass (run = 1); the per-piece body -- staging, row_coef / row_point, store policy, the FULL
+// straight-line variant -- is eval_bucketed_kernel's, line by line, with the chunk's own rec / nq / out / limit.
+constexpr int RING_GROUP_MAX = 4;
+template <class T>
+struct EvalGroupArgs {
+  Eval1Args<T> A;   // tables, lanes, out_stride, n_int (its q / idx / t / out / nq / status / rec are not read)
+  const uint4* rec[RING_GROUP_MAX];
+  uint64_t nq[RING_GROUP_MAX];
+  T* out[RING_GROUP_MAX];
+  const StatusBlock* status[RING_GROUP_MAX];
+  uint32_t width;   // 1 .. RING_GROUP_MAX
+};
+
+template <class T, int STRAT, int U, int CQ, bool NT = true, bool FULL = false>
+__global__ __launch_bounds__(BLOCK) void eval_bucketed_group_kernel(EvalGroupArgs<T> G) {
+  constexpr int VN = Wide<T>::N;
+  using V = typename VecT<T, VN>::type;
+  __shared__ uint32_t s_q[CQ];
+  __shared__ uint32_t s_i[CQ];
+  __shared__ T s_s[CQ];  // cubic: t          linear: raw x
+  const Eval1Args<T>& A = G.A;
+  const uint64_t LV = A.lanes / VN;
+  const uint32_t seg_vecs = BLOCK * U;
+  const uint32_t segs = (uint32_t)((LV + seg_vecs - 1) / seg_vecs);
+  const uint32_t width = G.width;
+  uint64_t nmax = 0;
+#pragma unroll
+  for (int w = 0; w < RING_GROUP_MAX; ++w) {
+    const uint64_t n_w = (uint32_t)w < width ? (G.nq[w] + CQ - 1) / CQ : 0;
+    if (n_w > nmax) nmax = n_w;
+  }
+  const uint64_t n_virtual = nmax * width;
+  const uint64_t per = (n_virtual + 7) / 8;
+  for (uint32_t seg = blockIdx.y; seg < segs; seg += gridDim.y) {
+    const uint64_t v0 = (uint64_t)seg * seg_vecs + threadIdx.x;
+    for (uint64_t vb = blockIdx.x; vb < per * 8; vb += gridDim.x) {
+      const uint64_t xcd = vb & 7u;
+      const uint64_t vi = xcd * per + (vb >> 3);
+      if (vi >= n_virtual) continue;   // (workgroup-uniform, as every branch up to the staging barrier)
+      const uint64_t rnd = vi / width;
+      const uint32_t c = (uint32_t)(vi - rnd * width);
+      const uint4* rec = G.rec[0];
+      uint64_t nq = G.nq[0];
+      T* out = G.out[0];
+      const StatusBlock* status = G.status[0];
+#pragma unroll
+      for (int w = 1; w < RING_GROUP_MAX; ++w)
+        if (c == (uint32_t)w) {
+          rec = G.rec[w];
+          nq = G.nq[w];
+          out = G.out[w];
+          status = G.status[w];
+        }
+      const uint64_t n_c = (nq + CQ - 1) / CQ;
+      uint64_t chunk = rnd;
+      if (n_c != nmax) {
+        chunk = rnd * n_c / nmax;
+        if ((rnd + 1) * n_c / nmax == chunk) continue;   // a later round evaluates this piece
+      }
+      const unsigned long long n_valid = nq;  // every query is grouped ...
+      unsigned long long limit = status->first_fail[0];  // ... and rows at or after the chunk's first failure are skipped
+      if (limit > nq) limit = nq;
+      V ryl[U], ryr[U], ra[U], rb[U];
+      uint32_t cur = 0xffffffffu;
+      const uint64_t p0 = chunk * CQ;
+      const uint32_t cnt = (n_valid - p0 < (uint64_t)CQ) ? (uint32_t)(n_valid - p0) : (uint32_t)CQ;
+      __syncthreads();
+      for (uint32_t j = threadIdx.x; j < cnt; j += BLOCK) {
+        const uint4 r = rec[p0 + j];
+        s_q[j] = r.x;
+        s_i[j] = r.y;
+        s_s[j] = rec_value(r, T(0));
+      }
+      __syncthreads();
+      auto emit = [&](uint32_t i, uint32_t qi, T sj) {
+        const RowCoef<T, STRAT> cf = row_coef<T, STRAT>(A.knots, i, sj, sj);
+        V* o = reinterpret_cast<V*>(out + (uint64_t)qi * A.out_stride);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const uint64_t v = v0 + (uint64_t)u * BLOCK;
+          if (FULL || v < LV) store_stream<NT>(o + v, row_point<T, STRAT, V>(cf, ryl[u], ryr[u], ra[u], rb[u]));
+        }
+      };
+      for (uint32_t j = 0; j < cnt;) {
+        const uint32_t i = NDI_CHK((uint32_t)__builtin_amdgcn_readfirstlane((int)s_i[j]), A.n_int, BC_INTERVAL);
+        const uint32_t qi = NDI_CHK((uint32_t)__builtin_amdgcn_readfirstlane((int)s_q[j]), nq, BC_QUERY);
+        if (qi >= limit) { ++j; continue; }
+        if (i != cur) {
+          cur = i;
+          const V* yl = reinterpret_cast<const V*>(A.data + (uint64_t)i * A.lanes);
+          const V* yr = yl + LV;
+          const V* pa = reinterpret_cast<const V*>(A.ca + (uint64_t)i * A.lanes);
+          const V* pb = reinterpret_cast<const V*>(A.cb + (uint64_t)i * A.lanes);
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            const uint64_t v = v0 + (uint64_t)u * BLOCK;
+            if (FULL || v < LV) {
+              ryl[u] = yl[v];
+              ryr[u] = yr[v];
+              if (STRAT == ST_CUBIC) {
+                ra[u] = pa[v];
+                rb[u] = pb[v];
+              }
+            }
+          }
+          // (no explicit drain of the loads here: see the note in eval_bucketed_kernel)
+        }
+        emit(i, qi, s_s[j]);
+        ++j;
+      }
+    }
+  }
+}
+
 // BUCKETED for rows shorter than one workgroup pass (fewer than 256 vectors): the workgroup is split into NG = 256 / G
 // groups of G threads (G = power of two >= vectors per row; lanes beyond the row idle), each group streams its own
 // run of CQ consecutive grouped records and keeps the interval's four operand vectors in registers -- one vector per

@@ -482,8 +482,10 @@ constexpr size_t FUSED_LDS_LIMIT = 160 * 1024;          // eval_fused_kernel wit
 // workspace: per (handle, stream) scratch, reused across stream-ordered evaluations
 // ---------------------------------------------------------------------------------------------
 // One set of per-chunk scratch: what the locate / group kernels of a chunk write and its evaluation reads.  A
-// workspace carries two, so that the ring evaluation can locate + group chunk k+1 on a side stream while chunk k is
-// being evaluated (the set is handed back by the eval_done event).
+// workspace carries MAX_SETS of them (buffers are allocated on first use; every path but the ring uses set 0 -- the
+// antiderivative pair also set 1): the ring evaluation locates + groups the next chunks on a side stream while the
+// previous ones are being evaluated, chunk k in set k mod 2W for a group width of W (a set is handed back by its
+// eval_done event).
 struct Scratch {
   DevBuf idx, idx2, t, perm, counts, cursor, hist, status, recq, chunkbin;
   DevBuf perm2, recq2, chist, cursor2;   // two-level 2-D grouping: coarse-ordered records, row histograms, consumable cursors
@@ -502,7 +504,8 @@ struct Scratch {
 };
 
 struct Workspace {
-  Scratch sc[2];
+  static constexpr uint32_t MAX_SETS = 8;
+  Scratch sc[MAX_SETS];
   DevBuf status, qdev, qdev2, stage;   // status: the range pre-pass of the ring / sharded evaluations
   StatusBlock* host_status = nullptr;  // pinned
   void* pin = nullptr;                 // pinned bounce buffer of the small-batch host path
@@ -541,7 +544,7 @@ struct Workspace {
   }
   void ensure_status() {
     status.reserve(sizeof(StatusBlock));
-    for (Scratch& s : sc) s.status.reserve(sizeof(StatusBlock));
+    for (int i = 0; i < 2; ++i) sc[i].status.reserve(sizeof(StatusBlock));   // (prep() reserves the status of the set it fills)
     if (!host_status) NDI_HIP(hipHostMalloc((void**)&host_status, sizeof(StatusBlock), hipHostMallocDefault));
   }
   hipStream_t side_stream() {
@@ -811,6 +814,18 @@ static ShortKnobs short_knobs() {
 // The ring's locate + group of chunk k + 1 run on a side stream beside chunk k's evaluation (measured against running
 // them on the evaluation stream: profiles/r03_ring_overlap.md).
 static constexpr bool ring_overlap() { return true; }
+
+// NDI_RING_GROUP: how the ring producer groups the chunks whose slots are free into one evaluation launch (1-D long-row
+// bucketed plan; float_host.hpp ring_produce).  0 = one launch per chunk; 1 = full-width groups from the first chunk on;
+// 2 = a narrow first launch (chunk 0 alone: only its own search + grouping are exposed), full-width groups after it.
+// Read once, or per call under NDI_TUNE_LIVE.
+constexpr int RING_GROUP_DEFAULT = 1;
+static int ring_group_mode() {
+  static const bool live = std::getenv("NDI_TUNE_LIVE") != nullptr;
+  static const int once = ShortKnobs::env("NDI_RING_GROUP", RING_GROUP_DEFAULT);
+  const int m = live ? ShortKnobs::env("NDI_RING_GROUP", RING_GROUP_DEFAULT) : once;
+  return m >= 0 && m <= 2 ? m : RING_GROUP_DEFAULT;
+}
 
 static ndi_status check_ring_desc(const ndi_ring_desc* ring, uint64_t lanes, uint64_t* stride) {
   if (!ring || ring->n_slots == 0 || ring->chunk_queries == 0)
@@ -2026,6 +2041,64 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     }
     NDI_HIP(hipGetLastError());
     ps.done();
+  }
+
+  // ---- ring groups: one evaluation launch for several chunks of a ring (float_host.hpp ring_produce) ----------------
+  // Only the long-row bucketed plan has a group form; every other plan keeps one launch per chunk.
+  static constexpr bool ring_groups = true;
+  static bool groupable(const Plan1& P) { return P.kind == Plan1::BUCKETED; }
+
+  // Evaluates the w >= 1 chunks prepared into sc[0 .. w) with the plans P[0 .. w) -- all groupable, one row pitch -- in
+  // ONE launch (w = 1: the single-chunk kernel, launch_eval).
+  void launch_eval_group(hipStream_t s, Scratch* const* sc, const Plan1* P, uint32_t w) {
+    if (std::getenv("NDI_TRACE_PLAN"))
+      std::fprintf(stderr, "[ndi plan] ring bucketed L=%llu lv=%llu width=%u nq=%llu\n", (unsigned long long)lanes,
+                   (unsigned long long)P[0].LV, w, (unsigned long long)P[0].nq);
+    if (w == 1) {
+      launch_eval(s, *sc[0], P[0]);
+      return;
+    }
+    if (w > (uint32_t)RING_GROUP_MAX) throw HipFailure{hipErrorInvalidValue, "launch_eval_group: group too wide", __LINE__};
+    EvalGroupArgs<T> G{};
+    G.A.knots = pyr.view.lv0;
+    G.A.data = data.as<T>();
+    G.A.ca = ca.as<T>();
+    G.A.cb = cb.as<T>();
+    G.A.lanes = lanes;
+    G.A.out_stride = P[0].out_stride;
+    G.A.n_int = (uint32_t)(n - 1);
+    G.width = w;
+    constexpr int CQ = 128;
+    uint64_t nmax = 0;
+    for (uint32_t i = 0; i < w; ++i) {
+      if (!groupable(P[i]) || P[i].out_stride != P[0].out_stride || P[i].LV != P[0].LV)
+        throw HipFailure{hipErrorInvalidValue, "launch_eval_group: plans of one group differ", __LINE__};
+      G.rec[i] = sc[i]->perm.as<uint4>();
+      G.nq[i] = P[i].nq;
+      G.out[i] = P[i].out;
+      G.status[i] = sc[i]->status.as<StatusBlock>();
+      nmax = std::max<uint64_t>(nmax, (P[i].nq + CQ - 1) / CQ);
+    }
+    const uint64_t LV = P[0].LV;
+    const int U = LV >= 2048 ? 8 : (LV >= 1024 ? 4 : (LV >= 512 ? 2 : 1));   // as launch_eval
+    const uint64_t segs = (LV + (uint64_t)BLOCK * U - 1) / ((uint64_t)BLOCK * U);
+    const uint64_t per_xcd = (nmax * w + 7) / 8;
+    const unsigned gx = (unsigned)std::max<uint64_t>(8, std::min<uint64_t>(per_xcd * 8, 65528));
+    dim3 grid(gx, (unsigned)std::min<uint64_t>(segs, 64));
+    const bool full = LV % ((uint64_t)BLOCK * U) == 0;
+#define NDI_BG(ST, UU)                                                                                            \
+  do {                                                                                                            \
+    if (full) launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_bucketed_group_kernel<T, ST, UU, CQ, true, true>, G); \
+    else launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_bucketed_group_kernel<T, ST, UU, CQ, true, false>, G);   \
+  } while (0)
+    if (strategy == NDI_CUBIC_SPLINE) {
+      if (U == 8) NDI_BG(ST_CUBIC, 8); else if (U == 4) NDI_BG(ST_CUBIC, 4);
+      else if (U == 2) NDI_BG(ST_CUBIC, 2); else NDI_BG(ST_CUBIC, 1);
+    } else {
+      if (U == 8) NDI_BG(ST_LINEAR, 8); else if (U == 4) NDI_BG(ST_LINEAR, 4);
+      else if (U == 2) NDI_BG(ST_LINEAR, 2); else NDI_BG(ST_LINEAR, 1);
+    }
+#undef NDI_BG
   }
 
   void launch_fused(hipStream_t s, Scratch& sc, const Plan1& P) {
