@@ -187,13 +187,10 @@ struct AntiderivImpl final : Interp1DBase, FloatEngine<T, AntiderivImpl<T>> {
       if (std::getenv("NDI_TRACE_PLAN"))
         std::fprintf(stderr, "[ndi plan] antiderivative eval form=rows linear=%d pair=%d vec=1 lv=%llu tile_q=0 grid=%u x %u\n",
                      (int)linear, (int)pair, (unsigned long long)LV, grid.x, grid.y);
-      if (linear) {
-        if (pair) launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, antideriv_eval_rows_kernel<T, true, true>, A);
-        else launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, antideriv_eval_rows_kernel<T, true, false>, A);
-      } else {
-        if (pair) launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, antideriv_eval_rows_kernel<T, false, true>, A);
-        else launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, antideriv_eval_rows_kernel<T, false, false>, A);
-      }
+      pick_bool(linear, [&](auto lin_) {
+        constexpr bool LIN = lin_;
+        pick_bool(pair, [&](auto pair_) { launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, antideriv_eval_rows_kernel<T, LIN, pair_>, A); });
+      });
       return;
     }
     const uint32_t tile_q = (uint32_t)std::max<uint64_t>(1, 1024 / std::max<uint64_t>(LV, 1));
@@ -203,14 +200,15 @@ struct AntiderivImpl final : Interp1DBase, FloatEngine<T, AntiderivImpl<T>> {
       std::fprintf(stderr, "[ndi plan] antiderivative eval form=flat linear=%d pair=%d vec=%d lv=%llu tile_q=%u grid=%u x 1\n",
                    (int)linear, (int)pair, (int)vec_ok, (unsigned long long)LV, tile_q, gx);
     ProfScope ps(s, PC_EVAL);
-#define NDI_AF(LIN, PAIR)                                                                                          \
-  do {                                                                                                             \
-    if (vec_ok) hipLaunchKernelGGL((antideriv_eval_flat_kernel<T, LIN, PAIR, VN>), dim3(gx), dim3(BLOCK), 0, s, A, tile_q); \
-    else hipLaunchKernelGGL((antideriv_eval_flat_kernel<T, LIN, PAIR, 1>), dim3(gx), dim3(BLOCK), 0, s, A, tile_q);        \
-  } while (0)
-    if (linear) { if (pair) NDI_AF(true, true); else NDI_AF(true, false); }
-    else { if (pair) NDI_AF(false, true); else NDI_AF(false, false); }
-#undef NDI_AF
+    pick_bool(linear, [&](auto lin_) {
+      constexpr bool LIN = lin_;
+      pick_bool(pair, [&](auto pair_) {
+        constexpr bool PAIR = pair_;
+        pick_or<1, VN>(vec_ok ? VN : 1, [&](auto vec_) {
+          hipLaunchKernelGGL((antideriv_eval_flat_kernel<T, LIN, PAIR, vec_>), dim3(gx), dim3(BLOCK), 0, s, A, tile_q);
+        });
+      });
+    });
     NDI_HIP(hipGetLastError());
     ps.done();
   }

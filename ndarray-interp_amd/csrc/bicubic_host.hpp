@@ -118,6 +118,12 @@ static ndi_status create2d_bicubic(const ndi_interp2d_desc& d, const ndi_boundar
   return NDI_OK;
 }
 
+// The vector-width x knots-in-LDS ladder of the three Bicubic launchers (surface, integral, jet): f(Int<VEC>, KLDS).
+template <class T, class F>
+static void bicubic_pick_form(bool vec, bool klds, F&& f) {
+  pick_or<1, Wide<T>::N>(vec ? Wide<T>::N : 1, [&](auto vec_) { pick_bool(klds, [&](auto kl_) { f(vec_, kl_); }); });
+}
+
 // Plan2::BICUBIC: the launch (the range pre-pass, when there is one, was enqueued by prep)
 template <class T>
 static void bicubic_launch_eval(const Interp2DImpl<T>& h, hipStream_t s, StatusBlock* st, const T* qx, const T* qy,
@@ -147,39 +153,21 @@ static void bicubic_launch_eval(const Interp2DImpl<T>& h, hipStream_t s, StatusB
   const bool klds = knots + strips <= LDS_STAGE_LIMIT;
   const size_t lds = (klds ? knots : 0) + strips;
   // staging the axes is the fixed cost of a workgroup: no more workgroups than a few per resident slot
-  const size_t wg_per_cu = std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, 32 / (TB / 64)));
   const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + TB - 1) / TB,
-                                                                        std::max<uint64_t>(1, (uint64_t)cu_count() * wg_per_cu * 4 / gy)));
+                                                                        std::max<uint64_t>(1, (uint64_t)cu_count() * wgs_per_cu(lds, TB) * 4 / gy)));
   if (std::getenv("NDI_TRACE_PLAN"))
     std::fprintf(stderr, "[ndi plan] bicubic vec=%d lv=%llu klds=%d grid=%u x %u lds=%zu prepass=%d guess=%d,%d levels=%d,%d "
                  "nu=%d,%d\n",
                  (int)vec, (unsigned long long)A.lv, (int)klds, gx, gy, lds, check ? 0 : 1, A.px.guess, A.py.guess,
                  A.px.levels, A.py.levels, h.nu_x, h.nu_y);
-#define NDI_BC(VEC, KL, NX, NY)                                                          \
-  do {                                                                                   \
-    auto kern = eval_bicubic_kernel<T, VEC, KL, TB, NX, NY>;                             \
-    allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)LDS_STAGE_LIMIT);        \
-    launch1<T>(s, PC_EVAL, dim3(gx, gy), dim3(TB), lds, kern, A);                        \
-  } while (0)
-#define NDI_BC_FORM(NX, NY)                                                              \
-  do {                                                                                   \
-    if (vec) { if (klds) NDI_BC(VN, true, NX, NY); else NDI_BC(VN, false, NX, NY); }     \
-    else { if (klds) NDI_BC(1, true, NX, NY); else NDI_BC(1, false, NX, NY); }           \
-  } while (0)
-  switch (h.nu_x * 3 + h.nu_y) {   // the orders were checked when the handle was made (Interp2DImpl::partial): 0 .. 2 each
-    case 0: NDI_BC_FORM(0, 0); break;
-    case 1: NDI_BC_FORM(0, 1); break;
-    case 2: NDI_BC_FORM(0, 2); break;
-    case 3: NDI_BC_FORM(1, 0); break;
-    case 4: NDI_BC_FORM(1, 1); break;
-    case 5: NDI_BC_FORM(1, 2); break;
-    case 6: NDI_BC_FORM(2, 0); break;
-    case 7: NDI_BC_FORM(2, 1); break;
-    case 8: NDI_BC_FORM(2, 2); break;
-    default: throw HipFailure{hipErrorInvalidValue, "bicubic_launch_eval: partial orders outside 0 .. 2", __LINE__};
-  }
-#undef NDI_BC_FORM
-#undef NDI_BC
+  // the orders were checked when the handle was made (Interp2DImpl::partial): 0 .. 2 each
+  const bool known = pick<0, 1, 2, 3, 4, 5, 6, 7, 8>(h.nu_x * 3 + h.nu_y, [&](auto nu_) {
+    constexpr int NX = nu_ / 3, NY = nu_ % 3;
+    bicubic_pick_form<T>(vec, klds, [&](auto vec_, auto kl_) {
+      launch_lds<T>(eval_bicubic_kernel<T, vec_, kl_, TB, NX, NY>, LDS_STAGE_LIMIT, s, PC_EVAL, dim3(gx, gy), dim3(TB), lds, A);
+    });
+  });
+  if (!known) throw HipFailure{hipErrorInvalidValue, "bicubic_launch_eval: partial orders outside 0 .. 2", __LINE__};
 }
 
 // ndi_interp2d_tables: zx, zy, zxy as plain [nx][ny][lanes] arrays (any of them may be NULL)

@@ -101,27 +101,17 @@ static void bicubic_integral_launch_eval(const Interp2DImpl<T>& h, hipStream_t s
   const size_t knots = (h.px.lds_bytes + h.py.lds_bytes + 15) & ~(size_t)15;
   const bool klds = knots + strips <= LDS_STAGE_LIMIT;
   const size_t lds = (klds ? knots : 0) + strips;
-  const size_t wg_per_cu = std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, 32 / (TB / 64)));
   const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + TB - 1) / TB,
-                                                                        std::max<uint64_t>(1, (uint64_t)cu_count() * wg_per_cu * 4 / gy)));
+                                                                        std::max<uint64_t>(1, (uint64_t)cu_count() * wgs_per_cu(lds, TB) * 4 / gy)));
   if (std::getenv("NDI_TRACE_PLAN"))
     std::fprintf(stderr, "[ndi plan] bicubic integral rect=%d vec=%d lv=%llu klds=%d grid=%u x %u lds=%zu prepass=%d\n",
                  (int)rect, (int)vec, (unsigned long long)A.lv, (int)klds, gx, gy, lds, check ? 0 : 1);
-#define NDI_BI(VEC, KL, RC)                                                              \
-  do {                                                                                   \
-    auto kern = eval_bicubic_integral_kernel<T, VEC, KL, TB, RC>;                        \
-    allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)LDS_STAGE_LIMIT);        \
-    launch1<T>(s, PC_EVAL, dim3(gx, gy), dim3(TB), lds, kern, A);                        \
-  } while (0)
-#define NDI_BI_FORM(RC)                                                                  \
-  do {                                                                                   \
-    if (vec) { if (klds) NDI_BI(VN, true, RC); else NDI_BI(VN, false, RC); }             \
-    else { if (klds) NDI_BI(1, true, RC); else NDI_BI(1, false, RC); }                   \
-  } while (0)
-  if (rect) NDI_BI_FORM(true);
-  else NDI_BI_FORM(false);
-#undef NDI_BI_FORM
-#undef NDI_BI
+  pick_bool(rect, [&](auto rect_) {
+    constexpr bool RC = rect_;
+    bicubic_pick_form<T>(vec, klds, [&](auto vec_, auto kl_) {
+      launch_lds<T>(eval_bicubic_integral_kernel<T, vec_, kl_, TB, RC>, LDS_STAGE_LIMIT, s, PC_EVAL, dim3(gx, gy), dim3(TB), lds, A);
+    });
+  });
 }
 
 // ndi_interp2d_integral_tables: the five prefix tables as plain [nx][ny][lanes] arrays (any of them may be NULL)

@@ -40,27 +40,17 @@ static void bicubic_jet_launch(const Interp2DImpl<T>& h, int order, hipStream_t 
   const size_t knots = (h.px.lds_bytes + h.py.lds_bytes + 15) & ~(size_t)15;
   const bool klds = knots + strips <= LDS_STAGE_LIMIT;
   const size_t lds = (klds ? knots : 0) + strips;
-  const size_t wg_per_cu = std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, 32 / (TB / 64)));
   const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + TB - 1) / TB,
-                                                                        std::max<uint64_t>(1, (uint64_t)cu_count() * wg_per_cu * 4 / gy)));
+                                                                        std::max<uint64_t>(1, (uint64_t)cu_count() * wgs_per_cu(lds, TB) * 4 / gy)));
   if (std::getenv("NDI_TRACE_PLAN"))
     std::fprintf(stderr, "[ndi plan] bicubic_jet order=%d vec=%d lv=%llu klds=%d grid=%u x %u lds=%zu prepass=%d\n", order,
                  (int)vec, (unsigned long long)A.lv, (int)klds, gx, gy, lds, check ? 0 : 1);
-#define NDI_BJ(VEC, KL, ORD)                                                             \
-  do {                                                                                   \
-    auto kern = eval_bicubic_jet_kernel<T, VEC, KL, TB, ORD>;                            \
-    allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)LDS_STAGE_LIMIT);        \
-    launch1<T>(s, PC_EVAL, dim3(gx, gy), dim3(TB), lds, kern, A);                        \
-  } while (0)
-#define NDI_BJ_FORM(ORD)                                                                 \
-  do {                                                                                   \
-    if (vec) { if (klds) NDI_BJ(VN, true, ORD); else NDI_BJ(VN, false, ORD); }           \
-    else { if (klds) NDI_BJ(1, true, ORD); else NDI_BJ(1, false, ORD); }                 \
-  } while (0)
-  if (order == 1) NDI_BJ_FORM(1);
-  else NDI_BJ_FORM(2);
-#undef NDI_BJ_FORM
-#undef NDI_BJ
+  pick_or<2, 1>(order, [&](auto ord_) {
+    constexpr int ORD = ord_;
+    bicubic_pick_form<T>(vec, klds, [&](auto vec_, auto kl_) {
+      launch_lds<T>(eval_bicubic_jet_kernel<T, vec_, kl_, TB, ORD>, LDS_STAGE_LIMIT, s, PC_EVAL, dim3(gx, gy), dim3(TB), lds, A);
+    });
+  });
 }
 
 // ndi_interp2d_eval_jet of a Bicubic surface handle (Interp2DImpl::eval_jet has refused every other handle).  Every
@@ -103,20 +93,11 @@ static ndi_status bicubic_jet_eval(Interp2DImpl<T>& h, int order, const void* qx
   const Queries<T> orig{(const T*)qx_, (const T*)qy_};
   const Queries<T> q = h.stage_queries(s, ws, orig, nq, o.q_memspace);
   ws.ensure_status();
-  g_last_path.store(NDI_PATH_GATHER);
-  const T x0 = h.px.host_knots.front(), xn = h.px.host_knots.back(), y0 = h.py.host_knots.front(), yn = h.py.host_knots.back();
   // one batch on device pointers; the status is on the host and the stream idle when it returns
   auto batch = [&](uint64_t off, uint64_t cq, T* const* outs, uint64_t stride, bool fresh) -> FirstFail {
     StatusBlock* st = ws.sc[0].status.template as<StatusBlock>();
     reset_status(st, s);
-    if (!fresh) {
-      const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((cq + BLOCK - 1) / BLOCK, 4096));
-      ProfScope ps(s, PC_LOCATE);
-      hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, q.a + off, q.b + off, cq, x0, xn, y0, yn, h.mode,
-                         &st->first_fail[0]);
-      NDI_HIP(hipGetLastError());
-      ps.done();
-    }
+    h.range_prepass(s, ws.sc[0], q + off, cq, fresh);
     bicubic_jet_launch<T>(h, order, s, st, q.a + off, q.b + off, cq, outs, stride, fresh);
     NDI_HIP(hipMemcpyAsync(ws.host_status, st, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
     NDI_HIP(hipStreamSynchronize(s));

@@ -124,23 +124,36 @@ struct FloatEngine {
     return {a, upload(ws.qdev2, q.b)};
   }
 
+  // range_check_kernel over the one or two query arrays of a batch against the family's range_limits: the lowest failing
+  // index per array into st->first_fail.
+  void launch_range_check(hipStream_t s, StatusBlock* st, Queries<T> q, uint64_t nq) {
+    T lim[4];
+    self().range_limits(lim);
+    const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
+    ProfScope ps(s, PC_LOCATE);
+    hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, q.a, q.b, nq, lim[0], lim[1], lim[2], lim[3],
+                       self().mode, &st->first_fail[0]);
+    NDI_HIP(hipGetLastError());
+    ps.done();
+  }
+
+  // The tail of every query-order plan: the path is recorded, and the range pre-pass the evaluation kernel relies on is
+  // enqueued -- unless `in_kernel`: a fresh output (NDI_EVAL_FRESH_OUTPUT: the buffer is dropped on Err) needs no
+  // pre-pass, the kernel's own range test reports the failure.  Returns in_kernel, the plan's l_check.  (The SMALL
+  // plans always pre-check and pass false.)
+  bool range_prepass(hipStream_t s, Scratch& sc, Queries<T> q, uint64_t nq, bool in_kernel) {
+    g_last_path.store(NDI_PATH_GATHER);
+    if (!in_kernel) launch_range_check(s, sc.status.as<StatusBlock>(), q, nq);
+    return in_kernel;
+  }
+
   // Range pre-pass over a whole batch (8 B per query and array): the lowest failing index per array lands in
   // ws.host_status once the stream has been synchronised.  The ring and the sharded evaluations need it before any row
   // is produced.
   void enqueue_prepass(hipStream_t s, Workspace& ws, Queries<T> q, uint64_t nq) {
     ws.ensure_status();
     reset_status(ws.status.p, s);
-    StatusBlock* st = ws.status.as<StatusBlock>();
-    T lim[4];
-    self().range_limits(lim);
-    const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-    {
-      ProfScope ps(s, PC_LOCATE);
-      hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, q.a, q.b, nq, lim[0], lim[1], lim[2], lim[3],
-                         self().mode, &st->first_fail[0]);
-      NDI_HIP(hipGetLastError());
-      ps.done();
-    }
+    launch_range_check(s, ws.status.as<StatusBlock>(), q, nq);
     NDI_HIP(hipMemcpyAsync(ws.host_status, ws.status.p, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
   }
 

@@ -68,9 +68,9 @@ static unsigned half_grid(uint64_t units, unsigned cap_per_cu) {
 // thread), beyond that one query per group of lanes, the group as wide as the row's 16-byte vectors (8 .. 64 lanes).
 // NDI_HALF_MAP = 1 / 2 forces the element / group mapping (tests).
 static bool half_group_mapping(uint64_t lanes) {
-  static const int env = [] { const char* e = std::getenv("NDI_HALF_MAP"); return e ? std::atoi(e) : 0; }();
-  if (env == 1) return false;
-  if (env == 2) return true;
+  static const Knob map{"NDI_HALF_MAP", 0};
+  if (map.get() == 1) return false;
+  if (map.get() == 2) return true;
   return lanes > 32;
 }
 static uint32_t half_glog(uint64_t lanes, bool vec) {

@@ -47,9 +47,9 @@ static unsigned int_grid(uint64_t items) {
 // data: a query per lane), one query per wavefront beyond (the search is done once per query and the row is streamed
 // by the wave).  NDI_INT_MAP = 1 / 2 forces the element / wave mapping (tests).
 static bool int_wave_mapping(uint64_t lanes) {
-  static const int env = [] { const char* e = std::getenv("NDI_INT_MAP"); return e ? std::atoi(e) : 0; }();
-  if (env == 1) return false;
-  if (env == 2) return true;
+  static const Knob map{"NDI_INT_MAP", 0};
+  if (map.get() == 1) return false;
+  if (map.get() == 2) return true;
   return lanes > 32;
 }
 

@@ -95,18 +95,10 @@ struct InverseImpl final : Interp1DBase, FloatEngine<T, InverseImpl<T>> {
   // One batch on device pointers: status reset, the range pre-pass on [Lo, Hi], ONE evaluation launch.
   // (path and flags: the engine's; this family has one form and always its range test)
   void enqueue(hipStream_t s, Workspace& ws, Queries<T> qs, uint64_t nq, T* out, uint64_t out_stride, int, int) {
-    g_last_path.store(NDI_PATH_GATHER);
     ws.sc[0].status.reserve(sizeof(StatusBlock));
     reset_status(ws.sc[0].status.p, s);
     StatusBlock* st = ws.sc[0].status.as<StatusBlock>();
-    {
-      const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-      ProfScope ps(s, PC_LOCATE);
-      hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, qs.a, (const T*)nullptr, nq, Lo, Hi, Lo, Hi,
-                         (int)EX_NO, &st->first_fail[0]);
-      NDI_HIP(hipGetLastError());
-      ps.done();
-    }
+    this->range_prepass(s, ws.sc[0], {qs.a, nullptr}, nq, false);   // (mode is EX_NO: the node range only)
     InverseEvalArgs<T> A{};
     A.knots = pyr.view.lv0;
     A.N = node_table();
@@ -129,6 +121,7 @@ struct InverseImpl final : Interp1DBase, FloatEngine<T, InverseImpl<T>> {
   // ---- what the host engine (float_host.hpp) takes from this family: no small-row paths, no ring -----------------------
   static constexpr bool small_rows = false, ring = false;
   static const char* axis_name(int) { return "v"; }
+  void range_limits(T lim[4]) const { lim[0] = lim[2] = Lo; lim[1] = lim[3] = Hi; }
   // a value outside [Lo, Hi] is a range failure, a NaN its own status -- whatever the source's extrapolation mode was
   ndi_status failure_status(T v) { return v == v ? NDI_OUT_OF_BOUNDS : NDI_NAN_QUERY; }
 

@@ -21,20 +21,13 @@
 //                          0 = the plain tables, 1 = the element-record copy (where it fits its cap)
 //   NDI_LANEWISE_WGS       workgroups per CU of the element kernels' grids
 struct LanewiseKnobs {
-  int mode = 0, records = -1, wgs = 8;
-  static LanewiseKnobs read() {
-    LanewiseKnobs k;
-    k.mode = ShortKnobs::env("NDI_LANEWISE_MODE", k.mode);
-    k.records = ShortKnobs::env("NDI_LANEWISE_RECORDS", k.records);
-    k.wgs = ShortKnobs::env("NDI_LANEWISE_WGS", k.wgs);
-    if (k.wgs < 1 || k.wgs > 64) k.wgs = 8;
-    return k;
-  }
+  int mode, records, wgs;
 };
 static LanewiseKnobs lanewise_knobs() {
-  static const bool live = std::getenv("NDI_TUNE_LIVE") != nullptr;
-  static const LanewiseKnobs once = LanewiseKnobs::read();
-  return live ? LanewiseKnobs::read() : once;
+  static const Knob mode{"NDI_LANEWISE_MODE", 0, Knob::live}, records{"NDI_LANEWISE_RECORDS", -1, Knob::live},
+      wgs{"NDI_LANEWISE_WGS", 8, Knob::live};
+  const int w = wgs.get();
+  return {mode.get(), records.get(), w < 1 || w > 64 ? 8 : w};
 }
 
 // Grid of an element kernel over `total` elements and the geometry its threads advance by.
@@ -298,19 +291,17 @@ void Interp1DImpl<T>::lanewise_enqueue(hipStream_t s, Workspace& ws, const T* q,
   if (std::getenv("NDI_TRACE_PLAN"))
     std::fprintf(stderr, "[ndi plan] lanewise form=fused cubic=%d stage=%d lut=%d records=%d check=%d grid=%u\n", (int)cubic,
                  (int)stage, bx.lut ? 1 : (bx32.lut ? 2 : 0), (int)(A.rec != nullptr), A.check, grid);
-#define NDI_LW(STRAT, STAGE, REC)                                                                                      \
-  do {                                                                                                                 \
-    if (STAGE) allow_dynamic_lds(reinterpret_cast<const void*>(&eval_lanewise_kernel<T, STRAT, STAGE, REC>), (int)LDS_STAGE_LIMIT); \
-    launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), shmem, eval_lanewise_kernel<T, STRAT, STAGE, REC>, A);              \
-  } while (0)
-  if (cubic) {
-    if (stage) { if (A.rec) NDI_LW(ST_CUBIC, true, true); else NDI_LW(ST_CUBIC, true, false); }
-    else { if (A.rec) NDI_LW(ST_CUBIC, false, true); else NDI_LW(ST_CUBIC, false, false); }
-  } else {
-    if (stage) { if (A.rec) NDI_LW(ST_LINEAR, true, true); else NDI_LW(ST_LINEAR, true, false); }
-    else { if (A.rec) NDI_LW(ST_LINEAR, false, true); else NDI_LW(ST_LINEAR, false, false); }
-  }
-#undef NDI_LW
+  pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
+    constexpr int ST = st_;
+    pick_bool(stage, [&](auto stage_) {
+      constexpr bool STAGE = stage_;
+      pick_bool(A.rec != nullptr, [&](auto rec_) {
+        auto kern = eval_lanewise_kernel<T, ST, STAGE, rec_>;
+        if (STAGE) allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)LDS_STAGE_LIMIT);
+        launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), shmem, kern, A);
+      });
+    });
+  });
 }
 
 template <class T>

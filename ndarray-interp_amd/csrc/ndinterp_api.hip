@@ -638,6 +638,13 @@ static void launch1(hipStream_t s, int cat, dim3 grid, dim3 block, size_t shmem,
   ps.done();
 }
 
+// launch1 of a kernel whose dynamic LDS may exceed the 64 KiB default: `limit` is what it is allowed (allow_dynamic_lds).
+template <class T, class K, class A>
+static void launch_lds(K kernel, size_t limit, hipStream_t s, int cat, dim3 grid, dim3 block, size_t shmem, const A& args) {
+  allow_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)limit);
+  launch1<T>(s, cat, grid, block, shmem, kernel, args);
+}
+
 static void reset_status(void* status, hipStream_t s) {
   // first_fail[0..1] = NO_FAIL (all ones), the rest zero -- ONE launch (two hipMemsetAsync calls cost the host twice
   // the enqueue time of a kernel, and the host path of a 0.8 ms step matters: DESIGN.md 4.4)
@@ -651,12 +658,9 @@ constexpr uint32_t GROUP_MAX_BLOCKS = 256;   // query slices of the block-local 
 constexpr uint32_t GROUP_MAX_BLOCKS_2D = 1024;   // upper limit of NDI_GROUP_BLOCKS for the 2-D tile grouping
 // NDI_GROUP_BLOCKS (A/B, read once): fewer, longer slices -- longer runs per (slice, bin) in the record scatter
 static uint32_t group_blocks() {
-  static const uint32_t v = [] {
-    const char* e = std::getenv("NDI_GROUP_BLOCKS");
-    const int k = e ? std::atoi(e) : 0;
-    return (uint32_t)(k >= 8 && k <= (int)GROUP_MAX_BLOCKS_2D ? k : (int)GROUP_MAX_BLOCKS);
-  }();
-  return v;
+  static const Knob knob{"NDI_GROUP_BLOCKS", 0};
+  const int k = knob.get();
+  return (uint32_t)(k >= 8 && k <= (int)GROUP_MAX_BLOCKS_2D ? k : (int)GROUP_MAX_BLOCKS);
 }
 constexpr uint32_t GROUP_MAX_BINS = 16384;   // histogram must fit LDS next to the pyramid
 
@@ -680,16 +684,18 @@ static unsigned cu_count() {
   return cache[dev] = (unsigned)std::max(n, 1);
 }
 
+// Workgroups of `tb` threads and `lds` bytes each that a CU holds at once (160 KiB LDS, 32 waves), at least one.
+static size_t wgs_per_cu(size_t lds, unsigned tb) {
+  return std::max<size_t>(1, std::min<size_t>((160 * 1024) / std::max<size_t>(lds, 1), 32 / (tb / 64)));
+}
+
 // Workgroup size for a kernel that needs `lds` bytes per workgroup: as few threads as keep 32 waves on a CU
 // (160 KiB LDS, at most 1024 threads per workgroup).
 static unsigned threads_for_lds(size_t lds) {
-  const size_t per_cu = std::max<size_t>(1, (160 * 1024) / std::max<size_t>(lds, 1));
   unsigned best = 256;
   size_t best_waves = 0;
   for (unsigned threads : {256u, 512u, 1024u}) {
-    const size_t waves_per_wg = threads / 64;
-    const size_t wgs = std::min<size_t>(per_cu, 32 / waves_per_wg);
-    const size_t waves = wgs * waves_per_wg;
+    const size_t waves = wgs_per_cu(lds, threads) * (threads / 64);
     if (waves > best_waves) {
       best_waves = waves;
       best = threads;
@@ -720,9 +726,9 @@ static void run_locate(hipStream_t s, const DevicePyramid<T>& pyr, const T* q, u
                          : std::min<uint64_t>((nq + 1023) / 1024, 2048);
   blocks = std::max<uint64_t>(blocks, 1);
   A.bx = BucketIndex<T>{nullptr, 0, T(0)};
-  constexpr int lut_env = 1;   // (the bucket index: A/B settled in round 3)
-  if (lut_env && A.stage_lds && nq >= 4096) pyr.ensure_bucket_index();
-  if (lut_env && A.stage_lds && pyr.lut_bytes && nq >= 4096 &&
+  // (the bucket index: A/B settled in round 3)
+  if (A.stage_lds && nq >= 4096) pyr.ensure_bucket_index();
+  if (A.stage_lds && pyr.lut_bytes && nq >= 4096 &&
       shmem + pyr.lut_bytes + (hist ? (size_t)nb * 4 : 0) <= LDS_STAGE_LIMIT) {
     A.bx = pyr.bidx;          // bucket index staged behind the pyramid: [pyramid | lut | histogram]
     shmem += pyr.lut_bytes;
@@ -731,7 +737,7 @@ static void run_locate(hipStream_t s, const DevicePyramid<T>& pyr, const T* q, u
     blocks = std::min<uint64_t>(blocks, (uint64_t)cu_count() * std::max<size_t>(1, (160 * 1024) / total));
   }
   A.bx32 = BucketIndex32<T>{nullptr, 0, T(0)};
-  if (lut_env && !A.stage_lds && nq >= 4096) {
+  if (!A.stage_lds && nq >= 4096) {
     pyr.ensure_bucket_index32();
     A.bx32 = pyr.bidx32;
   }
@@ -745,17 +751,14 @@ static void run_locate(hipStream_t s, const DevicePyramid<T>& pyr, const T* q, u
   A.slice = slice;
   A.hist = hist;
   A.nb = nb;
-  allow_dynamic_lds(reinterpret_cast<const void*>(&locate_kernel<T, true, LOCATE_QB>), (int)LDS_STAGE_LIMIT);
-  allow_dynamic_lds(reinterpret_cast<const void*>(&locate_kernel<T, false, LOCATE_QB>), (int)LDS_STAGE_LIMIT);
-  allow_dynamic_lds(reinterpret_cast<const void*>(&locate_kernel<T, true, 1>), (int)LDS_STAGE_LIMIT);
-  allow_dynamic_lds(reinterpret_cast<const void*>(&locate_kernel<T, false, 1>), (int)LDS_STAGE_LIMIT);
   if (slice_out) *slice_out = slice;
   if (blocks_out) *blocks_out = (uint32_t)blocks;
   const bool deep = slice / threads >= 16;   // batches per wave: queries of 4 batches requested together only then
-  if (A.stage_lds && deep) launch1<T>(s, PC_LOCATE, dim3((unsigned)blocks), dim3(threads), shmem, locate_kernel<T, true, LOCATE_QB>, A);
-  else if (A.stage_lds) launch1<T>(s, PC_LOCATE, dim3((unsigned)blocks), dim3(threads), shmem, locate_kernel<T, true, 1>, A);
-  else if (deep) launch1<T>(s, PC_LOCATE, dim3((unsigned)blocks), dim3(threads), shmem, locate_kernel<T, false, LOCATE_QB>, A);
-  else launch1<T>(s, PC_LOCATE, dim3((unsigned)blocks), dim3(threads), shmem, locate_kernel<T, false, 1>, A);
+  pick_bool(A.stage_lds != 0, [&](auto stage) {
+    pick_or<1, LOCATE_QB>(deep ? LOCATE_QB : 1, [&](auto qb) {
+      launch_lds<T>(&locate_kernel<T, stage.value, qb.value>, LDS_STAGE_LIMIT, s, PC_LOCATE, dim3((unsigned)blocks), dim3(threads), shmem, A);
+    });
+  });
 }
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -787,28 +790,13 @@ static ndi_status take_opts(const ndi_eval_opts* opts, ndi_eval_opts& o) {
 }
 
 struct ShortKnobs {
-  int mode = 0, unr = 2, tb = 0, lds = -1, wgs = 0, cq = 64, rowb = 1024, pack = -1, maxlv = 256;
-  static int env(const char* name, int dflt) {
-    const char* e = std::getenv(name);
-    return e && *e ? std::atoi(e) : dflt;
-  }
-  static ShortKnobs read() {
-    ShortKnobs k;
-    k.mode = env("NDI_SHORT_MODE", k.mode);
-    k.unr = env("NDI_FUSED_UNR", k.unr);
-    k.tb = env("NDI_FUSED_TB", k.tb);
-    k.lds = env("NDI_FUSED_LDS", k.lds);
-    k.wgs = env("NDI_FUSED_WGS", k.wgs);
-    k.cq = env("NDI_SHORT_CQ", k.cq);
-    k.rowb = env("NDI_SHORT_ROWB", k.rowb);
-    k.pack = env("NDI_FUSED_PACK", k.pack);
-    return k;
-  }
+  int mode, unr, tb, lds, wgs, cq, rowb, pack, maxlv = 256;
 };
 static ShortKnobs short_knobs() {
-  static const bool live = std::getenv("NDI_TUNE_LIVE") != nullptr;
-  static const ShortKnobs once = ShortKnobs::read();
-  return live ? ShortKnobs::read() : once;
+  static const Knob mode{"NDI_SHORT_MODE", 0, Knob::live}, unr{"NDI_FUSED_UNR", 2, Knob::live}, tb{"NDI_FUSED_TB", 0, Knob::live},
+      lds{"NDI_FUSED_LDS", -1, Knob::live}, wgs{"NDI_FUSED_WGS", 0, Knob::live}, cq{"NDI_SHORT_CQ", 64, Knob::live},
+      rowb{"NDI_SHORT_ROWB", 1024, Knob::live}, pack{"NDI_FUSED_PACK", -1, Knob::live};
+  return {mode.get(), unr.get(), tb.get(), lds.get(), wgs.get(), cq.get(), rowb.get(), pack.get()};
 }
 
 // The ring's locate + group of chunk k + 1 run on a side stream beside chunk k's evaluation (measured against running
@@ -821,9 +809,8 @@ static constexpr bool ring_overlap() { return true; }
 // Read once, or per call under NDI_TUNE_LIVE.
 constexpr int RING_GROUP_DEFAULT = 1;
 static int ring_group_mode() {
-  static const bool live = std::getenv("NDI_TUNE_LIVE") != nullptr;
-  static const int once = ShortKnobs::env("NDI_RING_GROUP", RING_GROUP_DEFAULT);
-  const int m = live ? ShortKnobs::env("NDI_RING_GROUP", RING_GROUP_DEFAULT) : once;
+  static const Knob knob{"NDI_RING_GROUP", RING_GROUP_DEFAULT, Knob::live};
+  const int m = knob.get();
   return m >= 0 && m <= 2 ? m : RING_GROUP_DEFAULT;
 }
 
@@ -980,6 +967,7 @@ static const char* hermite_rule_name(int rule) {
 template <class T>
 struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
   int strategy = NDI_LINEAR;   // the evaluation class: NDI_CUBIC_SPLINE = "has a / b tables" (Pchip, Akima, CubicHermite too)
+  int strat() const { return strategy == NDI_CUBIC_SPLINE ? ST_CUBIC : ST_LINEAR; }   // ... as the kernels' STRAT
   int rule = HR_SPLINE;        // ... and which rule chose the knot derivatives behind those tables (HermiteRule)
   int deriv = 0;               // derivative order: 0 = the interpolant; 1, 2 = ndi_interp1d_derivative of a handle of `rule`
   int mode = EX_NO;
@@ -1095,10 +1083,8 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
   // smallest strip set: the query-order kernel then re-forms a / b per item instead of gathering them (TLDS == 2).
   // NDI_SPLINE_KEEP_K=0 drops them.
   T* reserve_k() {
-    static const bool tune_live = std::getenv("NDI_TUNE_LIVE") != nullptr;
-    static const int once = ShortKnobs::env("NDI_SPLINE_KEEP_K", 1);
-    const int keep = tune_live ? ShortKnobs::env("NDI_SPLINE_KEEP_K", 1) : once;
-    if (!keep || lanes > 2048 || fused_lds_bytes(false, 256, 2) > FUSED_LDS_LIMIT) {
+    static const Knob keep{"NDI_SPLINE_KEEP_K", 1, Knob::live};
+    if (!keep.get() || lanes > 2048 || fused_lds_bytes(false, 256, 2) > FUSED_LDS_LIMIT) {
       ck.release();   // (a slice of the handle's arena may have been set aside: ck.p != nullptr means "k was kept")
       return nullptr;
     }
@@ -1125,9 +1111,8 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     // or two waves doing 2n dependent steps.  The blocked sweeps (kernels.hpp, spline_blocked_*) take over -- the one
     // path whose tables are not bit-identical to the reference order (a few ulp; NDI_SPLINE_BLOCKED=0 keeps the serial
     // kernels, =1 forces the blocked ones wherever they apply).
-    static const bool tune_live = std::getenv("NDI_TUNE_LIVE") != nullptr;
-    static const int blocked_once = ShortKnobs::env("NDI_SPLINE_BLOCKED", -1);
-    const int blocked_env = tune_live ? ShortKnobs::env("NDI_SPLINE_BLOCKED", -1) : blocked_once;
+    static const Knob blocked_knob{"NDI_SPLINE_BLOCKED", -1, Knob::live};
+    const int blocked_env = blocked_knob.get();
     // ... and only on axes whose neighbouring knot spacings differ by less than 1e3 (f32) / 1e9 (f64): the re-associated
     // sweeps are accurate relative to the NEIGHBOURING table magnitudes, and where the spacing jumps by 1e6 from one
     // interval to the next those magnitudes jump likewise -- in f32 evaluated rows then miss the 1e-5 bar (4 of 5000 rows
@@ -1147,8 +1132,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
                          (blocked_env > 0 || (blocked_env < 0 && n >= 2048 && lanes <= 256 && tame));
     // Long axes: the x-only elimination factors on the device as well (spline_eliminate_kernel); the host then forms only
     // the boundary rows' scalars.
-    constexpr int elim_env = 1;
-    const bool dev_elim = blocked && tame && !periodic && n >= 32768 && elim_env != 0;
+    const bool dev_elim = blocked && tame && !periodic && n >= 32768;
     SplineEnds<T> ends;
     SplinePlan<T> P = dev_elim ? make_spline_plan_scalars<T>(pyr.host_knots.data(), n, d.left.kind, d.left.value, d.right.kind,
                                                              d.right.value, ends)
@@ -1159,8 +1143,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     // substitution and the a / b epilogue in spline_build_general_kernel<FUSED>, dx / up formed from the resident knots;
     // the x-only factors w, mid' travel through a kept pinned buffer into a kept device buffer: no allocation, no free,
     // no status read-back (only the periodic build has one).  Same operations as the three-kernel form: bit-identical.
-    constexpr int small_env = 1;
-    if (small_env && P.mode == SPLINE_GENERAL && !blocked && (uint64_t)n * lanes <= (1u << 17)) {
+    if (P.mode == SPLINE_GENERAL && !blocked && (uint64_t)n * lanes <= (1u << 17)) {
       BuildScratch& bs = build_scratch();
       const size_t plan_b = 2 * (size_t)n * sizeof(T);
       T* hp = static_cast<T*>(bs.pinned(plan_b));
@@ -1192,9 +1175,8 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
       const unsigned grid1 = (unsigned)((lanes + 63) / 64);
       // the smallest systems -- data and right-hand sides fit LDS twice over, one workgroup covers the trailing axis --
       // form their right-hand sides with the whole workgroup and sweep out of LDS (spline_build_lds_kernel)
-      constexpr int lds_env = 1;
       const size_t lds_need = 2 * (size_t)n * lanes * sizeof(T);
-      if (lds_env && lanes <= (uint64_t)BLOCK && lds_need <= 96 * 1024 && n >= 4) {
+      if (lanes <= (uint64_t)BLOCK && lds_need <= 96 * 1024 && n >= 4) {
         allow_dynamic_lds(reinterpret_cast<const void*>(&spline_build_lds_kernel<T, true>), 96 * 1024);
         allow_dynamic_lds(reinterpret_cast<const void*>(&spline_build_lds_kernel<T, false>), 96 * 1024);
         if (A.kout) hipLaunchKernelGGL((spline_build_lds_kernel<T, true>), dim3(1), dim3(BLOCK), lds_need, (hipStream_t) nullptr, A);
@@ -1323,9 +1305,8 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
       case SPLINE_GENERAL: {
         // Wide trailing axes: four waves per 64 lanes, the right-hand sides never leave the chip (spline_build_wide_kernel).
         // NDI_SPLINE_WIDE=0 / 1: A/B (1 takes it for every width).
-        static const bool tune_live_w = std::getenv("NDI_TUNE_LIVE") != nullptr;
-        static const int wide_once = ShortKnobs::env("NDI_SPLINE_WIDE", -1);
-        const int wide_env = tune_live_w ? ShortKnobs::env("NDI_SPLINE_WIDE", -1) : wide_once;
+        static const Knob wide_knob{"NDI_SPLINE_WIDE", -1, Knob::live};
+        const int wide_env = wide_knob.get();
         if (!A.kout && n >= 4 && (wide_env > 0 || (wide_env < 0 && lanes >= 1024))) {
           constexpr int RW = 16, RBW = 3 * RW;       // rows per producer wave / per block
           const size_t shm = (size_t)(4 * RBW * 64 + 2 * 4 * RBW) * sizeof(T);
@@ -1534,11 +1515,10 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
   // or exact O(1) guess), batches that give every workgroup several times its staging bytes to write.
   // NDI_LANES_KERNEL=0 leaves these shapes to the query-order kernel (A/B); =1 takes it whenever it fits.
   bool plan_lanes(hipStream_t s, Scratch& sc, Plan1& P, int path, int flags) {
-    static const bool tune_live = std::getenv("NDI_TUNE_LIVE") != nullptr;
     // rows of up to 56 bytes: at 64 bytes the query-order kernel is level (f64 x 8: 65 vs 61-65 Gqueries/s) or ahead
     // (f32 x 16: 74 vs 57), profiles/r05_small_shapes_rates.txt
-    static const int on_once = ShortKnobs::env("NDI_LANES_KERNEL", -1);
-    const int on = tune_live ? ShortKnobs::env("NDI_LANES_KERNEL", -1) : on_once;
+    static const Knob on_knob{"NDI_LANES_KERNEL", -1, Knob::live};
+    const int on = on_knob.get();
     constexpr int maxb = 56;
     if (on == 0 || path == NDI_PATH_BUCKETED || n < 3 || n > 16384) return false;
     if (on < 0 && short_knobs().mode != 0) return false;   // a pinned short-row variant (NDI_SHORT_MODE) is what runs
@@ -1556,22 +1536,10 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     if (P.f_lds > FUSED_LDS_LIMIT) return false;
     constexpr int VN = Wide<T>::N;
     P.l_qpl = (lanes == 1 && P.out_stride == 1 && aligned16(P.q) && aligned16(P.out)) ? VN : 1;
-    const size_t wg_per_cu = std::max<size_t>(1, std::min<size_t>((160 * 1024) / P.f_lds, 32 / (P.f_tb / 64)));
     const uint64_t per_wg = (uint64_t)P.f_tb * (lanes == 1 ? (uint64_t)P.l_qpl : 1);
-    P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((P.nq + per_wg - 1) / per_wg, (uint64_t)cu_count() * wg_per_cu));
+    P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((P.nq + per_wg - 1) / per_wg, (uint64_t)cu_count() * wgs_per_cu(P.f_lds, P.f_tb)));
     P.kind = Plan1::LANES;
-    g_last_path.store(NDI_PATH_GATHER);
-    // fresh output (interp_array: the buffer is dropped on Err): no pre-pass, the kernel's own range test reports the failure
-    P.l_check = (flags & NDI_EVAL_FRESH_OUTPUT) != 0;
-    if (P.l_check) return true;
-    StatusBlock* st = sc.status.as<StatusBlock>();
-    const T k0 = pyr.host_knots.front(), kn = pyr.host_knots.back();
-    const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((P.nq + BLOCK - 1) / BLOCK, 4096));
-    ProfScope ps(s, PC_LOCATE);
-    hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, P.q, (const T*)nullptr, P.nq, k0, kn, k0, kn,
-                       mode, &st->first_fail[0]);
-    NDI_HIP(hipGetLastError());
-    ps.done();
+    P.l_check = this->range_prepass(s, sc, {P.q, nullptr}, P.nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
     return true;
   }
 
@@ -1596,37 +1564,20 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
                    P.l_qpl, pyr.dlut.lut ? "dense" : "guess", pyr.dlut.m, pyr.dlut.maxk, P.f_tb, P.f_grid, P.f_lds, P.l_check ? 0 : 1);
     constexpr int VN = Wide<T>::N;
     const dim3 grid(P.f_grid), block(P.f_tb);
-#define NDI_LK(KERN)                                                                      \
-  do {                                                                                    \
-    auto kern = KERN;                                                                     \
-    allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)FUSED_LDS_LIMIT);         \
-    launch1<T>(s, PC_EVAL, grid, block, P.f_lds, kern, F);                                \
-  } while (0)
-#define NDI_LS(ST, QPL)                                                                   \
-  do {                                                                                    \
-    if (P.f_tb == 1024) NDI_LK((eval_scalar_kernel<T, ST, QPL, 1024>));                   \
-    else NDI_LK((eval_scalar_kernel<T, ST, QPL, 256>));                                   \
-  } while (0)
-#define NDI_LL(ST, LC)                                                                    \
-  do {                                                                                    \
-    if (P.f_tb == 1024) NDI_LK((eval_lanes_kernel<T, ST, LC, 1024>));                     \
-    else NDI_LK((eval_lanes_kernel<T, ST, LC, 256>));                                     \
-  } while (0)
-#define NDI_LLC(ST)                                                                       \
-  do {                                                                                    \
-    if (lanes == 2) NDI_LL(ST, 2); else if (lanes == 5) NDI_LL(ST, 5);                    \
-    else if (lanes == 8) NDI_LL(ST, 8); else NDI_LL(ST, 0);                               \
-  } while (0)
-    if (lanes == 1) {
-      if (strategy == NDI_CUBIC_SPLINE) { if (P.l_qpl == VN) NDI_LS(ST_CUBIC, VN); else NDI_LS(ST_CUBIC, 1); }
-      else { if (P.l_qpl == VN) NDI_LS(ST_LINEAR, VN); else NDI_LS(ST_LINEAR, 1); }
-    } else {
-      if (strategy == NDI_CUBIC_SPLINE) NDI_LLC(ST_CUBIC); else NDI_LLC(ST_LINEAR);
-    }
-#undef NDI_LLC
-#undef NDI_LL
-#undef NDI_LS
-#undef NDI_LK
+    pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
+      constexpr int ST = st_;
+      pick_or<256, 1024>((int)P.f_tb, [&](auto tb_) {
+        constexpr int TB = tb_;
+        if (lanes == 1)
+          pick_or<1, VN>(P.l_qpl, [&](auto qpl_) {
+            launch_lds<T>(eval_scalar_kernel<T, ST, qpl_, TB>, FUSED_LDS_LIMIT, s, PC_EVAL, grid, block, P.f_lds, F);
+          });
+        else
+          pick_or<0, 2, 5, 8>((int)lanes, [&](auto lc_) {
+            launch_lds<T>(eval_lanes_kernel<T, ST, lc_, TB>, FUSED_LDS_LIMIT, s, PC_EVAL, grid, block, P.f_lds, F);
+          });
+      });
+    });
   }
 
   // LDS footprint of eval_fused_kernel: [pyramid | lut | per-wave strips | tables]
@@ -1645,15 +1596,13 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
   // Query-order fused search + evaluation (short rows): decides the variant and its launch shape, and enqueues the
   // range pre-pass the kernel relies on.  Returns false when the shape is not eligible.
   bool plan_fused(hipStream_t s, Scratch& sc, Plan1& P, const ShortKnobs& K, int flags = 0) {
-    constexpr int long_axes = 1;     // (axes beyond half the LDS: one large workgroup per CU)
-    constexpr int global_axes = 1;   // (axes beyond LDS: the u32 bucket index in global memory)
     const uint64_t LV = P.LV;
     if (LV == 0 || 64ull * LV * LV >= (1ull << 32) || (uint64_t)n * LV >= (1ull << 32) * 1ull) return false;   // 32-bit item / vector indices
-    constexpr int lut_env = 1;   // (the bucket index: A/B settled in round 3)
-    if (pyr.lds_bytes > (long_axes ? LDS_STAGE_LIMIT - 8 * 1024 : LDS_STAGE_LIMIT / 2)) {
+    // (axes beyond half the LDS: one large workgroup per CU; the bucket index: A/B settled in round 3)
+    if (pyr.lds_bytes > LDS_STAGE_LIMIT - 8 * 1024) {
       // Axes too long for LDS: the same kernel with the knots left in global memory and searched through the u32 bucket
       // index (TLDS == 3) -- one launch, no idx[] / t[] round trip.  Batches below 4096 queries keep the two-kernel form.
-      if (!global_axes || !long_axes || !lut_env || P.nq < 4096) return false;
+      if (P.nq < 4096) return false;
       pyr.ensure_bucket_index32();
       P.f_lut = false;
       P.f_unr = 2;
@@ -1664,24 +1613,14 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
       P.f_pack = (K.pack > 0 || (K.pack < 0 && lanes * sizeof(T) < 128)) && ensure_packed(s);
       P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((P.nq + 255) / 256, (uint64_t)cu_count() * 8 * 4));
       P.kind = Plan1::FUSED;
-      g_last_path.store(NDI_PATH_GATHER);
-      P.l_check = (flags & NDI_EVAL_FRESH_OUTPUT) != 0;   // fresh output: the kernel's own range test, no pre-pass
-      if (P.l_check) return true;
-      StatusBlock* st = sc.status.as<StatusBlock>();
-      const T k0 = pyr.host_knots.front(), kn = pyr.host_knots.back();
-      const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((P.nq + BLOCK - 1) / BLOCK, 4096));
-      ProfScope ps(s, PC_LOCATE);
-      hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, P.q, (const T*)nullptr, P.nq, k0, kn, k0, kn,
-                         mode, &st->first_fail[0]);
-      NDI_HIP(hipGetLastError());
-      ps.done();
+      P.l_check = this->range_prepass(s, sc, {P.q, nullptr}, P.nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
       return true;
     }
-    if (lut_env && P.nq >= 4096) pyr.ensure_bucket_index();
+    if (P.nq >= 4096) pyr.ensure_bucket_index();
     // the bucket index beside the knots when it costs no more than half the waves a CU could hold without it
     auto waves_at = [&](bool with_lut, unsigned tb) -> size_t {
       const size_t need = fused_lds_bytes(with_lut, tb, 0);
-      return need > LDS_STAGE_LIMIT ? 0 : std::min<size_t>((160 * 1024) / need, 32 / (tb / 64)) * (tb / 64);
+      return need > LDS_STAGE_LIMIT ? 0 : wgs_per_cu(need, tb) * (tb / 64);
     };
     auto best_tb = [&](bool with_lut, unsigned& tb_out) -> size_t {
       size_t best = 0;
@@ -1693,7 +1632,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     };
     unsigned tb_plain = 256, tb_lut = 256;
     const size_t w_plain = best_tb(false, tb_plain);
-    const size_t w_lut = (lut_env && P.nq >= 4096 && pyr.lut_bytes != 0) ? best_tb(true, tb_lut) : 0;
+    const size_t w_lut = (P.nq >= 4096 && pyr.lut_bytes != 0) ? best_tb(true, tb_lut) : 0;
     if (w_plain == 0 && w_lut == 0) return false;
     P.f_lut = w_lut != 0 && 2 * w_lut >= w_plain;
     const unsigned tb_auto = P.f_lut ? tb_lut : tb_plain;
@@ -1716,7 +1655,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
           if (K.tb && (unsigned)K.tb != tb) continue;
           const size_t need = fused_lds_bytes(P.f_lut, tb, form);
           if (need > FUSED_LDS_LIMIT) continue;
-          const size_t waves = std::min<size_t>((160 * 1024) / need, 32 / (tb / 64)) * (tb / 64);
+          const size_t waves = wgs_per_cu(need, tb) * (tb / 64);
           if (waves > best_waves) {
             best_waves = waves;
             P.f_tlds = form;
@@ -1741,9 +1680,8 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     // interval order (eval_fused_sorted_kernel: the operand rows of neighbouring items coincide and come from L1 -- the
     // query-order form is bound by the L2 request rate on these).  NDI_FUSED_SORTED=0 / 1: A/B.
     {
-      static const bool tune_live5 = std::getenv("NDI_TUNE_LIVE") != nullptr;
-      static const int fs_once = ShortKnobs::env("NDI_FUSED_SORTED", -1);
-      const int fs = tune_live5 ? ShortKnobs::env("NDI_FUSED_SORTED", -1) : fs_once;
+      static const Knob fs_knob{"NDI_FUSED_SORTED", -1, Knob::live};
+      const int fs = fs_knob.get();
       const bool cubic = strategy == NDI_CUBIC_SPLINE;
       const size_t lds_s = ((pyr.lds_bytes + 15) & ~(size_t)15) + (P.f_lut ? pyr.lut_bytes : 0) + (((size_t)(n - 1) * 4 + 15) & ~(size_t)15) +
                            (size_t)4096 / (cubic ? 1 : 2) * (4 + (cubic ? 1 : 2) * sizeof(T));
@@ -1759,35 +1697,14 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
         const uint64_t nqw = cubic ? 4096 : 2048;
         P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((P.nq + nqw - 1) / nqw, (uint64_t)cu_count() * per_cu * 4));
         P.kind = Plan1::FUSED;
-        g_last_path.store(NDI_PATH_GATHER);
-        P.l_check = (flags & NDI_EVAL_FRESH_OUTPUT) != 0;
-        if (P.l_check) return true;
-        StatusBlock* st = sc.status.as<StatusBlock>();
-        const T k0 = pyr.host_knots.front(), kn = pyr.host_knots.back();
-        const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((P.nq + BLOCK - 1) / BLOCK, 4096));
-        ProfScope ps(s, PC_LOCATE);
-        hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, P.q, (const T*)nullptr, P.nq, k0, kn, k0, kn,
-                           mode, &st->first_fail[0]);
-        NDI_HIP(hipGetLastError());
-        ps.done();
+        P.l_check = this->range_prepass(s, sc, {P.q, nullptr}, P.nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
         return true;
       }
     }
-    const size_t wg_per_cu = std::max<size_t>(1, std::min<size_t>((160 * 1024) / std::max<size_t>(P.f_lds, 1), 32 / (P.f_tb / 64)));
-    const uint64_t want = (uint64_t)cu_count() * (K.wgs > 0 ? (size_t)K.wgs : wg_per_cu * (P.f_tlds ? 1 : 4));
+    const uint64_t want = (uint64_t)cu_count() * (K.wgs > 0 ? (size_t)K.wgs : wgs_per_cu(P.f_lds, P.f_tb) * (P.f_tlds ? 1 : 4));
     P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((P.nq + P.f_tb - 1) / P.f_tb, want));
     P.kind = Plan1::FUSED;
-    g_last_path.store(NDI_PATH_GATHER);
-    P.l_check = (flags & NDI_EVAL_FRESH_OUTPUT) != 0;     // fresh output: the kernel's own range test, no pre-pass
-    if (P.l_check) return true;
-    StatusBlock* st = sc.status.as<StatusBlock>();
-    const T k0 = pyr.host_knots.front(), kn = pyr.host_knots.back();
-    const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((P.nq + BLOCK - 1) / BLOCK, 4096));
-    ProfScope ps(s, PC_LOCATE);
-    hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, P.q, (const T*)nullptr, P.nq, k0, kn, k0, kn,
-                       mode, &st->first_fail[0]);
-    NDI_HIP(hipGetLastError());
-    ps.done();
+    P.l_check = this->range_prepass(s, sc, {P.q, nullptr}, P.nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
     return true;
   }
 
@@ -1819,14 +1736,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
       // short trailing axes: range pre-check (so rows after the first failing query stay untouched in the
       // caller's buffer), then search + evaluation fused in one launch -- no index / t round trip through HBM
       P.kind = Plan1::SMALL;
-      g_last_path.store(NDI_PATH_GATHER);
-      const T k0 = pyr.host_knots.front(), kn = pyr.host_knots.back();
-      const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-      ProfScope ps(s, PC_LOCATE);
-      hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, q, (const T*)nullptr, nq, k0, kn, k0, kn,
-                         mode, &st->first_fail[0]);
-      NDI_HIP(hipGetLastError());
-      ps.done();
+      this->range_prepass(s, sc, {q, nullptr}, nq, false);
       return P;
     }
     constexpr int VN = Wide<T>::N;
@@ -1914,12 +1824,33 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     return P;
   }
 
+  // The long-row grouped evaluation: eval_bucketed_kernel for one chunk, eval_bucketed_group_kernel (GROUP) for the chunks
+  // of a ring group.  U vectors per thread by row length, gx workgroups per segment row; rows of whole segments only
+  // take the straight-line kernel variant.
+  static constexpr int BUCKETED_CQ = 128;   // queries per chunk of the two kernels: their CQ, and the unit of both grids
+  template <bool GROUP, class Args>
+  void launch_bucketed(hipStream_t s, uint64_t LV, unsigned gx, const Args& A) {
+    constexpr int CQ = BUCKETED_CQ;
+    const int U = LV >= 2048 ? 8 : (LV >= 1024 ? 4 : (LV >= 512 ? 2 : 1));
+    const uint64_t segs = (LV + (uint64_t)BLOCK * U - 1) / ((uint64_t)BLOCK * U);
+    const dim3 grid(gx, (unsigned)std::min<uint64_t>(segs, 64));
+    const bool full = LV % ((uint64_t)BLOCK * U) == 0;
+    pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
+      constexpr int ST = st_;
+      pick_or<1, 8, 4, 2>(U, [&](auto u_) {
+        constexpr int UU = u_;
+        pick_bool(full, [&](auto full_) {
+          if constexpr (GROUP) launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_bucketed_group_kernel<T, ST, UU, CQ, true, full_>, A);
+          else launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_bucketed_kernel<T, ST, UU, CQ, true, full_>, A);
+        });
+      });
+    });
+  }
+
   void launch_eval(hipStream_t s, Scratch& sc, const Plan1& P) {
     StatusBlock* st = sc.status.as<StatusBlock>();
     const uint64_t nq = P.nq;
     if (P.kind == Plan1::SMALL) {
-      allow_dynamic_lds(reinterpret_cast<const void*>(&eval_small_kernel<T, ST_CUBIC>), (int)LDS_STAGE_LIMIT);
-      allow_dynamic_lds(reinterpret_cast<const void*>(&eval_small_kernel<T, ST_LINEAR>), (int)LDS_STAGE_LIMIT);
       EvalSmallArgs<T> S{};
       S.pyr = pyr.view;
       S.data = data.as<T>();
@@ -1935,8 +1866,9 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
       S.prechecked = 1;
       const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
       const size_t shmem = (pyr.lds_bytes + 15) & ~(size_t)15;
-      if (strategy == NDI_CUBIC_SPLINE) launch1<T>(s, PC_EVAL, dim3(g), dim3(BLOCK), shmem, eval_small_kernel<T, ST_CUBIC>, S);
-      else launch1<T>(s, PC_EVAL, dim3(g), dim3(BLOCK), shmem, eval_small_kernel<T, ST_LINEAR>, S);
+      pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
+        launch_lds<T>(eval_small_kernel<T, st_>, LDS_STAGE_LIMIT, s, PC_EVAL, dim3(g), dim3(BLOCK), shmem, S);
+      });
       return;
     }
     if (P.kind == Plan1::FUSED) {
@@ -1962,36 +1894,19 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     A.status = st;
     A.n_int = (uint32_t)(n - 1);
 #ifdef NDI_BOUNDS
-    if (ShortKnobs::env("NDI_BOUNDS_SELFTEST", 0)) A.n_int = 1;   // checked build: provoke the checker (rows are then wrong)
+    if (env_int("NDI_BOUNDS_SELFTEST", 0)) A.n_int = 1;   // checked build: provoke the checker (rows are then wrong)
 #endif
     constexpr int VN = Wide<T>::N;
     const uint64_t LV = P.LV;
     if (P.kind == Plan1::BUCKETED) {
       A.rec = sc.perm.as<uint4>();
-      constexpr int CQ = 128;
-      const int U = LV >= 2048 ? 8 : (LV >= 1024 ? 4 : (LV >= 512 ? 2 : 1));
-      const uint64_t segs = (LV + (uint64_t)BLOCK * U - 1) / ((uint64_t)BLOCK * U);
+      constexpr int CQ = BUCKETED_CQ;
       // a multiple of 8 so that a workgroup keeps its XCD residue when it strides (XCD-aware chunk order);
       // every workgroup takes a run of consecutive chunks (operand rows stay in registers across them)
       const uint64_t per_xcd = ((nq + CQ - 1) / CQ + 7) / 8;
       A.run = BUCKETED_RUN;
       const uint64_t runs_per_xcd = (per_xcd + A.run - 1) / A.run;
-      const unsigned gx = (unsigned)std::max<uint64_t>(8, std::min<uint64_t>(runs_per_xcd * 8, 65528));
-      dim3 grid(gx, (unsigned)std::min<uint64_t>(segs, 64));
-      const bool full = LV % ((uint64_t)BLOCK * U) == 0;   // whole segments only: straight-line kernel variant
-#define NDI_BK(ST, UU)                                                                                      \
-  do {                                                                                                      \
-    if (full) launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_bucketed_kernel<T, ST, UU, CQ, true, true>, A); \
-    else launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_bucketed_kernel<T, ST, UU, CQ, true, false>, A);   \
-  } while (0)
-      if (strategy == NDI_CUBIC_SPLINE) {
-        if (U == 8) NDI_BK(ST_CUBIC, 8); else if (U == 4) NDI_BK(ST_CUBIC, 4);
-        else if (U == 2) NDI_BK(ST_CUBIC, 2); else NDI_BK(ST_CUBIC, 1);
-      } else {
-        if (U == 8) NDI_BK(ST_LINEAR, 8); else if (U == 4) NDI_BK(ST_LINEAR, 4);
-        else if (U == 2) NDI_BK(ST_LINEAR, 2); else NDI_BK(ST_LINEAR, 1);
-      }
-#undef NDI_BK
+      launch_bucketed<false>(s, LV, (unsigned)std::max<uint64_t>(8, std::min<uint64_t>(runs_per_xcd * 8, 65528)), A);
       return;
     }
     if (P.kind == Plan1::BUCKETED_SHORT) {
@@ -2002,20 +1917,15 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
       const uint64_t wq = (uint64_t)(BLOCK / G) * CQ;
       const uint64_t per_xcd = ((nq + wq - 1) / wq + 7) / 8;
       const unsigned gx = (unsigned)std::max<uint64_t>(8, std::min<uint64_t>(per_xcd * 8, 65528));
-#define NDI_BS(ST, GG)                                                                                          \
-  do {                                                                                                          \
-    if (CQ == 16) launch1<T>(s, PC_EVAL, dim3(gx), dim3(BLOCK), 0, eval_bucketed_short_kernel<T, ST, GG, 16>, A); \
-    else launch1<T>(s, PC_EVAL, dim3(gx), dim3(BLOCK), 0, eval_bucketed_short_kernel<T, ST, GG, 64>, A);          \
-  } while (0)
-#define NDI_BSG(ST)                                                                   \
-  do {                                                                                \
-    if (G == 8) NDI_BS(ST, 8); else if (G == 16) NDI_BS(ST, 16);                      \
-    else if (G == 32) NDI_BS(ST, 32); else if (G == 64) NDI_BS(ST, 64);               \
-    else if (G == 128) NDI_BS(ST, 128); else NDI_BS(ST, 256);                         \
-  } while (0)
-      if (strategy == NDI_CUBIC_SPLINE) NDI_BSG(ST_CUBIC); else NDI_BSG(ST_LINEAR);
-#undef NDI_BSG
-#undef NDI_BS
+      pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
+        constexpr int ST = st_;
+        pick_or<256, 8, 16, 32, 64, 128>((int)G, [&](auto g_) {
+          constexpr int GG = g_;
+          pick_or<64, 16>(CQ, [&](auto cq_) {
+            launch1<T>(s, PC_EVAL, dim3(gx), dim3(BLOCK), 0, eval_bucketed_short_kernel<T, ST, GG, cq_>, A);
+          });
+        });
+      });
       return;
     }
     if (P.kind == Plan1::ROWS) {
@@ -2023,8 +1933,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
       const uint64_t segs = (LV + BLOCK - 1) / BLOCK;
       const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nq, 65536));
       dim3 grid(gx, (unsigned)std::min<uint64_t>(segs, 64));
-      if (strategy == NDI_CUBIC_SPLINE) launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_rows_kernel<T, ST_CUBIC, 1>, A);
-      else launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_rows_kernel<T, ST_LINEAR, 1>, A);
+      pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) { launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_rows_kernel<T, st_, 1>, A); });
       return;
     }
     // flat
@@ -2032,13 +1941,12 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     const uint64_t ntiles = (nq + tile_q - 1) / tile_q;
     const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ntiles, 16384));
     ProfScope ps(s, PC_EVAL);
-    if (strategy == NDI_CUBIC_SPLINE) {
-      if (P.vec_ok) hipLaunchKernelGGL((eval_flat_kernel<T, ST_CUBIC, VN>), dim3(gx), dim3(BLOCK), 0, s, A, tile_q);
-      else hipLaunchKernelGGL((eval_flat_kernel<T, ST_CUBIC, 1>), dim3(gx), dim3(BLOCK), 0, s, A, tile_q);
-    } else {
-      if (P.vec_ok) hipLaunchKernelGGL((eval_flat_kernel<T, ST_LINEAR, VN>), dim3(gx), dim3(BLOCK), 0, s, A, tile_q);
-      else hipLaunchKernelGGL((eval_flat_kernel<T, ST_LINEAR, 1>), dim3(gx), dim3(BLOCK), 0, s, A, tile_q);
-    }
+    pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
+      constexpr int ST = st_;
+      pick_or<1, VN>(P.vec_ok ? VN : 1, [&](auto vec_) {
+        hipLaunchKernelGGL((eval_flat_kernel<T, ST, vec_>), dim3(gx), dim3(BLOCK), 0, s, A, tile_q);
+      });
+    });
     NDI_HIP(hipGetLastError());
     ps.done();
   }
@@ -2068,7 +1976,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     G.A.out_stride = P[0].out_stride;
     G.A.n_int = (uint32_t)(n - 1);
     G.width = w;
-    constexpr int CQ = 128;
+    constexpr int CQ = BUCKETED_CQ;
     uint64_t nmax = 0;
     for (uint32_t i = 0; i < w; ++i) {
       if (!groupable(P[i]) || P[i].out_stride != P[0].out_stride || P[i].LV != P[0].LV)
@@ -2080,25 +1988,8 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
       nmax = std::max<uint64_t>(nmax, (P[i].nq + CQ - 1) / CQ);
     }
     const uint64_t LV = P[0].LV;
-    const int U = LV >= 2048 ? 8 : (LV >= 1024 ? 4 : (LV >= 512 ? 2 : 1));   // as launch_eval
-    const uint64_t segs = (LV + (uint64_t)BLOCK * U - 1) / ((uint64_t)BLOCK * U);
     const uint64_t per_xcd = (nmax * w + 7) / 8;
-    const unsigned gx = (unsigned)std::max<uint64_t>(8, std::min<uint64_t>(per_xcd * 8, 65528));
-    dim3 grid(gx, (unsigned)std::min<uint64_t>(segs, 64));
-    const bool full = LV % ((uint64_t)BLOCK * U) == 0;
-#define NDI_BG(ST, UU)                                                                                            \
-  do {                                                                                                            \
-    if (full) launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_bucketed_group_kernel<T, ST, UU, CQ, true, true>, G); \
-    else launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_bucketed_group_kernel<T, ST, UU, CQ, true, false>, G);   \
-  } while (0)
-    if (strategy == NDI_CUBIC_SPLINE) {
-      if (U == 8) NDI_BG(ST_CUBIC, 8); else if (U == 4) NDI_BG(ST_CUBIC, 4);
-      else if (U == 2) NDI_BG(ST_CUBIC, 2); else NDI_BG(ST_CUBIC, 1);
-    } else {
-      if (U == 8) NDI_BG(ST_LINEAR, 8); else if (U == 4) NDI_BG(ST_LINEAR, 4);
-      else if (U == 2) NDI_BG(ST_LINEAR, 2); else NDI_BG(ST_LINEAR, 1);
-    }
-#undef NDI_BG
+    launch_bucketed<true>(s, LV, (unsigned)std::max<uint64_t>(8, std::min<uint64_t>(per_xcd * 8, 65528)), G);
   }
 
   void launch_fused(hipStream_t s, Scratch& sc, const Plan1& P) {
@@ -2129,7 +2020,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     F.check = P.l_check ? 1 : 0;
     F.debug = 0;
 #ifdef NDI_TUNING
-    F.debug = ShortKnobs::env("NDI_FUSED_DEBUG", 0);
+    F.debug = env_int("NDI_FUSED_DEBUG", 0);
 #endif
     constexpr int VN = Wide<T>::N;
     const dim3 grid(P.f_grid), block(P.f_tb);
@@ -2137,15 +2028,12 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
       if (std::getenv("NDI_TRACE_PLAN"))
         std::fprintf(stderr, "[ndi plan] fused sorted lut=%d tb=%u grid=%u lds=%zu prepass=%d\n", (int)P.f_lut, P.f_tb, P.f_grid,
                      P.f_lds, P.l_check ? 0 : 1);
-#define NDI_FSK(ST, VEC, QPT)                                                                          \
-  do {                                                                                                 \
-    auto kern = eval_fused_sorted_kernel<T, ST, VEC, 512, QPT>;                                        \
-    allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)(FUSED_LDS_LIMIT - 256));              \
-    launch1<T>(s, PC_EVAL, grid, dim3(512), P.f_lds, kern, F);                                         \
-  } while (0)
-      if (strategy == NDI_CUBIC_SPLINE) { if (P.vec_ok) NDI_FSK(ST_CUBIC, VN, 8); else NDI_FSK(ST_CUBIC, 1, 8); }
-      else { if (P.vec_ok) NDI_FSK(ST_LINEAR, VN, 4); else NDI_FSK(ST_LINEAR, 1, 4); }
-#undef NDI_FSK
+      pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
+        constexpr int ST = st_, QPT = ST == ST_CUBIC ? 8 : 4;   // 4096 queries per workgroup round, Linear 2048 (plan_fused)
+        pick_or<1, VN>(P.vec_ok ? VN : 1, [&](auto vec_) {
+          launch_lds<T>(eval_fused_sorted_kernel<T, ST, vec_, 512, QPT>, FUSED_LDS_LIMIT - 256, s, PC_EVAL, grid, dim3(512), P.f_lds, F);
+        });
+      });
       return;
     }
     if (std::getenv("NDI_TRACE_PLAN"))   // which variant a batch took (tests assert on it; read per call)
@@ -2153,45 +2041,27 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
                    P.f_tlds == 2 ? "lds{y,k}" : (P.f_tlds == 1 ? "lds{y,a,b}" : (P.f_tlds == 3 ? "memory,knots=global" : "memory")),
                    (int)P.f_lut, (int)P.f_pack,
                    P.f_unr, P.f_tb, P.f_grid, P.f_lds, P.l_check ? 0 : 1);
-#define NDI_FU(ST, VEC, UNR, TB, TL)                                                                   \
-  do {                                                                                                 \
-    auto kern = eval_fused_kernel<T, ST, VEC, UNR, TB, TL>;                                            \
-    allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)FUSED_LDS_LIMIT);                      \
-    launch1<T>(s, PC_EVAL, grid, block, P.f_lds, kern, F);                                             \
-  } while (0)
-#define NDI_FU_TB(ST, VEC, UNR, TL)                                      \
-  do {                                                                   \
-    if (P.f_tb == 1024) NDI_FU(ST, VEC, UNR, 1024, TL);                  \
-    else if (P.f_tb == 512) NDI_FU(ST, VEC, UNR, 512, TL);               \
-    else NDI_FU(ST, VEC, UNR, 256, TL);                                  \
-  } while (0)
-#define NDI_FU_UNR(ST, VEC, TL)                                          \
-  do {                                                                   \
-    if (P.f_unr == 4) NDI_FU_TB(ST, VEC, 4, TL);                         \
-    else if (P.f_unr == 1) NDI_FU_TB(ST, VEC, 1, TL);                    \
-    else NDI_FU_TB(ST, VEC, 2, TL);                                      \
-  } while (0)
-#define NDI_FU_ST(VEC, TL)                                                              \
-  do {                                                                                  \
-    if (strategy == NDI_CUBIC_SPLINE) NDI_FU_UNR(ST_CUBIC, VEC, TL);                    \
-    else NDI_FU_UNR(ST_LINEAR, VEC, TL);                                                \
-  } while (0)
-    if (P.f_tlds == 3) {   // knots in global memory: one launch shape
-      if (strategy == NDI_CUBIC_SPLINE) { if (P.vec_ok) NDI_FU(ST_CUBIC, VN, 2, 256, 3); else NDI_FU(ST_CUBIC, 1, 2, 256, 3); }
-      else { if (P.vec_ok) NDI_FU(ST_LINEAR, VN, 2, 256, 3); else NDI_FU(ST_LINEAR, 1, 2, 256, 3); }
-    } else if (P.vec_ok) {
-      if (P.f_tlds == 2) NDI_FU_UNR(ST_CUBIC, VN, 2);
-      else if (P.f_tlds) NDI_FU_ST(VN, 1);
-      else NDI_FU_ST(VN, 0);
-    } else {
-      if (P.f_tlds == 2) NDI_FU_UNR(ST_CUBIC, 1, 2);
-      else if (P.f_tlds) NDI_FU_ST(1, 1);
-      else NDI_FU_ST(1, 0);
-    }
-#undef NDI_FU_ST
-#undef NDI_FU_UNR
-#undef NDI_FU_TB
-#undef NDI_FU
+    // TLDS: 0 = tables from memory, 1 = {y, a, b} in LDS, 2 = {y, k} in LDS (the spline only), 3 = knots in global memory
+    // (one launch shape: UNR 2, TB 256)
+    pick<ST_CUBIC, ST_LINEAR>(P.f_tlds == 2 ? (int)ST_CUBIC : strat(), [&](auto st_) {
+      constexpr int ST = st_;
+      pick_or<1, VN>(P.vec_ok ? VN : 1, [&](auto vec_) {
+        constexpr int VEC = vec_;
+        pick_or<1, 0, 2, 3>(P.f_tlds, [&](auto tl_) {
+          constexpr int TL = tl_;
+          if constexpr (TL == 3) {
+            launch_lds<T>(eval_fused_kernel<T, ST, VEC, 2, 256, 3>, FUSED_LDS_LIMIT, s, PC_EVAL, grid, block, P.f_lds, F);
+          } else if constexpr (TL != 2 || ST == ST_CUBIC) {
+            pick_or<2, 4, 1>(P.f_unr, [&](auto unr_) {
+              constexpr int UNR = unr_;
+              pick_or<256, 1024, 512>((int)P.f_tb, [&](auto tb_) {
+                launch_lds<T>(eval_fused_kernel<T, ST, VEC, UNR, tb_, TL>, FUSED_LDS_LIMIT, s, PC_EVAL, grid, block, P.f_lds, F);
+              });
+            });
+          }
+        });
+      });
+    });
   }
 
   // ---- what the host engine (float_host.hpp) takes from this family ------------------------------------------------
@@ -2673,32 +2543,23 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     StatusBlock* st = sc.status.as<StatusBlock>();
     if (bicubic) {   // one kernel for AUTO and GATHER (eval_bicubic_kernel); BUCKETED was refused at the entry point
       P.kind = integral ? Plan2::BICUBIC_INT : Plan2::BICUBIC;   // (an integral handle: eval_bicubic_integral_kernel)
-      g_last_path.store(NDI_PATH_GATHER);
-      P.l_check = (flags & NDI_EVAL_FRESH_OUTPUT) != 0;   // fresh output: the kernel's own range test, no pre-pass
-      if (P.l_check) return P;
-      const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-      ProfScope ps(s, PC_LOCATE);
-      hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, qx, qy, nq, px.host_knots.front(),
-                         px.host_knots.back(), py.host_knots.front(), py.host_knots.back(), mode, &st->first_fail[0]);
-      NDI_HIP(hipGetLastError());
-      ps.done();
+      P.l_check = this->range_prepass(s, sc, {qx, qy}, nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
       return P;
     }
     sc.idx.reserve(nq * sizeof(uint32_t));
     sc.idx2.reserve(nq * sizeof(uint32_t));
     const size_t both = ((px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15);
     // 1-2 values per grid point: one query per thread -- both searches and the evaluation in one launch, no (xi, yi)
-    // round trip, two reciprocals per query instead of three divisions per value.  (NDI_SMALL2D_LANES extends it to
-    // unaligned rows of up to that many values for A/B runs: measured SLOWER from 3 values -- 100 x 100 x 5 f64: 11 vs
+    // round trip, two reciprocals per query instead of three divisions per value.  (Extended to unaligned rows of more
+    // values in A/B runs, since removed: measured SLOWER from 3 values -- 100 x 100 x 5 f64: 11 vs
     // 21 Gqueries/s -- a thread per query turns every operand load into 64 scattered sectors, where the item-per-lane
     // gather kernel reads each query's 40-byte segments whole.)
     // Grids that fit LDS beside their axes (the reference's 100 x 100 scalar grid: 80 KB in f64), rows of up to 64 bytes,
     // large batches: query per lane with every corner read served by LDS (eval_scalar2d_kernel / eval_lanes2d_kernel).
     // NDI_LANES2D_KERNEL=0: A/B.
     {
-      static const bool tune_live2 = std::getenv("NDI_TUNE_LIVE") != nullptr;
-      static const int on_once = ShortKnobs::env("NDI_LANES2D_KERNEL", -1);
-      const int on = tune_live2 ? ShortKnobs::env("NDI_LANES2D_KERNEL", -1) : on_once;
+      static const Knob on_knob{"NDI_LANES2D_KERNEL", -1, Knob::live};
+      const int on = on_knob.get();
       const size_t grid_b = (size_t)nx * ny * lanes * sizeof(T);
       if (on != 0 && path != NDI_PATH_BUCKETED && !pair_packed && nx <= 16384 && ny <= 16384 && lanes * sizeof(T) <= (on > 0 ? 64 : 56) &&
           grid_b + (nx + ny) * 5 * sizeof(T) <= FUSED_LDS_LIMIT && (uint64_t)nx * ny * lanes < (1ull << 31) &&
@@ -2717,18 +2578,9 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
           P.f_tb = tb;
           P.f_lds = need_of(tb);
           P.l_qpl = (lanes == 1 && out_stride == 1 && aligned16(qx) && aligned16(qy) && aligned16(out)) ? VNl : 1;
-          const size_t wg_per_cu = std::max<size_t>(1, std::min<size_t>((160 * 1024) / P.f_lds, 32 / (P.f_tb / 64)));
           const uint64_t per_wg = (uint64_t)P.f_tb * (lanes == 1 ? (uint64_t)P.l_qpl : 1);
-          P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + per_wg - 1) / per_wg, (uint64_t)cu_count() * wg_per_cu));
-          g_last_path.store(NDI_PATH_GATHER);
-          P.l_check = (flags & NDI_EVAL_FRESH_OUTPUT) != 0;   // fresh output: the kernel's own range test, no pre-pass
-          if (P.l_check) return P;
-          const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-          ProfScope ps(s, PC_LOCATE);
-          hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, qx, qy, nq, px.host_knots.front(),
-                             px.host_knots.back(), py.host_knots.front(), py.host_knots.back(), mode, &st->first_fail[0]);
-          NDI_HIP(hipGetLastError());
-          ps.done();
+          P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + per_wg - 1) / per_wg, (uint64_t)cu_count() * wgs_per_cu(P.f_lds, P.f_tb)));
+          P.l_check = this->range_prepass(s, sc, {qx, qy}, nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
           return P;
         }
       }
@@ -2737,9 +2589,8 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     // run of 4 L values per query, one division per value instead of three, an item per lane (eval_slopes2d_kernel; the
     // copy, 2 x the grid, is built on first use).  NDI_SLOPES2D_KERNEL=0 / 1: A/B.
     {
-      static const bool tune_live5 = std::getenv("NDI_TUNE_LIVE") != nullptr;
-      static const int on_once5 = ShortKnobs::env("NDI_SLOPES2D_KERNEL", -1);
-      const int on = tune_live5 ? ShortKnobs::env("NDI_SLOPES2D_KERNEL", -1) : on_once5;
+      static const Knob on_knob{"NDI_SLOPES2D_KERNEL", -1, Knob::live};
+      const int on = on_knob.get();
       const size_t cell_b = (size_t)lanes * sizeof(T);
       // (f32 rows beyond 48 bytes: 13 .. 16 trips -- the compiler stops unrolling and the per-trip arrays go to scratch; the
       //  query-order kernel was level there anyway)
@@ -2764,56 +2615,33 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
           P.f_tb = tb;
           P.f_lds = need;
           P.f_lds_wide = wide_fits;
-          const size_t wg_per_cu = std::max<size_t>(1, std::min<size_t>((160 * 1024) / P.f_lds, 32 / (P.f_tb / 64)));
-          P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + P.f_tb - 1) / P.f_tb, (uint64_t)cu_count() * wg_per_cu));
-          g_last_path.store(NDI_PATH_GATHER);
-          P.l_check = (flags & NDI_EVAL_FRESH_OUTPUT) != 0;   // fresh output: the kernel's own range test, no pre-pass
-          if (P.l_check) return P;
-          const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-          ProfScope ps(s, PC_LOCATE);
-          hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, qx, qy, nq, px.host_knots.front(),
-                             px.host_knots.back(), py.host_knots.front(), py.host_knots.back(), mode, &st->first_fail[0]);
-          NDI_HIP(hipGetLastError());
-          ps.done();
+          P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + P.f_tb - 1) / P.f_tb, (uint64_t)cu_count() * wgs_per_cu(P.f_lds, P.f_tb)));
+          P.l_check = this->range_prepass(s, sc, {qx, qy}, nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
           return P;
         }
       }
     }
-    constexpr int small2d_lanes = 2;
-    constexpr int VNs = Wide<T>::N;
-    const bool small2d = lanes <= 2 || (lanes <= (uint64_t)small2d_lanes && lanes % VNs != 0);
-    constexpr long f2_minlanes = 1;
-    constexpr long f2_minq0 = 65536;
-    const bool small2d_yields = (long)lanes >= f2_minlanes && f2_minq0 >= 0 && (long)std::min<uint64_t>(nq, 1ull << 40) >= 8 * f2_minq0;
+    const bool small2d = lanes <= 2;
+    const bool small2d_yields = lanes >= 1 && nq >= 8 * 65536;   // (to the query-order kernel below, at 8 x its own floor)
     if (small2d && !small2d_yields && both <= LDS_STAGE_LIMIT && path != NDI_PATH_BUCKETED) {
       // short trailing axes: range pre-check, then both searches + evaluation fused in one launch
       P.kind = Plan2::SMALL;
-      g_last_path.store(NDI_PATH_GATHER);
-      const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-      ProfScope ps(s, PC_LOCATE);
-      hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, qx, qy, nq, px.host_knots.front(),
-                         px.host_knots.back(), py.host_knots.front(), py.host_knots.back(), mode,
-                         &st->first_fail[0]);
-      NDI_HIP(hipGetLastError());
-      ps.done();
+      this->range_prepass(s, sc, {qx, qy}, nq, false);
       return P;
     }
     // Rows of fewer than 256 vectors on axes that fit LDS twice over (the reference's 100 x 100 x 5; few-channel grids),
     // batches from 65 536 queries: query order with both searches fused in (eval_fused2d_kernel) -- no (xi, yi)
     // round trip, one reciprocal per direction and query.  Grids the tile order takes (below) are left to it.
     {
-      constexpr long minq = 65536;
       constexpr int VNf = Wide<T>::N;
       const bool vec = (lanes % VNf == 0) && (out_stride % VNf == 0) && aligned16(out);
       const uint64_t LVf = vec ? lanes / VNf : lanes;
       const uint64_t cell_e = pair_packed ? 2 * lanes : lanes, row_c = pair_packed ? ny - 1 : ny;
       const uint64_t grid_vecs = nx * row_c * cell_e / (vec ? VNf : 1);
-      constexpr int lut_env2 = 1;
       // workgroup size and search: the combination that keeps most waves on a CU beside the staged axes (the gathers
       // are latency-bound: waves first); the bucket indices when they cost no waves, or at most half of them
-      constexpr int lut2_env = -1;
       size_t lut_b = 0;
-      if (lut_env2 && lut2_env != 0 && nq >= 4096 && both <= LDS_STAGE_LIMIT) {
+      if (nq >= 4096 && both <= LDS_STAGE_LIMIT) {
         px.ensure_bucket_index();
         py.ensure_bucket_index();
         lut_b = px.lut_bytes + py.lut_bytes;
@@ -2823,7 +2651,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
         for (unsigned tb : {256u, 512u, 1024u}) {
           const size_t need = both + (with_lut ? lut_b : 0) + (size_t)(tb / 64) * 64 * (sizeof(uint32_t) + 6 * sizeof(T));
           if (need > LDS_STAGE_LIMIT) continue;
-          const size_t waves = std::min<size_t>((160 * 1024) / need, 32 / (tb / 64)) * (tb / 64);
+          const size_t waves = wgs_per_cu(need, tb) * (tb / 64);
           if (waves > best) { best = waves; tb_out = tb; lds_out = need; }
         }
         return best;
@@ -2832,25 +2660,16 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
       size_t lds0 = 0, lds1 = 0;
       const size_t w0 = plan(false, tb0, lds0);
       const size_t w1 = lut_b ? plan(true, tb1, lds1) : 0;
-      const bool lut = w1 != 0 && (lut2_env > 0 || 2 * w1 >= w0);
+      const bool lut = w1 != 0 && 2 * w1 >= w0;
       const unsigned TBf = lut ? tb1 : tb0;
       const size_t lds = lut ? lds1 : lds0;
       const bool tile_candidate = path == NDI_PATH_BUCKETED || (path == NDI_PATH_AUTO && auto_tiles(nq) && lanes * sizeof(T) >= 64);
-      if (minq >= 0 && (long)std::min<uint64_t>(nq, 1ull << 40) >= minq && (long)lanes >= f2_minlanes && LVf < 256 && 64 * LVf * LVf < (1ull << 32) &&
+      if (nq >= 65536 && lanes >= 1 && LVf < 256 && 64 * LVf * LVf < (1ull << 32) &&
           grid_vecs < (1ull << 32) && (lut ? w1 : w0) != 0 && !tile_candidate) {
         P.kind = Plan2::FUSED2;
         P.f_vec = vec; P.f_lv = LVf; P.f_lut = lut; P.f_lds = lds; P.f_tb = TBf;
-        const size_t wg_per_cu = std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, 32 / (TBf / 64)));
-        P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + TBf - 1) / TBf, (uint64_t)cu_count() * wg_per_cu * 4));
-        g_last_path.store(NDI_PATH_GATHER);
-        P.l_check = (flags & NDI_EVAL_FRESH_OUTPUT) != 0;   // fresh output: the kernel's own range test, no pre-pass
-        if (P.l_check) return P;
-        const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-        ProfScope ps(s, PC_LOCATE);
-        hipLaunchKernelGGL(range_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, qx, qy, nq, px.host_knots.front(),
-                           px.host_knots.back(), py.host_knots.front(), py.host_knots.back(), mode, &st->first_fail[0]);
-        NDI_HIP(hipGetLastError());
-        ps.done();
+        P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + TBf - 1) / TBf, (uint64_t)cu_count() * wgs_per_cu(lds, TBf) * 4));
+        P.l_check = this->range_prepass(s, sc, {qx, qy}, nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
         return P;
       }
     }
@@ -2863,9 +2682,8 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     constexpr int VNp = Wide<T>::N;
     const bool vec_ok_p = (lanes % VNp == 0) && (out_stride % VNp == 0) && aligned16(out);
     const uint64_t LVp = vec_ok_p ? lanes / VNp : 0;
-    constexpr int lut_env = 1;   // (the bucket index: A/B settled in round 3)
     size_t both_l = both;
-    const bool use_lut = lut_env && nq >= 4096 && both <= LDS_STAGE_LIMIT;
+    const bool use_lut = nq >= 4096 && both <= LDS_STAGE_LIMIT;   // (the bucket index: A/B settled in round 3)
     if (use_lut) {
       px.ensure_bucket_index();
       py.ensure_bucket_index();
@@ -2881,7 +2699,8 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     bool shape_ok = false;
     if (vec_ok_p && !pair_packed && LVp >= 1 && LVp <= 1024 && 1024 % LVp == 0 && both <= LDS_STAGE_LIMIT &&
         nx < (1ull << 31) && ny < (1ull << 31) && ny * lanes < (1ull << 32) && out_stride < (1ull << 32)) {
-      static const int ts_env = [] { const char* e = std::getenv("NDI_TILE_TS"); return e ? std::atoi(e) : -1; }();
+      static const Knob ts_knob{"NDI_TILE_TS", -1};
+      const int ts_env = ts_knob.get();
       // the largest tile that leaves room for two workgroups per CU, else the largest that fits at all
       // the tile must fit the kernel's register double-buffer (6 x 1024 16-byte vectors = 96 KiB) next to 24-32 KiB of
       // static LDS; the smaller budget is tried first (shorter staging per tile)
@@ -2906,15 +2725,14 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     else if (path == NDI_PATH_AUTO) tiled = can_tile && auto_tiles(nq);
     const uint32_t sx = ts, sy = ts;
     const bool compact_records = std::is_same<T, float>::value && nx <= 65536 && ny <= 65536;
-    static const int cw_env = [] { const char* e = std::getenv("NDI_TILE_CELLWORDS"); return e ? std::atoi(e) : 1; }();   // A/B
-    const bool cell_words = tiled && compact_records && both <= LDS_STAGE_LIMIT && cw_env;
+    static const Knob cw_knob{"NDI_TILE_CELLWORDS", 1};   // A/B
+    const bool cell_words = tiled && compact_records && both <= LDS_STAGE_LIMIT && cw_knob.get();
     g_last_path.store(tiled ? NDI_PATH_BUCKETED : NDI_PATH_GATHER);
     // Two-level grouping (tile row, then tile: coarse_scatter2d_kernel / fine_scatter2d_kernel) when the one-pass scatter
     // would leave fewer than a line's worth of records per (slice, tile) and the batch is large enough to pay for the
     // second pass.  NDI_GROUP_TWO_LEVEL=0 / 1: A/B.
-    static const bool tl_live = std::getenv("NDI_TUNE_LIVE") != nullptr;
-    static const int tl_once = ShortKnobs::env("NDI_GROUP_TWO_LEVEL", -1);
-    const int tl_env = tl_live ? ShortKnobs::env("NDI_GROUP_TWO_LEVEL", -1) : tl_once;
+    static const Knob tl_knob{"NDI_GROUP_TWO_LEVEL", -1, Knob::live};
+    const int tl_env = tl_knob.get();
     const uint32_t ntx = tiled ? nb / nty : 0;
     const bool two_level = tiled && both <= LDS_STAGE_LIMIT && ntx >= 2 && ntx <= 4096 && nty <= 4096 &&
                            (tl_env == 1 || (tl_env < 0 && nq >= (1u << 20) && (double)nq / group_blocks() / nb < 8.0));
@@ -2959,10 +2777,9 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
         sc.hist.reserve((size_t)blocks * LA.hist_w * blocks * sizeof(uint32_t));
         LA.hist = sc.hist.as<uint32_t>();
       }
-      allow_dynamic_lds(reinterpret_cast<const void*>(&locate2_kernel<T, LOCATE_QB>), (int)LDS_STAGE_LIMIT);
-      allow_dynamic_lds(reinterpret_cast<const void*>(&locate2_kernel<T, 1>), (int)LDS_STAGE_LIMIT);
-      if (slice / threads >= 16) launch1<T>(s, PC_LOCATE, dim3((unsigned)blocks), dim3(threads), shmem, locate2_kernel<T, LOCATE_QB>, LA);
-      else launch1<T>(s, PC_LOCATE, dim3((unsigned)blocks), dim3(threads), shmem, locate2_kernel<T, 1>, LA);
+      pick_or<1, LOCATE_QB>(slice / threads >= 16 ? LOCATE_QB : 1, [&](auto qb_) {
+        launch_lds<T>(locate2_kernel<T, qb_>, LDS_STAGE_LIMIT, s, PC_LOCATE, dim3((unsigned)blocks), dim3(threads), shmem, LA);
+      });
     } else {
       run_locate<T>(s, px, qx, nq, sc.idx.as<uint32_t>(), nullptr, nullptr, &st->first_fail[0], mode);
       run_locate<T>(s, py, qy, nq, sc.idx2.as<uint32_t>(), nullptr, nullptr, &st->first_fail[1], mode);
@@ -2992,8 +2809,8 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
         if (!P.compact) sc.recq2.reserve(nq * 2 * sizeof(T));
         sc.cursor2.reserve(((size_t)nb + 4) * sizeof(uint32_t));
         const size_t shm_c = ((size_t)3 * ntx + (size_t)2 * gthreads) * 4;
-        static const int ft_env = [] { const char* e = std::getenv("NDI_GROUP_FINE_THREADS"); return e ? std::atoi(e) : 0; }();
-        constexpr int fg_env = 0;
+        static const Knob ft_knob{"NDI_GROUP_FINE_THREADS", 0};
+        const int ft_env = ft_knob.get();
         constexpr int FR = 4;   // records per thread and round of the fine pass (2 / 8 measured level: r05_c3_fine_round_variants.txt)
         const unsigned fthreads = (ft_env == 256 || ft_env == 512 || ft_env == 1024) ? (unsigned)ft_env : 1024u;
         // parts per tile row: one round per workgroup on evenly spread queries (measured at C3, profiles/r05_tuning.md:
@@ -3001,8 +2818,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
         // flight 115 us -- the pass wants its parallelism across workgroups)
         const uint64_t per_row = (nq + ntx - 1) / ntx;
         const uint64_t rounds_row = (per_row + (uint64_t)FR * fthreads - 1) / ((uint64_t)FR * fthreads);
-        uint32_t G = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rounds_row, 4096));
-        if (fg_env > 0) G = (uint32_t)std::min<int>(fg_env, 4096);
+        const uint32_t G = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rounds_row, 4096));
         const unsigned fgrid = (unsigned)(((ntx + 7u) / 8u) * 8u * G);
         if (std::getenv("NDI_TRACE_PLAN"))
           std::fprintf(stderr, "[ndi plan] two-level grouping ntx=%u nty=%u slices=%llu G=%u\n", ntx, nty,
@@ -3010,50 +2826,42 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
         const uint32_t* yi_c = P.compact ? yi_in : (const uint32_t*)sc.idx2.as<uint32_t>();
         T* rq2 = P.compact ? (T*)nullptr : sc.recq2.as<T>();
         T* rq1 = P.compact ? (T*)nullptr : sc.recq.as<T>();
-#define NDI_COARSE(CP)                                                                                              \
-  do {                                                                                                              \
-    allow_dynamic_lds(reinterpret_cast<const void*>(&coarse_scatter2d_kernel<T, CP>), (int)(64 * 1024));            \
-    hipLaunchKernelGGL((coarse_scatter2d_kernel<T, CP>), dim3((unsigned)blocks), dim3(gthreads), shm_c, s,          \
-                       (const uint32_t*)sc.idx.as<uint32_t>(), yi_c, qx, qy, nq, slice,                             \
-                       (const uint32_t*)sc.chist.as<uint32_t>(), (const uint32_t*)sc.hist.as<uint32_t>(), nb, ntx,  \
-                       sx, sc.perm2.as<uint4>(), rq2, sc.counts.as<uint32_t>());                                    \
-  } while (0)
-#define NDI_FINE(CP, R)                                                                                             \
-  hipLaunchKernelGGL((fine_scatter2d_kernel<T, CP, R>), dim3(fgrid), dim3(fthreads), (size_t)nty * 8, s,            \
-                     (const uint4*)sc.perm2.as<uint4>(), (const T*)rq2, sc.perm.as<uint4>(), rq1,                   \
-                     (const uint32_t*)sc.cursor.as<uint32_t>(), sc.cursor2.as<uint32_t>(), nq, ntx, nty, sy, G)
-        static const int csort_env = [] { const char* e = std::getenv("NDI_GROUP_COARSE_SORT"); return e ? std::atoi(e) : 1; }();
-        const size_t shm_cs = ((((size_t)6 * ntx + 2 * gthreads) * 4 + 15) & ~(size_t)15) + (size_t)4 * gthreads * 20;
-        if (P.compact && std::is_same<T, float>::value && csort_env && shm_cs <= 150 * 1024) {   // trips sorted in LDS (NDI_GROUP_COARSE_SORT=0: direct, A/B)
-          auto kern = coarse_scatter2d_kernel<T, true, true>;
-          allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)(150 * 1024));
-          hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(gthreads), shm_cs, s,
+        auto coarse = [&](auto kern, size_t limit, size_t shm) {
+          allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)limit);
+          hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(gthreads), shm, s,
                              (const uint32_t*)sc.idx.as<uint32_t>(), yi_c, qx, qy, nq, slice,
                              (const uint32_t*)sc.chist.as<uint32_t>(), (const uint32_t*)sc.hist.as<uint32_t>(), nb, ntx,
                              sx, sc.perm2.as<uint4>(), rq2, sc.counts.as<uint32_t>());
-        } else if (P.compact) NDI_COARSE(true); else NDI_COARSE(false);
+        };
+        static const Knob csort_knob{"NDI_GROUP_COARSE_SORT", 1};
+        const size_t shm_cs = ((((size_t)6 * ntx + 2 * gthreads) * 4 + 15) & ~(size_t)15) + (size_t)4 * gthreads * 20;
+        // trips sorted in LDS (NDI_GROUP_COARSE_SORT=0: direct, A/B)
+        if (P.compact && std::is_same<T, float>::value && csort_knob.get() && shm_cs <= 150 * 1024) coarse(coarse_scatter2d_kernel<T, true, true>, 150 * 1024, shm_cs);
+        else if (P.compact) coarse(coarse_scatter2d_kernel<T, true>, 64 * 1024, shm_c);
+        else coarse(coarse_scatter2d_kernel<T, false>, 64 * 1024, shm_c);
         hipLaunchKernelGGL(scan_bin_totals_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t*)sc.counts.as<uint32_t>(), nb,
                            sc.cursor.as<uint32_t>(), sc.cursor2.as<uint32_t>(), st, chunk, sc.chunkbin.as<uint32_t>());
-        static const int fsort_env = [] { const char* e = std::getenv("NDI_GROUP_FINE_SORT"); return e ? std::atoi(e) : 1; }();
+        static const Knob fsort_knob{"NDI_GROUP_FINE_SORT", 1};
+        const int fsort_env = fsort_knob.get();
         if (P.compact && std::is_same<T, float>::value && fsort_env) {   // the round's records sorted in LDS, coalesced copy-out (NDI_GROUP_FINE_SORT=0: the direct form, A/B)
-#define NDI_FSORT(SR, STB)                                                                                          \
-  do {                                                                                                              \
-    const uint64_t rr = (per_row + (uint64_t)SR * STB - 1) / ((uint64_t)SR * STB);                                  \
-    const uint32_t Gs = fg_env > 0 ? G : (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rr, 4096));             \
-    const unsigned sgrid = (unsigned)(((ntx + 7u) / 8u) * 8u * Gs);                                                 \
-    const size_t shm_s = ((((size_t)3 * nty + 16) * 4 + 15) & ~(size_t)15) + (size_t)SR * STB * 20;                 \
-    auto kern = fine_scatter2d_sorted_kernel<SR, STB>;                                                              \
-    allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)(128 * 1024));                                      \
-    hipLaunchKernelGGL(kern, dim3(sgrid), dim3(STB), shm_s, s, (const uint4*)sc.perm2.as<uint4>(), sc.perm.as<uint4>(), \
-                       (const uint32_t*)sc.cursor.as<uint32_t>(), sc.cursor2.as<uint32_t>(), nq, ntx, nty, sy, Gs); \
-  } while (0)
-          if (fsort_env == 2) NDI_FSORT(8, 512); else if (fsort_env == 3) NDI_FSORT(4, 1024); else if (fsort_env == 4) NDI_FSORT(2, 512);
-          else if (fsort_env == 5) NDI_FSORT(4, 256); else NDI_FSORT(4, 512);
-#undef NDI_FSORT
-        } else if (P.compact) NDI_FINE(true, FR);
-        else NDI_FINE(false, FR);
-#undef NDI_COARSE
-#undef NDI_FINE
+          // records per thread and round x workgroup size: 1 = 4 x 512; 2 .. 5 = 8 x 512, 4 x 1024, 2 x 512, 4 x 256 (A/B)
+          pick_or<1, 2, 3, 4, 5>(fsort_env, [&](auto v_) {
+            constexpr int V = v_, SR = V == 2 ? 8 : (V == 4 ? 2 : 4), STB = V == 3 ? 1024 : (V == 5 ? 256 : 512);
+            const uint64_t rr = (per_row + (uint64_t)SR * STB - 1) / ((uint64_t)SR * STB);
+            const uint32_t Gs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rr, 4096));
+            const unsigned sgrid = (unsigned)(((ntx + 7u) / 8u) * 8u * Gs);
+            const size_t shm_s = ((((size_t)3 * nty + 16) * 4 + 15) & ~(size_t)15) + (size_t)SR * STB * 20;
+            auto kern = fine_scatter2d_sorted_kernel<SR, STB>;
+            allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)(128 * 1024));
+            hipLaunchKernelGGL(kern, dim3(sgrid), dim3(STB), shm_s, s, (const uint4*)sc.perm2.as<uint4>(), sc.perm.as<uint4>(),
+                               (const uint32_t*)sc.cursor.as<uint32_t>(), sc.cursor2.as<uint32_t>(), nq, ntx, nty, sy, Gs);
+          });
+        } else
+          pick_bool(P.compact, [&](auto cp_) {
+            hipLaunchKernelGGL((fine_scatter2d_kernel<T, cp_, FR>), dim3(fgrid), dim3(fthreads), (size_t)nty * 8, s,
+                               (const uint4*)sc.perm2.as<uint4>(), (const T*)rq2, sc.perm.as<uint4>(), rq1,
+                               (const uint32_t*)sc.cursor.as<uint32_t>(), sc.cursor2.as<uint32_t>(), nq, ntx, nty, sy, G);
+          });
       } else if (P.compact)
         hipLaunchKernelGGL((group_scatter2d_kernel<T, true>), dim3((unsigned)blocks), dim3(gthreads), (size_t)nb * 4, s,
                            (const uint32_t*)sc.idx.as<uint32_t>(), yi_in, qx, qy, nq,
@@ -3072,8 +2880,8 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
 
   // grouped positions per unit of work of eval_bilinear_tiles_kernel (sweep: profiles/r03_c3_grouped.md)
   static uint32_t tile_chunk() {
-    static const int chunk_env = [] { const char* e = std::getenv("NDI_TILE_CHUNK"); return e ? std::atoi(e) : 0; }();
-    return chunk_env > 0 ? (uint32_t)chunk_env : 8192u;
+    static const Knob chunk_knob{"NDI_TILE_CHUNK", 0};
+    return chunk_knob.get() > 0 ? (uint32_t)chunk_knob.get() : 8192u;
   }
 
   // AUTO for 2-D: tile-grouped order when the batch has enough queries per grid cell to pay for staging every
@@ -3125,8 +2933,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
       // large batches: bucket indices behind the pyramids (as the two-axis search stages them), and from two values per
       // query the shared-divisor division (two reciprocals per query instead of three divisions per value: same bits)
       size_t shm = both;
-      constexpr int lut_env = 1;   // (the bucket index: A/B settled in round 3)
-      if (lut_env && nq >= 4096) {
+      if (nq >= 4096) {   // (the bucket index: A/B settled in round 3)
         px.ensure_bucket_index();
         py.ensure_bucket_index();
         if ((px.lut_bytes || py.lut_bytes) && both + px.lut_bytes + py.lut_bytes <= LDS_STAGE_LIMIT / 2) {
@@ -3149,7 +2956,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
       F.dx = px.dlut; F.dy = py.dlut;
       F.recs = slopes.as<T>();
 #ifdef NDI_TUNING
-      F.debug = ShortKnobs::env("NDI_SLOPES2D_DEBUG", 0);
+      F.debug = env_int("NDI_SLOPES2D_DEBUG", 0);
 #endif
       if (slopes_cells()) {
         F.col_bytes = (uint32_t)slopes_cell_stride_bytes();
@@ -3172,30 +2979,19 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
       // rows leave as 16-byte vectors through a wave-private strip when the buffer allows it (+2-6 % over one value per lane)
       const int contig = P.out_stride != lanes ? 0 : (aligned16(P.out) && P.f_lds_wide) ? 2 : 1;
       const int mk = (int)std::max(px.dlut.lut ? px.dlut.maxk : 0u, py.dlut.lut ? py.dlut.maxk : 0u) <= 4 ? 4 : 8;
-#define NDI_SL2K(LCS, MKS, CT)                                                            \
-  do {                                                                                    \
-    auto kern = eval_slopes2d_kernel<T, LCS, MKS, CT, 256>;                               \
-    allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)FUSED_LDS_LIMIT);         \
-    launch1<T>(s, PC_EVAL, dim3(P.f_grid), dim3(256), P.f_lds, kern, F);                  \
-  } while (0)
-#define NDI_SL2(LCS)                                                                      \
-  case LCS:                                                                               \
-    if (mk == 4) { if (contig == 2) NDI_SL2K(LCS, 4, 2); else if (contig) NDI_SL2K(LCS, 4, 1); else NDI_SL2K(LCS, 4, 0); }    \
-    else { if (contig == 2) NDI_SL2K(LCS, 8, 2); else if (contig) NDI_SL2K(LCS, 8, 1); else NDI_SL2K(LCS, 8, 0); }            \
-    break
-      switch ((int)lanes) {
-        NDI_SL2(1); NDI_SL2(2); NDI_SL2(3); NDI_SL2(4); NDI_SL2(5); NDI_SL2(6); NDI_SL2(7); NDI_SL2(8);
-        default:
-          if constexpr (sizeof(T) == 4) {
-            switch ((int)lanes) {
-              NDI_SL2(9); NDI_SL2(10); NDI_SL2(11); NDI_SL2(12);
-              default: break;
-            }
-          }
-          break;
-      }
-#undef NDI_SL2K
-#undef NDI_SL2
+      auto launch = [&](auto lc_) {
+        constexpr int LCS = lc_;
+        pick_or<8, 4>(mk, [&](auto mk_) {
+          constexpr int MKS = mk_;
+          pick_or<1, 2, 0>(contig, [&](auto ct_) {
+            launch_lds<T>(eval_slopes2d_kernel<T, LCS, MKS, ct_, 256>, FUSED_LDS_LIMIT, s, PC_EVAL, dim3(P.f_grid), dim3(256), P.f_lds, F);
+          });
+        });
+      };
+      // (prep plans rows of up to 64 bytes, f32 of up to 48: lanes 9 .. 12 exist for 4-byte elements only)
+      bool known = pick<1, 2, 3, 4, 5, 6, 7, 8>((int)lanes, launch);
+      if constexpr (sizeof(T) == 4) known = known || pick<9, 10, 11, 12>((int)lanes, launch);
+      if (!known) throw HipFailure{hipErrorInvalidValue, "launch_eval: no slope-record kernel for this lane count", __LINE__};
       return;
     }
     if (P.kind == Plan2::LANES2) {
@@ -3216,20 +3012,14 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
         std::fprintf(stderr, "[ndi plan] lanes2d L=%llu qpl=%d maxk=%u,%u tb=%u grid=%u lds=%zu prepass=%d\n", (unsigned long long)lanes,
                      P.l_qpl, px.dlut.maxk, py.dlut.maxk, P.f_tb, P.f_grid, P.f_lds, P.l_check ? 0 : 1);
       constexpr int VNl = Wide<T>::N;
-#define NDI_L2(KERN)                                                                      \
-  do {                                                                                    \
-    auto kern = KERN;                                                                     \
-    allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)FUSED_LDS_LIMIT);         \
-    launch1<T>(s, PC_EVAL, dim3(P.f_grid), dim3(P.f_tb), P.f_lds, kern, F);               \
-  } while (0)
-      if (lanes == 1 && P.l_qpl == VNl) {
-        if (P.f_tb == 1024) NDI_L2((eval_scalar2d_kernel<T, VNl, 1024>)); else NDI_L2((eval_scalar2d_kernel<T, VNl, 256>));
-      } else if (lanes == 1) {
-        if (P.f_tb == 1024) NDI_L2((eval_scalar2d_kernel<T, 1, 1024>)); else NDI_L2((eval_scalar2d_kernel<T, 1, 256>));
-      } else {
-        if (P.f_tb == 1024) NDI_L2((eval_lanes2d_kernel<T, 1024>)); else NDI_L2((eval_lanes2d_kernel<T, 256>));
-      }
-#undef NDI_L2
+      pick_or<256, 1024>((int)P.f_tb, [&](auto tb_) {
+        constexpr int TB = tb_;
+        if (lanes == 1)
+          pick_or<1, VNl>(P.l_qpl, [&](auto qpl_) {
+            launch_lds<T>(eval_scalar2d_kernel<T, qpl_, TB>, FUSED_LDS_LIMIT, s, PC_EVAL, dim3(P.f_grid), dim3(P.f_tb), P.f_lds, F);
+          });
+        else launch_lds<T>(eval_lanes2d_kernel<T, TB>, FUSED_LDS_LIMIT, s, PC_EVAL, dim3(P.f_grid), dim3(P.f_tb), P.f_lds, F);
+      });
       return;
     }
     if (P.kind == Plan2::FUSED2) {
@@ -3255,18 +3045,12 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
         std::fprintf(stderr, "[ndi plan] fused2d vec=%d lv=%u lut=%d tb=%u grid=%u lds=%zu prepass=%d\n", (int)P.f_vec, F.lv, (int)P.f_lut,
                      P.f_tb, P.f_grid, P.f_lds, P.l_check ? 0 : 1);
       constexpr int VNf = Wide<T>::N;
-#define NDI_F2(VEC, TB)                                                                      \
-  do {                                                                                       \
-    auto kern = eval_fused2d_kernel<T, VEC, 2, TB>;                                          \
-    allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)LDS_STAGE_LIMIT);            \
-    launch1<T>(s, PC_EVAL, dim3(P.f_grid), dim3(TB), P.f_lds, kern, F);                      \
-  } while (0)
-      if (P.f_vec) {
-        if (P.f_tb == 1024) NDI_F2(VNf, 1024); else if (P.f_tb == 512) NDI_F2(VNf, 512); else NDI_F2(VNf, 256);
-      } else {
-        if (P.f_tb == 1024) NDI_F2(1, 1024); else if (P.f_tb == 512) NDI_F2(1, 512); else NDI_F2(1, 256);
-      }
-#undef NDI_F2
+      pick_or<1, VNf>(P.f_vec ? VNf : 1, [&](auto vec_) {
+        constexpr int VEC = vec_;
+        pick_or<256, 1024, 512>((int)P.f_tb, [&](auto tb_) {
+          launch_lds<T>(eval_fused2d_kernel<T, VEC, 2, tb_>, LDS_STAGE_LIMIT, s, PC_EVAL, dim3(P.f_grid), dim3(tb_), P.f_lds, F);
+        });
+      });
       return;
     }
     Eval2Args<T> A{};
@@ -3300,14 +3084,14 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
       // Channel split: two 512-thread workgroups per CU, each staging one half of the trailing axis of its tile (values +
       // x slopes), when two such half-tiles fit the CU's LDS beside 256 records each and a half-row still fills whole
       // 16-byte vectors.  NDI_TILE_SPLIT=0 keeps one 1024-thread workgroup per CU (A/B).
-      static const int split_env = [] { const char* e = std::getenv("NDI_TILE_SPLIT"); return e ? std::atoi(e) : -1; }();
-      static const int slope_env0 = [] { const char* e = std::getenv("NDI_TILE_SLOPES"); return e ? std::atoi(e) : 1; }();
+      static const Knob split_knob{"NDI_TILE_SPLIT", -1}, slope_knob{"NDI_TILE_SLOPES", 1}, wg_knob{"NDI_TILE_WG", 0};
+      const int slope_env = slope_knob.get();
       const uint64_t lv_full = lanes / Wide<T>::N;
       const size_t shm_half = (s1 * s1 + (s1 - 1) * s1) * (lanes / 2) * sizeof(T) + 5 * s1 * sizeof(T) + 16;
-      const size_t static512s = 256 * 16 + (P.compact ? 2 : 2 * 256) * sizeof(T) + 320;
-      const bool split2 = split_env != 0 && slope_env0 != 0 && lv_full >= 2 && lv_full % 2 == 0 &&
+      const size_t static512 = 256 * 16 + (P.compact ? 2 : 2 * 256) * sizeof(T) + 320;   // 256 records beside a tile
+      const bool split2 = split_knob.get() != 0 && slope_env != 0 && lv_full >= 2 && lv_full % 2 == 0 &&
                           s1 * s1 * (lv_full / 2) <= 5 * 512 && 512 % (lv_full / 2) == 0 &&
-                          2 * (shm_half + static512s) <= 160 * 1024;
+                          2 * (shm_half + static512) <= 160 * 1024;
       // (Four quarter-row workgroups per CU were measured slower -- 1.05-1.08 vs 0.77-0.85 ms at C3: 64-byte half-line stores,
       //  four decodes per record -- and are gone: profiles/r05_tuning.md 2.)
       A.ch_split = split2 ? 2u : 1u;
@@ -3320,7 +3104,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
       }
       A.debug = 0;
 #ifdef NDI_TUNING
-      A.debug = ShortKnobs::env("NDI_FUSED_DEBUG", 0);
+      A.debug = env_int("NDI_FUSED_DEBUG", 0);
 #endif
       const size_t shm = s1 * s1 * lanes * sizeof(T) + 5 * s1 * sizeof(T) + 16;
       const uint64_t nchunks = (nq + A.chunk - 1) / A.chunk;
@@ -3330,55 +3114,36 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
       // One 1024-thread workgroup per CU.  NDI_TILE_WG=512 (A/B only): two 512-thread workgroups per CU when two tiles
       // (+ 256 records each) fit the 160 KiB and the tile fits the 10 x 512-vector register double buffer -- measured
       // slower at C3 (1.54 vs 1.17 ms: twice the tile staging per CU, half the rows per trip).
-      static const int wg_env = [] { const char* e = std::getenv("NDI_TILE_WG"); return e ? std::atoi(e) : 0; }();
       const size_t tile_vecs = s1 * s1 * (lanes / VNt);
-      const size_t static512 = 256 * 16 + (P.compact ? 2 : 2 * 256) * sizeof(T) + 320;
-      const bool two_wg = wg_env == 512 && tile_vecs <= 10 * 512 && 2 * (shm + static512) <= 160 * 1024 &&
+      const bool two_wg = wg_knob.get() == 512 && tile_vecs <= 10 * 512 && 2 * (shm + static512) <= 160 * 1024 &&
                           (lanes / VNt) <= 512 && 512 % (lanes / VNt) == 0;
       // x slopes of the tile staged next to its values (one division per channel and query instead of three): needs a
       // second tile-sized array in LDS, so the records are handed over 256 at a time.  NDI_TILE_SLOPES=0: A/B.
-      static const int slope_env = [] { const char* e = std::getenv("NDI_TILE_SLOPES"); return e ? std::atoi(e) : 1; }();
       const size_t shm_slope = (s1 * s1 + (s1 - 1) * s1) * lanes * sizeof(T) + 5 * s1 * sizeof(T) + 16;
       const bool slopes = slope_env != 0 && !two_wg && shm_slope + static512 <= 160 * 1024;
       // ... 1024 at a time when that still fits (compact f32 records at C3: 143.9 KiB + 16 KiB)
       const size_t static1024 = 1024 * 16 + (P.compact ? 2 : 2 * 1024) * sizeof(T) + 320;
       const bool slopes_rb1024 = slopes && shm_slope + static1024 <= 160 * 1024 && slope_env != 256;
-#define NDI_TILES(TTB, RB, MX, CP, SL)                                                                        \
-  do {                                                                                                        \
-    auto kern = eval_bilinear_tiles_kernel<T, VNt, TTB, RB, MX, CP, SL>;                                      \
-    allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)(160 * 1024 - RB * (16 + 2 * sizeof(T)) - 512)); \
-    launch1<T>(s, PC_EVAL, dim3(gx), dim3(TTB), (SL) ? shm_slope : shm, kern, A);                             \
-  } while (0)
       if (std::getenv("NDI_TRACE_PLAN"))
         std::fprintf(stderr, "[ndi plan] tiles ts=%u split=%u compact=%d grid=%u\n", P.ts, A.ch_split, (int)P.compact, gx);
-      if (split2) {
-        if constexpr (std::is_same<T, float>::value) {
-          if (P.compact) {
-            auto kern = eval_bilinear_tiles_kernel<T, VNt, 512, 256, 5, true, true>;
-            allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)(80 * 1024 - 256 * (16 + 2 * sizeof(T)) - 512));
-            launch1<T>(s, PC_EVAL, dim3(gx), dim3(512), shm_half, kern, A);
-            return;
-          }
+      // The kernel's forms: workgroup size, records per hand-over, vectors per thread of the staging double buffer, x
+      // slopes staged, and the LDS a workgroup may take (a half-tile workgroup shares its CU with a second one).
+      struct TileForm { int tb, rb, maxi; bool slope; int lds_kib; };
+      static constexpr TileForm forms[5] = {{512, 256, 5, true, 80}, {1024, 1024, 6, true, 160}, {1024, 256, 6, true, 160},
+                                            {512, 256, 10, false, 160}, {1024, 1024, 6, false, 160}};
+      const int form = split2 ? 0 : (slopes_rb1024 ? 1 : (slopes ? 2 : (two_wg ? 3 : 4)));
+      const size_t shm_form = split2 ? shm_half : (slopes ? shm_slope : shm);
+      pick<0, 1, 2, 3, 4>(form, [&](auto f_) {
+        constexpr TileForm V = forms[f_];
+        auto launch = [&](auto cp_) {
+          launch_lds<T>(eval_bilinear_tiles_kernel<T, VNt, V.tb, V.rb, V.maxi, cp_, V.slope>,
+                        V.lds_kib * 1024 - V.rb * (16 + 2 * sizeof(T)) - 512, s, PC_EVAL, dim3(gx), dim3(V.tb), shm_form, A);
+        };
+        if constexpr (std::is_same<T, float>::value) {   // compact records exist for f32 only
+          if (P.compact) return launch(std::true_type{});
         }
-        auto kern = eval_bilinear_tiles_kernel<T, VNt, 512, 256, 5, false, true>;
-        allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)(80 * 1024 - 256 * (16 + 2 * sizeof(T)) - 512));
-        launch1<T>(s, PC_EVAL, dim3(gx), dim3(512), shm_half, kern, A);
-        return;
-      }
-      if constexpr (std::is_same<T, float>::value) {
-        if (P.compact) {
-          if (slopes_rb1024) NDI_TILES(1024, 1024, 6, true, true);
-          else if (slopes) NDI_TILES(1024, 256, 6, true, true);
-          else if (two_wg) NDI_TILES(512, 256, 10, true, false);
-          else NDI_TILES(1024, 1024, 6, true, false);
-          return;
-        }
-      }
-      if (slopes_rb1024) NDI_TILES(1024, 1024, 6, false, true);
-      else if (slopes) NDI_TILES(1024, 256, 6, false, true);
-      else if (two_wg) NDI_TILES(512, 256, 10, false, false);
-      else NDI_TILES(1024, 1024, 6, false, false);
-#undef NDI_TILES
+        launch(std::false_type{});
+      });
       return;
     }
     constexpr int VN = Wide<T>::N;
@@ -3386,10 +3151,8 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     const uint64_t LV = vec_ok ? lanes / VN : lanes;
     // knots in LDS: both axes must fit next to each other with two 1024-thread workgroups per CU, and the batch
     // must be large enough to amortise the staging
-    constexpr int klds_env = -1;
     const size_t knot_bytes = (size_t)(nx + ny) * sizeof(T);
-    bool klds = vec_ok && knot_bytes <= 72 * 1024 && nq >= (1u << 20);
-    if (klds_env >= 0) klds = klds_env != 0 && vec_ok && knot_bytes <= LDS_STAGE_LIMIT;
+    const bool klds = vec_ok && knot_bytes <= 72 * 1024 && nq >= (1u << 20);
     ProfScope ps(s, PC_EVAL);
     if (klds) {
       constexpr int TB = 1024;
@@ -3401,20 +3164,18 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
       // (A/B on two boxes: 0.773 -> 0.726 and 0.749 -> 0.736 ms; the measured ceiling of the access mix is
       // 0.72-0.74), neutral with index axes; long rows (C3, HBM-bound at 7.1 TB/s) get 3 % slower with it and keep
       // the IEEE divisions.  Same bits either way.
-      allow_dynamic_lds(reinterpret_cast<const void*>(&eval_bilinear_kernel<T, VN, false, 2, TB, true>), (int)LDS_STAGE_LIMIT);
-      allow_dynamic_lds(reinterpret_cast<const void*>(&eval_bilinear_kernel<T, VN, false, 2, TB, true, true>), (int)LDS_STAGE_LIMIT);
-      constexpr int sdiv_env = -1;
-      const bool sdiv = sdiv_env >= 0 ? sdiv_env != 0 : pair_packed;
-      if (sdiv)
-        hipLaunchKernelGGL((eval_bilinear_kernel<T, VN, false, 2, TB, true, true>), dim3(gx), dim3(TB), (knot_bytes + 15) & ~(size_t)15, s, A, tile_q);
-      else
-        hipLaunchKernelGGL((eval_bilinear_kernel<T, VN, false, 2, TB, true>), dim3(gx), dim3(TB), (knot_bytes + 15) & ~(size_t)15, s, A, tile_q);
+      pick_bool(pair_packed, [&](auto sdiv_) {
+        auto kern = eval_bilinear_kernel<T, VN, false, 2, TB, true, sdiv_>;
+        allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)LDS_STAGE_LIMIT);
+        hipLaunchKernelGGL(kern, dim3(gx), dim3(TB), (knot_bytes + 15) & ~(size_t)15, s, A, tile_q);
+      });
     } else {
       const uint32_t tile_q = (uint32_t)std::max<uint64_t>(1, 1024 / std::max<uint64_t>(LV, 1));
       const uint64_t ntiles = (nq + tile_q - 1) / tile_q;
       const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ntiles, 32768));
-      if (vec_ok) hipLaunchKernelGGL((eval_bilinear_kernel<T, VN>), dim3(gx), dim3(BLOCK), 0, s, A, tile_q);
-      else hipLaunchKernelGGL((eval_bilinear_kernel<T, 1>), dim3(gx), dim3(BLOCK), 0, s, A, tile_q);
+      pick_or<1, VN>(vec_ok ? VN : 1, [&](auto vec_) {
+        hipLaunchKernelGGL((eval_bilinear_kernel<T, vec_>), dim3(gx), dim3(BLOCK), 0, s, A, tile_q);
+      });
     }
     NDI_HIP(hipGetLastError());
     ps.done();
@@ -3668,7 +3429,8 @@ static ndi_status create2d(const ndi_interp2d_desc& d, Interp2DBase** out) {
   // Short trailing axes (<= 64 B per grid point): keep the pair-packed layout instead of the plain one -- unless the
   // whole grid fits a CU's LDS (the reference's 100 x 100 bench grids): those stay plain, the layout eval_lanes2d_kernel
   // stages, and never leave L2 for the other kernels.  NDI_PAIR_PACK=1 packs every eligible grid (tests), 0 none.
-  static const int pack_env = [] { const char* e = std::getenv("NDI_PAIR_PACK"); return e ? std::atoi(e) : -1; }();
+  static const Knob pack_knob{"NDI_PAIR_PACK", -1};
+  const int pack_env = pack_knob.get();
   h->pair_packed = d.lanes * sizeof(T) <= 64 && d.ny >= 2 && (pack_env > 0 || (pack_env < 0 && bytes > FUSED_LDS_LIMIT));
   if (h->pair_packed) {
     const size_t packed = (size_t)d.nx * (d.ny - 1) * 2 * d.lanes * sizeof(T);
@@ -4994,8 +4756,9 @@ NDI_API ndi_status ndi_output_alloc(int32_t device, uint64_t bytes, uint32_t max
   ndi::DeviceGuard dg(device);
   using clk = std::chrono::steady_clock;
   const auto t0 = clk::now();
-  static const double accept_tbs = [] { const char* e = std::getenv("NDI_OUTPUT_ACCEPT_TBPS"); return e ? std::atof(e) : 6.6; }();
-  static const int tries_env = ndi::ShortKnobs::env("NDI_OUTPUT_TRIES", 0);
+  static const double accept_tbs = [] { const char* e = std::getenv("NDI_OUTPUT_ACCEPT_TBPS"); return e && *e ? std::atof(e) : 6.6; }();   // (a rate, not an integer Knob; read once)
+  static const ndi::Knob tries_knob{"NDI_OUTPUT_TRIES", 0};
+  const int tries_env = tries_knob.get();
   uint32_t tries = max_tries;
   if (tries == 0) {       // as many candidates as fit into about half of what is free, 2 .. 8
     size_t fr = 0, tot = 0;
@@ -5114,7 +4877,8 @@ NDI_API ndi_status ndi_output_free(void* p) {
   }
   ndi::DeviceGuard dg(dev);
   // keep it for the next request of this size?  (buffers of >= 1 GiB only; two at most, a third of the device's memory)
-  static const int keep_env = ndi::ShortKnobs::env("NDI_OUTPUT_KEEP", 2);
+  static const ndi::Knob keep_knob{"NDI_OUTPUT_KEEP", 2};
+  const int keep_env = keep_knob.get();
   bool kept = false;
   if (keep_env > 0 && bytes >= ((size_t)1 << 30)) {
     size_t fr = 0, tot = 0;
