@@ -252,7 +252,8 @@ typedef struct ndi_interp2d_desc {
  *  patch with t / u outside [0, 1], as the 1-D spline does.
  *  Refused before any device work, each with a message naming Bicubic and the reason: fewer than 3 points on an axis
  *  (NDI_NOT_ENOUGH_DATA); with NDI_BAD_ARG integer and f16 / bf16 element types and any boundary kind outside ndi_bc_kind
- *  (periodic ends and per-lane boundaries have no encoding here and are not provided).  NDI_PATH_AUTO and NDI_PATH_GATHER
+ *  (a periodic END has no encoding here -- a periodic AXIS is ndi_interp2d_create_bicubic_periodic, below -- and per-lane
+ *  boundaries are not provided).  NDI_PATH_AUTO and NDI_PATH_GATHER
  *  take the one evaluation kernel; NDI_PATH_BUCKETED is NDI_BAD_ARG naming the strategy, and so is
  *  ndi_interp2d_probe_ceiling.
  *  Device memory: the node table {z, zx, zy, zxy} per grid node, T[nx][ny][4][C] = four times the grid, plus the two knot
@@ -344,7 +345,50 @@ typedef struct ndi_interp2d_desc {
  *  the BUCKETED refusal, and the replica signature (the rule is not part of it, just as the boundary kinds are not).
  *  Device memory: the node table and the two knot axes; the build is a stencil that writes the table directly and keeps no
  *  grid-sized temporary beyond the uploaded z (host data), or the four uploaded arrays of the hermite call.
- * Not provided: periodic and per-lane boundaries, a different rule per axis, integrals of Bilinear or of partial
+ * Periodic axes (ndi_interp2d_create_bicubic_periodic): the same Bicubic handle built so that the surface closes on itself
+ * along x, along y or along both (longitude x latitude, angle x radius, a torus), and which wraps out-of-range queries on
+ * those axes when it extrapolates.  `periodic_axes` is a bit set: bit 0 is x, bit 1 is y; 0 builds, bit for bit, the handle
+ * ndi_interp2d_create_bicubic builds.  Numerical contract -- this project's own; every line one IEEE operation in T, in
+ * this order, nothing fused.
+ *  Build: a pass along a periodic axis is the CubicSpline coefficient build with periodic = 1 in the REFERENCE operation
+ *  order (cubic_spline.rs:480-496 on 3 knots, :498-565 otherwise), followed by the same rule
+ *                 zx[i]    = (dz + a[i]) / dx        i < nx-1
+ *                 zx[nx-1] = zx[0]                   a copy
+ *  (the cyclic system has k[nx-1] = k[0]: the rule's first row and its last row (dz - b[nx-2]) / dx are two roundings of
+ *  that one knot derivative, an ulp apart; the copy makes them one); the cross pass along a periodic y is the periodic pass on zx.  A pass along a non-periodic axis is exactly the
+ *  one above, the true not-a-knot row included, with that axis' two ends of any ndi_bc_kind.  The two `bc` entries of a
+ *  periodic axis must be {NDI_BC_NOT_A_KNOT, 0} (or bc == NULL): a periodic end has no kind.
+ *  The data must be periodic: z[0][j][c] != z[nx-1][j][c] for any j, c (along y: z[i][0][c] != z[i][ny-1][c]) is
+ *  NDI_VALUE with a message naming Bicubic and the axis -- exact equality, as in the reference (cubic_spline.rs:501-507),
+ *  so a NaN in the seam row fails it.
+ *  The seam: along the pass the last row is the first row's copy, and across it the lanes of one pass run identical
+ *  operations, so equal first and last data rows give a table that is periodic
+ *  BIT FOR BIT: zx, zy, zxy at index 0 and at index n-1 of a periodic axis are the same bits.  Partials, the jet and the
+ *  integrals read that table and nothing else, so they are seamless with it.
+ *  Evaluation, per axis (cubic_spline.rs:763-769, 805-809).  extrapolate == 0: both axes take the inclusive range test; a
+ *  periodic axis changes only the build.  extrapolate != 0: the handle WRAPS on its periodic axes -- a coordinate q outside
+ *  [k0, kn] (the axis' first and last knot) is replaced before the search, and only when it is outside, by
+ *     d = q - k0
+ *     p = kn - k0
+ *     r = fmod(d, p)
+ *     if (r < 0) r = r + |p|
+ *     qs = r + k0
+ *  and cell, t, u, hx, hy come from qs.  fl(r + k0) may land an ulp past kn: the search then clamps to the last cell with t
+ *  just over 1, as the 1-D handle does.  +-inf wraps to NaN and then fails exactly as a NaN query does (NDI_NAN_QUERY).  A
+ *  non-periodic axis of such a handle continues its end cell's patch, as above.  x is tested before y for the same query,
+ *  the lowest failing flat index wins, rows before it are written and later rows untouched; NDI_EVAL_FRESH_OUTPUT and
+ *  NDI_EVAL_ROWS_AFTER_ERROR_UNSPECIFIED are unchanged.
+ *  The periodic bits live on the handle: _clone copies them, ndi_interp2d_partial inherits them with the shared table, and
+ *  ndi_interp2d_eval, async_launch / _finish, the ring, the sharded calls and ndi_interp2d_eval_jet honour them; part k of a
+ *  jet stays, bit for bit, the separate partial handle's rows, wrapped queries included.  They are part of the replica
+ *  signature: a sharded set that mixes handles with different periodic bits is refused.  ndi_interp2d_tables is unchanged.
+ *  ndi_interp2d_antiderivative of a handle that wraps is NDI_BAD_ARG, naming the reason (the integral of a periodic surface
+ *  is not periodic; the 1-D antiderivative refuses the Periodic extrapolation mode likewise); with extrapolate == 0 the
+ *  integral handle of a periodic build is the one above.
+ *  Handles that do not wrap launch the kernel instances they always did; the wrap is a compile-time variant of the
+ *  evaluation kernels, taken once per query before the search.
+ * Not provided: periodic local rules (ndi_interp2d_create_bicubic_local / _hermite), per-lane boundaries, integrals of
+ * wrapping handles, a blocked-sweep periodic build for narrow grids, a different rule per axis, integrals of Bilinear or of partial
  * handles, partials of an integral handle, a second antiderivative, a ring / sharded / async_launch form of the four-array
  * rectangle call and of the jet call, a jet of a partial or of an integral handle, null entries in the jet's `outs` to skip
  * parts, jet orders above 2, third derivatives, a tile-grouped evaluation form, a blocked-sweep build for narrow grids,
@@ -413,6 +457,14 @@ ndi_status ndi_interp2d_create(const ndi_interp2d_desc* desc, ndi_interp2d** out
 /* The Bicubic strategy (contract above ndi_interp1d).  `bc`: four boundaries in the order x-left, x-right, y-left, y-right,
  * or NULL for NotAKnot on all four.  A new symbol; ndi_interp2d_desc keeps its layout. */
 ndi_status ndi_interp2d_create_bicubic(const ndi_interp2d_desc* desc, const ndi_boundary* bc, ndi_interp2d** out);
+/* Bicubic with periodic axes (contract above ndi_interp1d).  periodic_axes: bit 0 is x, bit 1 is y; 0 is
+ * ndi_interp2d_create_bicubic.  NDI_BAD_ARG, *out cleared first: bits outside 0 .. 3; a `bc` entry of a periodic axis other
+ * than {NDI_BC_NOT_A_KNOT, 0} (the message names Bicubic, the axis and the reason); and every refusal of
+ * ndi_interp2d_create_bicubic (element types, null arguments; NDI_NOT_ENOUGH_DATA below 3 points on an axis).  NDI_VALUE:
+ * the first and last data rows along a periodic axis differ.  A new symbol: no new enumerator, no struct change, no
+ * version change. */
+ndi_status ndi_interp2d_create_bicubic_periodic(const ndi_interp2d_desc* desc, const ndi_boundary* bc,
+                                                int32_t periodic_axes, ndi_interp2d** out);
 /* Bicubic with the node derivatives of a local rule (contract above ndi_interp1d).  rule: NDI_PCHIP or NDI_AKIMA
  * (ndi_strategy1d), the same on both axes.  Refused before any device work, *out cleared first, the message naming the
  * strategy and the reason: NDI_BAD_ARG for a null `desc` or `out`, any other rule, integer and f16 / bf16 dtypes;

@@ -103,6 +103,8 @@ SYMBOLS = {
     "ndi_interp1d_destroy": (None, [_P]),
     "ndi_interp2d_create": (C.c_int, [C.POINTER(Interp2DDesc), C.POINTER(_P)]),
     "ndi_interp2d_create_bicubic": (C.c_int, [C.POINTER(Interp2DDesc), C.POINTER(Boundary), C.POINTER(_P)]),
+    "ndi_interp2d_create_bicubic_periodic": (C.c_int, [C.POINTER(Interp2DDesc), C.POINTER(Boundary), C.c_int32,
+                                                       C.POINTER(_P)]),
     "ndi_interp2d_create_bicubic_local": (C.c_int, [C.POINTER(Interp2DDesc), C.c_int32, C.POINTER(_P)]),
     "ndi_interp2d_create_bicubic_hermite": (C.c_int, [C.POINTER(Interp2DDesc), _P, _P, _P, C.POINTER(_P)]),
     "ndi_interp2d_tables": (C.c_int, [_P, _P, _P, _P, C.c_int32]),

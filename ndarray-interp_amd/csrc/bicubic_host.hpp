@@ -13,12 +13,17 @@
 //   cross   knots y on the transposed copy of zx, end values 0       -> zxyT
 // then one pack into the node table.  Everything is launched on the NULL stream and complete when create returns; the
 // temporaries are freed before that.
+// A pass along a periodic axis (ndi_interp2d_create_bicubic_periodic) is the same temporary 1-D handle built with
+// periodic = 1 -- the reference's cyclic system, or its closed form on 3 knots -- and the cross pass along a periodic y is
+// that pass on zx: no solver of its own.  Its last row is then a copy of its first (the same knot derivative, rounded
+// twice by the rule); the lanes of a pass run identical operations, so with equal first and last data rows every table
+// has the same bits at index 0 and at index n-1 of a periodic axis.
 #pragma once
 
 // knot derivatives of the spline through `src` (n, lanes) on the device-resident knots: out (n, lanes)
 template <class T>
 static ndi_status bicubic_axis_pass(int dtype, int device, const T* knots_dev, uint64_t n, uint64_t lanes, const T* src,
-                                    const ndi_boundary& left, const ndi_boundary& right, T* out) {
+                                    const ndi_boundary& left, const ndi_boundary& right, T* out, bool periodic = false) {
   ndi_interp1d_desc d{};
   d.dtype = dtype;
   d.strategy = NDI_CUBIC_SPLINE;
@@ -32,6 +37,7 @@ static ndi_status bicubic_axis_pass(int dtype, int device, const T* knots_dev, u
   d.build_flags = NDI_BUILD_REFERENCE_ORDER | BUILD_TRUE_NOT_A_KNOT;
   d.left = left;
   d.right = right;
+  d.periodic = periodic ? 1 : 0;   // (the ends are not read then); a mismatch of the end rows comes back as NDI_VALUE
   Interp1DBase* base = nullptr;
   const ndi_status st = create1d<T>(d, &base);
   if (st != NDI_OK) return st;
@@ -50,6 +56,10 @@ static ndi_status bicubic_axis_pass(int dtype, int device, const T* knots_dev, u
   if (vec) hipLaunchKernelGGL((derivative_build_kernel<T, VN>), dim3(grid), dim3(BLOCK), 0, (hipStream_t) nullptr, D);
   else hipLaunchKernelGGL((derivative_build_kernel<T, 1>), dim3(grid), dim3(BLOCK), 0, (hipStream_t) nullptr, D);
   NDI_HIP(hipGetLastError());
+  // A periodic pass: the rule's first and last row are two roundings of the same knot derivative (the cyclic system has
+  // k[n-1] = k[0]); the last row takes the first row's bits, a copy, so the table is periodic bit for bit.
+  if (periodic)
+    NDI_HIP(hipMemcpyAsync(out + (n - 1) * lanes, out, (size_t)lanes * sizeof(T), hipMemcpyDeviceToDevice, (hipStream_t) nullptr));
   NDI_HIP(hipStreamSynchronize(nullptr));   // the temporary handle's tables are read until here
   return NDI_OK;
 }
@@ -58,10 +68,19 @@ static unsigned bicubic_copy_grid(uint64_t total) {
   return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + BLOCK - 1) / BLOCK, 1u << 20));
 }
 
+// NDI_VALUE of a periodic pass, restated for the 2-D caller: which axis, and what must be equal
+static ndi_status bicubic_periodic_mismatch(ndi_status st, const char* axis, const char* what) {
+  if (st != NDI_VALUE) return st;
+  return fail(NDI_VALUE, "Bicubic: the %s axis is periodic, so the first and the last %s must be equal, element for element "
+              "(exact equality, NaN included)", axis, what);
+}
+
 template <class T>
-static ndi_status create2d_bicubic(const ndi_interp2d_desc& d, const ndi_boundary bc[4], Interp2DBase** out) {
+static ndi_status create2d_bicubic(const ndi_interp2d_desc& d, const ndi_boundary bc[4], Interp2DBase** out,
+                                   int periodic_axes = 0) {
   DeviceGuard dg(d.device);
   Range rg("ndi_interp2d_create_bicubic");
+  const bool per_x = (periodic_axes & 1) != 0, per_y = (periodic_axes & 2) != 0;
   std::unique_ptr<Interp2DImpl<T>> h(new Interp2DImpl<T>());
   h->dtype = d.dtype;
   h->device = d.device;
@@ -70,6 +89,7 @@ static ndi_status create2d_bicubic(const ndi_interp2d_desc& d, const ndi_boundar
   h->ny = d.ny;
   h->lanes = d.lanes;
   h->bicubic = true;
+  h->periodic_axes = periodic_axes;
   std::vector<T> x = d.x ? fetch_axis<T>(d.x, d.x_len, d.memspace) : default_axis<T>(d.nx);
   std::vector<T> y = d.y ? fetch_axis<T>(d.y, d.y_len, d.memspace) : default_axis<T>(d.ny);
   if (const ndi_status st = check_desc_2d(d, x.data(), y.data()); st != NDI_OK) return st;
@@ -88,16 +108,16 @@ static ndi_status create2d_bicubic(const ndi_interp2d_desc& d, const ndi_boundar
   hipStream_t s0 = nullptr;
   DevBuf zx, zyT, zxyT;
   zx.reserve(bytes);
-  ndi_status st = bicubic_axis_pass<T>(d.dtype, d.device, h->px.view.lv0, nx, ny * L, z, bc[0], bc[1], zx.as<T>());
-  if (st != NDI_OK) return st;
+  ndi_status st = bicubic_axis_pass<T>(d.dtype, d.device, h->px.view.lv0, nx, ny * L, z, bc[0], bc[1], zx.as<T>(), per_x);
+  if (st != NDI_OK) return bicubic_periodic_mismatch(st, "x", "data row (z[0][j][c] and z[nx-1][j][c])");
   {
     DevBuf tr;                               // the transposed copy the y-passes read: z, then zx
     tr.reserve(bytes);
     zyT.reserve(bytes);
     hipLaunchKernelGGL(transpose_nodes_kernel<T>, dim3(g), dim3(BLOCK), 0, s0, z, tr.as<T>(), nx, ny, L);
     NDI_HIP(hipGetLastError());
-    st = bicubic_axis_pass<T>(d.dtype, d.device, h->py.view.lv0, ny, nx * L, tr.as<T>(), bc[2], bc[3], zyT.as<T>());
-    if (st != NDI_OK) return st;
+    st = bicubic_axis_pass<T>(d.dtype, d.device, h->py.view.lv0, ny, nx * L, tr.as<T>(), bc[2], bc[3], zyT.as<T>(), per_y);
+    if (st != NDI_OK) return bicubic_periodic_mismatch(st, "y", "data column (z[i][0][c] and z[i][ny-1][c])");
     zxyT.reserve(bytes);
     hipLaunchKernelGGL(transpose_nodes_kernel<T>, dim3(g), dim3(BLOCK), 0, s0, (const T*)zx.as<T>(), tr.as<T>(), nx, ny, L);
     NDI_HIP(hipGetLastError());
@@ -105,8 +125,8 @@ static ndi_status create2d_bicubic(const ndi_interp2d_desc& d, const ndi_boundar
     ndi_boundary cl = bc[2], cr = bc[3];
     cl.value = 0.0;
     cr.value = 0.0;
-    st = bicubic_axis_pass<T>(d.dtype, d.device, h->py.view.lv0, ny, nx * L, tr.as<T>(), cl, cr, zxyT.as<T>());
-    if (st != NDI_OK) return st;
+    st = bicubic_axis_pass<T>(d.dtype, d.device, h->py.view.lv0, ny, nx * L, tr.as<T>(), cl, cr, zxyT.as<T>(), per_y);
+    if (st != NDI_OK) return bicubic_periodic_mismatch(st, "y", "column of zx (a NaN among the x-derivatives)");
   }
   h->table = std::make_shared<DevBuf>();
   h->table->reserve(4 * bytes);
@@ -146,6 +166,7 @@ static void bicubic_launch_eval(const Interp2DImpl<T>& h, hipStream_t s, StatusB
   A.vchunk = (uint32_t)vchunk;
   const unsigned gy = (unsigned)((A.lv + vchunk - 1) / vchunk);
   A.mode = h.mode;
+  A.wrap = h.wrap_axes();
   A.first_fail = &st->first_fail[0];
   A.check = check ? 1 : 0;
   const size_t strips = (size_t)(TB / 64) * 64 * (sizeof(unsigned long long) + 4 * sizeof(T));
@@ -157,14 +178,19 @@ static void bicubic_launch_eval(const Interp2DImpl<T>& h, hipStream_t s, StatusB
                                                                         std::max<uint64_t>(1, (uint64_t)cu_count() * wgs_per_cu(lds, TB) * 4 / gy)));
   if (std::getenv("NDI_TRACE_PLAN"))
     std::fprintf(stderr, "[ndi plan] bicubic vec=%d lv=%llu klds=%d grid=%u x %u lds=%zu prepass=%d guess=%d,%d levels=%d,%d "
-                 "nu=%d,%d\n",
+                 "nu=%d,%d%s\n",
                  (int)vec, (unsigned long long)A.lv, (int)klds, gx, gy, lds, check ? 0 : 1, A.px.guess, A.py.guess,
-                 A.px.levels, A.py.levels, h.nu_x, h.nu_y);
+                 A.px.levels, A.py.levels, h.nu_x, h.nu_y,
+                 A.wrap == 0 ? "" : A.wrap == 1 ? " wrap=x" : A.wrap == 2 ? " wrap=y" : " wrap=xy");   // (the line as it was, else)
   // the orders were checked when the handle was made (Interp2DImpl::partial): 0 .. 2 each
   const bool known = pick<0, 1, 2, 3, 4, 5, 6, 7, 8>(h.nu_x * 3 + h.nu_y, [&](auto nu_) {
     constexpr int NX = nu_ / 3, NY = nu_ % 3;
-    bicubic_pick_form<T>(vec, klds, [&](auto vec_, auto kl_) {
-      launch_lds<T>(eval_bicubic_kernel<T, vec_, kl_, TB, NX, NY>, LDS_STAGE_LIMIT, s, PC_EVAL, dim3(gx, gy), dim3(TB), lds, A);
+    // a handle that wraps takes the WRAP variant; every other handle the instance it always took
+    pick_bool(A.wrap != 0, [&](auto wrap_) {
+      bicubic_pick_form<T>(vec, klds, [&](auto vec_, auto kl_) {
+        launch_lds<T>(eval_bicubic_kernel<T, vec_, kl_, TB, NX, NY, wrap_>, LDS_STAGE_LIMIT, s, PC_EVAL, dim3(gx, gy), dim3(TB),
+                      lds, A);
+      });
     });
   });
   if (!known) throw HipFailure{hipErrorInvalidValue, "bicubic_launch_eval: partial orders outside 0 .. 2", __LINE__};

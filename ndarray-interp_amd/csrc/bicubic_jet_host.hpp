@@ -34,6 +34,7 @@ static void bicubic_jet_launch(const Interp2DImpl<T>& h, int order, hipStream_t 
   A.vchunk = (uint32_t)vchunk;
   const unsigned gy = (unsigned)((A.lv + vchunk - 1) / vchunk);
   A.mode = h.mode;
+  A.wrap = h.wrap_axes();
   A.first_fail = &st->first_fail[0];
   A.check = check ? 1 : 0;
   const size_t strips = (size_t)(TB / 64) * 64 * (sizeof(unsigned long long) + 4 * sizeof(T));
@@ -48,7 +49,11 @@ static void bicubic_jet_launch(const Interp2DImpl<T>& h, int order, hipStream_t 
   pick_or<2, 1>(order, [&](auto ord_) {
     constexpr int ORD = ord_;
     bicubic_pick_form<T>(vec, klds, [&](auto vec_, auto kl_) {
-      launch_lds<T>(eval_bicubic_jet_kernel<T, vec_, kl_, TB, ORD>, LDS_STAGE_LIMIT, s, PC_EVAL, dim3(gx, gy), dim3(TB), lds, A);
+      // (a handle that wraps: the wrap kernel, as bicubic_launch_eval's WRAP variant)
+      if (A.wrap != 0)
+        launch_lds<T>(eval_bicubic_jet_wrap_kernel<T, vec_, kl_, TB, ORD>, LDS_STAGE_LIMIT, s, PC_EVAL, dim3(gx, gy), dim3(TB), lds, A);
+      else
+        launch_lds<T>(eval_bicubic_jet_kernel<T, vec_, kl_, TB, ORD>, LDS_STAGE_LIMIT, s, PC_EVAL, dim3(gx, gy), dim3(TB), lds, A);
     });
   });
 }

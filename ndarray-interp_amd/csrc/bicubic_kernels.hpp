@@ -20,6 +20,10 @@
 //                               partial derivative the kernel evaluates (ndi_interp2d_partial): the four forms along y
 //                               are H_NUY, the one along x is H_NUX (hermite_nu); (0, 0) is the surface itself and
 //                               compiles to the code it was before the orders existed.  Nothing else differs.
+//                               WRAP (a further parameter, false by default): the variant a handle launches that wraps
+//                               on a periodic axis (ndi_interp2d_create_bicubic_periodic with extrapolate): the per-axis
+//                               range test and the wrap of bicubic_wrap_query, once per query, before the search.  With
+//                               WRAP == false none of it is compiled and the instances are the code they were.
 //
 // Numerical contract (include/ndinterp.h, ndi_interp2d_create_bicubic): every line one IEEE operation in T, in the stated
 // order, nothing fused (-ffp-contract=off), so rows are bit-identical to the numpy restatement (tests/bicubic_ref.py).
@@ -82,9 +86,35 @@ struct BicubicArgs {
   uint32_t lv_magic;       // ceil(2^32 / lv) for 2 <= lv < 64
   uint32_t vchunk;         // vectors of a row per blockIdx.y (a multiple of 64; >= lv when gridDim.y == 1)
   int mode;
+  int wrap;                // WRAP variants: the axes that wrap (bit 0: x, bit 1: y); sits in the padding after `mode`
   unsigned long long* first_fail;   // [2]: x, y (range_check_kernel, or this kernel when `check`)
   int check;                        // fresh output: the kernel's own range test, no pre-pass
 };
+
+// A coordinate of a wrapping handle (a periodic axis of a handle built with extrapolate; the other axis of such a handle
+// passes `wraps == false`).  Out of range on a wrapping axis: cubic_spline.rs:805-809, one IEEE operation in T per line --
+//   d = q - k0;  p = kn - k0;  r = fmod(d, p);  if (r < 0) r = r + |p|;  qs = r + k0
+// (rem_euclid_t), in range: the coordinate itself.  +-inf wraps to NaN.  Returns the coordinate the search and t are formed
+// from; a NaN result is the only failure of such a handle (lane_query_fails' test of EX_PERIODIC / EX_YES).
+template <class T>
+__device__ __forceinline__ T bicubic_wrap_query(T q, T k0, T kn, bool wraps) {
+  const bool inr = (k0 <= q) && (q <= kn);
+  return (wraps && !inr) ? rem_euclid_t(q - k0, kn - k0) + k0 : q;
+}
+
+// The range pre-pass of a wrapping handle into a caller-owned buffer: range_check_kernel's geometry and first-error
+// semantics, each axis by its own rule -- finite after the wrap on a wrapping axis, not NaN on the other.
+template <class T>
+__global__ __launch_bounds__(BLOCK) void bicubic_wrap_check_kernel(const T* qx, const T* qy, uint64_t nq, T x0, T xn, T y0, T yn,
+                                                                   int wrap, unsigned long long* first_fail) {
+  const uint64_t step = (uint64_t)gridDim.x * BLOCK;
+  for (uint64_t qi = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; qi < nq; qi += step) {
+    const T xs = bicubic_wrap_query<T>(qx[qi], x0, xn, (wrap & 1) != 0);
+    const T ys = bicubic_wrap_query<T>(qy[qi], y0, yn, (wrap & 2) != 0);
+    if (!(xs == xs)) atomicMin(&first_fail[0], (unsigned long long)qi);
+    if (!(ys == ys)) atomicMin(&first_fail[1], (unsigned long long)qi);
+  }
+}
 
 // The cubic Hermite form of cubic_spline.rs:824-828 on end values pl, pr and end derivatives kl, kr over a spacing h:
 //   d = pr - pl;  a = kl h - d;  b = d - kr h;  (1-s) pl + s pr + s (1-s) (a (1-s) + b s)
@@ -119,7 +149,7 @@ __device__ __forceinline__ V hermite_nu(V pl, V pr, V kl, V kr, T h, T s, T c0, 
   }
 }
 
-template <class T, int VEC, bool KLDS, int TB, int NUX = 0, int NUY = 0>
+template <class T, int VEC, bool KLDS, int TB, int NUX = 0, int NUY = 0, bool WRAP = false>
 __global__ __launch_bounds__(TB) void eval_bicubic_kernel(BicubicArgs<T> A) {
   using V = typename VecT<T, VEC>::type;
   using PTR = typename std::conditional<KLDS, lds_ptr<T>, const T*>::type;
@@ -167,8 +197,14 @@ __global__ __launch_bounds__(TB) void eval_bicubic_kernel(BicubicArgs<T> A) {
     {
       const uint64_t p = base + lane;
       const bool in = p < limit;
-      const T x = in ? A.qx[p] : x0, y = in ? A.qy[p] : y0;
-      if (A.check && in && blockIdx.y == 0) lane_check2<T>(A.first_fail, p, x, y, x0, xn, y0, yn, A.mode);   // fresh output
+      T x = in ? A.qx[p] : x0, y = in ? A.qy[p] : y0;
+      if constexpr (WRAP) {                   // once per query, before the search; the test is on the wrapped coordinate
+        x = bicubic_wrap_query<T>(x, x0, xn, (A.wrap & 1) != 0);
+        y = bicubic_wrap_query<T>(y, y0, yn, (A.wrap & 2) != 0);
+        if (A.check && in && blockIdx.y == 0) lane_check2<T>(A.first_fail, p, x, y, x0, xn, y0, yn, (int)EX_YES);
+      } else {
+        if (A.check && in && blockIdx.y == 0) lane_check2<T>(A.first_fail, p, x, y, x0, xn, y0, yn, A.mode);   // fresh output
+      }
       const uint32_t xi = locate_index<T, PTR>(PX, x0, xn, x, lane);   // all 64 lanes take part
       const uint32_t yi = locate_index<T, PTR>(PY, y0, yn, y, lane);
       const T x1 = PX.lv0[xi], hx = PX.lv0[xi + 1] - x1, y1 = PY.lv0[yi], hy = PY.lv0[yi + 1] - y1;

@@ -143,7 +143,7 @@ struct FloatEngine {
   // plans always pre-check and pass false.)
   bool range_prepass(hipStream_t s, Scratch& sc, Queries<T> q, uint64_t nq, bool in_kernel) {
     g_last_path.store(NDI_PATH_GATHER);
-    if (!in_kernel) launch_range_check(s, sc.status.as<StatusBlock>(), q, nq);
+    if (!in_kernel) self().launch_range_check(s, sc.status.as<StatusBlock>(), q, nq);   // (a family may have its own test)
     return in_kernel;
   }
 
@@ -153,7 +153,7 @@ struct FloatEngine {
   void enqueue_prepass(hipStream_t s, Workspace& ws, Queries<T> q, uint64_t nq) {
     ws.ensure_status();
     reset_status(ws.status.p, s);
-    launch_range_check(s, ws.status.as<StatusBlock>(), q, nq);
+    self().launch_range_check(s, ws.status.as<StatusBlock>(), q, nq);
     NDI_HIP(hipMemcpyAsync(ws.host_status, ws.status.p, sizeof(StatusBlock), hipMemcpyDeviceToHost, s));
   }
 

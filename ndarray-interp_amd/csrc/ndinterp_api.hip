@@ -2413,6 +2413,10 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
   // partial-derivative handles (ndi_interp2d_partial), which only read it: freed with the last of them, in any order.
   std::shared_ptr<DevBuf> table;
   int nu_x = 0, nu_y = 0;     // Bicubic: the orders of the partial derivative this handle evaluates ((0, 0): the surface)
+  // Bicubic: the periodic axes of the build (ndi_interp2d_create_bicubic_periodic; bit 0: x, bit 1: y).  The handle WRAPS
+  // on such an axis when it extrapolates: an out-of-range coordinate is taken modulo the period before the search.
+  int periodic_axes = 0;
+  int wrap_axes() const { return mode != EX_NO ? periodic_axes : 0; }
   DevBuf itable;              // integral handles: the prefix records T[nx][ny][5][lanes] ({PP, Qz, Qzy, Pz, Pzx}), owned
   bool pair_packed = false;   // data holds the pair-packed layout (pack_pairs_kernel)
   SpaceSet spaces;
@@ -2505,7 +2509,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     // (the strategy, the partial orders and the integral bit: no Bilinear / Bicubic mix, no surface beside its partial or
     // its integral, no two partials)
     const uint64_t f[3] = {nx, ny, (uint64_t)mode | ((uint64_t)bicubic << 8) | ((uint64_t)nu_x << 16) | ((uint64_t)nu_y << 24) |
-                                       ((uint64_t)integral << 32)};
+                                       ((uint64_t)integral << 32) | ((uint64_t)periodic_axes << 40)};
     return fnv1a(h, f, sizeof(f));
   }
   ndi_status tables(void* zx, void* zy, void* zxy, int memspace) override {
@@ -3191,6 +3195,19 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     lim[0] = px.host_knots.front(); lim[1] = px.host_knots.back();
     lim[2] = py.host_knots.front(); lim[3] = py.host_knots.back();
   }
+  // The range pre-pass: the engine's (one mode for both axes), but for a Bicubic handle that wraps -- each axis by its own
+  // rule (bicubic_wrap_check_kernel).
+  void launch_range_check(hipStream_t s, StatusBlock* st, Queries<T> q, uint64_t nq) {
+    if (wrap_axes() == 0) return FloatEngine<T, Interp2DImpl<T>>::launch_range_check(s, st, q, nq);
+    T lim[4];
+    range_limits(lim);
+    const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
+    ProfScope ps(s, PC_LOCATE);
+    hipLaunchKernelGGL(bicubic_wrap_check_kernel<T>, dim3(g), dim3(BLOCK), 0, s, q.a, q.b, nq, lim[0], lim[1], lim[2], lim[3],
+                       wrap_axes(), &st->first_fail[0]);
+    NDI_HIP(hipGetLastError());
+    ps.done();
+  }
   Plan2 prep(hipStream_t s, Scratch& sc, Queries<T> q, uint64_t nq, T* out, uint64_t out_stride, int path,
              bool beside_eval = false, int flags = 0) {
     return prep(s, sc, q.a, q.b, nq, out, out_stride, path, beside_eval, flags);
@@ -3256,6 +3273,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     h->py.upload(py.host_knots.data(), ny);
     if (bicubic) {   // the node table as it is: no rebuild; a replica owns its copy and keeps the partial orders
       h->nu_x = nu_x; h->nu_y = nu_y;
+      h->periodic_axes = periodic_axes;
       h->table = std::make_shared<DevBuf>();
       h->table->reserve(table->bytes);
       copy_across_devices(h->table->p, dev, table->p, device, table->bytes);
@@ -3297,6 +3315,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     h->mode = mode; h->nx = nx; h->ny = ny;
     h->bicubic = true;
     h->nu_x = (int)tx; h->nu_y = (int)ty;
+    h->periodic_axes = periodic_axes;   // the table is shared: so are its periodic axes, and the wrap with them
     h->px.upload(px.host_knots.data(), nx);
     h->py.upload(py.host_knots.data(), ny);
     h->table = table;
@@ -3314,12 +3333,17 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     if (nu_x != 0 || nu_y != 0)
       return fail(NDI_BAD_ARG, "Bicubic: a partial-derivative handle (orders (%d, %d)) has no antiderivative handle: the "
                   "integral of a partial is not provided (ndi_interp2d_antiderivative takes the surface handle)", nu_x, nu_y);
+    if (wrap_axes() != 0)
+      return fail(NDI_BAD_ARG, "Bicubic: this handle wraps queries on %s (a periodic axis with extrapolate): the integral of a "
+                  "periodic surface is not periodic, and the antiderivative of a wrapping handle is not provided (build "
+                  "with extrapolate = 0)", wrap_axes() == 3 ? "x and y" : wrap_axes() == 1 ? "x" : "y");
     DeviceGuard dg(device);
     std::unique_ptr<Interp2DImpl<T>> h(new Interp2DImpl<T>());
     h->dtype = dtype; h->device = device; h->lanes = lanes;
     h->mode = mode; h->nx = nx; h->ny = ny;
     h->bicubic = true;
     h->integral = true;
+    h->periodic_axes = periodic_axes;   // (it never wraps -- refused above; kept for the replica signature)
     h->px.upload(px.host_knots.data(), nx);
     h->py.upload(py.host_knots.data(), ny);
     h->table = table;
@@ -4056,8 +4080,10 @@ NDI_API ndi_status ndi_interp2d_create(const ndi_interp2d_desc* desc, ndi_interp
   NDI_CATCH
 }
 
-// Every refusal is decided before any device work, so it behaves the same everywhere.
-NDI_API ndi_status ndi_interp2d_create_bicubic(const ndi_interp2d_desc* desc, const ndi_boundary* bc, ndi_interp2d** out) {
+// Every refusal is decided before any device work, so it behaves the same everywhere.  `periodic_axes` < 0: the plain
+// entry point (no periodic argument to check).
+static ndi_status create_bicubic_spline(const ndi_interp2d_desc* desc, const ndi_boundary* bc, int periodic_axes,
+                                        ndi_interp2d** out) {
   if (!desc || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
   *out = nullptr;
   if (desc->dtype < NDI_F32 || desc->dtype > NDI_BF16) return ndi::fail(NDI_BAD_ARG, "unknown dtype");
@@ -4070,6 +4096,13 @@ NDI_API ndi_status ndi_interp2d_create_bicubic(const ndi_interp2d_desc* desc, co
   static const char* const END[4] = {"x-left", "x-right", "y-left", "y-right"};
   for (int k = 0; bc && k < 4; ++k) {
     b4[k] = bc[k];
+    if (periodic_axes > 0 && ((periodic_axes >> (k / 2)) & 1)) {
+      if (bc[k].kind != NDI_BC_NOT_A_KNOT || bc[k].value != 0.0)
+        return ndi::fail(NDI_BAD_ARG, "Bicubic: the %s axis is periodic and takes no boundary condition: a periodic end has no "
+                         "kind, its bc entries must be {NDI_BC_NOT_A_KNOT, 0} (%s end: kind %d, value %g)", k < 2 ? "x" : "y",
+                         END[k], (int)bc[k].kind, bc[k].value);
+      continue;
+    }
     if (bc[k].kind < NDI_BC_NOT_A_KNOT || bc[k].kind > NDI_BC_SECOND_DERIV)
       return ndi::fail(NDI_BAD_ARG, "Bicubic takes one non-periodic boundary kind with a scalar value per end (ndi_bc_kind); "
                        "periodic and per-lane boundaries are not provided (%s end: kind %d)", END[k], (int)bc[k].kind);
@@ -4084,13 +4117,27 @@ NDI_API ndi_status ndi_interp2d_create_bicubic(const ndi_interp2d_desc* desc, co
   ndi_status ds = need_device(desc->device);
   if (ds != NDI_OK) return ds;
   NDI_TRY
+  const int per = periodic_axes > 0 ? periodic_axes : 0;
   ndi::Interp2DBase* impl = nullptr;
-  ndi_status st = desc->dtype == NDI_F32 ? ndi::create2d_bicubic<float>(*desc, b4, &impl)
-                                         : ndi::create2d_bicubic<double>(*desc, b4, &impl);
+  ndi_status st = desc->dtype == NDI_F32 ? ndi::create2d_bicubic<float>(*desc, b4, &impl, per)
+                                         : ndi::create2d_bicubic<double>(*desc, b4, &impl, per);
   if (st != NDI_OK) return st;
   *out = new ndi_interp2d{impl};
   return ndi::bounds_verdict(NDI_OK, impl->device);
   NDI_CATCH
+}
+
+NDI_API ndi_status ndi_interp2d_create_bicubic(const ndi_interp2d_desc* desc, const ndi_boundary* bc, ndi_interp2d** out) {
+  return create_bicubic_spline(desc, bc, -1, out);
+}
+
+// Bicubic with periodic axes (bit 0 of periodic_axes: x, bit 1: y); with no bit set it is the call above.
+NDI_API ndi_status ndi_interp2d_create_bicubic_periodic(const ndi_interp2d_desc* desc, const ndi_boundary* bc,
+                                                        int32_t periodic_axes, ndi_interp2d** out) {
+  if (out) *out = nullptr;
+  if (periodic_axes < 0 || periodic_axes > 3)
+    return ndi::fail(NDI_BAD_ARG, "Bicubic: periodic_axes is a bit set of 1 (x) and 2 (y): 0 .. 3, got %d", (int)periodic_axes);
+  return create_bicubic_spline(desc, bc, periodic_axes, out);
 }
 
 // The Bicubic handles of a local rule (Pchip, Akima) and of caller-given node derivatives: bicubic_local_host.hpp.

@@ -321,6 +321,7 @@ class Bicubic(Interp2DStrategyBuilder, _DeviceStrategy2D):
         super().__init__()
         self._bc_x = self._bc_y = RowBoundary.NotAKnot
         self._given = None
+        self._periodic = 0      # bit 0: x, bit 1: y (ndi_interp2d_create_bicubic_periodic)
 
     @staticmethod
     def new() -> "Bicubic":
@@ -367,7 +368,8 @@ class Bicubic(Interp2DStrategyBuilder, _DeviceStrategy2D):
         if isinstance(bc, BoundaryCondition) and bc.tag in ("NotAKnot", "Natural", "Clamped"):
             return getattr(RowBoundary, bc.tag)
         if isinstance(bc, BoundaryCondition) and bc.tag == "Periodic":
-            raise TypeError("Bicubic has no periodic ends: its boundaries are one non-periodic kind per end")
+            raise TypeError("Bicubic has no periodic ends: its boundaries are one non-periodic kind per end; a periodic "
+                            "axis is Bicubic.new().periodic_x() / .periodic_y() (both: .periodic())")
         if isinstance(bc, BoundaryCondition) and bc.tag == "Individual":
             raise TypeError("Bicubic takes no per-lane (Individual) boundaries: one kind and scalar value per end "
                             "(RowBoundary.Mixed(left, right) gives an axis two different ends)")
@@ -389,12 +391,44 @@ class Bicubic(Interp2DStrategyBuilder, _DeviceStrategy2D):
         self._bc_y = self._ends(bc)
         return self
 
+    def periodic_x(self) -> "Bicubic":
+        """The x axis is periodic with period x[-1] - x[0]: the build closes the spline along x on itself (the first and
+        the last data row must be equal, exactly), and with `extrapolate(True)` an x outside the range is wrapped into it
+        instead of continuing the end patch.  The axis takes no boundary condition."""
+        self._no_ends()
+        self._periodic |= 1
+        return self
+
+    def periodic_y(self) -> "Bicubic":
+        """`periodic_x` for the y axis."""
+        self._no_ends()
+        self._periodic |= 2
+        return self
+
+    def periodic(self) -> "Bicubic":
+        """Both axes periodic: a torus."""
+        return self.periodic_x().periodic_y()
+
+    @property
+    def wraps(self) -> int:
+        """The axes on which this strategy wraps out-of-range queries (bit 0: x, bit 1: y): the periodic axes of a strategy
+        that extrapolates."""
+        return self._periodic if self._extrapolate else 0
+
+    @staticmethod
+    def _is_default(ends) -> bool:
+        return all(int(e.kind) == _capi.BC_NOT_A_KNOT and float(e.value) == 0.0 for e in (ends.left, ends.right))
+
     def build(self, x, y, data, device=None):
         dt = np_dtype_of(data)
         if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
             got = "bfloat16" if is_bf16(dt) else dt
             raise TypeError(f"Bicubic covers float32/float64 only, got {got}: a spline divides (integer data takes "
                             "Bilinear) and the spline build has no half-precision form")
+        for bit, name, ends in ((1, "x", self._bc_x), (2, "y", self._bc_y)):
+            if self._periodic & bit and not self._is_default(ends):
+                raise TypeError(f"Bicubic: the {name} axis is periodic and takes no boundary condition: a periodic end has "
+                                f"no kind (boundary_{name} / boundary gave it one)")
         if self.rule in ("pchip", "akima"):
             code = _capi.PCHIP if self.rule == "pchip" else _capi.AKIMA
             return self._create(x, y, data, device,
@@ -403,6 +437,10 @@ class Bicubic(Interp2DStrategyBuilder, _DeviceStrategy2D):
             return self._create_hermite(x, y, data, device)
         ends = (self._bc_x.left, self._bc_x.right, self._bc_y.left, self._bc_y.right)
         bc = (_capi.Boundary * 4)(*[_capi.Boundary(int(e.kind), float(e.value)) for e in ends])
+        if self._periodic:
+            per = self._periodic
+            return self._create(x, y, data, device,
+                                lambda d, h: _capi.lib().ndi_interp2d_create_bicubic_periodic(C.byref(d), bc, per, C.byref(h)))
         return self._create(x, y, data, device,
                             lambda d, h: _capi.lib().ndi_interp2d_create_bicubic(C.byref(d), bc, C.byref(h)))
 
@@ -480,6 +518,11 @@ class Bicubic(Interp2DStrategyBuilder, _DeviceStrategy2D):
         if self.orders != (0, 0):
             raise ValueError(f"Bicubic.antiderivative: a partial-derivative strategy (orders {self.orders}) has no "
                              "antiderivative; ask the surface's strategy")
+        if self.wraps:
+            axes = " and ".join(n for b, n in ((1, "x"), (2, "y")) if self.wraps & b)
+            raise TypeError(f"Bicubic.antiderivative: this strategy wraps queries on {axes} (a periodic axis with "
+                            "extrapolate): the integral of a periodic surface is not periodic, and the antiderivative of a "
+                            "wrapping strategy is not provided (build without extrapolate)")
         if self._h is None:
             from .errors import DeviceError
             raise DeviceError("Bicubic.antiderivative needs a built strategy: the node table lives on the device and the "

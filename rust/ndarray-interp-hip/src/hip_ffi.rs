@@ -231,6 +231,12 @@ extern "C" {
         bc: *const ndi_boundary,
         out: *mut *mut ndi_interp2d,
     ) -> i32;
+    pub fn ndi_interp2d_create_bicubic_periodic(
+        desc: *const ndi_interp2d_desc,
+        bc: *const ndi_boundary,
+        periodic_axes: i32,
+        out: *mut *mut ndi_interp2d,
+    ) -> i32;
     pub fn ndi_interp2d_create_bicubic_local(desc: *const ndi_interp2d_desc, rule: i32, out: *mut *mut ndi_interp2d) -> i32;
     pub fn ndi_interp2d_create_bicubic_hermite(
         desc: *const ndi_interp2d_desc,
