@@ -53,7 +53,7 @@ static void antideriv_prefix_build(int device, uint64_t n, uint64_t lanes, const
     else hipLaunchKernelGGL((antideriv_local_lanes_kernel<T, 1, LINEAR>), dim3(grid), dim3(BLOCK), 0, s0, A);
   }
   NDI_HIP(hipGetLastError());
-  if (std::getenv("NDI_TRACE_PLAN"))   // grid: the local kernel's; kb / vec_local: 0 on the local kernel that has no such field
+  if (trace_plan())   // grid: the local kernel's; kb / vec_local: 0 on the local kernel that has no such field
     std::fprintf(stderr, "[ndi plan] antiderivative build linear=%d staged=%d kb=%u vec=%d vec_local=%d nblk=%llu single=%d fuse=%d "
                  "grid=%u\n", (int)LINEAR, (int)staged, A.kb, (int)vec, (int)vec_local, (unsigned long long)A.nblk, (int)A.single,
                  (int)(!A.single && fuse), local_grid);
@@ -184,7 +184,7 @@ struct AntiderivImpl final : Interp1DBase, FloatEngine<T, AntiderivImpl<T>> {
     if (vec_ok && LV >= (uint64_t)BLOCK) {   // long rows
       const uint64_t segs = (LV + BLOCK - 1) / BLOCK;
       const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nq, 65536)), (unsigned)std::min<uint64_t>(segs, 64));
-      if (std::getenv("NDI_TRACE_PLAN"))
+      if (trace_plan())
         std::fprintf(stderr, "[ndi plan] antiderivative eval form=rows linear=%d pair=%d vec=1 lv=%llu tile_q=0 grid=%u x %u\n",
                      (int)linear, (int)pair, (unsigned long long)LV, grid.x, grid.y);
       pick_bool(linear, [&](auto lin_) {
@@ -196,7 +196,7 @@ struct AntiderivImpl final : Interp1DBase, FloatEngine<T, AntiderivImpl<T>> {
     const uint32_t tile_q = (uint32_t)std::max<uint64_t>(1, 1024 / std::max<uint64_t>(LV, 1));
     const uint64_t ntiles = (nq + tile_q - 1) / tile_q;
     const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ntiles, 16384));
-    if (std::getenv("NDI_TRACE_PLAN"))
+    if (trace_plan())
       std::fprintf(stderr, "[ndi plan] antiderivative eval form=flat linear=%d pair=%d vec=%d lv=%llu tile_q=%u grid=%u x 1\n",
                    (int)linear, (int)pair, (int)vec_ok, (unsigned long long)LV, tile_q, gx);
     ProfScope ps(s, PC_EVAL);

@@ -176,7 +176,7 @@ static void bicubic_launch_eval(const Interp2DImpl<T>& h, hipStream_t s, StatusB
   // staging the axes is the fixed cost of a workgroup: no more workgroups than a few per resident slot
   const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + TB - 1) / TB,
                                                                         std::max<uint64_t>(1, (uint64_t)cu_count() * wgs_per_cu(lds, TB) * 4 / gy)));
-  if (std::getenv("NDI_TRACE_PLAN"))
+  if (trace_plan())
     std::fprintf(stderr, "[ndi plan] bicubic vec=%d lv=%llu klds=%d grid=%u x %u lds=%zu prepass=%d guess=%d,%d levels=%d,%d "
                  "nu=%d,%d%s\n",
                  (int)vec, (unsigned long long)A.lv, (int)klds, gx, gy, lds, check ? 0 : 1, A.px.guess, A.py.guess,

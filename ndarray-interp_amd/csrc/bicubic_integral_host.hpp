@@ -33,7 +33,7 @@ static void bicubic_integral_build(const Interp2DImpl<T>& src, Interp2DImpl<T>& 
   const int dev = src.device;
   const unsigned g = bicubic_copy_grid(total);
   hipStream_t s0 = nullptr;
-  if (std::getenv("NDI_TRACE_PLAN"))
+  if (trace_plan())
     std::fprintf(stderr, "[ndi plan] bicubic integral build nx=%llu ny=%llu lanes=%llu xview=%llu yview=%llu passes=5\n",
                  (unsigned long long)nx, (unsigned long long)ny, (unsigned long long)L, (unsigned long long)(ny * L),
                  (unsigned long long)(nx * L));
@@ -103,7 +103,7 @@ static void bicubic_integral_launch_eval(const Interp2DImpl<T>& h, hipStream_t s
   const size_t lds = (klds ? knots : 0) + strips;
   const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + TB - 1) / TB,
                                                                         std::max<uint64_t>(1, (uint64_t)cu_count() * wgs_per_cu(lds, TB) * 4 / gy)));
-  if (std::getenv("NDI_TRACE_PLAN"))
+  if (trace_plan())
     std::fprintf(stderr, "[ndi plan] bicubic integral rect=%d vec=%d lv=%llu klds=%d grid=%u x %u lds=%zu prepass=%d\n",
                  (int)rect, (int)vec, (unsigned long long)A.lv, (int)klds, gx, gy, lds, check ? 0 : 1);
   pick_bool(rect, [&](auto rect_) {

@@ -43,7 +43,7 @@ static void bicubic_jet_launch(const Interp2DImpl<T>& h, int order, hipStream_t 
   const size_t lds = (klds ? knots : 0) + strips;
   const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + TB - 1) / TB,
                                                                         std::max<uint64_t>(1, (uint64_t)cu_count() * wgs_per_cu(lds, TB) * 4 / gy)));
-  if (std::getenv("NDI_TRACE_PLAN"))
+  if (trace_plan())
     std::fprintf(stderr, "[ndi plan] bicubic_jet order=%d vec=%d lv=%llu klds=%d grid=%u x %u lds=%zu prepass=%d\n", order,
                  (int)vec, (unsigned long long)A.lv, (int)klds, gx, gy, lds, check ? 0 : 1);
   pick_or<2, 1>(order, [&](auto ord_) {

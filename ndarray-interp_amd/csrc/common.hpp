@@ -68,6 +68,10 @@ inline void pick_bool(bool v, F&& f) {
   else f(std::false_type{});
 }
 
+// NDI_TRACE_PLAN: every plan prints its `[ndi plan]` line to stderr.  A getenv per call: the tests switch the variable inside
+// a running process.
+inline bool trace_plan() { return std::getenv("NDI_TRACE_PLAN") != nullptr; }
+
 // An integer tuning variable of the environment (the table of all of them: DESIGN.md 8a).  Unset or empty: the default.
 // `once` is read when the Knob is constructed (a function-local static: the first call) and never again; `live` is too,
 // unless NDI_TUNE_LIVE was set at that moment -- then every get() re-reads it, so one process can sweep the variants.

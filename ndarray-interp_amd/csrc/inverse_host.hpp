@@ -109,7 +109,7 @@ struct InverseImpl final : Interp1DBase, FloatEngine<T, InverseImpl<T>> {
     A.status = st;
     const uint64_t total = nq * lanes;
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + BLOCK - 1) / BLOCK, 1u << 20));
-    if (std::getenv("NDI_TRACE_PLAN")) std::fprintf(stderr, "[ndi plan] inverse eval class=%d grid=%u\n", cls, grid);
+    if (trace_plan()) std::fprintf(stderr, "[ndi plan] inverse eval class=%d grid=%u\n", cls, grid);
     switch (cls) {
       case IC_LINEAR: launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), 0, inverse_eval_kernel<T, IC_LINEAR>, A); break;
       case IC_CUBIC: launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), 0, inverse_eval_kernel<T, IC_CUBIC>, A); break;

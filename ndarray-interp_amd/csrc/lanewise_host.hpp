@@ -81,7 +81,7 @@ static void lanewise_two_kernel(hipStream_t s, Workspace& ws, const DevicePyrami
   A.G = lanewise_geom(rows, lanes, lanes, out_stride, grid);
   A.first_fail = &st->first_fail[0];
   A.n_int = (uint32_t)(n - 1);
-  if (std::getenv("NDI_TRACE_PLAN"))
+  if (trace_plan())
     std::fprintf(stderr, "[ndi plan] lanewise form=two-kernel kind=%d packed_q=%d grid=%u\n", kind, (int)(q_stride != lanes), grid);
   switch (kind) {
     case LW_LINEAR: launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), 0, lanewise_point_kernel<T, LW_LINEAR>, A); break;
@@ -214,7 +214,7 @@ const void* Interp1DImpl<T>::lanewise_records(hipStream_t s) {
       R.state.store(2, std::memory_order_release);
       return nullptr;
     }
-    if (std::getenv("NDI_TRACE_PLAN")) std::fprintf(stderr, "[ndi plan] lanewise records built bytes=%zu\n", bytes);
+    if (trace_plan()) std::fprintf(stderr, "[ndi plan] lanewise records built bytes=%zu\n", bytes);
     R.stream = s;
     R.state.store(3, std::memory_order_release);
     return R.buf.p;
@@ -288,7 +288,7 @@ void Interp1DImpl<T>::lanewise_enqueue(hipStream_t s, Workspace& ws, const T* q,
   const bool want_records = K.records >= 0 ? K.records != 0
                                            : lanes < 64 && (cubic || (size_t)n * lanes * sizeof(T) > ((size_t)4 << 20));
   A.rec = want_records ? lanewise_records(s) : nullptr;
-  if (std::getenv("NDI_TRACE_PLAN"))
+  if (trace_plan())
     std::fprintf(stderr, "[ndi plan] lanewise form=fused cubic=%d stage=%d lut=%d records=%d check=%d grid=%u\n", (int)cubic,
                  (int)stage, bx.lut ? 1 : (bx32.lut ? 2 : 0), (int)(A.rec != nullptr), A.check, grid);
   pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
@@ -352,7 +352,7 @@ void InverseImpl<T>::lanewise_enqueue(hipStream_t s, Workspace& ws, const T* q, 
   W.check = check ? 1 : 0;
   W.first_fail = &st->first_fail[0];
   if (!check) lanewise_prepass<T>(s, q, W.G, T(0), T(0), (int)EX_NO, W.lo, W.hi, W.first_fail);
-  if (std::getenv("NDI_TRACE_PLAN"))
+  if (trace_plan())
     std::fprintf(stderr, "[ndi plan] lanewise form=inverse class=%d check=%d grid=%u\n", cls, W.check, grid);
   switch (cls) {
     case IC_LINEAR: launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), 0, inverse_lanewise_kernel<T, IC_LINEAR>, W); break;

@@ -691,6 +691,12 @@ static size_t wgs_per_cu(size_t lds, unsigned tb) {
 
 // Workgroup size for a kernel that needs `lds` bytes per workgroup: as few threads as keep 32 waves on a CU
 // (160 KiB LDS, at most 1024 threads per workgroup).
+// The grid of a query-order kernel whose workgroups walk the batch: one workgroup per `per_wg` queries, at most `rounds`
+// times what the chip holds at once beside `lds` bytes of LDS each.
+static unsigned resident_grid(uint64_t nq, uint64_t per_wg, size_t lds, unsigned tb, unsigned rounds = 1) {
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + per_wg - 1) / per_wg, (uint64_t)cu_count() * wgs_per_cu(lds, tb) * rounds));
+}
+
 static unsigned threads_for_lds(size_t lds) {
   unsigned best = 256;
   size_t best_waves = 0;
@@ -1537,7 +1543,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     constexpr int VN = Wide<T>::N;
     P.l_qpl = (lanes == 1 && P.out_stride == 1 && aligned16(P.q) && aligned16(P.out)) ? VN : 1;
     const uint64_t per_wg = (uint64_t)P.f_tb * (lanes == 1 ? (uint64_t)P.l_qpl : 1);
-    P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((P.nq + per_wg - 1) / per_wg, (uint64_t)cu_count() * wgs_per_cu(P.f_lds, P.f_tb)));
+    P.f_grid = resident_grid(P.nq, per_wg, P.f_lds, P.f_tb);
     P.kind = Plan1::LANES;
     P.l_check = this->range_prepass(s, sc, {P.q, nullptr}, P.nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
     return true;
@@ -1559,7 +1565,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     F.mode = mode;
     F.first_fail = &sc.status.as<StatusBlock>()->first_fail[0];
     F.check = P.l_check ? 1 : 0;
-    if (std::getenv("NDI_TRACE_PLAN"))
+    if (trace_plan())
       std::fprintf(stderr, "[ndi plan] lanes L=%llu qpl=%d index=%s m=%u maxk=%u tb=%u grid=%u lds=%zu prepass=%d\n", (unsigned long long)lanes,
                    P.l_qpl, pyr.dlut.lut ? "dense" : "guess", pyr.dlut.m, pyr.dlut.maxk, P.f_tb, P.f_grid, P.f_lds, P.l_check ? 0 : 1);
     constexpr int VN = Wide<T>::N;
@@ -1959,7 +1965,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
   // Evaluates the w >= 1 chunks prepared into sc[0 .. w) with the plans P[0 .. w) -- all groupable, one row pitch -- in
   // ONE launch (w = 1: the single-chunk kernel, launch_eval).
   void launch_eval_group(hipStream_t s, Scratch* const* sc, const Plan1* P, uint32_t w) {
-    if (std::getenv("NDI_TRACE_PLAN"))
+    if (trace_plan())
       std::fprintf(stderr, "[ndi plan] ring bucketed L=%llu lv=%llu width=%u nq=%llu\n", (unsigned long long)lanes,
                    (unsigned long long)P[0].LV, w, (unsigned long long)P[0].nq);
     if (w == 1) {
@@ -2025,7 +2031,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     constexpr int VN = Wide<T>::N;
     const dim3 grid(P.f_grid), block(P.f_tb);
     if (P.f_sorted) {
-      if (std::getenv("NDI_TRACE_PLAN"))
+      if (trace_plan())
         std::fprintf(stderr, "[ndi plan] fused sorted lut=%d tb=%u grid=%u lds=%zu prepass=%d\n", (int)P.f_lut, P.f_tb, P.f_grid,
                      P.f_lds, P.l_check ? 0 : 1);
       pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
@@ -2036,7 +2042,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
       });
       return;
     }
-    if (std::getenv("NDI_TRACE_PLAN"))   // which variant a batch took (tests assert on it; read per call)
+    if (trace_plan())   // which variant a batch took (tests assert on it; read per call)
       std::fprintf(stderr, "[ndi plan] fused tables=%s lut=%d pack=%d unr=%d tb=%u grid=%u lds=%zu prepass=%d\n",
                    P.f_tlds == 2 ? "lds{y,k}" : (P.f_tlds == 1 ? "lds{y,a,b}" : (P.f_tlds == 3 ? "memory,knots=global" : "memory")),
                    (int)P.f_lut, (int)P.f_pack,
@@ -2403,8 +2409,33 @@ template <class T>
 static ndi_status bicubic_jet_eval(Interp2DImpl<T>& h, int order, const void* qx, const void* qy, uint64_t nq,
                                    void* const* outs, uint64_t out_stride, const ndi_eval_opts* opts, ndi_oob_info* info);
 
+// What Interp2DImpl::prep decides for a batch and launch_eval runs (both in bilinear_host.hpp): the kind and its launch geometry.
+template <class T>
+struct Plan2 {
+  enum Kind { SMALL, GATHER, TILED, FUSED2, LANES2, SLOPES2, BICUBIC, BICUBIC_INT } kind = GATHER;
+  int l_qpl = 1;          // LANES2, scalar grids: queries per lane (1, or one 16-byte vector)
+  bool l_check = false;   // LANES2: no range pre-pass (NDI_EVAL_FRESH_OUTPUT)
+  bool f_lds_wide = false;   // SLOPES2: f_lds includes the result strip of the 16-byte store path
+  // FUSED2 (eval_fused2d_kernel)
+  bool f_vec = false, f_lut = false;
+  uint64_t f_lv = 0;
+  unsigned f_grid = 1, f_tb = 256;
+  size_t f_lds = 0;
+  bool compact = false;   // TILED: self-contained 16-byte records (group_scatter2d_kernel<T, true>)
+  uint32_t ts = 0, nty = 0, nb = 0;   // TILED: tile shift, tiles per grid row, number of tiles
+  const T* qx = nullptr;
+  const T* qy = nullptr;
+  uint64_t nq = 0;
+  T* out = nullptr;
+  uint64_t out_stride = 0;
+};
+template <class T>
+static EvalSmall2Args<T> small2_args(const Interp2DImpl<T>& h, StatusBlock* st, const T* qx, const T* qy, T* out, uint64_t nq,
+                                     uint64_t out_stride, int prechecked);
+
 template <class T>
 struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
+  using Plan = Plan2<T>;      // (the engine in float_host.hpp reads Impl::Plan)
   int mode = EX_NO;
   uint64_t nx = 0, ny = 0;
   DevicePyramid<T> px, py;
@@ -2419,6 +2450,10 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
   int wrap_axes() const { return mode != EX_NO ? periodic_axes : 0; }
   DevBuf itable;              // integral handles: the prefix records T[nx][ny][5][lanes] ({PP, Qz, Qzy, Pz, Pzx}), owned
   bool pair_packed = false;   // data holds the pair-packed layout (pack_pairs_kernel)
+  // The stored grid as the kernels address it: cells per grid row and elements per cell of `data` (a pair-packed cell holds
+  // the values of two neighbouring grid points of a row, and a row has one cell fewer).
+  struct Layout { uint64_t row_cells, cell_elems; };
+  Layout layout() const { return pair_packed ? Layout{ny - 1, 2 * lanes} : Layout{ny, lanes}; }
   SpaceSet spaces;
   OwnedRing ring_own;
   // lazy copies of the grid are built on first use by a kernel on the caller's stream, as Interp1DImpl::ensure_packed builds
@@ -2480,8 +2515,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
         const unsigned gr = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + BLOCK - 1) / BLOCK, 65536));
         if (slopes_cells()) NDI_HIP(hipMemsetAsync(slopes.p, 0, bytes, s));     // (the padding is never read; kept defined)
         hipLaunchKernelGGL(slope_pack_kernel<T>, dim3(gr), dim3(BLOCK), 0, s, (const T*)data.as<T>(), (const T*)px.view.lv0,
-                           slopes.as<T>(), nx, ny, lanes, (uint64_t)(pair_packed ? ny - 1 : ny),
-                           (uint64_t)(pair_packed ? 2 * lanes : lanes),
+                           slopes.as<T>(), nx, ny, lanes, layout().row_cells, layout().cell_elems,
                            (uint64_t)(slopes_cells() ? slopes_cell_stride_bytes() / sizeof(T) : 0));
         NDI_HIP(hipGetLastError());
         NDI_HIP(hipEventRecord(slopes_ev, s));
@@ -2517,370 +2551,13 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     return bicubic_tables<T>(*this, zx, zy, zxy, memspace);
   }
 
-  // Two stages as in Interp1DImpl: prep() = both searches (+ the optional tile grouping) into a scratch set,
-  // launch_eval() = the bilinear kernel reading that set.
-  struct Plan2 {
-    enum Kind { SMALL, GATHER, TILED, FUSED2, LANES2, SLOPES2, BICUBIC, BICUBIC_INT } kind = GATHER;
-    int l_qpl = 1;          // LANES2, scalar grids: queries per lane (1, or one 16-byte vector)
-    bool l_check = false;   // LANES2: no range pre-pass (NDI_EVAL_FRESH_OUTPUT)
-    bool f_lds_wide = false;   // SLOPES2: f_lds includes the result strip of the 16-byte store path
-    // FUSED2 (eval_fused2d_kernel)
-    bool f_vec = false, f_lut = false;
-    uint64_t f_lv = 0;
-    unsigned f_grid = 1, f_tb = 256;
-    size_t f_lds = 0;
-    bool compact = false;   // TILED: self-contained 16-byte records (group_scatter2d_kernel<T, true>)
-    uint32_t ts = 0, nty = 0, nb = 0;   // TILED: tile shift, tiles per grid row, number of tiles
-    const T* qx = nullptr;
-    const T* qy = nullptr;
-    uint64_t nq = 0;
-    T* out = nullptr;
-    uint64_t out_stride = 0;
-  };
 
-  Plan2 prep(hipStream_t s, Scratch& sc, const T* qx, const T* qy, uint64_t nq, T* out, uint64_t out_stride,
-             int path, bool beside_eval = false, int flags = 0) {
-    Plan2 P;
-    P.qx = qx; P.qy = qy; P.nq = nq; P.out = out; P.out_stride = out_stride;
-    sc.status.reserve(sizeof(StatusBlock));
-    reset_status(sc.status.p, s);
-    StatusBlock* st = sc.status.as<StatusBlock>();
-    if (bicubic) {   // one kernel for AUTO and GATHER (eval_bicubic_kernel); BUCKETED was refused at the entry point
-      P.kind = integral ? Plan2::BICUBIC_INT : Plan2::BICUBIC;   // (an integral handle: eval_bicubic_integral_kernel)
-      P.l_check = this->range_prepass(s, sc, {qx, qy}, nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
-      return P;
-    }
-    sc.idx.reserve(nq * sizeof(uint32_t));
-    sc.idx2.reserve(nq * sizeof(uint32_t));
-    const size_t both = ((px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15);
-    // 1-2 values per grid point: one query per thread -- both searches and the evaluation in one launch, no (xi, yi)
-    // round trip, two reciprocals per query instead of three divisions per value.  (Extended to unaligned rows of more
-    // values in A/B runs, since removed: measured SLOWER from 3 values -- 100 x 100 x 5 f64: 11 vs
-    // 21 Gqueries/s -- a thread per query turns every operand load into 64 scattered sectors, where the item-per-lane
-    // gather kernel reads each query's 40-byte segments whole.)
-    // Grids that fit LDS beside their axes (the reference's 100 x 100 scalar grid: 80 KB in f64), rows of up to 64 bytes,
-    // large batches: query per lane with every corner read served by LDS (eval_scalar2d_kernel / eval_lanes2d_kernel).
-    // NDI_LANES2D_KERNEL=0: A/B.
-    {
-      static const Knob on_knob{"NDI_LANES2D_KERNEL", -1, Knob::live};
-      const int on = on_knob.get();
-      const size_t grid_b = (size_t)nx * ny * lanes * sizeof(T);
-      if (on != 0 && path != NDI_PATH_BUCKETED && !pair_packed && nx <= 16384 && ny <= 16384 && lanes * sizeof(T) <= (on > 0 ? 64 : 56) &&
-          grid_b + (nx + ny) * 5 * sizeof(T) <= FUSED_LDS_LIMIT && (uint64_t)nx * ny * lanes < (1ull << 31) &&
-          (on > 0 || (nq >= 65536 && (double)nq * (double)lanes * sizeof(T) >= 4.0 * (double)cu_count() * (double)grid_b))) {
-        px.ensure_dense_lut();
-        py.ensure_dense_lut();
-        const size_t fixed = (((size_t)(nx + LANE_SENTINELS) * sizeof(T) + 15) & ~(size_t)15) +
-                             (((size_t)(ny + LANE_SENTINELS) * sizeof(T) + 15) & ~(size_t)15) +
-                             px.dlut_bytes + py.dlut_bytes + (size_t)(nx - 1 + ny - 1) * 4 * sizeof(T) + ((grid_b + 15) & ~(size_t)15);
-        auto need_of = [&](unsigned tb) { return fixed + (lanes > 1 ? (size_t)(tb / 64) * 64 * lanes * sizeof(T) : 0); };
-        unsigned tb = need_of(256) * 4 <= 160 * 1024 ? 256u : 1024u;
-        if (need_of(tb) > FUSED_LDS_LIMIT) tb = 256u;   // (the strips of 16 waves do not fit: 4 waves)
-        if (px.dense_ok && py.dense_ok && need_of(tb) <= FUSED_LDS_LIMIT) {
-          constexpr int VNl = Wide<T>::N;
-          P.kind = Plan2::LANES2;
-          P.f_tb = tb;
-          P.f_lds = need_of(tb);
-          P.l_qpl = (lanes == 1 && out_stride == 1 && aligned16(qx) && aligned16(qy) && aligned16(out)) ? VNl : 1;
-          const uint64_t per_wg = (uint64_t)P.f_tb * (lanes == 1 ? (uint64_t)P.l_qpl : 1);
-          P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + per_wg - 1) / per_wg, (uint64_t)cu_count() * wgs_per_cu(P.f_lds, P.f_tb)));
-          P.l_check = this->range_prepass(s, sc, {qx, qy}, nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
-          return P;
-        }
-      }
-    }
-    // Short rows (up to 64 bytes) on a grid that does not fit LDS, large batches: slope records {z, m} -- one contiguous
-    // run of 4 L values per query, one division per value instead of three, an item per lane (eval_slopes2d_kernel; the
-    // copy, 2 x the grid, is built on first use).  NDI_SLOPES2D_KERNEL=0 / 1: A/B.
-    {
-      static const Knob on_knob{"NDI_SLOPES2D_KERNEL", -1, Knob::live};
-      const int on = on_knob.get();
-      const size_t cell_b = (size_t)lanes * sizeof(T);
-      // (f32 rows beyond 48 bytes: 13 .. 16 trips -- the compiler stops unrolling and the per-trip arrays go to scratch; the
-      //  query-order kernel was level there anyway)
-      if (on != 0 && path != NDI_PATH_BUCKETED && lanes >= 1 && cell_b <= (sizeof(T) == 4 ? 48 : 64) && nx <= 16384 && ny <= 16384 &&
-          (uint64_t)slopes_bytes() < (1ull << 32) && slopes_bytes() <= SLOPES_LIMIT &&
-          // AUTO: measured ahead of (f64 x 8, f32 x 16: level with) the query-order kernel on every row of up to 64 bytes
-          // (profiles/r06_slopes2d_rates.txt); batches large enough to pay for building the copy; 1-2 values per point:
-          // the one-thread-per-query kernel keeps the smaller batches, as before
-          (on > 0 || (nq >= (lanes <= 2 ? 524288u : 65536u) && (double)nq * (double)cell_b >= 2.0 * (double)slopes_bytes()))) {
-        px.ensure_dense_lut();
-        py.ensure_dense_lut();
-        const size_t fixed = (((size_t)(nx + LANE_SENTINELS) * sizeof(T) + 15) & ~(size_t)15) +
-                             (((size_t)(ny + LANE_SENTINELS) * sizeof(T) + 15) & ~(size_t)15) +
-                             px.dlut_bytes + py.dlut_bytes + (size_t)(ny - 1) * 4 * sizeof(T);
-        const unsigned tb = 256u;
-        size_t need = fixed + (size_t)(tb / 64) * 2 * 64 * (4 + 4 * sizeof(T));
-        const size_t res_strip = (size_t)(tb / 64) * 64 * lanes * sizeof(T);      // the rows of a batch, for 16-byte stores
-        const bool wide_fits = need + res_strip <= FUSED_LDS_LIMIT;
-        if (wide_fits) need += res_strip;
-        if (px.dense_ok && py.dense_ok && need <= FUSED_LDS_LIMIT && ensure_slopes(s)) {
-          P.kind = Plan2::SLOPES2;
-          P.f_tb = tb;
-          P.f_lds = need;
-          P.f_lds_wide = wide_fits;
-          P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + P.f_tb - 1) / P.f_tb, (uint64_t)cu_count() * wgs_per_cu(P.f_lds, P.f_tb)));
-          P.l_check = this->range_prepass(s, sc, {qx, qy}, nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
-          return P;
-        }
-      }
-    }
-    const bool small2d = lanes <= 2;
-    const bool small2d_yields = lanes >= 1 && nq >= 8 * 65536;   // (to the query-order kernel below, at 8 x its own floor)
-    if (small2d && !small2d_yields && both <= LDS_STAGE_LIMIT && path != NDI_PATH_BUCKETED) {
-      // short trailing axes: range pre-check, then both searches + evaluation fused in one launch
-      P.kind = Plan2::SMALL;
-      this->range_prepass(s, sc, {qx, qy}, nq, false);
-      return P;
-    }
-    // Rows of fewer than 256 vectors on axes that fit LDS twice over (the reference's 100 x 100 x 5; few-channel grids),
-    // batches from 65 536 queries: query order with both searches fused in (eval_fused2d_kernel) -- no (xi, yi)
-    // round trip, one reciprocal per direction and query.  Grids the tile order takes (below) are left to it.
-    {
-      constexpr int VNf = Wide<T>::N;
-      const bool vec = (lanes % VNf == 0) && (out_stride % VNf == 0) && aligned16(out);
-      const uint64_t LVf = vec ? lanes / VNf : lanes;
-      const uint64_t cell_e = pair_packed ? 2 * lanes : lanes, row_c = pair_packed ? ny - 1 : ny;
-      const uint64_t grid_vecs = nx * row_c * cell_e / (vec ? VNf : 1);
-      // workgroup size and search: the combination that keeps most waves on a CU beside the staged axes (the gathers
-      // are latency-bound: waves first); the bucket indices when they cost no waves, or at most half of them
-      size_t lut_b = 0;
-      if (nq >= 4096 && both <= LDS_STAGE_LIMIT) {
-        px.ensure_bucket_index();
-        py.ensure_bucket_index();
-        lut_b = px.lut_bytes + py.lut_bytes;
-      }
-      auto plan = [&](bool with_lut, unsigned& tb_out, size_t& lds_out) -> size_t {
-        size_t best = 0;
-        for (unsigned tb : {256u, 512u, 1024u}) {
-          const size_t need = both + (with_lut ? lut_b : 0) + (size_t)(tb / 64) * 64 * (sizeof(uint32_t) + 6 * sizeof(T));
-          if (need > LDS_STAGE_LIMIT) continue;
-          const size_t waves = wgs_per_cu(need, tb) * (tb / 64);
-          if (waves > best) { best = waves; tb_out = tb; lds_out = need; }
-        }
-        return best;
-      };
-      unsigned tb0 = 256, tb1 = 256;
-      size_t lds0 = 0, lds1 = 0;
-      const size_t w0 = plan(false, tb0, lds0);
-      const size_t w1 = lut_b ? plan(true, tb1, lds1) : 0;
-      const bool lut = w1 != 0 && 2 * w1 >= w0;
-      const unsigned TBf = lut ? tb1 : tb0;
-      const size_t lds = lut ? lds1 : lds0;
-      const bool tile_candidate = path == NDI_PATH_BUCKETED || (path == NDI_PATH_AUTO && auto_tiles(nq) && lanes * sizeof(T) >= 64);
-      if (nq >= 65536 && lanes >= 1 && LVf < 256 && 64 * LVf * LVf < (1ull << 32) &&
-          grid_vecs < (1ull << 32) && (lut ? w1 : w0) != 0 && !tile_candidate) {
-        P.kind = Plan2::FUSED2;
-        P.f_vec = vec; P.f_lv = LVf; P.f_lut = lut; P.f_lds = lds; P.f_tb = TBf;
-        P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + TBf - 1) / TBf, (uint64_t)cu_count() * wgs_per_cu(lds, TBf) * 4));
-        P.l_check = this->range_prepass(s, sc, {qx, qy}, nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
-        return P;
-      }
-    }
-    // BUCKETED for 2-D = tile grouping: the queries are ordered by the tile of 2^ts x 2^ts cells they fall in and
-    // eval_bilinear_tiles_kernel evaluates tile by tile out of LDS, so every grid value is read from memory once
-    // per tile instead of four times per query.  It pays when a tile sees several queries per cell (C3: 2.4) and
-    // cannot when the batch touches less data than the tiles hold (C5's share: 0.19 queries per cell): AUTO
-    // decides by queries per cell (auto_tiles).  Needs vector rows whose length divides the workgroup, the plain
-    // grid layout, a tile that fits LDS and a tile histogram that fits next to the pyramids in locate2_kernel.
-    constexpr int VNp = Wide<T>::N;
-    const bool vec_ok_p = (lanes % VNp == 0) && (out_stride % VNp == 0) && aligned16(out);
-    const uint64_t LVp = vec_ok_p ? lanes / VNp : 0;
-    size_t both_l = both;
-    const bool use_lut = nq >= 4096 && both <= LDS_STAGE_LIMIT;   // (the bucket index: A/B settled in round 3)
-    if (use_lut) {
-      px.ensure_bucket_index();
-      py.ensure_bucket_index();
-      if ((px.lut_bytes || py.lut_bytes) && both + px.lut_bytes + py.lut_bytes <= LDS_STAGE_LIMIT)
-        both_l = both + px.lut_bytes + py.lut_bytes;
-    }
-    auto ntiles_of = [&](uint64_t pts, uint32_t sh) { return (uint32_t)(((pts - 1) + ((uint64_t)1 << sh) - 1) >> sh); };
-    auto tile_bytes = [&](uint32_t sh) {
-      const size_t s1 = ((size_t)1 << sh) + 1;
-      return s1 * s1 * lanes * sizeof(T) + 5 * s1 * sizeof(T) + 16;
-    };
-    uint32_t ts = 0, nty = 0, nb = 0;
-    bool shape_ok = false;
-    if (vec_ok_p && !pair_packed && LVp >= 1 && LVp <= 1024 && 1024 % LVp == 0 && both <= LDS_STAGE_LIMIT &&
-        nx < (1ull << 31) && ny < (1ull << 31) && ny * lanes < (1ull << 32) && out_stride < (1ull << 32)) {
-      static const Knob ts_knob{"NDI_TILE_TS", -1};
-      const int ts_env = ts_knob.get();
-      // the largest tile that leaves room for two workgroups per CU, else the largest that fits at all
-      // the tile must fit the kernel's register double-buffer (6 x 1024 16-byte vectors = 96 KiB) next to 24-32 KiB of
-      // static LDS; the smaller budget is tried first (shorter staging per tile)
-      for (size_t budget : {(size_t)76 * 1024, (size_t)96 * 1024}) {
-        for (int sh = 6; sh >= 1 && !shape_ok; --sh) {
-          if (ts_env >= 0 && sh != ts_env) continue;
-          const uint64_t bins = (uint64_t)ntiles_of(nx, sh) * ntiles_of(ny, sh);
-          if (tile_bytes(sh) <= budget && bins <= GROUP_MAX_BINS &&
-              ((both_l + 15) & ~(size_t)15) + (size_t)bins * 4 <= LDS_STAGE_LIMIT) {
-            ts = (uint32_t)sh;
-            nty = ntiles_of(ny, sh);
-            nb = (uint32_t)bins;
-            shape_ok = true;
-          }
-        }
-        if (shape_ok) break;
-      }
-    }
-    const bool can_tile = shape_ok && nq >= 2 && nq < 0xffffffffull;
-    bool tiled = false;
-    if (path == NDI_PATH_BUCKETED) tiled = can_tile;
-    else if (path == NDI_PATH_AUTO) tiled = can_tile && auto_tiles(nq);
-    const uint32_t sx = ts, sy = ts;
-    const bool compact_records = std::is_same<T, float>::value && nx <= 65536 && ny <= 65536;
-    static const Knob cw_knob{"NDI_TILE_CELLWORDS", 1};   // A/B
-    const bool cell_words = tiled && compact_records && both <= LDS_STAGE_LIMIT && cw_knob.get();
-    g_last_path.store(tiled ? NDI_PATH_BUCKETED : NDI_PATH_GATHER);
-    // Two-level grouping (tile row, then tile: coarse_scatter2d_kernel / fine_scatter2d_kernel) when the one-pass scatter
-    // would leave fewer than a line's worth of records per (slice, tile) and the batch is large enough to pay for the
-    // second pass.  NDI_GROUP_TWO_LEVEL=0 / 1: A/B.
-    static const Knob tl_knob{"NDI_GROUP_TWO_LEVEL", -1, Knob::live};
-    const int tl_env = tl_knob.get();
-    const uint32_t ntx = tiled ? nb / nty : 0;
-    const bool two_level = tiled && both <= LDS_STAGE_LIMIT && ntx >= 2 && ntx <= 4096 && nty <= 4096 &&
-                           (tl_env == 1 || (tl_env < 0 && nq >= (1u << 20) && (double)nq / group_blocks() / nb < 8.0));
-    uint64_t slice = 0, blocks = 0;
-    if (both <= LDS_STAGE_LIMIT) {   // both axes in one launch
-      Locate2Args<T> LA{};
-      LA.px = px.view; LA.py = py.view;
-      LA.qx = qx; LA.qy = qy; LA.nq = nq;
-      LA.xi = sc.idx.as<uint32_t>(); LA.yi = sc.idx2.as<uint32_t>();
-      if (cell_words) LA.yi = nullptr;   // one cell word per query: all the scatter needs
-      LA.first_fail = &st->first_fail[0];
-      LA.mode = mode;
-      LA.bx = BucketIndex<T>{nullptr, 0, T(0)};
-      LA.by = LA.bx;
-      if (both_l != both) {
-        LA.bx = px.bidx;      // [x pyramid | y pyramid | x lut | y lut]; an axis whose formula guess is exact has none
-        LA.by = py.bidx;
-      }
-      size_t shmem = both_l;
-      if (tiled) {
-        sc.hist.reserve((size_t)std::max<uint32_t>(group_blocks(), GROUP_MAX_BLOCKS) * nb * sizeof(uint32_t));
-        LA.hist = sc.hist.as<uint32_t>();
-        LA.nb = nb; LA.sx = sx; LA.sy = sy; LA.nty = nty;
-        shmem = ((both_l + 15) & ~(size_t)15) + (size_t)nb * 4;
-        if (two_level) {
-          sc.chist.reserve((size_t)std::max<uint32_t>(group_blocks(), GROUP_MAX_BLOCKS) * ntx * sizeof(uint32_t));
-          LA.chist = sc.chist.as<uint32_t>();
-          LA.ntx = ntx;
-        }
-      }
-      const unsigned threads = beside_eval ? 256u : threads_for_lds(shmem);
-      blocks = std::max<uint64_t>(1, std::min<uint64_t>((nq + 1023) / 1024, tiled ? group_blocks() : 2048));
-      if ((LA.bx.lut || LA.by.lut || tiled) && !(tiled && group_blocks() > GROUP_MAX_BLOCKS))   // staging is the fixed cost of a
-        // workgroup: no more workgroups than the chip holds at once (NDI_GROUP_BLOCKS > 256 lifts the cap: A/B)
-        blocks = std::min<uint64_t>(blocks, (uint64_t)cu_count() * std::max<size_t>(1, (160 * 1024) / shmem));
-      slice = (nq + blocks - 1) / blocks;
-      slice = (slice + threads - 1) / threads * threads;
-      blocks = (nq + slice - 1) / slice;
-      LA.slice = slice;
-      if (two_level) {   // column-block-major tile histograms: (blocks * hist_w) words per block, ceil(nb / hist_w) <= blocks blocks
-        LA.hist_w = (uint32_t)((nb + blocks - 1) / blocks);
-        sc.hist.reserve((size_t)blocks * LA.hist_w * blocks * sizeof(uint32_t));
-        LA.hist = sc.hist.as<uint32_t>();
-      }
-      pick_or<1, LOCATE_QB>(slice / threads >= 16 ? LOCATE_QB : 1, [&](auto qb_) {
-        launch_lds<T>(locate2_kernel<T, qb_>, LDS_STAGE_LIMIT, s, PC_LOCATE, dim3((unsigned)blocks), dim3(threads), shmem, LA);
-      });
-    } else {
-      run_locate<T>(s, px, qx, nq, sc.idx.as<uint32_t>(), nullptr, nullptr, &st->first_fail[0], mode);
-      run_locate<T>(s, py, qy, nq, sc.idx2.as<uint32_t>(), nullptr, nullptr, &st->first_fail[1], mode);
-    }
-    if (tiled) {
-      P.kind = Plan2::TILED;
-      P.ts = ts; P.nty = nty; P.nb = nb;
-      P.compact = compact_records;
-      // the scatter is a latency-bound chain (load -> LDS atomic -> scattered store): many waves per CU
-      const unsigned gthreads = beside_eval ? 256u : (slice >= 4096 ? 1024u : (unsigned)BLOCK);
-      sc.perm.reserve(nq * sizeof(uint4));            // grouped records
-      if (!P.compact) sc.recq.reserve(nq * 2 * sizeof(T));
-      sc.counts.reserve(((size_t)nb + 4) * sizeof(uint32_t));   // (+4: the fused scan reads / writes 16-byte pieces)
-      sc.cursor.reserve(((size_t)nb + 4) * sizeof(uint32_t));
-      allow_dynamic_lds(reinterpret_cast<const void*>(&group_scatter2d_kernel<T, true>), (int)(GROUP_MAX_BINS * 4));
-      allow_dynamic_lds(reinterpret_cast<const void*>(&group_scatter2d_kernel<T, false>), (int)(GROUP_MAX_BINS * 4));
-      ProfScope ps(s, PC_GROUP);
-      const uint32_t chunk = tile_chunk();
-      sc.chunkbin.reserve(((nq + chunk - 1) / chunk) * sizeof(uint32_t));
-      if (!two_level)   // slice offsets, the scan of the tile totals and the tile each evaluation chunk starts in: one launch
-        hipLaunchKernelGGL(group_offsets_scan_kernel, dim3((nb + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s,
-                           sc.hist.as<uint32_t>(), (uint32_t)blocks, nb, sc.counts.as<uint32_t>(),
-                           sc.cursor.as<uint32_t>(), st, nq, chunk, sc.chunkbin.as<uint32_t>());
-      const uint32_t* yi_in = cell_words ? (const uint32_t*)nullptr : (const uint32_t*)sc.idx2.as<uint32_t>();
-      if (two_level) {
-        sc.perm2.reserve(nq * sizeof(uint4));
-        if (!P.compact) sc.recq2.reserve(nq * 2 * sizeof(T));
-        sc.cursor2.reserve(((size_t)nb + 4) * sizeof(uint32_t));
-        const size_t shm_c = ((size_t)3 * ntx + (size_t)2 * gthreads) * 4;
-        static const Knob ft_knob{"NDI_GROUP_FINE_THREADS", 0};
-        const int ft_env = ft_knob.get();
-        constexpr int FR = 4;   // records per thread and round of the fine pass (2 / 8 measured level: r05_c3_fine_round_variants.txt)
-        const unsigned fthreads = (ft_env == 256 || ft_env == 512 || ft_env == 1024) ? (unsigned)ft_env : 1024u;
-        // parts per tile row: one round per workgroup on evenly spread queries (measured at C3, profiles/r05_tuning.md:
-        // 2560 one-round workgroups 78 us; 512 workgroups walking five rounds each with the next round's records in
-        // flight 115 us -- the pass wants its parallelism across workgroups)
-        const uint64_t per_row = (nq + ntx - 1) / ntx;
-        const uint64_t rounds_row = (per_row + (uint64_t)FR * fthreads - 1) / ((uint64_t)FR * fthreads);
-        const uint32_t G = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rounds_row, 4096));
-        const unsigned fgrid = (unsigned)(((ntx + 7u) / 8u) * 8u * G);
-        if (std::getenv("NDI_TRACE_PLAN"))
-          std::fprintf(stderr, "[ndi plan] two-level grouping ntx=%u nty=%u slices=%llu G=%u\n", ntx, nty,
-                       (unsigned long long)blocks, G);
-        const uint32_t* yi_c = P.compact ? yi_in : (const uint32_t*)sc.idx2.as<uint32_t>();
-        T* rq2 = P.compact ? (T*)nullptr : sc.recq2.as<T>();
-        T* rq1 = P.compact ? (T*)nullptr : sc.recq.as<T>();
-        auto coarse = [&](auto kern, size_t limit, size_t shm) {
-          allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)limit);
-          hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(gthreads), shm, s,
-                             (const uint32_t*)sc.idx.as<uint32_t>(), yi_c, qx, qy, nq, slice,
-                             (const uint32_t*)sc.chist.as<uint32_t>(), (const uint32_t*)sc.hist.as<uint32_t>(), nb, ntx,
-                             sx, sc.perm2.as<uint4>(), rq2, sc.counts.as<uint32_t>());
-        };
-        static const Knob csort_knob{"NDI_GROUP_COARSE_SORT", 1};
-        const size_t shm_cs = ((((size_t)6 * ntx + 2 * gthreads) * 4 + 15) & ~(size_t)15) + (size_t)4 * gthreads * 20;
-        // trips sorted in LDS (NDI_GROUP_COARSE_SORT=0: direct, A/B)
-        if (P.compact && std::is_same<T, float>::value && csort_knob.get() && shm_cs <= 150 * 1024) coarse(coarse_scatter2d_kernel<T, true, true>, 150 * 1024, shm_cs);
-        else if (P.compact) coarse(coarse_scatter2d_kernel<T, true>, 64 * 1024, shm_c);
-        else coarse(coarse_scatter2d_kernel<T, false>, 64 * 1024, shm_c);
-        hipLaunchKernelGGL(scan_bin_totals_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t*)sc.counts.as<uint32_t>(), nb,
-                           sc.cursor.as<uint32_t>(), sc.cursor2.as<uint32_t>(), st, chunk, sc.chunkbin.as<uint32_t>());
-        static const Knob fsort_knob{"NDI_GROUP_FINE_SORT", 1};
-        const int fsort_env = fsort_knob.get();
-        if (P.compact && std::is_same<T, float>::value && fsort_env) {   // the round's records sorted in LDS, coalesced copy-out (NDI_GROUP_FINE_SORT=0: the direct form, A/B)
-          // records per thread and round x workgroup size: 1 = 4 x 512; 2 .. 5 = 8 x 512, 4 x 1024, 2 x 512, 4 x 256 (A/B)
-          pick_or<1, 2, 3, 4, 5>(fsort_env, [&](auto v_) {
-            constexpr int V = v_, SR = V == 2 ? 8 : (V == 4 ? 2 : 4), STB = V == 3 ? 1024 : (V == 5 ? 256 : 512);
-            const uint64_t rr = (per_row + (uint64_t)SR * STB - 1) / ((uint64_t)SR * STB);
-            const uint32_t Gs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rr, 4096));
-            const unsigned sgrid = (unsigned)(((ntx + 7u) / 8u) * 8u * Gs);
-            const size_t shm_s = ((((size_t)3 * nty + 16) * 4 + 15) & ~(size_t)15) + (size_t)SR * STB * 20;
-            auto kern = fine_scatter2d_sorted_kernel<SR, STB>;
-            allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)(128 * 1024));
-            hipLaunchKernelGGL(kern, dim3(sgrid), dim3(STB), shm_s, s, (const uint4*)sc.perm2.as<uint4>(), sc.perm.as<uint4>(),
-                               (const uint32_t*)sc.cursor.as<uint32_t>(), sc.cursor2.as<uint32_t>(), nq, ntx, nty, sy, Gs);
-          });
-        } else
-          pick_bool(P.compact, [&](auto cp_) {
-            hipLaunchKernelGGL((fine_scatter2d_kernel<T, cp_, FR>), dim3(fgrid), dim3(fthreads), (size_t)nty * 8, s,
-                               (const uint4*)sc.perm2.as<uint4>(), (const T*)rq2, sc.perm.as<uint4>(), rq1,
-                               (const uint32_t*)sc.cursor.as<uint32_t>(), sc.cursor2.as<uint32_t>(), nq, ntx, nty, sy, G);
-          });
-      } else if (P.compact)
-        hipLaunchKernelGGL((group_scatter2d_kernel<T, true>), dim3((unsigned)blocks), dim3(gthreads), (size_t)nb * 4, s,
-                           (const uint32_t*)sc.idx.as<uint32_t>(), yi_in, qx, qy, nq,
-                           slice, (const uint32_t*)sc.hist.as<uint32_t>(), (const uint32_t*)sc.cursor.as<uint32_t>(),
-                           nb, sx, sy, nty, sc.perm.as<uint4>(), (T*)nullptr);
-      else
-        hipLaunchKernelGGL((group_scatter2d_kernel<T, false>), dim3((unsigned)blocks), dim3(gthreads), (size_t)nb * 4, s,
-                           (const uint32_t*)sc.idx.as<uint32_t>(), (const uint32_t*)sc.idx2.as<uint32_t>(), qx, qy, nq,
-                           slice, (const uint32_t*)sc.hist.as<uint32_t>(), (const uint32_t*)sc.cursor.as<uint32_t>(),
-                           nb, sx, sy, nty, sc.perm.as<uint4>(), sc.recq.as<T>());
-      NDI_HIP(hipGetLastError());
-      ps.done();
-    }
-    return P;
-  }
+  // Two stages as in Interp1DImpl: prep() = the plan -- a query-order kernel that searches for itself, or both searches
+  // (+ the tile grouping) into a scratch set -- and launch_eval() = the kernel of that plan.  Both, with the planners and
+  // launchers they call: bilinear_host.hpp.
+  Plan prep(hipStream_t s, Scratch& sc, Queries<T> q, uint64_t nq, T* out, uint64_t out_stride, int path,
+            bool beside_eval = false, int flags = 0);
+  void launch_eval(hipStream_t s, Scratch& sc, const Plan& P);
 
   // grouped positions per unit of work of eval_bilinear_tiles_kernel (sweep: profiles/r03_c3_grouped.md)
   static uint32_t tile_chunk() {
@@ -2905,289 +2582,8 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
            grid_bytes >= ((size_t)20 << 20);
   }
 
-  void launch_eval(hipStream_t s, Scratch& sc, const Plan2& P) {
-    StatusBlock* st = sc.status.as<StatusBlock>();
-    const uint64_t nq = P.nq;
-    if (P.kind == Plan2::BICUBIC) {
-      bicubic_launch_eval<T>(*this, s, st, P.qx, P.qy, nq, P.out, P.out_stride, P.l_check);
-      return;
-    }
-    if (P.kind == Plan2::BICUBIC_INT) {
-      bicubic_integral_launch_eval<T>(*this, s, st, P.qx, P.qy, (const T*)nullptr, (const T*)nullptr, nq, P.out, P.out_stride,
-                                      P.l_check);
-      return;
-    }
-    if (P.kind == Plan2::SMALL) {
-      const size_t both = ((px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15);
-      const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-      allow_dynamic_lds(reinterpret_cast<const void*>(&eval_small2d_kernel<T>), (int)LDS_STAGE_LIMIT);
-      EvalSmall2Args<T> S{};
-      S.px = px.view; S.py = py.view;
-      S.data = data.as<T>();
-      S.qx = P.qx; S.qy = P.qy;
-      S.out = P.out;
-      S.nq = nq;
-      S.out_stride = P.out_stride;
-      S.row_cells = pair_packed ? ny - 1 : ny;
-      S.cell_elems = pair_packed ? 2 * lanes : lanes;
-      S.lanes = (uint32_t)lanes;
-      S.mode = mode;
-      S.first_fail = &st->first_fail[0];
-      S.prechecked = 1;
-      // large batches: bucket indices behind the pyramids (as the two-axis search stages them), and from two values per
-      // query the shared-divisor division (two reciprocals per query instead of three divisions per value: same bits)
-      size_t shm = both;
-      if (nq >= 4096) {   // (the bucket index: A/B settled in round 3)
-        px.ensure_bucket_index();
-        py.ensure_bucket_index();
-        if ((px.lut_bytes || py.lut_bytes) && both + px.lut_bytes + py.lut_bytes <= LDS_STAGE_LIMIT / 2) {
-          S.bx = px.bidx;
-          S.by = py.bidx;
-          shm = both + px.lut_bytes + py.lut_bytes;
-        }
-      }
-      S.sdiv = lanes >= 2 ? 1 : 0;
-      unsigned gs = g;
-      if (shm > both)   // staging is the fixed cost of a workgroup: no more workgroups than the chip holds at once
-        gs = (unsigned)std::min<uint64_t>(g, (uint64_t)cu_count() * std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / shm)));
-      launch1<T>(s, PC_EVAL, dim3(gs), dim3(BLOCK), shm, eval_small2d_kernel<T>, S);
-      return;
-    }
-    if (P.kind == Plan2::SLOPES2) {
-      EvalSlopes2Args<T> F{};
-      F.xk = px.view.lv0; F.yk = py.view.lv0;
-      F.nx = (uint32_t)nx; F.ny = (uint32_t)ny;
-      F.dx = px.dlut; F.dy = py.dlut;
-      F.recs = slopes.as<T>();
-#ifdef NDI_TUNING
-      F.debug = env_int("NDI_SLOPES2D_DEBUG", 0);
-#endif
-      if (slopes_cells()) {
-        F.col_bytes = (uint32_t)slopes_cell_stride_bytes();
-        F.row_bytes = (uint32_t)((ny - 1) * slopes_cell_stride_bytes());
-      } else {
-        F.col_bytes = (uint32_t)(2 * lanes * sizeof(T));
-        F.row_bytes = (uint32_t)(ny * 2 * lanes * sizeof(T));
-      }
-      F.qx = P.qx; F.qy = P.qy;
-      F.out = P.out;
-      F.nq = nq;
-      F.out_stride = P.out_stride;
-      F.lanes = (uint32_t)lanes;
-      F.mode = mode;
-      F.first_fail = &st->first_fail[0];
-      F.check = P.l_check ? 1 : 0;
-      if (std::getenv("NDI_TRACE_PLAN"))
-        std::fprintf(stderr, "[ndi plan] slopes2d L=%llu recs=%s tb=%u grid=%u lds=%zu prepass=%d\n", (unsigned long long)lanes,
-                     slopes_cells() ? "cell" : "point", P.f_tb, P.f_grid, P.f_lds, P.l_check ? 0 : 1);
-      // rows leave as 16-byte vectors through a wave-private strip when the buffer allows it (+2-6 % over one value per lane)
-      const int contig = P.out_stride != lanes ? 0 : (aligned16(P.out) && P.f_lds_wide) ? 2 : 1;
-      const int mk = (int)std::max(px.dlut.lut ? px.dlut.maxk : 0u, py.dlut.lut ? py.dlut.maxk : 0u) <= 4 ? 4 : 8;
-      auto launch = [&](auto lc_) {
-        constexpr int LCS = lc_;
-        pick_or<8, 4>(mk, [&](auto mk_) {
-          constexpr int MKS = mk_;
-          pick_or<1, 2, 0>(contig, [&](auto ct_) {
-            launch_lds<T>(eval_slopes2d_kernel<T, LCS, MKS, ct_, 256>, FUSED_LDS_LIMIT, s, PC_EVAL, dim3(P.f_grid), dim3(256), P.f_lds, F);
-          });
-        });
-      };
-      // (prep plans rows of up to 64 bytes, f32 of up to 48: lanes 9 .. 12 exist for 4-byte elements only)
-      bool known = pick<1, 2, 3, 4, 5, 6, 7, 8>((int)lanes, launch);
-      if constexpr (sizeof(T) == 4) known = known || pick<9, 10, 11, 12>((int)lanes, launch);
-      if (!known) throw HipFailure{hipErrorInvalidValue, "launch_eval: no slope-record kernel for this lane count", __LINE__};
-      return;
-    }
-    if (P.kind == Plan2::LANES2) {
-      EvalLanes2Args<T> F{};
-      F.xk = px.view.lv0; F.yk = py.view.lv0;
-      F.nx = (uint32_t)nx; F.ny = (uint32_t)ny;
-      F.dx = px.dlut; F.dy = py.dlut;
-      F.data = data.as<T>();
-      F.qx = P.qx; F.qy = P.qy;
-      F.out = P.out;
-      F.nq = nq;
-      F.out_stride = P.out_stride;
-      F.lanes = (uint32_t)lanes;
-      F.mode = mode;
-      F.first_fail = &st->first_fail[0];
-      F.check = P.l_check ? 1 : 0;
-      if (std::getenv("NDI_TRACE_PLAN"))
-        std::fprintf(stderr, "[ndi plan] lanes2d L=%llu qpl=%d maxk=%u,%u tb=%u grid=%u lds=%zu prepass=%d\n", (unsigned long long)lanes,
-                     P.l_qpl, px.dlut.maxk, py.dlut.maxk, P.f_tb, P.f_grid, P.f_lds, P.l_check ? 0 : 1);
-      constexpr int VNl = Wide<T>::N;
-      pick_or<256, 1024>((int)P.f_tb, [&](auto tb_) {
-        constexpr int TB = tb_;
-        if (lanes == 1)
-          pick_or<1, VNl>(P.l_qpl, [&](auto qpl_) {
-            launch_lds<T>(eval_scalar2d_kernel<T, qpl_, TB>, FUSED_LDS_LIMIT, s, PC_EVAL, dim3(P.f_grid), dim3(P.f_tb), P.f_lds, F);
-          });
-        else launch_lds<T>(eval_lanes2d_kernel<T, TB>, FUSED_LDS_LIMIT, s, PC_EVAL, dim3(P.f_grid), dim3(P.f_tb), P.f_lds, F);
-      });
-      return;
-    }
-    if (P.kind == Plan2::FUSED2) {
-      EvalFused2Args<T> F{};
-      F.px = px.view; F.py = py.view;
-      F.bx = P.f_lut ? px.bidx : BucketIndex<T>{nullptr, 0, T(0)};
-      F.by = P.f_lut ? py.bidx : BucketIndex<T>{nullptr, 0, T(0)};
-      F.data = data.as<T>();
-      F.qx = P.qx; F.qy = P.qy;
-      F.out = P.out;
-      F.nq = nq;
-      F.out_stride = P.out_stride;
-      F.lanes = (uint32_t)lanes;
-      F.lv = (uint32_t)P.f_lv;
-      F.lv_magic = F.lv >= 2 ? (uint32_t)(((1ull << 32) + F.lv - 1) / F.lv) : 0u;
-      const uint64_t vec = P.f_vec ? Wide<T>::N : 1;
-      F.cell_vecs = (uint32_t)((pair_packed ? 2 * lanes : lanes) / vec);
-      F.row_vecs = (uint32_t)((pair_packed ? ny - 1 : ny) * (pair_packed ? 2 * lanes : lanes) / vec);
-      F.mode = mode;
-      F.first_fail = &st->first_fail[0];
-      F.check = P.l_check ? 1 : 0;
-      if (std::getenv("NDI_TRACE_PLAN"))
-        std::fprintf(stderr, "[ndi plan] fused2d vec=%d lv=%u lut=%d tb=%u grid=%u lds=%zu prepass=%d\n", (int)P.f_vec, F.lv, (int)P.f_lut,
-                     P.f_tb, P.f_grid, P.f_lds, P.l_check ? 0 : 1);
-      constexpr int VNf = Wide<T>::N;
-      pick_or<1, VNf>(P.f_vec ? VNf : 1, [&](auto vec_) {
-        constexpr int VEC = vec_;
-        pick_or<256, 1024, 512>((int)P.f_tb, [&](auto tb_) {
-          launch_lds<T>(eval_fused2d_kernel<T, VEC, 2, tb_>, LDS_STAGE_LIMIT, s, PC_EVAL, dim3(P.f_grid), dim3(tb_), P.f_lds, F);
-        });
-      });
-      return;
-    }
-    Eval2Args<T> A{};
-    A.xk = px.view.lv0;
-    A.yk = py.view.lv0;
-    A.data = data.as<T>();
-    A.qx = P.qx;
-    A.qy = P.qy;
-    A.xi = sc.idx.as<uint32_t>();
-    A.yi = sc.idx2.as<uint32_t>();
-    A.out = P.out;
-    A.nx = nx;
-    A.ny = ny;
-    A.lanes = lanes;
-    A.out_stride = P.out_stride;
-    A.nq = nq;
-    A.row_cells = pair_packed ? ny - 1 : ny;
-    A.cell_elems = pair_packed ? 2 * lanes : lanes;
-    A.status = st;
-    A.rec_i = nullptr;
-    A.rec_q = nullptr;
-    constexpr int VNt = Wide<T>::N;
-    if (P.kind == Plan2::TILED) {
-      A.rec_i = sc.perm.as<uint4>();
-      A.rec_q = P.compact ? nullptr : sc.recq.as<T>();
-      A.bin_start = sc.cursor.as<uint32_t>();
-      A.nb = P.nb; A.ts = P.ts; A.nty = P.nty;
-      A.chunk = tile_chunk();
-      A.chunk_bin = sc.chunkbin.as<uint32_t>();
-      const size_t s1 = ((size_t)1 << P.ts) + 1;
-      // Channel split: two 512-thread workgroups per CU, each staging one half of the trailing axis of its tile (values +
-      // x slopes), when two such half-tiles fit the CU's LDS beside 256 records each and a half-row still fills whole
-      // 16-byte vectors.  NDI_TILE_SPLIT=0 keeps one 1024-thread workgroup per CU (A/B).
-      static const Knob split_knob{"NDI_TILE_SPLIT", -1}, slope_knob{"NDI_TILE_SLOPES", 1}, wg_knob{"NDI_TILE_WG", 0};
-      const int slope_env = slope_knob.get();
-      const uint64_t lv_full = lanes / Wide<T>::N;
-      const size_t shm_half = (s1 * s1 + (s1 - 1) * s1) * (lanes / 2) * sizeof(T) + 5 * s1 * sizeof(T) + 16;
-      const size_t static512 = 256 * 16 + (P.compact ? 2 : 2 * 256) * sizeof(T) + 320;   // 256 records beside a tile
-      const bool split2 = split_knob.get() != 0 && slope_env != 0 && lv_full >= 2 && lv_full % 2 == 0 &&
-                          s1 * s1 * (lv_full / 2) <= 5 * 512 && 512 % (lv_full / 2) == 0 &&
-                          2 * (shm_half + static512) <= 160 * 1024;
-      // (Four quarter-row workgroups per CU were measured slower -- 1.05-1.08 vs 0.77-0.85 ms at C3: 64-byte half-line stores,
-      //  four decodes per record -- and are gone: profiles/r05_tuning.md 2.)
-      A.ch_split = split2 ? 2u : 1u;
-      {   // item -> (grid row, vector) of the tile staging: ceil(2^32 / vectors per tile row), full and last-column tiles
-        const uint64_t lvv = lv_full / A.ch_split;
-        const uint64_t full = (((uint64_t)1 << P.ts) + 1) * lvv;
-        const uint64_t edge = (ny - ((uint64_t)(P.nty - 1) << P.ts)) * lvv;
-        A.rvm_full = (uint32_t)((((uint64_t)1 << 32) + full - 1) / full);
-        A.rvm_edge = (uint32_t)((((uint64_t)1 << 32) + edge - 1) / edge);
-      }
-      A.debug = 0;
-#ifdef NDI_TUNING
-      A.debug = env_int("NDI_FUSED_DEBUG", 0);
-#endif
-      const size_t shm = s1 * s1 * lanes * sizeof(T) + 5 * s1 * sizeof(T) + 16;
-      const uint64_t nchunks = (nq + A.chunk - 1) / A.chunk;
-      const uint64_t resident = (uint64_t)cu_count() * std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (shm + 64)));
-      const unsigned gmul = 8u * A.ch_split;   // XCD-aware chunk order; the halves of a chunk are neighbours on one XCD
-      const unsigned gx = (unsigned)((std::max<uint64_t>(1, std::min<uint64_t>(nchunks * A.ch_split, resident * 4 * A.ch_split)) + gmul - 1) / gmul * gmul);
-      // One 1024-thread workgroup per CU.  NDI_TILE_WG=512 (A/B only): two 512-thread workgroups per CU when two tiles
-      // (+ 256 records each) fit the 160 KiB and the tile fits the 10 x 512-vector register double buffer -- measured
-      // slower at C3 (1.54 vs 1.17 ms: twice the tile staging per CU, half the rows per trip).
-      const size_t tile_vecs = s1 * s1 * (lanes / VNt);
-      const bool two_wg = wg_knob.get() == 512 && tile_vecs <= 10 * 512 && 2 * (shm + static512) <= 160 * 1024 &&
-                          (lanes / VNt) <= 512 && 512 % (lanes / VNt) == 0;
-      // x slopes of the tile staged next to its values (one division per channel and query instead of three): needs a
-      // second tile-sized array in LDS, so the records are handed over 256 at a time.  NDI_TILE_SLOPES=0: A/B.
-      const size_t shm_slope = (s1 * s1 + (s1 - 1) * s1) * lanes * sizeof(T) + 5 * s1 * sizeof(T) + 16;
-      const bool slopes = slope_env != 0 && !two_wg && shm_slope + static512 <= 160 * 1024;
-      // ... 1024 at a time when that still fits (compact f32 records at C3: 143.9 KiB + 16 KiB)
-      const size_t static1024 = 1024 * 16 + (P.compact ? 2 : 2 * 1024) * sizeof(T) + 320;
-      const bool slopes_rb1024 = slopes && shm_slope + static1024 <= 160 * 1024 && slope_env != 256;
-      if (std::getenv("NDI_TRACE_PLAN"))
-        std::fprintf(stderr, "[ndi plan] tiles ts=%u split=%u compact=%d grid=%u\n", P.ts, A.ch_split, (int)P.compact, gx);
-      // The kernel's forms: workgroup size, records per hand-over, vectors per thread of the staging double buffer, x
-      // slopes staged, and the LDS a workgroup may take (a half-tile workgroup shares its CU with a second one).
-      struct TileForm { int tb, rb, maxi; bool slope; int lds_kib; };
-      static constexpr TileForm forms[5] = {{512, 256, 5, true, 80}, {1024, 1024, 6, true, 160}, {1024, 256, 6, true, 160},
-                                            {512, 256, 10, false, 160}, {1024, 1024, 6, false, 160}};
-      const int form = split2 ? 0 : (slopes_rb1024 ? 1 : (slopes ? 2 : (two_wg ? 3 : 4)));
-      const size_t shm_form = split2 ? shm_half : (slopes ? shm_slope : shm);
-      pick<0, 1, 2, 3, 4>(form, [&](auto f_) {
-        constexpr TileForm V = forms[f_];
-        auto launch = [&](auto cp_) {
-          launch_lds<T>(eval_bilinear_tiles_kernel<T, VNt, V.tb, V.rb, V.maxi, cp_, V.slope>,
-                        V.lds_kib * 1024 - V.rb * (16 + 2 * sizeof(T)) - 512, s, PC_EVAL, dim3(gx), dim3(V.tb), shm_form, A);
-        };
-        if constexpr (std::is_same<T, float>::value) {   // compact records exist for f32 only
-          if (P.compact) return launch(std::true_type{});
-        }
-        launch(std::false_type{});
-      });
-      return;
-    }
-    constexpr int VN = Wide<T>::N;
-    const bool vec_ok = (lanes % VN == 0) && (P.out_stride % VN == 0) && aligned16(P.out);
-    const uint64_t LV = vec_ok ? lanes / VN : lanes;
-    // knots in LDS: both axes must fit next to each other with two 1024-thread workgroups per CU, and the batch
-    // must be large enough to amortise the staging
-    const size_t knot_bytes = (size_t)(nx + ny) * sizeof(T);
-    const bool klds = vec_ok && knot_bytes <= 72 * 1024 && nq >= (1u << 20);
-    ProfScope ps(s, PC_EVAL);
-    if (klds) {
-      constexpr int TB = 1024;
-      const uint32_t tile_q = (uint32_t)std::max<uint64_t>(1, (uint64_t)TB * 2 / std::max<uint64_t>(LV, 1));
-      const uint64_t ntiles = (nq + tile_q - 1) / tile_q;
-      const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ntiles, 512));
-      // Short rows (the pair-packed layout, <= 64 bytes per grid point: C5) divide with the shared-divisor division
-      // of kernels.hpp -- two IEEE reciprocals per item instead of twelve divisions: 1.5-6 % faster at C5's share
-      // (A/B on two boxes: 0.773 -> 0.726 and 0.749 -> 0.736 ms; the measured ceiling of the access mix is
-      // 0.72-0.74), neutral with index axes; long rows (C3, HBM-bound at 7.1 TB/s) get 3 % slower with it and keep
-      // the IEEE divisions.  Same bits either way.
-      pick_bool(pair_packed, [&](auto sdiv_) {
-        auto kern = eval_bilinear_kernel<T, VN, false, 2, TB, true, sdiv_>;
-        allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)LDS_STAGE_LIMIT);
-        hipLaunchKernelGGL(kern, dim3(gx), dim3(TB), (knot_bytes + 15) & ~(size_t)15, s, A, tile_q);
-      });
-    } else {
-      const uint32_t tile_q = (uint32_t)std::max<uint64_t>(1, 1024 / std::max<uint64_t>(LV, 1));
-      const uint64_t ntiles = (nq + tile_q - 1) / tile_q;
-      const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ntiles, 32768));
-      pick_or<1, VN>(vec_ok ? VN : 1, [&](auto vec_) {
-        hipLaunchKernelGGL((eval_bilinear_kernel<T, vec_>), dim3(gx), dim3(BLOCK), 0, s, A, tile_q);
-      });
-    }
-    NDI_HIP(hipGetLastError());
-    ps.done();
-  }
-
   // ---- what the host engine (float_host.hpp) takes from this family: x is array a, y is array b ---------------------
   using Elem = T;
-  using Plan = Plan2;
   static constexpr int query_arrays = 2;
   static constexpr bool small_rows = true, ring = true;
   static const char* axis_name(int axis) { return axis == 0 ? "x" : "y"; }
@@ -3208,12 +2604,8 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     NDI_HIP(hipGetLastError());
     ps.done();
   }
-  Plan2 prep(hipStream_t s, Scratch& sc, Queries<T> q, uint64_t nq, T* out, uint64_t out_stride, int path,
-             bool beside_eval = false, int flags = 0) {
-    return prep(s, sc, q.a, q.b, nq, out, out_stride, path, beside_eval, flags);
-  }
   void enqueue(hipStream_t s, Workspace& ws, Queries<T> q, uint64_t nq, T* out, uint64_t out_stride, int path, int flags) {
-    launch_eval(s, ws.sc[0], prep(s, ws.sc[0], q.a, q.b, nq, out, out_stride, path, false, flags));
+    launch_eval(s, ws.sc[0], prep(s, ws.sc[0], q, nq, out, out_stride, path, false, flags));
   }
   // the small-row paths (Bilinear only): both pyramids in LDS
   size_t small_shmem() const { return (px.lds_bytes + py.lds_bytes + 15) & ~(size_t)15; }
@@ -3228,19 +2620,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
   }
   // The fused search + evaluation launch of the small-row paths: nq packed rows into out, the kernel's own range test.
   void launch_small(hipStream_t s, StatusBlock* st, Queries<T> q, T* out, uint64_t nq) {
-    EvalSmall2Args<T> A{};
-    A.px = px.view; A.py = py.view;
-    A.data = data.as<T>();
-    A.qx = q.a; A.qy = q.b;
-    A.out = out;
-    A.nq = nq;
-    A.out_stride = lanes;
-    A.row_cells = pair_packed ? ny - 1 : ny;
-    A.cell_elems = pair_packed ? 2 * lanes : lanes;
-    A.lanes = (uint32_t)lanes;
-    A.mode = mode;
-    A.first_fail = &st->first_fail[0];
-    A.prechecked = 0;
+    const EvalSmall2Args<T> A = small2_args<T>(*this, st, q.a, q.b, out, nq, lanes, 0);
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
     launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), small_shmem(), eval_small2d_kernel<T>, A);
   }
@@ -3398,7 +2778,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     for (int r = 0; r <= reps; ++r) {   // the first launch is a warm-up
       NDI_HIP(hipEventRecord(a, s));
       hipLaunchKernelGGL((probe_gather_kernel<T, VN>), dim3(g), dim3(BLOCK), 0, s, (const T*)data.as<T>(), nx, ny,
-                         pair_packed ? ny - 1 : ny, pair_packed ? 2 * lanes : lanes, lanes, nq,
+                         layout().row_cells, layout().cell_elems, lanes, nq,
                          (uint64_t)(12345 + r), (T*)out, out_stride);
       NDI_HIP(hipGetLastError());
       NDI_HIP(hipEventRecord(b, s));
@@ -3495,6 +2875,7 @@ static ndi_status create2d(const ndi_interp2d_desc& d, Interp2DBase** out) {
 // ---------------------------------------------------------------------------------------------
 // Interp2D Bicubic: build, launch and table read-back
 // ---------------------------------------------------------------------------------------------
+#include "bilinear_host.hpp"
 #include "bicubic_host.hpp"
 #include "bicubic_local_host.hpp"
 #include "bicubic_integral_host.hpp"

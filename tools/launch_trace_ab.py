@@ -11,7 +11,7 @@ library), each process under `rocprofv3 --kernel-trace` with the program after `
   * the `[ndi plan]` lines the library printed (NDI_TRACE_PLAN) and its launch counters (ndi_profile_read) per case,
   * the sha256 of every output the driver saved.
 
-Variables that are read once per process (NDI_TILE_SLOPES, NDI_TILE_WG, NDI_GROUP_*_SORT) get a process of their own.
+Variables that are read once per process (NDI_TILE_SLOPES, NDI_TILE_WG, NDI_TILE_TS, NDI_GROUP_*_SORT) get a process of their own.
 One process at a time, each under its own timeout; nothing more is started after a failing one.  No counters are
 collected.  With `--bench-rounds N` plain `bench.py` runs follow, the two libraries alternating, and the flagship
 `ms_per_step`, the host-path leg and the bilinear leg's `step_minus_kernels_ms` are compared against the parent's own
@@ -40,6 +40,9 @@ GROUPS = {   # process -> the read-once variables it runs under
     "tile_slopes0": {"NDI_TILE_SLOPES": "0"},
     "tile_wg512": {"NDI_TILE_WG": "512"},
     "group_nosort": {"NDI_GROUP_COARSE_SORT": "0", "NDI_GROUP_FINE_SORT": "0"},
+    "tile_slopes256": {"NDI_TILE_SLOPES": "256"},      # the slope form with 256 records per hand-over
+    "tile_ts5": {"NDI_TILE_TS": "5"},                  # a tile of 33 x 33 points: f64 slopes beside 1024 records (2 lanes)
+    **{f"group_fine_sort{v}": {"NDI_GROUP_FINE_SORT": str(v)} for v in (2, 3, 4, 5)},
 }
 LIVE = ("NDI_SHORT_MODE", "NDI_FUSED_UNR", "NDI_FUSED_TB", "NDI_FUSED_LDS", "NDI_FUSED_PACK", "NDI_FUSED_SORTED",
         "NDI_SHORT_CQ", "NDI_LANES_KERNEL", "NDI_LANES2D_KERNEL", "NDI_SLOPES2D_KERNEL", "NDI_GROUP_TWO_LEVEL",
@@ -305,6 +308,8 @@ def driver(group, save_dir):
             case(f"{k} GATHER scalar", OFF2, eval2(33, 17, 5, 3000, dt, GATHER))
             case(f"{k} GATHER 2^20 knots in LDS, pair-packed", OFF2, eval2(200, 200, vn, 1 << 20, dt, BUCKETED))
             case(f"{k} GATHER 2^20 knots in LDS", OFF2, eval2(30, 30, 3 * vn, 1 << 20, dt, BUCKETED))
+            n_long = 40000 if dt == F32 else 20000      # the two pyramids do not fit LDS together: one search launch per axis
+            case(f"{k} GATHER axes outside LDS", OFF2, eval2(n_long, 4, vn, 3000, dt, GATHER))
 
     def cases_tiles_only():
         for dt in (F32, F64):
