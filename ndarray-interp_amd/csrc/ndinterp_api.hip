@@ -970,6 +970,28 @@ static const char* hermite_rule_name(int rule) {
   return "?";
 }
 
+// What Interp1DImpl::prep decides for a batch and launch_eval runs (both in interp1d_host.hpp): the kind and its launch geometry.
+template <class T>
+struct Plan1 {
+  enum Kind { SMALL, BUCKETED, ROWS, FLAT, FUSED, BUCKETED_SHORT, LANES } kind = ROWS;
+  const T* q = nullptr;
+  uint64_t nq = 0;
+  T* out = nullptr;
+  uint64_t out_stride = 0;
+  bool vec_ok = false;
+  uint64_t LV = 0;
+  // FUSED (eval_fused_kernel)
+  bool f_lut = false, f_pack = false;
+  bool f_sorted = false;   // FUSED: the queries of a workgroup round ordered by interval in LDS (eval_fused_sorted_kernel)
+  int f_tlds = 0;   // 0: tables from memory, 1: {y, a, b} in LDS, 2: {y, k} in LDS
+  unsigned f_tb = 256, f_grid = 1;
+  int f_unr = 2;
+  size_t f_lds = 0;
+  int s_cq = 64;   // BUCKETED_SHORT
+  int l_qpl = 1;   // LANES, scalar data: queries per lane (1, or one 16-byte vector)
+  bool l_check = false;   // LANES: no range pre-pass, the kernel checks the queries itself (NDI_EVAL_FRESH_OUTPUT)
+};
+
 template <class T>
 struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
   int strategy = NDI_LINEAR;   // the evaluation class: NDI_CUBIC_SPLINE = "has a / b tables" (Pchip, Akima, CubicHermite too)
@@ -1098,412 +1120,19 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     return ck.as<T>();
   }
 
-  // ---- build (CubicSpline::build, cubic_spline.rs:754-771) --------------------------------
-  ndi_status build_spline(const ndi_interp1d_desc& d) {
-    Range rg("ndi:spline_build");
-    const bool per_lane = d.lane_left_kind || d.lane_left_value || d.lane_right_kind || d.lane_right_value;
-    if (per_lane) {
-      if (!(d.lane_left_kind && d.lane_left_value && d.lane_right_kind && d.lane_right_value))
-        return fail(NDI_BAD_ARG, "BoundaryCondition::Individual needs all four lane_* arrays");
-      if (d.periodic) return fail(NDI_BAD_ARG, "Periodic cannot be combined with per-lane boundaries");
-      return build_spline_individual(d);
-    }
-    const bool periodic = d.periodic != 0;
-    BuildClock clk;
-    const size_t tab = (size_t)(n - 1) * lanes * sizeof(T);
-    ca.reserve(tab);
-    cb.reserve(tab);
-    // Blocked sweeps or serial kernels?  Narrow trailing axes with many knots: the per-lane serial kernel would be one
-    // or two waves doing 2n dependent steps.  The blocked sweeps (kernels.hpp, spline_blocked_*) take over -- the one
-    // path whose tables are not bit-identical to the reference order (a few ulp; NDI_SPLINE_BLOCKED=0 keeps the serial
-    // kernels, =1 forces the blocked ones wherever they apply).
-    static const Knob blocked_knob{"NDI_SPLINE_BLOCKED", -1, Knob::live};
-    const int blocked_env = blocked_knob.get();
-    // ... and only on axes whose neighbouring knot spacings differ by less than 1e3 (f32) / 1e9 (f64): the re-associated
-    // sweeps are accurate relative to the NEIGHBOURING table magnitudes, and where the spacing jumps by 1e6 from one
-    // interval to the next those magnitudes jump likewise -- in f32 evaluated rows then miss the 1e-5 bar (4 of 5000 rows
-    // at 4e-5 on gaps drawn log-uniformly over six decades, tests/test_gpu_spline_blocked.py).  Such axes keep the serial
-    // kernels: bit-identical.
-    bool tame = true;
-    if (blocked_env != 0 && n >= 16) {      // (also when the blocked build is forced: the device-side elimination needs it)
-      const double lim = sizeof(T) == 4 ? 1e3 : 1e9;
-      const T* xs = pyr.host_knots.data();
-      for (uint64_t i = 2; tame && i < n; ++i) {
-        const double a = (double)xs[i] - (double)xs[i - 1], b = (double)xs[i - 1] - (double)xs[i - 2];
-        tame = a <= lim * b && b <= lim * a;
-      }
-    }
-    // (n >= 16: the system is the GENERAL or the PERIODIC one -- the closed forms are n == 3)
-    const bool blocked = n >= 16 && !(d.build_flags & NDI_BUILD_REFERENCE_ORDER) &&
-                         (blocked_env > 0 || (blocked_env < 0 && n >= 2048 && lanes <= 256 && tame));
-    // Long axes: the x-only elimination factors on the device as well (spline_eliminate_kernel); the host then forms only
-    // the boundary rows' scalars.
-    const bool dev_elim = blocked && tame && !periodic && n >= 32768;
-    SplineEnds<T> ends;
-    SplinePlan<T> P = dev_elim ? make_spline_plan_scalars<T>(pyr.host_knots.data(), n, d.left.kind, d.left.value, d.right.kind,
-                                                             d.right.value, ends)
-                               : make_spline_plan<T>(pyr.host_knots.data(), n, periodic, d.left.kind, d.left.value,
-                                                     d.right.kind, d.right.value, (d.build_flags & BUILD_TRUE_NOT_A_KNOT) != 0);
-    clk.mark("  host plan");
-    // Small systems (the reference's (100, 5); 1024 x 8; ...): ONE launch -- right-hand sides, elimination, back
-    // substitution and the a / b epilogue in spline_build_general_kernel<FUSED>, dx / up formed from the resident knots;
-    // the x-only factors w, mid' travel through a kept pinned buffer into a kept device buffer: no allocation, no free,
-    // no status read-back (only the periodic build has one).  Same operations as the three-kernel form: bit-identical.
-    if (P.mode == SPLINE_GENERAL && !blocked && (uint64_t)n * lanes <= (1u << 17)) {
-      BuildScratch& bs = build_scratch();
-      const size_t plan_b = 2 * (size_t)n * sizeof(T);
-      T* hp = static_cast<T*>(bs.pinned(plan_b));
-      T* dp = static_cast<T*>(bs.device_buf(device, plan_b));
-      std::memcpy(hp, P.w.data(), (size_t)n * sizeof(T));
-      std::memcpy(hp + n, P.midp.data(), (size_t)n * sizeof(T));
-      NDI_HIP(hipMemcpyAsync(dp, hp, plan_b, hipMemcpyHostToDevice, nullptr));
-      clk.mark("    plan staged + copy enqueued");
-      BuildArgs<T> A{};
-      A.data = data.as<T>();
-      A.ca = ca.as<T>();
-      A.cb = cb.as<T>();
-      A.x = pyr.view.lv0;
-      A.w = dp;
-      A.midp = dp + n;
-      A.up_len = P.up.size();
-      A.left_up0 = P.up.front();
-      A.up_last = P.up.back();
-      A.n = n;
-      A.lanes = lanes;
-      A.left_kind = P.left_kind;
-      A.right_kind = P.right_kind;
-      A.left_val = P.left_val;
-      A.right_val = P.right_val;
-      A.nkL_tmp1 = P.nkL_tmp1; A.nkL_d = P.nkL_d;
-      A.nkR_tmp1 = P.nkR_tmp1; A.nkR_d = P.nkR_d;
-      A.dx0_sq = P.dx0_sq; A.dxl_sq = P.dxl_sq;
-      A.kout = reserve_k();
-      const unsigned grid1 = (unsigned)((lanes + 63) / 64);
-      // the smallest systems -- data and right-hand sides fit LDS twice over, one workgroup covers the trailing axis --
-      // form their right-hand sides with the whole workgroup and sweep out of LDS (spline_build_lds_kernel)
-      const size_t lds_need = 2 * (size_t)n * lanes * sizeof(T);
-      if (lanes <= (uint64_t)BLOCK && lds_need <= 96 * 1024 && n >= 4) {
-        allow_dynamic_lds(reinterpret_cast<const void*>(&spline_build_lds_kernel<T, true>), 96 * 1024);
-        allow_dynamic_lds(reinterpret_cast<const void*>(&spline_build_lds_kernel<T, false>), 96 * 1024);
-        if (A.kout) hipLaunchKernelGGL((spline_build_lds_kernel<T, true>), dim3(1), dim3(BLOCK), lds_need, (hipStream_t) nullptr, A);
-        else hipLaunchKernelGGL((spline_build_lds_kernel<T, false>), dim3(1), dim3(BLOCK), lds_need, (hipStream_t) nullptr, A);
-      } else if (A.kout) hipLaunchKernelGGL((spline_build_general_kernel<T, false, true, true>), dim3(grid1), dim3(64), 0, (hipStream_t) nullptr, A);
-      else hipLaunchKernelGGL((spline_build_general_kernel<T, false, false, true>), dim3(grid1), dim3(64), 0, (hipStream_t) nullptr, A);
-      NDI_HIP(hipGetLastError());
-      clk.mark("    kernel enqueued");
-      NDI_HIP(hipStreamSynchronize(nullptr));   // the tables are complete when create() returns: any stream may read them
-      clk.mark("  fused small build");
-      return NDI_OK;
-    }
-    const bool per = P.mode == SPLINE_PERIODIC;
-    const uint64_t rows = per ? n - 2 : n;   // order of the system the two sweeps run over
-    uint64_t S = 64;
-    while (S * S < rows && S < 2048) S *= 2;         // ~sqrt(n) rows per block: local sweeps and carry chain balance
-    const uint64_t nblk = (rows + S - 1) / S;
-    // ONE temporary allocation (one hipMalloc, one hipFree -- each costs as much as the kernels of a small build):
-    //   [status | dx (n) | up (n) | w (n) | mid' (n) | k2 (n) | blocked: fP | dco | bP | rfull | ends | carry]
-    // dx and up are formed on the device from the knots already there (the same subtractions in T as the host plan's);
-    // w, mid' and k2 -- the results of the host's division chain -- are uploaded straight from their vectors.
-    const size_t plan_elems = 5 * (size_t)n;
-    const size_t blk_elems = blocked ? 3 * (size_t)n + (size_t)n * lanes + 2 * (size_t)nblk * lanes : 0;
-    // temporaries: kept per host thread up to 64 MiB (hipMalloc + hipFree of a 48 MB buffer cost 4 ms of a 1e6-knot build,
-    // and more than the kernels of a 4096 x 8 one); larger ones are allocated and freed here
-    DevBuf tmp;
-    const size_t tmp_bytes = 256 + (plan_elems + blk_elems) * sizeof(T);
-    void* tmp_p = nullptr;
-    if (tmp_bytes <= ((size_t)64 << 20)) {
-      tmp_p = build_scratch().device_buf(device, tmp_bytes);
-    } else {
-      tmp.reserve(tmp_bytes);
-      tmp_p = tmp.p;
-    }
-    NDI_HIP(hipMemsetAsync(tmp_p, 0, sizeof(StatusBlock), nullptr));
-    T* const plan = reinterpret_cast<T*>((char*)tmp_p + 256);
-    T* const d_dx = plan;
-    T* const d_up = plan + n;
-    T* const d_w = plan + 2 * (size_t)n;
-    T* const d_mid = plan + 3 * (size_t)n;
-    T* const d_k2 = plan + 4 * (size_t)n;
-    if (!P.w.empty()) NDI_HIP(hipMemcpyAsync(d_w, P.w.data(), P.w.size() * sizeof(T), hipMemcpyHostToDevice, nullptr));
-    if (!P.midp.empty()) NDI_HIP(hipMemcpyAsync(d_mid, P.midp.data(), P.midp.size() * sizeof(T), hipMemcpyHostToDevice, nullptr));
-    if (!P.k2.empty()) NDI_HIP(hipMemcpyAsync(d_k2, P.k2.data(), P.k2.size() * sizeof(T), hipMemcpyHostToDevice, nullptr));
-    {
-      const uint64_t up_len = dev_elim ? n : P.up.size();
-      const T up_first = dev_elim ? ends.up_first : (up_len ? P.up[0] : T(0));
-      const T up_last = dev_elim ? T(0) : (up_len ? P.up[up_len - 1] : T(0));
-      const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + BLOCK - 1) / BLOCK, 4096));
-      hipLaunchKernelGGL(spline_dx_up_kernel<T>, dim3(g), dim3(BLOCK), 0, (hipStream_t) nullptr, (const T*)pyr.view.lv0, d_dx, d_up,
-                         n, up_len, up_first, up_last);
-      if (dev_elim) {   // w, mid' where the host plan would have been uploaded
-        const uint64_t SE = 256;
-        const uint64_t tasks = (n + SE - 1) / SE;
-        hipLaunchKernelGGL(spline_eliminate_kernel<T>, dim3((unsigned)((tasks + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t) nullptr,
-                           (const T*)pyr.view.lv0, n, ends.up_first, ends.mid_first, ends.low_last, ends.mid_last, d_w, d_mid, SE);
-      }
-      NDI_HIP(hipGetLastError());
-    }
-    clk.mark("  tables alloc + plan upload");
-
-    BuildArgs<T> A{};
-    A.data = data.as<T>();
-    A.ca = ca.as<T>();
-    A.cb = cb.as<T>();
-    A.dx = d_dx;
-    A.up = d_up;
-    A.w = d_w;
-    A.midp = d_mid;
-    A.k2 = d_k2;
-    A.n = n;
-    A.lanes = lanes;
-    A.left_kind = P.left_kind;
-    A.right_kind = P.right_kind;
-    A.left_val = P.left_val;
-    A.right_val = P.right_val;
-    A.nkL_tmp1 = P.nkL_tmp1; A.nkL_d = P.nkL_d;
-    A.nkR_tmp1 = P.nkR_tmp1; A.nkR_d = P.nkR_d;
-    A.dx0_sq = P.dx0_sq; A.dxl_sq = P.dxl_sq;
-    A.per_den = P.per_den;
-    A.status = static_cast<StatusBlock*>(tmp_p);
-    A.kout = reserve_k();
-    const unsigned grid = (unsigned)((lanes + 63) / 64);
-    hipStream_t s = nullptr;
-    if (blocked) {
-      T* sp = plan + plan_elems;     // [fP | dco | bP | rfull | ends | carry]; the coefficient products are formed on the device
-      A.fP = sp;
-      A.dco = sp + n;
-      A.bP = sp + 2 * n;
-      A.rfull = sp + 3 * n;
-      A.ends = A.rfull + n * lanes;
-      A.carry = A.ends + nblk * lanes;
-      A.S = S;
-      A.nblocks = nblk;
-      A.rows = rows;
-      const unsigned gr = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n * lanes + BLOCK - 1) / BLOCK, 65536));
-      const unsigned gl = (unsigned)((nblk * lanes + BLOCK - 1) / BLOCK);
-      hipLaunchKernelGGL(spline_blocked_coef_kernel<T>, dim3((unsigned)((nblk + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s,
-                         A.w, A.up, A.midp, sp, sp + n, sp + 2 * n, rows, S, nblk);
-      if (per) hipLaunchKernelGGL(spline_periodic_rhs_kernel<T>, dim3(gr), dim3(BLOCK), 0, s, A);
-      else hipLaunchKernelGGL((spline_rhs_kernel<T, false>), dim3(gr), dim3(BLOCK), 0, s, A);
-      hipLaunchKernelGGL(spline_blocked_local_kernel<T>, dim3(gl), dim3(BLOCK), 0, s, A, 0);
-      hipLaunchKernelGGL(spline_blocked_carry_kernel<T>, dim3(grid), dim3(64), 0, s, A, 0);
-      hipLaunchKernelGGL(spline_blocked_fix_forward_kernel<T>, dim3(gr), dim3(BLOCK), 0, s, A);
-      hipLaunchKernelGGL(spline_blocked_local_kernel<T>, dim3(gl), dim3(BLOCK), 0, s, A, 1);
-      hipLaunchKernelGGL(spline_blocked_carry_kernel<T>, dim3(grid), dim3(64), 0, s, A, 1);
-      if (per) {
-        hipLaunchKernelGGL(spline_periodic_km1_kernel<T>, dim3(grid), dim3(64), 0, s, A);
-        hipLaunchKernelGGL(spline_periodic_finish_kernel<T>, dim3(gr), dim3(BLOCK), 0, s, A);
-      } else {
-        hipLaunchKernelGGL(spline_blocked_finish_kernel<T>, dim3(gr), dim3(BLOCK), 0, s, A);
-      }
-      NDI_HIP(hipGetLastError());
-      StatusBlock hs{};
-      if (per) NDI_HIP(hipMemcpy(&hs, tmp_p, sizeof(hs), hipMemcpyDeviceToHost));   // (only the periodic build reports through it)
-      else NDI_HIP(hipStreamSynchronize(s));                                         // the tables are complete on return
-      clk.mark("  blocked sweeps");
-      if (hs.periodic_mismatch != 0)
-        return fail(NDI_VALUE,
-                    "for periodic boundary condition the first and last value must be equal "
-                    "(%llu lane(s) differ)", hs.periodic_mismatch);
-      if (mode != EX_NO && periodic) mode = EX_PERIODIC;
-      return NDI_OK;
-    }
-    switch (P.mode) {
-      case SPLINE_GENERAL: {
-        // Wide trailing axes: four waves per 64 lanes, the right-hand sides never leave the chip (spline_build_wide_kernel).
-        // NDI_SPLINE_WIDE=0 / 1: A/B (1 takes it for every width).
-        static const Knob wide_knob{"NDI_SPLINE_WIDE", -1, Knob::live};
-        const int wide_env = wide_knob.get();
-        if (!A.kout && n >= 4 && (wide_env > 0 || (wide_env < 0 && lanes >= 1024))) {
-          constexpr int RW = 16, RBW = 3 * RW;       // rows per producer wave / per block
-          const size_t shm = (size_t)(4 * RBW * 64 + 2 * 4 * RBW) * sizeof(T);
-          auto kern = spline_build_wide_kernel<T, RW>;
-          allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)shm);
-          hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shm, s, A);
-          break;
-        }
-        const unsigned gr = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n * lanes + BLOCK - 1) / BLOCK, 65536));
-        hipLaunchKernelGGL((spline_rhs_kernel<T, false>), dim3(gr), dim3(BLOCK), 0, s, A);
-        if (A.kout) hipLaunchKernelGGL((spline_build_general_kernel<T, false, true>), dim3(grid), dim3(64), 0, s, A);
-        else hipLaunchKernelGGL((spline_build_general_kernel<T, false, false>), dim3(grid), dim3(64), 0, s, A);
-        break;
-      }
-      case SPLINE_PARABOLA3:
-        hipLaunchKernelGGL(spline_build_n3_kernel<T>, dim3(grid), dim3(64), 0, s, A, 0);
-        break;
-      case SPLINE_PERIODIC3:
-        hipLaunchKernelGGL(spline_build_n3_kernel<T>, dim3(grid), dim3(64), 0, s, A, 1);
-        break;
-      case SPLINE_PERIODIC:
-        hipLaunchKernelGGL(spline_build_periodic_kernel<T>, dim3(grid), dim3(64), 0, s, A);
-        break;
-    }
-    NDI_HIP(hipGetLastError());
-    StatusBlock hs{};
-    NDI_HIP(hipMemcpy(&hs, tmp_p, sizeof(hs), hipMemcpyDeviceToHost));  // synchronises
-    if (hs.periodic_mismatch != 0)
-      return fail(NDI_VALUE,
-                  "for periodic boundary condition the first and last value must be equal "
-                  "(%llu lane(s) differ)", hs.periodic_mismatch);
-    // Extrapolate::{No,Yes,Periodic}, cubic_spline.rs:763-769
-    if (mode != EX_NO && periodic) mode = EX_PERIODIC;
-    return NDI_OK;
-  }
-
-  // BoundaryCondition::Individual (cubic_spline.rs:332-347 + solve_for_k_individual :370-403): one scalar
-  // solve per trailing element in the reference; here every lane picks its end kinds / values and one of
-  // the precomputed elimination plans (4 left kinds x 4 right kinds, kind 3 = the n == 3 parabola rows).
-  ndi_status build_spline_individual(const ndi_interp1d_desc& d) {
-    const T* x = pyr.host_knots.data();
-    std::vector<uint8_t> cls(lanes);
-    std::vector<T> lval(lanes), rval(lanes);
-    for (uint64_t l = 0; l < lanes; ++l) {
-      int lk, rk;
-      double lv, rv;
-      specialize_end(d.lane_left_kind[l], d.lane_left_value[l], lk, lv);
-      specialize_end(d.lane_right_kind[l], d.lane_right_value[l], rk, rv);
-      if (n == 3 && lk == END_NOT_A_KNOT && rk == END_NOT_A_KNOT) lk = rk = 3;  // :569-596
-      cls[l] = (uint8_t)(lk | (rk << 2));
-      lval[l] = T(lv);
-      rval[l] = T(rv);
-    }
-    static const int to_ndi[3] = {NDI_BC_NOT_A_KNOT, NDI_BC_FIRST_DERIV, NDI_BC_SECOND_DERIV};
-    std::vector<T> w4(4 * n, T(0)), midp4(4 * n, T(1)), up0_4(4, T(0)), wl(16, T(0)), midl(16, T(1));
-    SplinePlan<T> ref;
-    for (int lk = 0; lk < 3; ++lk)
-      for (int rk = 0; rk < 3; ++rk) {
-        SplinePlan<T> P = make_spline_plan<T>(x, n, false, to_ndi[lk], 0.0, to_ndi[rk], 0.0);
-        int a = lk, b = rk;
-        if (P.mode == SPLINE_PARABOLA3) a = b = 3;
-        for (uint64_t i = 0; i + 1 < n; ++i) {
-          w4[a * n + i] = P.w[i];
-          midp4[a * n + i] = P.midp[i];
-        }
-        up0_4[a] = P.up[0];
-        wl[a * 4 + b] = P.w[n - 1];
-        midl[a * 4 + b] = P.midp[n - 1];
-        if (lk == 2 && rk == 2) ref = P;  // a general-mode plan: shared dx / interior up / not-a-knot scalars
-        if (P.mode != SPLINE_PARABOLA3 && lk == 0) { ref.nkL_tmp1 = P.nkL_tmp1; ref.nkL_d = P.nkL_d; }
-        if (P.mode != SPLINE_PARABOLA3 && rk == 0) { ref.nkR_tmp1 = P.nkR_tmp1; ref.nkR_d = P.nkR_d; }
-      }
-    {  // not-a-knot row scalars depend on x only; take them from plans that have them (n == 3 included)
-      SplinePlan<T> PL = make_spline_plan<T>(x, n, false, NDI_BC_NOT_A_KNOT, 0.0, NDI_BC_FIRST_DERIV, 0.0);
-      SplinePlan<T> PR = make_spline_plan<T>(x, n, false, NDI_BC_FIRST_DERIV, 0.0, NDI_BC_NOT_A_KNOT, 0.0);
-      ref.nkL_tmp1 = PL.nkL_tmp1; ref.nkL_d = PL.nkL_d;
-      ref.nkR_tmp1 = PR.nkR_tmp1; ref.nkR_d = PR.nkR_d;
-    }
-    const size_t tab = (size_t)(n - 1) * lanes * sizeof(T);
-    ca.reserve(tab);
-    cb.reserve(tab);
-    std::vector<T> pack;
-    auto put = [&pack](const std::vector<T>& v) { size_t o = pack.size(); pack.insert(pack.end(), v.begin(), v.end()); return o; };
-    const size_t o_dx = put(ref.dx), o_up = put(ref.up), o_w4 = put(w4), o_m4 = put(midp4), o_u0 = put(up0_4),
-                 o_wl = put(wl), o_ml = put(midl), o_lv = put(lval), o_rv = put(rval);
-    DevBuf plan, dcls;
-    plan.reserve(pack.size() * sizeof(T));
-    NDI_HIP(hipMemcpy(plan.p, pack.data(), pack.size() * sizeof(T), hipMemcpyHostToDevice));
-    dcls.reserve(lanes);
-    NDI_HIP(hipMemcpy(dcls.p, cls.data(), lanes, hipMemcpyHostToDevice));
-    BuildArgs<T> A{};
-    A.data = data.as<T>();
-    A.ca = ca.as<T>();
-    A.cb = cb.as<T>();
-    const T* base = plan.as<T>();
-    A.dx = base + o_dx; A.up = base + o_up; A.w = base + o_w4; A.midp = base + o_m4;
-    A.w4 = base + o_w4; A.midp4 = base + o_m4; A.up0_4 = base + o_u0; A.wl = base + o_wl; A.midl = base + o_ml;
-    A.lane_lval = base + o_lv; A.lane_rval = base + o_rv;
-    A.lane_cls = dcls.as<uint8_t>();
-    A.n = n;
-    A.lanes = lanes;
-    A.nkL_tmp1 = ref.nkL_tmp1; A.nkL_d = ref.nkL_d; A.nkR_tmp1 = ref.nkR_tmp1; A.nkR_d = ref.nkR_d;
-    A.dx0_sq = ref.dx0_sq; A.dxl_sq = ref.dxl_sq;
-    const unsigned gr = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n * lanes + BLOCK - 1) / BLOCK, 65536));
-    hipLaunchKernelGGL((spline_rhs_kernel<T, true>), dim3(gr), dim3(BLOCK), 0, (hipStream_t) nullptr, A);
-    A.kout = reserve_k();
-    if (A.kout)
-      hipLaunchKernelGGL((spline_build_general_kernel<T, true, true>), dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0,
-                         (hipStream_t) nullptr, A);
-    else
-      hipLaunchKernelGGL((spline_build_general_kernel<T, true, false>), dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0,
-                         (hipStream_t) nullptr, A);
-    NDI_HIP(hipGetLastError());
-    NDI_HIP(hipDeviceSynchronize());
-    return NDI_OK;
-  }
-
-  // ---- build of the local cubics: Pchip, Akima, CubicHermite (hermite_kernels.hpp) -----------------------
-  // One launch, no host plan, no temporaries: the knots are the pyramid's level 0, already resident.  `dydx` (HR_GIVEN):
-  // the caller's derivatives in `memspace`.  Like the spline build it runs on the NULL stream and the tables are complete
-  // when create returns.
-  template <int RULE>
-  void launch_hermite(const HermiteArgs<T>& A, bool vec) {
-    constexpr int VN = Wide<T>::N;
-    const uint64_t total = (n - 1) * (vec ? lanes / VN : lanes);
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + BLOCK - 1) / BLOCK, 1u << 20));
-    if (vec) hipLaunchKernelGGL((hermite_build_kernel<T, RULE, VN>), dim3(grid), dim3(BLOCK), 0, (hipStream_t) nullptr, A);
-    else hipLaunchKernelGGL((hermite_build_kernel<T, RULE, 1>), dim3(grid), dim3(BLOCK), 0, (hipStream_t) nullptr, A);
-  }
-
-  ndi_status build_hermite(const void* dydx, int memspace) {
-    Range rg("ndi:hermite_build");
-    const size_t tab = (size_t)(n - 1) * lanes * sizeof(T);
-    ca.reserve(tab);
-    cb.reserve(tab);
-    HermiteArgs<T> A{};
-    A.data = data.as<T>();
-    A.x = pyr.view.lv0;
-    A.ca = ca.as<T>();
-    A.cb = cb.as<T>();
-    A.n = n;
-    A.lanes = lanes;
-    A.kout = reserve_k();
-    DevBuf tmp;
-    if (rule == HR_GIVEN) {
-      if (memspace == NDI_MEM_DEVICE) {
-        A.dydx = static_cast<const T*>(dydx);
-      } else {   // host derivatives: uploaded into the kept k table where there is one, else into a temporary
-        T* dst = A.kout;
-        if (!dst) {
-          tmp.reserve((size_t)n * lanes * sizeof(T));
-          dst = tmp.as<T>();
-        }
-        NDI_HIP(hipMemcpy(dst, dydx, (size_t)n * lanes * sizeof(T), hipMemcpyHostToDevice));
-        A.dydx = dst;
-        A.kout = nullptr;
-      }
-    }
-    auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool vec = lanes % Wide<T>::N == 0 && aligned(A.data) && aligned(A.ca) && aligned(A.cb) && aligned(A.kout) &&
-                     aligned(A.dydx);
-    if (rule == HR_PCHIP) launch_hermite<HR_PCHIP>(A, vec);
-    else if (rule == HR_AKIMA) launch_hermite<HR_AKIMA>(A, vec);
-    else launch_hermite<HR_GIVEN>(A, vec);
-    NDI_HIP(hipGetLastError());
-    NDI_HIP(hipStreamSynchronize(nullptr));   // the tables are complete when create() returns: any stream may read them
-    return NDI_OK;
-  }
+  // ---- build: the CubicSpline tables (CubicSpline::build, cubic_spline.rs:754-771) and the local cubics -- Pchip, Akima,
+  // CubicHermite (hermite_kernels.hpp).  Both, with the forms they dispatch over: spline_build_host.hpp.
+  ndi_status build_spline(const ndi_interp1d_desc& d);
+  ndi_status build_hermite(const void* dydx, int memspace);
 
   // ---- evaluation core on device pointers --------------------------------------------------
   // A batch is evaluated in two stages that may run on different streams: prep() = search (+ grouping) into a
   // scratch set, launch_eval() = the evaluation kernel reading that set.  Plan1 carries what prep() decided.
-  struct Plan1 {
-    enum Kind { SMALL, BUCKETED, ROWS, FLAT, FUSED, BUCKETED_SHORT, LANES } kind = ROWS;
-    const T* q = nullptr;
-    uint64_t nq = 0;
-    T* out = nullptr;
-    uint64_t out_stride = 0;
-    bool vec_ok = false;
-    uint64_t LV = 0;
-    // FUSED (eval_fused_kernel)
-    bool f_lut = false, f_pack = false;
-    bool f_sorted = false;   // FUSED: the queries of a workgroup round ordered by interval in LDS (eval_fused_sorted_kernel)
-    int f_tlds = 0;   // 0: tables from memory, 1: {y, a, b} in LDS, 2: {y, k} in LDS
-    unsigned f_tb = 256, f_grid = 1;
-    int f_unr = 2;
-    size_t f_lds = 0;
-    int s_cq = 64;   // BUCKETED_SHORT
-    int l_qpl = 1;   // LANES, scalar data: queries per lane (1, or one 16-byte vector)
-    bool l_check = false;   // LANES: no range pre-pass, the kernel checks the queries itself (NDI_EVAL_FRESH_OUTPUT)
-  };
+  // Both, with the planners and launchers they call: interp1d_host.hpp.
+  using Plan = Plan1<T>;      // (the engine in float_host.hpp reads Impl::Plan)
+  Plan prep(hipStream_t s, Scratch& sc, const T* q, uint64_t nq, T* out, uint64_t out_stride, int path,
+            bool beside_eval = false, int flags = 0);
+  void launch_eval(hipStream_t s, Scratch& sc, const Plan& P);
 
   // LDS footprint of eval_scalar_kernel / eval_lanes_kernel: [knots | dense index | interval records | table records | strips]
   size_t lanes_lds_bytes(unsigned tb) const {
@@ -1516,82 +1145,15 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     return b;
   }
 
-  // Query per lane with the whole table set in LDS (eval_scalar_kernel / eval_lanes_kernel): rows of up to 56 bytes
-  // whose records fit LDS beside the knots, an axis the branch-free search covers (dense bucket index
-  // or exact O(1) guess), batches that give every workgroup several times its staging bytes to write.
-  // NDI_LANES_KERNEL=0 leaves these shapes to the query-order kernel (A/B); =1 takes it whenever it fits.
-  bool plan_lanes(hipStream_t s, Scratch& sc, Plan1& P, int path, int flags) {
-    // rows of up to 56 bytes: at 64 bytes the query-order kernel is level (f64 x 8: 65 vs 61-65 Gqueries/s) or ahead
-    // (f32 x 16: 74 vs 57), profiles/r05_small_shapes_rates.txt
-    static const Knob on_knob{"NDI_LANES_KERNEL", -1, Knob::live};
-    const int on = on_knob.get();
-    constexpr int maxb = 56;
-    if (on == 0 || path == NDI_PATH_BUCKETED || n < 3 || n > 16384) return false;
-    if (on < 0 && short_knobs().mode != 0) return false;   // a pinned short-row variant (NDI_SHORT_MODE) is what runs
-    if (lanes * sizeof(T) > (size_t)(on > 0 ? std::max(maxb, 64) : maxb)) return false;   // (forced: up to 64 bytes, for the tests)
-    const size_t tab = ((size_t)n * sizeof(T)) + (size_t)(n - 1) * (4 + lanes * 4) * sizeof(T);   // (before the index is known)
-    if (tab > FUSED_LDS_LIMIT) return false;
-    if (on < 0 && (P.nq < 65536 || (double)P.nq * (double)lanes * sizeof(T) < 4.0 * (double)cu_count() * (double)tab)) return false;
-    pyr.ensure_dense_lut();
-    if (!pyr.dense_ok) return false;
-    // workgroup: 256 threads when four or more fit a CU beside each other (small tables: the staging pass is cheap and
-    // short workgroups retire independently), else 1024
-    P.f_tb = lanes_lds_bytes(256) * 4 <= 160 * 1024 ? 256u : 1024u;
-    if (lanes_lds_bytes(P.f_tb) > FUSED_LDS_LIMIT) P.f_tb = 256u;   // (the strips of 16 waves do not fit: 4 waves)
-    P.f_lds = lanes_lds_bytes(P.f_tb);
-    if (P.f_lds > FUSED_LDS_LIMIT) return false;
-    constexpr int VN = Wide<T>::N;
-    P.l_qpl = (lanes == 1 && P.out_stride == 1 && aligned16(P.q) && aligned16(P.out)) ? VN : 1;
-    const uint64_t per_wg = (uint64_t)P.f_tb * (lanes == 1 ? (uint64_t)P.l_qpl : 1);
-    P.f_grid = resident_grid(P.nq, per_wg, P.f_lds, P.f_tb);
-    P.kind = Plan1::LANES;
-    P.l_check = this->range_prepass(s, sc, {P.q, nullptr}, P.nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
-    return true;
+  // The per-wave strips of eval_fused_kernel: an interval index and one operand (two: Linear, or the {y, k} form) per lane
+  static size_t fused_strip_bytes(unsigned tb, bool strip2) {
+    return (size_t)(tb / 64) * 64 * (sizeof(uint32_t) + (strip2 ? 2 : 1) * sizeof(T));
   }
-
-  void launch_lanes(hipStream_t s, Scratch& sc, const Plan1& P) {
-    EvalLanesArgs<T> F{};
-    F.knots = pyr.view.lv0;
-    F.n = (uint32_t)n;
-    F.dl = pyr.dlut;
-    F.data = data.as<T>();
-    F.ca = ca.as<T>();
-    F.cb = cb.as<T>();
-    F.q = P.q;
-    F.out = P.out;
-    F.nq = P.nq;
-    F.out_stride = P.out_stride;
-    F.lanes = (uint32_t)lanes;
-    F.mode = mode;
-    F.first_fail = &sc.status.as<StatusBlock>()->first_fail[0];
-    F.check = P.l_check ? 1 : 0;
-    if (trace_plan())
-      std::fprintf(stderr, "[ndi plan] lanes L=%llu qpl=%d index=%s m=%u maxk=%u tb=%u grid=%u lds=%zu prepass=%d\n", (unsigned long long)lanes,
-                   P.l_qpl, pyr.dlut.lut ? "dense" : "guess", pyr.dlut.m, pyr.dlut.maxk, P.f_tb, P.f_grid, P.f_lds, P.l_check ? 0 : 1);
-    constexpr int VN = Wide<T>::N;
-    const dim3 grid(P.f_grid), block(P.f_tb);
-    pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
-      constexpr int ST = st_;
-      pick_or<256, 1024>((int)P.f_tb, [&](auto tb_) {
-        constexpr int TB = tb_;
-        if (lanes == 1)
-          pick_or<1, VN>(P.l_qpl, [&](auto qpl_) {
-            launch_lds<T>(eval_scalar_kernel<T, ST, qpl_, TB>, FUSED_LDS_LIMIT, s, PC_EVAL, grid, block, P.f_lds, F);
-          });
-        else
-          pick_or<0, 2, 5, 8>((int)lanes, [&](auto lc_) {
-            launch_lds<T>(eval_lanes_kernel<T, ST, lc_, TB>, FUSED_LDS_LIMIT, s, PC_EVAL, grid, block, P.f_lds, F);
-          });
-      });
-    });
-  }
-
   // LDS footprint of eval_fused_kernel: [pyramid | lut | per-wave strips | tables]
   size_t fused_lds_bytes(bool with_lut, unsigned tb, int tables) const {
     size_t b = (pyr.lds_bytes + 15) & ~(size_t)15;
     if (with_lut) b += pyr.lut_bytes;
-    const bool strip2 = strategy != NDI_CUBIC_SPLINE || tables == 2;
-    b += (size_t)(tb / 64) * 64 * (sizeof(uint32_t) + (strip2 ? 2 : 1) * sizeof(T));
+    b += fused_strip_bytes(tb, strategy != NDI_CUBIC_SPLINE || tables == 2);
     if (tables) {
       const size_t rows = tables == 2 ? 2 * n : (strategy == NDI_CUBIC_SPLINE ? 3 * n - 2 : n);
       b += rows * lanes * sizeof(T);
@@ -1599,480 +1161,18 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     return b;
   }
 
-  // Query-order fused search + evaluation (short rows): decides the variant and its launch shape, and enqueues the
-  // range pre-pass the kernel relies on.  Returns false when the shape is not eligible.
-  bool plan_fused(hipStream_t s, Scratch& sc, Plan1& P, const ShortKnobs& K, int flags = 0) {
-    const uint64_t LV = P.LV;
-    if (LV == 0 || 64ull * LV * LV >= (1ull << 32) || (uint64_t)n * LV >= (1ull << 32) * 1ull) return false;   // 32-bit item / vector indices
-    // (axes beyond half the LDS: one large workgroup per CU; the bucket index: A/B settled in round 3)
-    if (pyr.lds_bytes > LDS_STAGE_LIMIT - 8 * 1024) {
-      // Axes too long for LDS: the same kernel with the knots left in global memory and searched through the u32 bucket
-      // index (TLDS == 3) -- one launch, no idx[] / t[] round trip.  Batches below 4096 queries keep the two-kernel form.
-      if (P.nq < 4096) return false;
-      pyr.ensure_bucket_index32();
-      P.f_lut = false;
-      P.f_unr = 2;
-      P.f_tlds = 3;
-      P.f_tb = 256;
-      const bool strip2 = strategy != NDI_CUBIC_SPLINE;
-      P.f_lds = (size_t)(256 / 64) * 64 * (sizeof(uint32_t) + (strip2 ? 2 : 1) * sizeof(T));
-      P.f_pack = (K.pack > 0 || (K.pack < 0 && lanes * sizeof(T) < 128)) && ensure_packed(s);
-      P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((P.nq + 255) / 256, (uint64_t)cu_count() * 8 * 4));
-      P.kind = Plan1::FUSED;
-      P.l_check = this->range_prepass(s, sc, {P.q, nullptr}, P.nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
-      return true;
-    }
-    if (P.nq >= 4096) pyr.ensure_bucket_index();
-    // the bucket index beside the knots when it costs no more than half the waves a CU could hold without it
-    auto waves_at = [&](bool with_lut, unsigned tb) -> size_t {
-      const size_t need = fused_lds_bytes(with_lut, tb, 0);
-      return need > LDS_STAGE_LIMIT ? 0 : wgs_per_cu(need, tb) * (tb / 64);
-    };
-    auto best_tb = [&](bool with_lut, unsigned& tb_out) -> size_t {
-      size_t best = 0;
-      for (unsigned tb : {256u, 512u, 1024u}) {
-        const size_t w = waves_at(with_lut, tb);
-        if (w > best) { best = w; tb_out = tb; }
-      }
-      return best;
-    };
-    unsigned tb_plain = 256, tb_lut = 256;
-    const size_t w_plain = best_tb(false, tb_plain);
-    const size_t w_lut = (P.nq >= 4096 && pyr.lut_bytes != 0) ? best_tb(true, tb_lut) : 0;
-    if (w_plain == 0 && w_lut == 0) return false;
-    P.f_lut = w_lut != 0 && 2 * w_lut >= w_plain;
-    const unsigned tb_auto = P.f_lut ? tb_lut : tb_plain;
-    P.f_unr = (K.unr == 1 || K.unr == 4) ? K.unr : 2;
-    // Tables in LDS when they fit beside everything else, and when the batch gives every workgroup several times the
-    // table size to write (the staging pass is per workgroup).  Workgroup size: the one that keeps most waves on a
-    // CU beside the tables; among equals the largest (fewest staging passes).
-    // {y, k} (the spline's derivatives, kept by small builds) is two thirds of {y, a, b}: it fits where the latter
-    // does not, and leaves room for more waves where both do.  NDI_FUSED_LDS = 1 / 2 pins the form.
-    P.f_tlds = 0;
-    P.f_tb = (K.tb == 512 || K.tb == 1024) ? (unsigned)K.tb : tb_auto;
-    if (K.lds != 0) {
-      size_t best_waves = 0;
-      const bool yk_ok = strategy == NDI_CUBIC_SPLINE && ck.p;
-      const int pinned = (K.lds == 2 && !yk_ok) ? 1 : K.lds;
-      for (int form : {1, 2}) {   // equal wave counts: {y, a, b} (no per-item re-forming; 2-3 % faster where both fit)
-        if (form == 2 && !yk_ok) continue;
-        if (pinned > 0 && pinned <= 2 && pinned != form) continue;
-        for (unsigned tb : {1024u, 512u, 256u}) {
-          if (K.tb && (unsigned)K.tb != tb) continue;
-          const size_t need = fused_lds_bytes(P.f_lut, tb, form);
-          if (need > FUSED_LDS_LIMIT) continue;
-          const size_t waves = wgs_per_cu(need, tb) * (tb / 64);
-          if (waves > best_waves) {
-            best_waves = waves;
-            P.f_tlds = form;
-            P.f_tb = tb;
-          }
-        }
-      }
-      const size_t tab = fused_lds_bytes(false, 64, P.f_tlds) - fused_lds_bytes(false, 64, 0);
-      // not for small batches (the staging pass is per workgroup), and not for Linear rows of 128 B (f32: 64 B) or more:
-      // two operand reads per item from L2 beat the workgroups that fit around a 64-128 KiB table (f32 x 32: 5.6 vs 4.9
-      // TB/s, f32 x 16: 5.25 vs 4.76; f64 x 8 and f32 x 8 stay in LDS: 3.75 vs 2.8, 4.0 vs 2.8)
-      if (P.f_tlds && K.lds < 0 && (P.nq * lanes * sizeof(T) < 8 * (size_t)cu_count() * tab ||
-                                    (strategy != NDI_CUBIC_SPLINE && lanes * sizeof(T) >= (sizeof(T) == 4 ? 64 : 128)))) {
-        P.f_tlds = 0;
-        P.f_tb = (K.tb == 512 || K.tb == 1024) ? (unsigned)K.tb : tb_auto;
-      }
-    }
-    P.f_lds = fused_lds_bytes(P.f_lut, P.f_tb, P.f_tlds);
-    // rows shorter than a cache line read from L2: one contiguous record per interval instead of three row pieces
-    P.f_pack = !P.f_tlds && (K.pack > 0 || (K.pack < 0 && lanes * sizeof(T) < 128)) && ensure_packed(s);
-    // Tables from L2, rows of 64 bytes and more, a large batch on an axis of up to 4096 intervals: the workgroup-local
-    // interval order (eval_fused_sorted_kernel: the operand rows of neighbouring items coincide and come from L1 -- the
-    // query-order form is bound by the L2 request rate on these).  NDI_FUSED_SORTED=0 / 1: A/B.
-    {
-      static const Knob fs_knob{"NDI_FUSED_SORTED", -1, Knob::live};
-      const int fs = fs_knob.get();
-      const bool cubic = strategy == NDI_CUBIC_SPLINE;
-      const size_t lds_s = ((pyr.lds_bytes + 15) & ~(size_t)15) + (P.f_lut ? pyr.lut_bytes : 0) + (((size_t)(n - 1) * 4 + 15) & ~(size_t)15) +
-                           (size_t)4096 / (cubic ? 1 : 2) * (4 + (cubic ? 1 : 2) * sizeof(T));
-      // AUTO: where it was measured ahead (profiles/r05_tuning.md 10): CubicSpline (four operand rows per output row), rows of
-      // 128 bytes and more, at least two queries per interval and round (4096 queries: axes of up to 2049 knots)
-      P.f_sorted = fs != 0 && !P.f_tlds && n >= 3 && n - 1 <= 4096 && LV >= 2 && lanes * sizeof(T) >= 64 && lds_s <= FUSED_LDS_LIMIT - 256 &&
-                   (fs > 0 || (cubic && lanes * sizeof(T) >= 128 && n - 1 <= 2048 && P.nq >= (1u << 18)));
-      if (P.f_sorted) {
-        P.f_pack = false;
-        P.f_tb = 512;
-        P.f_lds = lds_s;
-        const size_t per_cu = std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds_s, 4));
-        const uint64_t nqw = cubic ? 4096 : 2048;
-        P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((P.nq + nqw - 1) / nqw, (uint64_t)cu_count() * per_cu * 4));
-        P.kind = Plan1::FUSED;
-        P.l_check = this->range_prepass(s, sc, {P.q, nullptr}, P.nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
-        return true;
-      }
-    }
-    const uint64_t want = (uint64_t)cu_count() * (K.wgs > 0 ? (size_t)K.wgs : wgs_per_cu(P.f_lds, P.f_tb) * (P.f_tlds ? 1 : 4));
-    P.f_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((P.nq + P.f_tb - 1) / P.f_tb, want));
-    P.kind = Plan1::FUSED;
-    P.l_check = this->range_prepass(s, sc, {P.q, nullptr}, P.nq, (flags & NDI_EVAL_FRESH_OUTPUT) != 0);
-    return true;
-  }
-
-  Plan1 prep(hipStream_t s, Scratch& sc, const T* q, uint64_t nq, T* out, uint64_t out_stride, int path,
-             bool beside_eval = false, int flags = 0) {
-    Plan1 P;
-    P.q = q; P.nq = nq; P.out = out; P.out_stride = out_stride;
-    sc.status.reserve(sizeof(StatusBlock));
-    reset_status(sc.status.p, s);
-    StatusBlock* st = sc.status.as<StatusBlock>();
-
-    // 1-2 lanes: one thread per query (search + evaluation in one launch, tables gathered from L2) is the latency path
-    // and the faster one up to a few million queries; beyond, the query-order kernel with the tables in LDS takes over
-    // (scalar data at 1e8 queries: 98 -> 157 Gqueries/s f64, 2 lanes 45 -> 141).  Measured crossover
-    // (profiles/r04_scalar_crossover.jsonl): ~8e6 output elements on <= 1024 knots, proportionally earlier on longer
-    // axes (8192 knots: ~1e6), whose table gathers miss L1.
-    if (plan_lanes(s, sc, P, path, flags)) return P;
-    constexpr long small_maxq = 8000000;
-    const bool small_first = lanes <= 2 && pyr.lds_bytes <= LDS_STAGE_LIMIT;
-    const double small_work = (double)nq * (double)lanes * (double)std::max<uint64_t>(n, 1024) / 1024.0;
-    if (small_first && small_work >= (double)small_maxq) {
-      const ShortKnobs K0 = short_knobs();
-      constexpr int VN0 = Wide<T>::N;
-      P.vec_ok = (lanes % VN0 == 0) && (out_stride % VN0 == 0) && aligned16(out);
-      P.LV = P.vec_ok ? lanes / VN0 : lanes;
-      if (K0.mode != 1 && K0.mode != 3 && plan_fused(s, sc, P, K0, flags)) return P;
-    }
-    if (small_first) {
-      // short trailing axes: range pre-check (so rows after the first failing query stay untouched in the
-      // caller's buffer), then search + evaluation fused in one launch -- no index / t round trip through HBM
-      P.kind = Plan1::SMALL;
-      this->range_prepass(s, sc, {q, nullptr}, nq, false);
-      return P;
-    }
-    constexpr int VN = Wide<T>::N;
-    P.vec_ok = (lanes % VN == 0) && (out_stride % VN == 0) && aligned16(out);
-    P.LV = P.vec_ok ? lanes / VN : lanes;
-    const bool rows_ok = P.vec_ok && P.LV >= (uint64_t)BLOCK;
-    const ShortKnobs K = short_knobs();
-    // rows shorter than one workgroup pass (or unaligned): grouped from a few hundred bytes per row upwards when the
-    // batch has enough queries per interval, else query order with the search fused in
-    const bool short_rows = !rows_ok || (P.vec_ok && P.LV < (uint64_t)K.maxlv);
-    // (axes whose interval histogram does not fit LDS are grouped with global atomics, as long rows are)
-    const bool group_ok = nq < 0xffffffffull && P.vec_ok && P.LV < (uint64_t)BLOCK;
-    bool bucketed = false, grouped_short = false;
-    if (path == NDI_PATH_BUCKETED) {
-      bucketed = rows_ok && nq < 0xffffffffull;
-      grouped_short = short_rows && group_ok && K.mode != 1 && K.mode != 2;
-    } else if (path == NDI_PATH_AUTO) {
-      bucketed = rows_ok && nq < 0xffffffffull && nq >= 5 * (n - 1);  // measured crossover (tools/auto_threshold.py)
-      // (Linear reads two operand rows per item instead of four: its query-order form already runs at 5-6 TB/s on rows
-      //  of 128 B - 2 KiB and beats the grouped form everywhere: profiles/r04_short_rows_linear_sweep.txt)
-      grouped_short = short_rows && group_ok && nq >= 5 * (n - 1) &&
-                      (K.mode == 3 ||
-                       // Linear: only when its one table outgrows L2 and the rows are 1 KiB or more (16 384 knots x 512 f32
-                       // lanes, 33.6 MB: 3.54 vs 2.55 TB/s)
-                       (K.mode == 0 && strategy != NDI_CUBIC_SPLINE && lanes * sizeof(T) >= 1024 &&
-                        (size_t)n * lanes * sizeof(T) >= ((size_t)8 << 20)) ||
-                       (K.mode == 0 && strategy == NDI_CUBIC_SPLINE &&
-                                       (lanes * sizeof(T) >= (uint64_t)K.rowb ||
-                                        // tables that outgrow L2 (its 4 MiB per XCD): the query-order form re-reads them
-                                        // from memory per query, the grouped form once per interval -- from 512-byte rows
-                                        // (8192 knots x 128 f32 lanes, 12.6 MB: 3.94 vs 2.21 TB/s; tools/group_vs_fused_probe.py)
-                                        (lanes * sizeof(T) >= 512 && (size_t)(3 * n - 2) * lanes * sizeof(T) >= ((size_t)8 << 20)))));
-    }
-    if (short_rows && !grouped_short && !bucketed && K.mode != 1 && K.mode != 3 && plan_fused(s, sc, P, K, flags)) return P;
-    g_last_path.store(bucketed || grouped_short ? NDI_PATH_BUCKETED : NDI_PATH_GATHER);
-    sc.idx.reserve(nq * sizeof(uint32_t));   // the two-kernel forms: interval index (and t) per query
-    if (strategy == NDI_CUBIC_SPLINE) sc.t.reserve(nq * sizeof(T));
-    T* t_out = strategy == NDI_CUBIC_SPLINE ? sc.t.as<T>() : nullptr;
-
-    if (bucketed || grouped_short) {
-      P.kind = bucketed ? Plan1::BUCKETED : Plan1::BUCKETED_SHORT;
-      P.s_cq = K.cq;
-      const uint32_t nb = (uint32_t)(n - 1);
-      sc.counts.reserve(((size_t)nb + 4) * sizeof(uint32_t));   // (+4: the fused scan reads / writes 16-byte pieces)
-      sc.cursor.reserve(((size_t)nb + 4) * sizeof(uint32_t));
-      sc.perm.reserve(nq * sizeof(uint4));
-      const T* sval = strategy == NDI_CUBIC_SPLINE ? (const T*)sc.t.as<T>() : q;   // t (cubic) / raw x (linear)
-      if (lds_sort_fits(pyr, nb)) {
-        // block-local counting sort: histogram per query slice in LDS, no global atomics
-        sc.hist.reserve((size_t)GROUP_MAX_BLOCKS * nb * sizeof(uint32_t));
-        uint64_t slice = 0;
-        uint32_t blocks = 0;
-        run_locate<T>(s, pyr, q, nq, sc.idx.as<uint32_t>(), nullptr, t_out,
-                      &st->first_fail[0], mode, sc.hist.as<uint32_t>(), nb, &slice, &blocks, beside_eval);
-        ProfScope ps(s, PC_GROUP);
-        hipLaunchKernelGGL(group_offsets_scan_kernel, dim3((nb + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s,
-                           sc.hist.as<uint32_t>(), blocks, nb, sc.counts.as<uint32_t>(), sc.cursor.as<uint32_t>(), st,
-                           nq, 0u, (uint32_t*)nullptr);
-        allow_dynamic_lds(reinterpret_cast<const void*>(&group_scatter_kernel<T>), (int)(GROUP_MAX_BINS * 4));
-        hipLaunchKernelGGL(group_scatter_kernel<T>, dim3(blocks), dim3(BLOCK), (size_t)nb * 4, s,
-                           (const uint32_t*)sc.idx.as<uint32_t>(), sval, nq, slice,
-                           (const uint32_t*)sc.hist.as<uint32_t>(), (const uint32_t*)sc.cursor.as<uint32_t>(),
-                           nb, sc.perm.as<uint4>());
-        NDI_HIP(hipGetLastError());
-        ps.done();
-      } else {
-        // many intervals: histogram and placement with global atomics
-        run_locate<T>(s, pyr, q, nq, sc.idx.as<uint32_t>(), nullptr, t_out, &st->first_fail[0], mode);
-        ProfScope ps(s, PC_GROUP);
-        NDI_HIP(hipMemsetAsync(sc.counts.p, 0, (size_t)nb * sizeof(uint32_t), s));
-        const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 2048));
-        hipLaunchKernelGGL(bucket_count_kernel, dim3(g), dim3(BLOCK), 0, s, (const uint32_t*)sc.idx.as<uint32_t>(), nq,
-                           (const StatusBlock*)st, sc.counts.as<uint32_t>());
-        hipLaunchKernelGGL(bucket_scan_kernel<256>, dim3(1), dim3(256), 0, s, sc.counts.as<uint32_t>(), nb,
-                           sc.cursor.as<uint32_t>(), st);
-        hipLaunchKernelGGL(bucket_scatter_kernel<T>, dim3(g), dim3(BLOCK), 0, s, (const uint32_t*)sc.idx.as<uint32_t>(),
-                           sval, nq, (const StatusBlock*)st, sc.cursor.as<uint32_t>(), sc.perm.as<uint4>());
-        NDI_HIP(hipGetLastError());
-        ps.done();
-      }
-      return P;
-    }
-    run_locate<T>(s, pyr, q, nq, sc.idx.as<uint32_t>(), nullptr, t_out, &st->first_fail[0], mode);
-    P.kind = rows_ok ? Plan1::ROWS : Plan1::FLAT;
-    return P;
-  }
-
-  // The long-row grouped evaluation: eval_bucketed_kernel for one chunk, eval_bucketed_group_kernel (GROUP) for the chunks
-  // of a ring group.  U vectors per thread by row length, gx workgroups per segment row; rows of whole segments only
-  // take the straight-line kernel variant.
+  // The long-row grouped evaluation (launch_bucketed, interp1d_host.hpp): eval_bucketed_kernel for one chunk,
+  // eval_bucketed_group_kernel for the chunks of a ring group.
   static constexpr int BUCKETED_CQ = 128;   // queries per chunk of the two kernels: their CQ, and the unit of both grids
-  template <bool GROUP, class Args>
-  void launch_bucketed(hipStream_t s, uint64_t LV, unsigned gx, const Args& A) {
-    constexpr int CQ = BUCKETED_CQ;
-    const int U = LV >= 2048 ? 8 : (LV >= 1024 ? 4 : (LV >= 512 ? 2 : 1));
-    const uint64_t segs = (LV + (uint64_t)BLOCK * U - 1) / ((uint64_t)BLOCK * U);
-    const dim3 grid(gx, (unsigned)std::min<uint64_t>(segs, 64));
-    const bool full = LV % ((uint64_t)BLOCK * U) == 0;
-    pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
-      constexpr int ST = st_;
-      pick_or<1, 8, 4, 2>(U, [&](auto u_) {
-        constexpr int UU = u_;
-        pick_bool(full, [&](auto full_) {
-          if constexpr (GROUP) launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_bucketed_group_kernel<T, ST, UU, CQ, true, full_>, A);
-          else launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_bucketed_kernel<T, ST, UU, CQ, true, full_>, A);
-        });
-      });
-    });
-  }
-
-  void launch_eval(hipStream_t s, Scratch& sc, const Plan1& P) {
-    StatusBlock* st = sc.status.as<StatusBlock>();
-    const uint64_t nq = P.nq;
-    if (P.kind == Plan1::SMALL) {
-      EvalSmallArgs<T> S{};
-      S.pyr = pyr.view;
-      S.data = data.as<T>();
-      S.ca = ca.as<T>();
-      S.cb = cb.as<T>();
-      S.q = P.q;
-      S.out = P.out;
-      S.nq = nq;
-      S.out_stride = P.out_stride;
-      S.lanes = (uint32_t)lanes;
-      S.mode = mode;
-      S.first_fail = &st->first_fail[0];
-      S.prechecked = 1;
-      const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-      const size_t shmem = (pyr.lds_bytes + 15) & ~(size_t)15;
-      pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
-        launch_lds<T>(eval_small_kernel<T, st_>, LDS_STAGE_LIMIT, s, PC_EVAL, dim3(g), dim3(BLOCK), shmem, S);
-      });
-      return;
-    }
-    if (P.kind == Plan1::FUSED) {
-      launch_fused(s, sc, P);
-      return;
-    }
-    if (P.kind == Plan1::LANES) {
-      launch_lanes(s, sc, P);
-      return;
-    }
-    Eval1Args<T> A{};
-    A.knots = pyr.view.lv0;
-    A.data = data.as<T>();
-    A.ca = ca.as<T>();
-    A.cb = cb.as<T>();
-    A.q = P.q;
-    A.idx = sc.idx.as<uint32_t>();
-    A.t = sc.t.as<T>();
-    A.out = P.out;
-    A.lanes = lanes;
-    A.out_stride = P.out_stride;
-    A.nq = nq;
-    A.status = st;
-    A.n_int = (uint32_t)(n - 1);
-#ifdef NDI_BOUNDS
-    if (env_int("NDI_BOUNDS_SELFTEST", 0)) A.n_int = 1;   // checked build: provoke the checker (rows are then wrong)
-#endif
-    constexpr int VN = Wide<T>::N;
-    const uint64_t LV = P.LV;
-    if (P.kind == Plan1::BUCKETED) {
-      A.rec = sc.perm.as<uint4>();
-      constexpr int CQ = BUCKETED_CQ;
-      // a multiple of 8 so that a workgroup keeps its XCD residue when it strides (XCD-aware chunk order);
-      // every workgroup takes a run of consecutive chunks (operand rows stay in registers across them)
-      const uint64_t per_xcd = ((nq + CQ - 1) / CQ + 7) / 8;
-      A.run = BUCKETED_RUN;
-      const uint64_t runs_per_xcd = (per_xcd + A.run - 1) / A.run;
-      launch_bucketed<false>(s, LV, (unsigned)std::max<uint64_t>(8, std::min<uint64_t>(runs_per_xcd * 8, 65528)), A);
-      return;
-    }
-    if (P.kind == Plan1::BUCKETED_SHORT) {
-      A.rec = sc.perm.as<uint4>();
-      uint32_t G = 8;
-      while (G < LV) G *= 2;   // threads per row: power of two >= vectors per row (LV < 256)
-      const int CQ = P.s_cq == 16 ? 16 : 64;
-      const uint64_t wq = (uint64_t)(BLOCK / G) * CQ;
-      const uint64_t per_xcd = ((nq + wq - 1) / wq + 7) / 8;
-      const unsigned gx = (unsigned)std::max<uint64_t>(8, std::min<uint64_t>(per_xcd * 8, 65528));
-      pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
-        constexpr int ST = st_;
-        pick_or<256, 8, 16, 32, 64, 128>((int)G, [&](auto g_) {
-          constexpr int GG = g_;
-          pick_or<64, 16>(CQ, [&](auto cq_) {
-            launch1<T>(s, PC_EVAL, dim3(gx), dim3(BLOCK), 0, eval_bucketed_short_kernel<T, ST, GG, cq_>, A);
-          });
-        });
-      });
-      return;
-    }
-    if (P.kind == Plan1::ROWS) {
-      // one 256-vector segment per workgroup pass and many workgroups: measured best on MI355X
-      const uint64_t segs = (LV + BLOCK - 1) / BLOCK;
-      const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nq, 65536));
-      dim3 grid(gx, (unsigned)std::min<uint64_t>(segs, 64));
-      pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) { launch1<T>(s, PC_EVAL, grid, dim3(BLOCK), 0, eval_rows_kernel<T, st_, 1>, A); });
-      return;
-    }
-    // flat
-    const uint32_t tile_q = (uint32_t)std::max<uint64_t>(1, 1024 / std::max<uint64_t>(LV, 1));
-    const uint64_t ntiles = (nq + tile_q - 1) / tile_q;
-    const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ntiles, 16384));
-    ProfScope ps(s, PC_EVAL);
-    pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
-      constexpr int ST = st_;
-      pick_or<1, VN>(P.vec_ok ? VN : 1, [&](auto vec_) {
-        hipLaunchKernelGGL((eval_flat_kernel<T, ST, vec_>), dim3(gx), dim3(BLOCK), 0, s, A, tile_q);
-      });
-    });
-    NDI_HIP(hipGetLastError());
-    ps.done();
-  }
 
   // ---- ring groups: one evaluation launch for several chunks of a ring (float_host.hpp ring_produce) ----------------
   // Only the long-row bucketed plan has a group form; every other plan keeps one launch per chunk.
   static constexpr bool ring_groups = true;
-  static bool groupable(const Plan1& P) { return P.kind == Plan1::BUCKETED; }
-
-  // Evaluates the w >= 1 chunks prepared into sc[0 .. w) with the plans P[0 .. w) -- all groupable, one row pitch -- in
-  // ONE launch (w = 1: the single-chunk kernel, launch_eval).
-  void launch_eval_group(hipStream_t s, Scratch* const* sc, const Plan1* P, uint32_t w) {
-    if (trace_plan())
-      std::fprintf(stderr, "[ndi plan] ring bucketed L=%llu lv=%llu width=%u nq=%llu\n", (unsigned long long)lanes,
-                   (unsigned long long)P[0].LV, w, (unsigned long long)P[0].nq);
-    if (w == 1) {
-      launch_eval(s, *sc[0], P[0]);
-      return;
-    }
-    if (w > (uint32_t)RING_GROUP_MAX) throw HipFailure{hipErrorInvalidValue, "launch_eval_group: group too wide", __LINE__};
-    EvalGroupArgs<T> G{};
-    G.A.knots = pyr.view.lv0;
-    G.A.data = data.as<T>();
-    G.A.ca = ca.as<T>();
-    G.A.cb = cb.as<T>();
-    G.A.lanes = lanes;
-    G.A.out_stride = P[0].out_stride;
-    G.A.n_int = (uint32_t)(n - 1);
-    G.width = w;
-    constexpr int CQ = BUCKETED_CQ;
-    uint64_t nmax = 0;
-    for (uint32_t i = 0; i < w; ++i) {
-      if (!groupable(P[i]) || P[i].out_stride != P[0].out_stride || P[i].LV != P[0].LV)
-        throw HipFailure{hipErrorInvalidValue, "launch_eval_group: plans of one group differ", __LINE__};
-      G.rec[i] = sc[i]->perm.as<uint4>();
-      G.nq[i] = P[i].nq;
-      G.out[i] = P[i].out;
-      G.status[i] = sc[i]->status.as<StatusBlock>();
-      nmax = std::max<uint64_t>(nmax, (P[i].nq + CQ - 1) / CQ);
-    }
-    const uint64_t LV = P[0].LV;
-    const uint64_t per_xcd = (nmax * w + 7) / 8;
-    launch_bucketed<true>(s, LV, (unsigned)std::max<uint64_t>(8, std::min<uint64_t>(per_xcd * 8, 65528)), G);
-  }
-
-  void launch_fused(hipStream_t s, Scratch& sc, const Plan1& P) {
-    EvalFusedArgs<T> F{};
-    F.pyr = pyr.view;
-    F.bx = P.f_lut ? pyr.bidx : BucketIndex<T>{nullptr, 0, T(0)};
-    F.data = data.as<T>();
-    F.ca = ca.as<T>();
-    F.cb = cb.as<T>();
-    F.ck = ck.as<T>();
-    F.bx32 = P.f_tlds == 3 ? pyr.bidx32 : BucketIndex32<T>{nullptr, 0, T(0)};
-    F.rec_stride = (uint32_t)P.LV;
-    if (P.f_pack) {   // {y[i], y[i+1], a[i], b[i]} per interval
-      F.data = packed.as<T>();
-      F.ca = packed.as<T>() + 2 * lanes;
-      F.cb = packed.as<T>() + 3 * lanes;
-      F.rec_stride = (uint32_t)P.LV * (strategy == NDI_CUBIC_SPLINE ? 4u : 2u);
-    }
-    F.q = P.q;
-    F.out = P.out;
-    F.nq = P.nq;
-    F.out_stride = P.out_stride;
-    F.lanes = (uint32_t)lanes;
-    F.lv = (uint32_t)P.LV;
-    F.lv_magic = F.lv >= 2 ? (uint32_t)(((1ull << 32) + F.lv - 1) / F.lv) : 0u;
-    F.mode = mode;
-    F.first_fail = &sc.status.as<StatusBlock>()->first_fail[0];
-    F.check = P.l_check ? 1 : 0;
-    F.debug = 0;
-#ifdef NDI_TUNING
-    F.debug = env_int("NDI_FUSED_DEBUG", 0);
-#endif
-    constexpr int VN = Wide<T>::N;
-    const dim3 grid(P.f_grid), block(P.f_tb);
-    if (P.f_sorted) {
-      if (trace_plan())
-        std::fprintf(stderr, "[ndi plan] fused sorted lut=%d tb=%u grid=%u lds=%zu prepass=%d\n", (int)P.f_lut, P.f_tb, P.f_grid,
-                     P.f_lds, P.l_check ? 0 : 1);
-      pick<ST_CUBIC, ST_LINEAR>(strat(), [&](auto st_) {
-        constexpr int ST = st_, QPT = ST == ST_CUBIC ? 8 : 4;   // 4096 queries per workgroup round, Linear 2048 (plan_fused)
-        pick_or<1, VN>(P.vec_ok ? VN : 1, [&](auto vec_) {
-          launch_lds<T>(eval_fused_sorted_kernel<T, ST, vec_, 512, QPT>, FUSED_LDS_LIMIT - 256, s, PC_EVAL, grid, dim3(512), P.f_lds, F);
-        });
-      });
-      return;
-    }
-    if (trace_plan())   // which variant a batch took (tests assert on it; read per call)
-      std::fprintf(stderr, "[ndi plan] fused tables=%s lut=%d pack=%d unr=%d tb=%u grid=%u lds=%zu prepass=%d\n",
-                   P.f_tlds == 2 ? "lds{y,k}" : (P.f_tlds == 1 ? "lds{y,a,b}" : (P.f_tlds == 3 ? "memory,knots=global" : "memory")),
-                   (int)P.f_lut, (int)P.f_pack,
-                   P.f_unr, P.f_tb, P.f_grid, P.f_lds, P.l_check ? 0 : 1);
-    // TLDS: 0 = tables from memory, 1 = {y, a, b} in LDS, 2 = {y, k} in LDS (the spline only), 3 = knots in global memory
-    // (one launch shape: UNR 2, TB 256)
-    pick<ST_CUBIC, ST_LINEAR>(P.f_tlds == 2 ? (int)ST_CUBIC : strat(), [&](auto st_) {
-      constexpr int ST = st_;
-      pick_or<1, VN>(P.vec_ok ? VN : 1, [&](auto vec_) {
-        constexpr int VEC = vec_;
-        pick_or<1, 0, 2, 3>(P.f_tlds, [&](auto tl_) {
-          constexpr int TL = tl_;
-          if constexpr (TL == 3) {
-            launch_lds<T>(eval_fused_kernel<T, ST, VEC, 2, 256, 3>, FUSED_LDS_LIMIT, s, PC_EVAL, grid, block, P.f_lds, F);
-          } else if constexpr (TL != 2 || ST == ST_CUBIC) {
-            pick_or<2, 4, 1>(P.f_unr, [&](auto unr_) {
-              constexpr int UNR = unr_;
-              pick_or<256, 1024, 512>((int)P.f_tb, [&](auto tb_) {
-                launch_lds<T>(eval_fused_kernel<T, ST, VEC, UNR, tb_, TL>, FUSED_LDS_LIMIT, s, PC_EVAL, grid, block, P.f_lds, F);
-              });
-            });
-          }
-        });
-      });
-    });
-  }
+  static bool groupable(const Plan& P) { return P.kind == Plan::BUCKETED; }
+  void launch_eval_group(hipStream_t s, Scratch* const* sc, const Plan* P, uint32_t w);   // (interp1d_host.hpp)
 
   // ---- what the host engine (float_host.hpp) takes from this family ------------------------------------------------
   using Elem = T;
-  using Plan = Plan1;
   static constexpr int query_arrays = 1;
   static constexpr bool small_rows = true, ring = true;
   static const char* axis_name(int) { return "x"; }
@@ -2080,8 +1180,8 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     lim[0] = lim[2] = pyr.host_knots.front();
     lim[1] = lim[3] = pyr.host_knots.back();
   }
-  Plan1 prep(hipStream_t s, Scratch& sc, Queries<T> q, uint64_t nq, T* out, uint64_t out_stride, int path,
-             bool beside_eval = false, int flags = 0) {
+  Plan prep(hipStream_t s, Scratch& sc, Queries<T> q, uint64_t nq, T* out, uint64_t out_stride, int path,
+            bool beside_eval = false, int flags = 0) {
     return prep(s, sc, q.a, nq, out, out_stride, path, beside_eval, flags);
   }
   void enqueue(hipStream_t s, Workspace& ws, Queries<T> q, uint64_t nq, T* out, uint64_t out_stride, int path, int flags) {
@@ -2098,26 +1198,9 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
     allow_dynamic_lds(reinterpret_cast<const void*>(&eval_small_kernel<T, ST_CUBIC>), (int)LDS_STAGE_LIMIT);
     allow_dynamic_lds(reinterpret_cast<const void*>(&eval_small_kernel<T, ST_LINEAR>), (int)LDS_STAGE_LIMIT);
   }
-  // The fused search + evaluation launch of the small-row paths: nq packed rows into out, the kernel's own range test.
-  void launch_small(hipStream_t s, StatusBlock* st, Queries<T> q, T* out, uint64_t nq) {
-    EvalSmallArgs<T> A{};
-    A.pyr = pyr.view;
-    A.data = data.as<T>();
-    A.ca = ca.as<T>();
-    A.cb = cb.as<T>();
-    A.q = q.a;
-    A.out = out;
-    A.nq = nq;
-    A.out_stride = lanes;
-    A.lanes = (uint32_t)lanes;
-    A.mode = mode;
-    A.first_fail = &st->first_fail[0];
-    A.prechecked = 0;
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + BLOCK - 1) / BLOCK, 4096));
-    const size_t shmem = (pyr.lds_bytes + 15) & ~(size_t)15;
-    if (strategy == NDI_CUBIC_SPLINE) launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), shmem, eval_small_kernel<T, ST_CUBIC>, A);
-    else launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), shmem, eval_small_kernel<T, ST_LINEAR>, A);
-  }
+  // The fused search + evaluation launch of the small-row paths: nq packed rows into out, the kernel's own range test
+  // (interp1d_host.hpp).
+  void launch_small(hipStream_t s, StatusBlock* st, Queries<T> q, T* out, uint64_t nq);
 
   ndi_status eval(const void* q_, uint64_t nq, void* out_, uint64_t out_stride,
                   const ndi_eval_opts* opts, ndi_oob_info* info) override {
@@ -2241,6 +1324,8 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
   ndi_status inverse(Interp1DBase** out) override;          // (defined behind InverseImpl)
 };
 
+#include "spline_build_host.hpp"
+#include "interp1d_host.hpp"
 #include "antiderivative_host.hpp"
 #include "inverse_host.hpp"
 #include "lanewise_host.hpp"

@@ -153,7 +153,7 @@ def test_lanewise_records(pkg, monkeypatch, capfd, source):
 def test_packed_intervals(pkg, monkeypatch, capfd, source):
     """the fused_pack variant of tests/test_gpu_short_rows.py on f32 rows of 3 lanes.  Q = 1025: four workgroups of the
     query-order kernel and below the 4096 queries at which plan_fused asks for the bucket index as well
-    (ndinterp_api.hip, plan_fused: `if (lut_env && P.nq >= 4096) pyr.ensure_bucket_index()`), so the injection meets
+    (interp1d_host.hpp, plan_fused1: `if (P.nq >= 4096) h.pyr.ensure_bucket_index()`), so the injection meets
     ensure_packed alone"""
     for k, v in (("NDI_SHORT_MODE", 2), ("NDI_FUSED_LDS", 0), ("NDI_FUSED_PACK", 1)):
         monkeypatch.setenv(k, str(v))
@@ -175,7 +175,7 @@ def test_packed_intervals(pkg, monkeypatch, capfd, source):
 @pytest.mark.parametrize("source", ["linear", "pchip"])
 def test_staged_bucket_index_row_wise(pkg, monkeypatch, capfd, dt, source):
     """257 clustered knots, 3 lanes, Q = 4097: the first odd batch at / above the 4096 queries from which plan_fused builds
-    the index (ndinterp_api.hip, plan_fused: `P.nq >= 4096`); the tables stay in memory and unpacked (NDI_FUSED_LDS=0,
+    the index (interp1d_host.hpp, plan_fused1: `P.nq >= 4096`); the tables stay in memory and unpacked (NDI_FUSED_LDS=0,
     NDI_FUSED_PACK=0), so the index is the only lazy table in the plan.  The `lut=` field of the `fused` line"""
     for k, v in (("NDI_SHORT_MODE", 2), ("NDI_FUSED_LDS", 0), ("NDI_FUSED_PACK", 0)):
         monkeypatch.setenv(k, str(v))

@@ -48,7 +48,7 @@ def check_equal(got, ref, what):
 
 
 def blocked_build(n, L):
-    """Shapes whose CubicSpline build takes the blocked Thomas sweeps by default (ndinterp_api.hip, build_spline):
+    """Shapes whose CubicSpline build takes the blocked Thomas sweeps by default (spline_build_host.hpp, build_form):
     narrow trailing axes on many knots.  The one path that is not bit-identical to the reference order."""
     return n >= 2048 and L <= 256 and os.environ.get("NDI_SPLINE_BLOCKED", "-1") != "0"
 

@@ -3,6 +3,7 @@ x-only plan on the host, the Thomas kernels -- next to the single-thread CPU por
 VERDICT r3 names: many knots with scalar / narrow data, the reference's (100, 5), and C2.
 
     python tools/build_probe.py > profiles/r05_build_probe.jsonl
+    NDI_LIB=libndinterp_hip_parent.so python tools/build_probe.py 100x5 1024x8 4096x8     # an A/B of two libraries: alternate
 """
 import json
 import os
@@ -33,7 +34,11 @@ def med(f, reps=5):
     return float(np.median(ts))
 
 
-for n, L in ((100, 5), (4096, 8), (100_000, 1), (1_000_000, 1), (1_000_000, 8), (4096, 256), (4096, 4096)):
+SHAPES = ((100, 5), (4096, 8), (100_000, 1), (1_000_000, 1), (1_000_000, 8), (4096, 256), (4096, 4096))
+if len(sys.argv) > 1:      # only these: `100x5 1024x8 4096x8`, the small builds whose milliseconds are host-side
+    SHAPES = tuple(tuple(int(v) for v in a.split("x")) for a in sys.argv[1:])
+
+for n, L in SHAPES:
     x = np.sort(rng.uniform(0, 1, n)) if n < 1_000_000 else np.cumsum(rng.uniform(0.5, 1.5, n))
     x = np.unique(x)
     n = x.size

@@ -2,8 +2,9 @@
 
 A refactor of the host code that picks and launches the kernels must change nothing a profiler or a caller can see.
 This tool runs a fixed matrix of shapes -- the values of the dispatch dimensions of the launch ladders, each at the
-smallest shape that reaches it; `launch_trace_ab_cases.txt` shows what every case reached and the notes in the report
-name the legs that none does -- once per library (`NDI_LIB` selects the file, a name beside the package's own
+smallest shape that reaches it, and every build form of the 1-D cubic tables (`cases_build`: a, b and one evaluation per
+build); `launch_trace_ab_cases.txt` shows what every case reached and the notes in the report name the legs that none
+does -- once per library (`NDI_LIB` selects the file, a name beside the package's own
 library), each process under `rocprofv3 --kernel-trace` with the program after `--`, and compares
 
   * the ordered list of (kernel name with template arguments, grid, workgroup, LDS bytes) of every process -- the
@@ -46,7 +47,8 @@ GROUPS = {   # process -> the read-once variables it runs under
 }
 LIVE = ("NDI_SHORT_MODE", "NDI_FUSED_UNR", "NDI_FUSED_TB", "NDI_FUSED_LDS", "NDI_FUSED_PACK", "NDI_FUSED_SORTED",
         "NDI_SHORT_CQ", "NDI_LANES_KERNEL", "NDI_LANES2D_KERNEL", "NDI_SLOPES2D_KERNEL", "NDI_GROUP_TWO_LEVEL",
-        "NDI_LANEWISE_MODE", "NDI_LANEWISE_RECORDS", "NDI_RING_GROUP")
+        "NDI_LANEWISE_MODE", "NDI_LANEWISE_RECORDS", "NDI_RING_GROUP", "NDI_SPLINE_BLOCKED", "NDI_SPLINE_WIDE",
+        "NDI_SPLINE_KEEP_K")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -253,6 +255,81 @@ def driver(group, save_dir):
                     return it.inverse().interp_array(t(queries(lo, hi, 2000, dt)))
                 case(f"inverse {d} {kind}", {}, inv)
 
+    # ---- the builds of the 1-D cubic tables (csrc/spline_build_host.hpp) -----------------------------------------------
+    def cases_build():
+        """Every build form at the smallest shape that reaches it.  Hashed: a, b, and one evaluation of 256 queries with the
+        tables in LDS wherever they fit -- {y, k} where the build kept k, so the k table is compared too."""
+        KEPT = {"NDI_SHORT_MODE": "2", "NDI_FUSED_LDS": "2"}
+        BC = pkg.BoundaryCondition
+
+        def built(n, lanes, dt, make_strategy, periodic=False, host=False):
+            def fn():
+                x = axis(n, dt)
+                y = rng.uniform(0.0, 1.0, (n, lanes)).astype(dt)
+                if periodic:
+                    y[-1] = y[0]
+                strat = make_strategy(x, y)
+                it = pkg.Interp1DBuilder.new(y if host else t(y)).x(x if host else t(x)).strategy(strat).build()
+                a, b = it.strategy.coefficients()
+                o = out_buffer(256, lanes, dt, "aligned")
+                it.strategy.interp_array_into(it, t(queries(x[0], x[-1], 256, dt)), o)
+                return [a, b, o]
+            return fn
+
+        def spline(bc=None, reference_order=False):
+            def make(x, y):
+                s = pkg.CubicSpline.new().reference_order(reference_order)
+                return s if bc is None else s.boundary(bc)
+            return make
+
+        def individual(x, y):
+            SB, lanes = pkg.SingleBoundary, y.shape[1]
+            ends = [SB.NotAKnot, SB.Natural, SB.Clamped, SB.FirstDeriv(0.5), SB.SecondDeriv(-0.25)]
+            rows = [pkg.RowBoundary.Mixed(ends[l % 5], ends[(l // 2 + 1) % 5]) for l in range(lanes)]
+            rows[-1] = pkg.RowBoundary.NotAKnot          # (with n == 3: the parabola rows)
+            r = np.empty((1, lanes), dtype=object)
+            r[0, :] = rows
+            return pkg.CubicSpline.new().boundary(BC.Individual(r))
+
+        for dt in (F32, F64):
+            d = "f32" if dt == F32 else "f64"
+            vn = 4 if dt == F32 else 2
+            k = f"build {d}"
+            case(f"{k} one workgroup in LDS (100, 5)", KEPT, built(100, 5, dt, spline()))
+            case(f"{k} one workgroup in LDS, k dropped", dict(KEPT, NDI_SPLINE_KEEP_K="0"), built(100, 5, dt, spline()))
+            case(f"{k} one workgroup in LDS, natural ends", KEPT, built(100, 5, dt, spline(BC.Natural)))
+            case(f"{k} one launch, over 96 KiB", KEPT, built(2000, 8, dt, spline()))
+            case(f"{k} one launch, over 256 lanes", KEPT, built(100, 300, dt, spline()))
+            case(f"{k} serial, three kernels", KEPT, built(600, 300, dt, spline()))
+            case(f"{k} serial, wide", KEPT, built(33, 5000, dt, spline()))
+            case(f"{k} serial, wide 1400 lanes", KEPT, built(97, 1400, dt, spline()))
+            case(f"{k} serial, wide forced", dict(KEPT, NDI_SPLINE_WIDE="1"), built(600, 300, dt, spline()))
+            case(f"{k} serial, wide off", dict(KEPT, NDI_SPLINE_WIDE="0"), built(33, 5000, dt, spline()))
+            case(f"{k} n = 3 parabola", KEPT, built(3, 5, dt, spline()))
+            case(f"{k} n = 3 periodic", KEPT, built(3, 5, dt, spline(BC.Periodic), periodic=True))
+            case(f"{k} serial periodic", KEPT, built(100, 5, dt, spline(BC.Periodic), periodic=True))
+            case(f"{k} blocked sweeps", KEPT, built(2048, 8, dt, spline()))
+            case(f"{k} blocked sweeps, periodic", KEPT, built(2048, 8, dt, spline(BC.Periodic), periodic=True))
+            case(f"{k} blocked sweeps, device-side elimination", KEPT, built(32768, 2, dt, spline()))
+            case(f"{k} NDI_SPLINE_BLOCKED=0", dict(KEPT, NDI_SPLINE_BLOCKED="0"), built(2048, 8, dt, spline()))
+            case(f"{k} NDI_SPLINE_BLOCKED=1", dict(KEPT, NDI_SPLINE_BLOCKED="1"), built(100, 5, dt, spline()))
+            case(f"{k} NDI_SPLINE_BLOCKED=1 periodic", dict(KEPT, NDI_SPLINE_BLOCKED="1"),
+                 built(100, 5, dt, spline(BC.Periodic), periodic=True))
+            case(f"{k} NDI_BUILD_REFERENCE_ORDER", KEPT, built(2048, 8, dt, spline(reference_order=True)))
+            case(f"{k} Individual n = 3", KEPT, built(3, 6, dt, individual))
+            case(f"{k} Individual", KEPT, built(10, 6, dt, individual))
+            case(f"{k} Individual, k dropped", dict(KEPT, NDI_SPLINE_KEEP_K="0"), built(10, 6, dt, individual))
+            for lanes, rows in ((2 * vn, "vector"), (3, "scalar")):
+                case(f"{k} Pchip {rows}", KEPT, built(33, lanes, dt, lambda x, y: pkg.Pchip.new()))
+                case(f"{k} Akima {rows}", KEPT, built(33, lanes, dt, lambda x, y: pkg.Akima.new()))
+                case(f"{k} CubicHermite {rows}, device derivatives", KEPT,
+                     built(33, lanes, dt, lambda x, y: pkg.CubicHermite.new(t(2.0 * y))))
+                case(f"{k} CubicHermite {rows}, host derivatives", KEPT,
+                     built(33, lanes, dt, lambda x, y: pkg.CubicHermite.new(2.0 * y), host=True))
+            # (host derivatives without a kept k table: the upload goes to a temporary)
+            case(f"{k} CubicHermite host derivatives, k dropped", dict(KEPT, NDI_SPLINE_KEEP_K="0"),
+                 built(33, 3, dt, lambda x, y: pkg.CubicHermite.new(2.0 * y), host=True))
+
     # ---- 2-D Bilinear -------------------------------------------------------------------------------------------------
     def h2(nx, ny, lanes, dt, clustered=False, strategy=None):
         gx, gy = axis(nx, dt, clustered), axis(ny, dt)      # (one clustered axis: its index alone takes 64 KiB of LDS)
@@ -360,6 +437,7 @@ def driver(group, save_dir):
     if group == "main":
         cases_1d()
         cases_families()
+        cases_build()
         cases_2d()
         cases_bicubic()
         cases_search()
