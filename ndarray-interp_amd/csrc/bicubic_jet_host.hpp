@@ -44,8 +44,9 @@ static void bicubic_jet_launch(const Interp2DImpl<T>& h, int order, hipStream_t 
   const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nq + TB - 1) / TB,
                                                                         std::max<uint64_t>(1, (uint64_t)cu_count() * wgs_per_cu(lds, TB) * 4 / gy)));
   if (trace_plan())
-    std::fprintf(stderr, "[ndi plan] bicubic_jet order=%d vec=%d lv=%llu klds=%d grid=%u x %u lds=%zu prepass=%d\n", order,
-                 (int)vec, (unsigned long long)A.lv, (int)klds, gx, gy, lds, check ? 0 : 1);
+    std::fprintf(stderr, "[ndi plan] bicubic_jet order=%d vec=%d lv=%llu klds=%d grid=%u x %u lds=%zu prepass=%d%s\n", order,
+                 (int)vec, (unsigned long long)A.lv, (int)klds, gx, gy, lds, check ? 0 : 1,
+                 A.wrap == 0 ? "" : A.wrap == 1 ? " wrap=x" : A.wrap == 2 ? " wrap=y" : " wrap=xy");   // (as bicubic_launch_eval's)
   pick_or<2, 1>(order, [&](auto ord_) {
     constexpr int ORD = ord_;
     bicubic_pick_form<T>(vec, klds, [&](auto vec_, auto kl_) {

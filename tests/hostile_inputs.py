@@ -792,3 +792,161 @@ def bicubic_sub_exponent(dtype, fx, fy, order, recorded=True):
             best = scan(np.arange(lo, hi + 1))
         _SUB[key] = -best[3]
     return _SUB[key]
+
+
+# ---- Bicubic with periodic axes: hostile grids and wrapped queries (tests/test_gpu_bicubic_periodic_hostile.py and
+# tests/test_gpu_bicubic_periodic_plans.py; self-check in tests/test_hostile_inputs.py) ----------------------------------------
+PERIODIC_AXES = {"x": 1, "y": 2, "xy": 3}
+SEAM_LANE = "+0 / -0 seam"
+WRAP_PERIODS = (1, 2, 3, 1000, 2**20)
+
+
+def bicubic_wrap_axis_queries(k):
+    """The hostile queries of one wrapping axis, p = kn - k0 (every operation in k's dtype): every knot and the float either
+    side of it -- not clipped, so one ulp outside either end is a query; every knot shifted by m p, m in -2, -1, 1, 2;
+    k0 - m p and kn + m p and the float either side of each for m in 1, 2, 3, 1000, 2^20; k0 less the smallest normal and
+    less the smallest subnormal (a tiny negative remainder: r + |p| rounds to p); +-max, max / 4, +-1e30."""
+    T = k.dtype.type
+    f = np.finfo(k.dtype)
+    lo, hi = T(-np.inf), T(np.inf)
+    k0, kn = k[0], k[-1]
+    p = kn - k0
+    q = [k, np.nextafter(k, lo), np.nextafter(k, hi)]
+    q += [k + T(m) * p for m in (-2, -1, 1, 2)]
+    far = np.array([e for m in WRAP_PERIODS for e in (k0 - T(m) * p, kn + T(m) * p)], k.dtype)
+    q += [far, np.nextafter(far, lo), np.nextafter(far, hi)]
+    q.append(np.array([k0 - f.tiny, k0 - f.smallest_subnormal, f.max, -f.max, f.max / T(4), 1e30, -1e30], k.dtype))
+    q = np.concatenate(q).astype(k.dtype)
+    assert np.all(np.isfinite(q))
+    return q
+
+
+def bicubic_periodic_queries(x, y, axes, seed=0, n_random=300):
+    """(qx, qy) for a handle that wraps on `axes` (bit 0: x, bit 1: y): the cross product of bicubic_wrap_axis_queries on a
+    wrapping axis and bicubic_axis_queries (in range) on the other, then `n_random` points up to 3.5 periods outside on a
+    wrapping axis and in range on the other."""
+    ax = bicubic_wrap_axis_queries(x) if axes & 1 else bicubic_axis_queries(x)
+    ay = bicubic_wrap_axis_queries(y) if axes & 2 else bicubic_axis_queries(y)
+    gx, gy = np.meshgrid(ax, ay, indexing="ij")
+    rng = np.random.default_rng([seed, len(x), len(y), axes])
+
+    def draws(k, wraps):
+        p = k[-1] - k[0]
+        u = rng.uniform(-3.5 if wraps else 0.0, 4.5 if wraps else 1.0, n_random).astype(k.dtype)
+        r = (k[0] + u * p).astype(k.dtype)
+        return r if wraps else np.clip(r, k[0], k[-1])
+    return np.concatenate([gx.ravel(), draws(x, axes & 1)]), np.concatenate([gy.ravel(), draws(y, axes & 2)])
+
+
+def bicubic_periodic_ends(axes, mixed):
+    """the four ends of a periodic case: not-a-knot (not read) on a periodic axis, the default or MIXED_BC's on the other"""
+    import bicubic_ref
+    bc = list(bicubic_ref.MIXED_BC if mixed else bicubic_ref.DEFAULT_BC)
+    if axes & 1:
+        bc[0] = bc[1] = bicubic_ref.NOT_A_KNOT
+    if axes & 2:
+        bc[2] = bc[3] = bicubic_ref.NOT_A_KNOT
+    return tuple(bc)
+
+
+def bicubic_periodic_cases(dtype, grid_index):
+    """(fx, fy, axes, mixed) for every pair of bicubic_pairs: the periodic-axes setting cycles x, y, xy over the pairs (one
+    step on for the second grid), the other axis takes the default ends on even pairs and MIXED_BC's on odd ones."""
+    names = tuple(PERIODIC_AXES)
+    return [(fx, fy, names[(i + grid_index) % 3], i % 2 == 1) for i, (fx, fy) in enumerate(bicubic_pairs(dtype))]
+
+
+def bicubic_periodic_parts(C):
+    return -(-len(BICUBIC_RECIPES) // (C - 1))
+
+
+def bicubic_periodic_nodes(dtype, nx, ny, C, axes, part=0, top_exp=0, seed=0, finite_only=False):
+    """(z, names): z (nx, ny, C), periodic along `axes`.  Lanes 0 .. C - 2 are bicubic_nodes' (recipe
+    (part * (C - 1) + l) mod 9, the same lane as there) followed by make_periodic: the last row / column repeats the first.  A
+    planted NaN that this leaves on a seam row or column moves one node inwards (a NaN on the seam is a refusal, not a
+    case).  Lane C - 1 is the seam lane: the integer background made periodic, then +0 in the first row and -0 in the last
+    along each periodic axis -- equal under ==, so the build accepts it, and not the same bits."""
+    import bicubic_periodic_ref
+    z = np.empty((nx, ny, C), dtype)
+    names = []
+    for l in range(C - 1):
+        r = (part * (C - 1) + l) % len(BICUBIC_RECIPES)
+        rng = np.random.default_rng([seed, nx, ny, r])
+        if finite_only and r in BICUBIC_NONFINITE:
+            r = 0
+        names.append(BICUBIC_RECIPES[r])
+        z[:, :, l] = bicubic_lane(r, dtype, nx, ny, rng, top_exp)
+    z[:, :, C - 1] = bicubic_lane("integers", dtype, nx, ny, np.random.default_rng([seed, nx, ny, len(BICUBIC_RECIPES)]))
+    names.append(SEAM_LANE)
+    for i, j, l in np.argwhere(np.isnan(z)):      # NaN off the seam: swapped with the node one step inwards, then the copy
+        i2 = min(max(i, 1), nx - 2) if axes & 1 else i
+        j2 = min(max(j, 1), ny - 2) if axes & 2 else j
+        z[i, j, l], z[i2, j2, l] = z[i2, j2, l], z[i, j, l]
+    z = bicubic_periodic_ref.make_periodic(z, axes)
+    s = z[:, :, C - 1]
+    if axes & 1:
+        s[0], s[-1] = 0.0, -0.0
+    if axes & 2:
+        s[:, 0], s[:, -1] = 0.0, -0.0
+    return z, names
+
+
+def bicubic_periodic_reference(x, y, z, bc, axes, qx=None, qy=None, tabs=None, wrap=True, order=(0, 0)):
+    """(tables, rows) of the periodic restatement (tests/bicubic_periodic_ref.py) with numpy's warnings off.  `tabs`: evaluate
+    on these tables; `wrap=False`: the handle built without extrapolate, which does not wrap."""
+    import bicubic_periodic_ref
+    with np.errstate(all="ignore"):
+        if tabs is None:
+            tabs = bicubic_periodic_ref.tables(x, y, z, bc, axes)
+        if qx is None:
+            return tabs, None
+        return tabs, bicubic_periodic_ref.evaluate_partial(x, y, z, *tabs, qx, qy, order[0], order[1], axes if wrap else 0)
+
+
+def bicubic_periodic_recorded(dtype, fx, fy, axes):
+    """tests/golden/bicubic_periodic_exponents.json: what bicubic_periodic_top_exponent found, recorded so that the device
+    tests do not search again; tests/test_hostile_inputs.py runs every search and holds the file to the results."""
+    import json
+    import os
+    if "periodic" not in _SEARCH:
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bicubic_periodic_exponents.json")) as f:
+            _SEARCH["periodic"] = json.load(f)
+    return _SEARCH["periodic"].get(np.dtype(dtype).name, {}).get(f"{fx} {fy}", {}).get(axes)
+
+
+def bicubic_periodic_top_ok(dtype, fx, fy, axes, e):
+    """integers times 2^e: the periodic restatement's three tables and its rows on the hostile wrapped queries are ALL finite,
+    on both grids and with both end sets of the other axis"""
+    a = PERIODIC_AXES[axes]
+    for nx, ny in BICUBIC_GRIDS:
+        x, y = bicubic_grid(fx, fy, dtype, nx, ny)
+        import bicubic_periodic_ref
+        z = bicubic_periodic_ref.make_periodic(
+            bicubic_lane("top scale", dtype, nx, ny, np.random.default_rng([0, nx, ny, 7]), e)[:, :, None], a)
+        qx, qy = bicubic_periodic_queries(x, y, a)
+        for mixed in (False, True):
+            try:
+                tabs, rows = bicubic_periodic_reference(x, y, z, bicubic_periodic_ends(a, mixed), a, qx, qy)
+            except ValueError:       # zx overflowed to NaN on the seam of y: the cross pass refuses it, as the build would
+                return False
+            if not (all(np.isfinite(t).all() for t in tabs) and np.isfinite(rows).all()):
+                return False
+    return True
+
+
+def bicubic_periodic_top_exponent(dtype, fx, fy, axes, recorded=True):
+    """bicubic_top_exponent for a build periodic along `axes` ("x", "y", "xy") whose handle wraps: the largest e, in steps
+    of one, at which bicubic_periodic_top_ok holds -- measured on the restatement alone, never on a device.  The exponents
+    of bicubic_top_exponent were found for not-a-knot builds and in-range queries at a 90 % finite share; the cyclic system
+    and the end cells under wrapped queries overflow earlier on some pairs.  Bisection, as there."""
+    if recorded and bicubic_periodic_recorded(dtype, fx, fy, axes) is not None:
+        return bicubic_periodic_recorded(dtype, fx, fy, axes)
+    key = (np.dtype(dtype), fx, fy, axes)
+    if key not in _TOP:
+        lo, hi = 0, np.finfo(dtype).maxexp
+        assert bicubic_periodic_top_ok(dtype, fx, fy, axes, lo), key
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if bicubic_periodic_top_ok(dtype, fx, fy, axes, mid) else (lo, mid)
+        _TOP[key] = lo
+    return _TOP[key]

@@ -10,7 +10,10 @@
   be, non-finite in the planted lanes only, with queries that tell a left-sided cell search from the right-sided one;
 * the same grids under the eight partial derivatives (tests/test_gpu_bicubic_partial_hostile.py): a top-scale and a subnormal
   lane per order, each exponent found by search and recorded, the subnormal lane judged by a flush-to-zero mutant, six
-  mutants of H1 / H2 told apart, and the cases that claim nothing named in literals.
+  mutants of H1 / H2 told apart, and the cases that claim nothing named in literals;
+* the same grids made periodic (tests/test_gpu_bicubic_periodic_hostile.py): every family on a wrapping axis under every
+  periodic-axes setting, hostile wrapped queries whose wrapped coordinates are never NaN and never below k0, finite tables
+  and rows in every lane that claims them, a +0 / -0 seam lane, and the periodic top-scale exponents searched and recorded.
 """
 import os
 
@@ -652,3 +655,112 @@ def test_default_arguments_give_the_bits_they_gave(dt):
         for o in ORDERS:
             check_bits(hostile.bicubic_reference(x, y, z, None, qx, qy, tabs=tabs, order=o)[1],
                        partial_ref.evaluate(x, y, z, *tabs, qx, qy, *o), f"order {o}")
+
+
+# ---- the hostile Bicubic grids with periodic axes (tests/test_gpu_bicubic_periodic_hostile.py) ---------------------------------
+import bicubic_periodic_ref as periodic_ref        # noqa: E402
+
+PERIODIC_FINITE = [n for n in hostile.BICUBIC_RECIPES + (hostile.SEAM_LANE,) if n not in ("inf node", "nan node", "top scale")]
+
+
+def test_the_periodic_configurations_put_every_family_on_a_wrapping_axis():
+    """Every knot family sits on a wrapping axis under each of the three periodic-axes settings at both grid sizes, in
+    both dtypes; either end set of the other axis occurs beside x and beside y; the configurations are bicubic_pairs."""
+    for dt in DTYPES:
+        for gi in range(len(hostile.BICUBIC_GRIDS)):
+            cases = hostile.bicubic_periodic_cases(dt, gi)
+            assert [c[:2] for c in cases] == hostile.bicubic_pairs(dt)
+            for fam in hostile.BICUBIC_FAMILIES:
+                assert any(fx == fam for fx, fy, a, m in cases if a == "x"), (dt, gi, fam, "x")
+                assert any(fy == fam for fx, fy, a, m in cases if a == "y"), (dt, gi, fam, "y")
+                assert any(fx == fam for fx, fy, a, m in cases if a == "xy") and any(fy == fam for fx, fy, a, m in cases if a == "xy")
+            for a in ("x", "y"):
+                assert {m for fx, fy, s, m in cases if s == a} == {False, True}, (dt, gi, a)
+
+
+def test_bicubic_wrapped_queries_are_what_they_claim():
+    """The hostile set of a wrapping axis, on 3, 4, 6 and 65 knots of the five families and of `triple` and on the past-the-end
+    axis of tests/test_gpu_bicubic_periodic_plans.py: the named points are in it, no wrapped coordinate is NaN and none is
+    below k0 -- so a finite lane has finite rows; a wrapped coordinate may exceed kn, and on the past-the-end axis one does."""
+    for dt in DTYPES:
+        T = np.dtype(dt).type
+        f = np.finfo(dt)
+        axes = [hostile.bicubic_knots(fam, dt, n) for fam in hostile.BICUBIC_FAMILIES + ("triple",) for n in (3, 4, 6, 65)]
+        k0, kn = T(-10) / T(7), T(3 if dt == np.float32 else 1)
+        past = [np.concatenate([[k0], (float(k0) + (float(kn) - float(k0)) * np.arange(1, n - 1) / (n - 1)).astype(dt), [kn]]).astype(dt)
+                for n in (3, 8, 65, 1000)]
+        for k in axes + past:
+            q = hostile.bicubic_wrap_axis_queries(k)
+            assert q.dtype == np.dtype(dt) and np.all(np.isfinite(q))
+            p = k[-1] - k[0]
+            have = set(q.tolist())
+            for v in (np.nextafter(k[0], T(-np.inf)), np.nextafter(k[-1], T(np.inf)), k[0] - f.tiny, k[0] - f.smallest_subnormal, f.max,
+                      -f.max, k[0] - T(2**20) * p, k[-1] + T(2**20) * p, k[1] + T(2) * p, k[1] - p):
+                assert v in have
+            w = periodic_ref.wrap(k, q)
+            assert not np.isnan(w).any() and not (w < k[0]).any(), k[:3]
+        for k in past:
+            assert T((k[-1] - k[0]) + k[0]) == np.nextafter(k[-1], T(np.inf))
+            w = periodic_ref.wrap(k, hostile.bicubic_wrap_axis_queries(k))
+            assert (w > k[-1]).any() and w.max() == np.nextafter(k[-1], T(np.inf))
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_bicubic_periodic_lanes_are_what_they_claim(dt):
+    """Conditions on the restatement, for every pair, both grids and all three periodic-axes settings with the default ends
+    (and with the ends the device test gives the case): every lane but `inf node`, `nan node` and `top scale` has
+    all-finite tables and all-finite rows on the hostile wrapped queries; the inf and NaN lanes do not, their non-finite
+    node is off the seam, and the other lanes have the bits they have without them; the seam lane is +0 in the first and
+    -0 in the last row / column of a periodic axis, which the mismatch test (==) accepts; lanes 0 .. C - 2 are
+    bicubic_nodes' made periodic."""
+    for gi, (nx, ny) in enumerate(hostile.BICUBIC_GRIDS):
+        mixed_of = {c[:3]: c[3] for c in hostile.bicubic_periodic_cases(dt, gi)}
+        for fx, fy in hostile.bicubic_pairs(dt):
+            x, y = hostile.bicubic_grid(fx, fy, dt, nx, ny)
+            for axes, a in hostile.PERIODIC_AXES.items():
+                top = hostile.bicubic_periodic_top_exponent(dt, fx, fy, axes)
+                z, names = hostile.bicubic_periodic_nodes(dt, nx, ny, 10, a, 0, top)
+                zf, _ = hostile.bicubic_periodic_nodes(dt, nx, ny, 10, a, 0, top, finite_only=True)
+                what = f"{np.dtype(dt).name} {fx} x {fy} {nx}x{ny} periodic {axes}"
+                assert names == list(hostile.BICUBIC_RECIPES) + [hostile.SEAM_LANE]
+                plain = periodic_ref.make_periodic(hostile.bicubic_nodes(dt, nx, ny, 9, 0, top)[0], a)
+                check_bits(z[..., :9], plain, f"{what}: the nine recipes made periodic")
+                s = z[..., 9]
+                if a & 1:
+                    assert np.all(z[0] == z[-1]) and not np.isnan(z[0]).any(), what
+                    assert np.all(s[0, 1:-1] == 0) and not np.signbit(s[0, 1:-1]).any() and np.signbit(s[-1, 1:-1]).all(), what
+                if a & 2:
+                    assert np.all(z[:, 0] == z[:, -1]) and not np.isnan(z[:, 0]).any(), what
+                    assert np.all(s[1:-1, 0] == 0) and not np.signbit(s[1:-1, 0]).any() and np.signbit(s[1:-1, -1]).all(), what
+                qx, qy = hostile.bicubic_periodic_queries(x, y, a)
+                for mixed in sorted({False, mixed_of.get((fx, fy, axes), False)}):
+                    bc = hostile.bicubic_periodic_ends(a, mixed)
+                    tabs, rows = hostile.bicubic_periodic_reference(x, y, z, bc, a, qx, qy)
+                    ftabs, frows = hostile.bicubic_periodic_reference(x, y, zf, bc, a, qx, qy)
+                    for l, name in enumerate(names):
+                        if name in PERIODIC_FINITE:
+                            assert all(np.isfinite(t[..., l]).all() for t in tabs), (what, mixed, name, "tables")
+                            assert np.isfinite(rows[:, l]).all(), (what, mixed, name, "rows")
+                        if l in hostile.BICUBIC_NONFINITE:
+                            assert not np.isfinite(rows[:, l]).all() and np.isfinite(frows[:, l]).all(), (what, mixed, name)
+                        else:
+                            for u, v in zip(tabs + (rows,), ftabs + (frows,)):
+                                check_bits(u[..., l], v[..., l], f"{what}: lane {name} beside the non-finite lanes")
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_bicubic_periodic_top_scale_is_the_largest(dt):
+    """The "top scale" lane of a periodic build: integers times 2^e with the largest e at which the periodic restatement's
+    three tables and its rows on the hostile wrapped queries are ALL finite on both grids and with both end sets of the other
+    axis -- searched again here for every (pair, setting), equal to the recorded value
+    (tests/golden/bicubic_periodic_exponents.json), and one step up is not all-finite.  Printed beside the exponents of the
+    not-a-knot build (90 % finite, in-range queries), which overflow under a periodic build on some pairs."""
+    found = {}
+    for fx, fy in hostile.bicubic_pairs(dt):
+        for axes in hostile.PERIODIC_AXES:
+            e = hostile.bicubic_periodic_top_exponent(dt, fx, fy, axes, recorded=False)
+            assert e == hostile.bicubic_periodic_recorded(dt, fx, fy, axes), (fx, fy, axes, e)
+            assert hostile.bicubic_periodic_top_ok(dt, fx, fy, axes, e) and not hostile.bicubic_periodic_top_ok(dt, fx, fy, axes, e + 1)
+            found[fx, fy, axes] = (e, hostile.bicubic_top_exponent(dt, fx, fy))
+    below = {k: v for k, v in found.items() if v[0] < v[1]}
+    print(f"{np.dtype(dt).name}: periodic top scales 2^e (beside the not-a-knot build's) = {found}; below it: {below}")
