@@ -737,7 +737,8 @@ ndi_status ndi_interp1d_eval(const ndi_interp1d* h, const void* q, uint64_t nq, 
  * Host arrays go through device staging in row chunks; only rows before the failing row are copied back.  Linear / cubic
  * handles may keep an element-record copy of their tables for this call (built on the first lane-wise call, at most 1 GiB,
  * released by ndi_interp1d_trim; a clone builds its own).
- * Not provided: lane-wise 2-D evaluation, the ring, the sharded calls, async_launch, integer and f16 / bf16 element types. */
+ * Not provided: the ring, the sharded calls, async_launch, integer and f16 / bf16 element types.  (The 2-D form is
+ * ndi_interp2d_eval_lanewise, below.) */
 ndi_status ndi_interp1d_eval_lanewise(const ndi_interp1d* h, const void* q, uint64_t nq, uint64_t q_row_stride,
                                       void* out, uint64_t out_row_stride, const ndi_eval_opts* opts, ndi_oob_info* info);
 
@@ -746,6 +747,36 @@ ndi_status ndi_interp1d_eval_lanewise(const ndi_interp1d* h, const void* q, uint
 ndi_status ndi_interp2d_eval(const ndi_interp2d* h, const void* qx, const void* qy, uint64_t nq,
                              void* out, uint64_t out_row_stride, const ndi_eval_opts* opts,
                              ndi_oob_info* info);
+
+/* Lane-wise 2-D evaluation, an (x, y) per lane (this project's own; the reference evaluates all lanes at one point):
+ *     out[j * out_row_stride + l] = f_l(qx[j * q_row_stride + l], qy[j * q_row_stride + l]),   j < nq, l < lanes.
+ * `qx` and `qy` are T[nq][q_row_stride] in opts->q_memspace and share one pitch, `out` is T[nq][out_row_stride] in
+ * opts->out_memspace; both strides are in elements and at least lanes.
+ * Value rule: out[j][l] is, bit for bit and zero signs included, element l of the row ndi_interp2d_eval(h) writes for the single query (qx[j][l], qy[j][l]).
+ * It holds for every handle the call accepts, every extrapolation mode, every table layout and every kernel form.
+ * Handles accepted (f32 and f64 only): Bilinear, in whichever layout the handle keeps its grid; Bicubic from every build
+ * (the spline with any boundary kinds, pchip, akima, hermite, periodic axes -- a handle that wraps takes the wrap once per
+ * coordinate, before the search) and every partial-derivative handle of one (orders 0 .. 2 per variable).  An integral
+ * handle (ndi_interp2d_antiderivative: the integral of a surface per lane is not provided), integer and f16 / bf16
+ * handles are NDI_BAD_ARG with a message that names the reason.
+ * Failures: the lowest failing flat ELEMENT index j * lanes + l wins (computed with lanes, not with the strides).  The two
+ * axes are recorded separately and x is reported before y for the same element: info->index is that index, info->value
+ * is qx[j][l] or qy[j][l], info->axis is 0 or 1; status and message are those of ndi_interp2d_eval on the handle
+ * ("x = ... is not in range" / "y = ...", NDI_NAN_QUERY where the handle extrapolates; on a wrapping axis the test is
+ * "finite after the wrap", so +-inf is NDI_NAN_QUERY).  Rows j < index / lanes are written whole; the failing row and all
+ * later rows are untouched.  NDI_EVAL_FRESH_OUTPUT and NDI_EVAL_ROWS_AFTER_ERROR_UNSPECIFIED drop the pre-pass over the
+ * queries that this needs: the report is the same, the rows at and after the failing row are then unspecified.
+ * Refused before any device work: a null `h`, with nq > 0 a null `qx`, `qy` or `out`, a stride below lanes,
+ * NDI_PATH_BUCKETED, unknown flag bits or a non-zero `reserved` (all NDI_BAD_ARG); async_launch != 0 is NDI_UNSUPPORTED
+ * (the finish record carries no element index).  nq == 0 is NDI_OK and touches nothing.
+ * Host arrays go through device staging in row chunks of 256 MiB per array; only rows before the failing row are copied
+ * back.  A Bicubic handle may keep a node-record copy of its node table for this call ({z, zx, zy, zxy} of a node and lane
+ * side by side: built on the first lane-wise call that wants it, the size of the node table and at most 1 GiB, shared
+ * with the partial handles as the node table is, released by ndi_interp2d_trim; a clone builds its own).
+ * Not provided: integral handles, the ring, the sharded calls, async_launch, integer and f16 / bf16 element types. */
+ndi_status ndi_interp2d_eval_lanewise(const ndi_interp2d* h, const void* qx, const void* qy, uint64_t nq,
+                                      uint64_t q_row_stride, void* out, uint64_t out_row_stride,
+                                      const ndi_eval_opts* opts, ndi_oob_info* info);
 
 /* Completes async_launch evaluations on `stream`: synchronises it and reports the
  * status of the last batch enqueued there. */

@@ -127,6 +127,8 @@ SYMBOLS = {
     "ndi_interp1d_eval_lanewise": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _P, C.c_uint64, C.POINTER(EvalOpts),
                                              C.POINTER(OobInfo)]),
     "ndi_interp2d_eval": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(EvalOpts), C.POINTER(OobInfo)]),
+    "ndi_interp2d_eval_lanewise": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_uint64, C.POINTER(EvalOpts),
+                                             C.POINTER(OobInfo)]),
     "ndi_interp1d_finish": (C.c_int, [_P, _P, C.POINTER(OobInfo)]),
     "ndi_interp2d_finish": (C.c_int, [_P, _P, C.POINTER(OobInfo)]),
     "ndi_interp1d_eval_ring": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(RingDesc), RING_CONSUMER, _P,

@@ -38,6 +38,7 @@
 #include "bicubic_local_kernels.hpp"
 #include "bicubic_integral_kernels.hpp"
 #include "bicubic_jet_kernels.hpp"
+#include "lanewise2d_kernels.hpp"
 
 #define NDI_API extern "C" __attribute__((visibility("default")))
 
@@ -1470,6 +1471,16 @@ struct Interp2DBase {
     return fail(NDI_BAD_ARG, "Bilinear has no value-and-gradient (jet) evaluation: its slope jumps at every grid line and it "
                 "keeps no node derivatives (ndi_interp2d_eval_jet takes a Bicubic surface handle)");
   }
+  // ndi_interp2d_eval_lanewise (lanewise2d_host.hpp): f32 / f64 Bilinear and Bicubic surface / partial handles only
+  virtual ndi_status eval_lanewise(const void* qx, const void* qy, uint64_t nq, uint64_t q_stride, void* out,
+                                   uint64_t out_stride, const ndi_eval_opts* opts, ndi_oob_info* info) {
+    if (integral)
+      return fail(NDI_BAD_ARG, "eval_lanewise: this is an integral handle (ndi_interp2d_antiderivative); the integral of a "
+                  "surface per lane is not provided: the lane-wise evaluation takes Bilinear handles, Bicubic surface "
+                  "handles and their partial-derivative handles");
+    return fail(NDI_BAD_ARG, "eval_lanewise: %s handle is a Bilinear interpolator of a narrow element type; the lane-wise "
+                "evaluation takes f32 / f64 handles", (dtype == NDI_I32 || dtype == NDI_I64) ? "an integer" : "an f16 / bf16");
+  }
 };
 
 template <class T>
@@ -1535,6 +1546,9 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
   int wrap_axes() const { return mode != EX_NO ? periodic_axes : 0; }
   DevBuf itable;              // integral handles: the prefix records T[nx][ny][5][lanes] ({PP, Qz, Qzy, Pz, Pzx}), owned
   bool pair_packed = false;   // data holds the pair-packed layout (pack_pairs_kernel)
+  // Bicubic: the node-record copy of the lane-wise evaluation (lanewise2d_host.hpp), shared with the partial handles exactly
+  // as `table` is; a replica has its own
+  std::shared_ptr<LanewiseRecords> lw_records = std::make_shared<LanewiseRecords>();
   // The stored grid as the kernels address it: cells per grid row and elements per cell of `data` (a pair-packed cell holds
   // the values of two neighbouring grid points of a row, and a row has one cell fewer).
   struct Layout { uint64_t row_cells, cell_elems; };
@@ -1715,6 +1729,12 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     return this->run_eval("ndi_interp2d_eval", {(const T*)qx_, (const T*)qy_}, nq, out_, out_stride, opts, info);
   }
   ndi_status finish(void* stream, ndi_oob_info* info) override { return this->run_finish(stream, info); }
+  // lane-wise evaluation (defined in lanewise2d_host.hpp)
+  const void* lanewise_records(hipStream_t s);
+  void lanewise_enqueue(hipStream_t s, Workspace& ws, const T* qx, const T* qy, uint64_t q_stride, uint64_t rows, T* out,
+                        uint64_t out_stride, bool check);
+  ndi_status eval_lanewise(const void* qx, const void* qy, uint64_t nq, uint64_t q_stride, void* out, uint64_t out_stride,
+                           const ndi_eval_opts* opts, ndi_oob_info* info) override;
   // Interp2D::interp_array through a device-output ring.
   ndi_status eval_ring(const void* qx_, const void* qy_, uint64_t nq, const ndi_ring_desc* ring,
                        ndi_ring_consumer consume, void* user, const ndi_eval_opts* opts,
@@ -1784,6 +1804,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
     h->px.upload(px.host_knots.data(), nx);
     h->py.upload(py.host_knots.data(), ny);
     h->table = table;
+    h->lw_records = lw_records;
     *out = h.release();
     return NDI_OK;
   }
@@ -1893,6 +1914,7 @@ struct Interp2DImpl final : Interp2DBase, FloatEngine<T, Interp2DImpl<T>> {
         (void)hipGetLastError();
       }
     }
+    if (bicubic && !integral) lw_records->drop();   // the lane-wise node-record copy: the next call that wants it rebuilds it
     return NDI_OK;
   }
 };
@@ -1965,6 +1987,7 @@ static ndi_status create2d(const ndi_interp2d_desc& d, Interp2DBase** out) {
 #include "bicubic_local_host.hpp"
 #include "bicubic_integral_host.hpp"
 #include "bicubic_jet_host.hpp"
+#include "lanewise2d_host.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // Locator: VectorExtensions::get_lower_index with the knot pyramid resident on the device
@@ -2878,6 +2901,18 @@ NDI_API ndi_status ndi_interp2d_eval(const ndi_interp2d* h, const void* qx, cons
   if (const ndi_status ps = bicubic_path_check(h, opts); ps != NDI_OK) return ps;
   NDI_TRY
   return ndi::bounds_verdict(h->impl->eval(qx, qy, nq, out, out_row_stride, opts, info), h->impl->device);
+  NDI_CATCH
+}
+
+// Every refusal is decided before any device work: the null handle here, the rest in the handle's eval_lanewise().
+NDI_API ndi_status ndi_interp2d_eval_lanewise(const ndi_interp2d* h, const void* qx, const void* qy, uint64_t nq,
+                                              uint64_t q_row_stride, void* out, uint64_t out_row_stride,
+                                              const ndi_eval_opts* opts, ndi_oob_info* info) {
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  NDI_TRY
+  const ndi_status st = h->impl->eval_lanewise(qx, qy, nq, q_row_stride, out, out_row_stride, opts, info);
+  if (st == NDI_BAD_ARG || st == NDI_UNSUPPORTED) return st;   // a refusal: no device was touched
+  return ndi::bounds_verdict(st, h->impl->device);
   NDI_CATCH
 }
 

@@ -171,6 +171,42 @@ class _DeviceStrategy2D(Interp2DStrategy):
         if st != _capi.OK:
             raise_eval(st, info, int_query(self._np_dtype, [qx, qy], info))
 
+    def interp_lanewise_into(self, interpolator, xs2d, ys2d, out2d, *, fresh=False, rows_after_error_unspecified=False):
+        """`out2d[j, l] = f_l(xs2d[j, l], ys2d[j, l])` (ndi_interp2d_eval_lanewise): an (x, y) per lane, `(Q, lanes)` in and
+        out, host or device.  Errors name the flat element index `j * lanes + l` and the axis.  Handles the library refuses
+        (integral handles, integers, f16 / bf16) raise `ValueError` with its message."""
+        qx = Buf(xs2d, self._np_dtype)
+        qy = Buf(ys2d, self._np_dtype)
+        if qx.memspace != qy.memspace:
+            raise TypeError("xs and ys must live in the same memory space")
+        _check_out_dtype(out2d, self._np_dtype)
+        opts = _capi.EvalOpts()
+        opts.q_memspace = qx.memspace
+        opts.path = _capi.PATH_AUTO if self.path == _capi.PATH_BUCKETED else self.path
+        opts.flags = (_capi.EVAL_FRESH_OUTPUT if fresh else _capi.EVAL_DEFAULT) | \
+            (_capi.EVAL_ROWS_AFTER_ERROR_UNSPECIFIED if rows_after_error_unspecified else 0)
+        if is_torch(out2d):
+            if not out2d.is_cuda:
+                raise TypeError("torch output buffers must live on the device; use numpy for host buffers")
+            opts.out_memspace = _capi.MEM_DEVICE
+            optr = out2d.data_ptr()
+            stride = out2d.stride(0) if out2d.dim() > 1 and out2d.shape[0] > 1 else self._lanes
+            opts.stream = current_stream_ptr(self._device)
+        else:
+            opts.out_memspace = _capi.MEM_HOST
+            optr = out2d.ctypes.data
+            stride = out2d.strides[0] // out2d.itemsize if out2d.ndim > 1 and out2d.shape[0] > 1 else self._lanes
+            if qx.memspace == _capi.MEM_DEVICE:
+                opts.stream = current_stream_ptr(self._device)
+        info = _capi.OobInfo()
+        nq = qx.size // self._lanes
+        st = _capi.lib().ndi_interp2d_eval_lanewise(self._h, qx.ptr, qy.ptr, nq, self._lanes, optr, max(stride, self._lanes),
+                                                    C.byref(opts), C.byref(info))
+        if st in (_capi.BAD_ARG, _capi.UNSUPPORTED):
+            raise ValueError(_capi.last_error())
+        if st != _capi.OK:
+            raise_eval(st, info)
+
     def finish(self):
         info = _capi.OobInfo()
         st = _capi.lib().ndi_interp2d_finish(self._h, current_stream_ptr(self._device), C.byref(info))
@@ -809,6 +845,60 @@ class Interp2D:
             elif done:
                 where = np.unravel_index(np.arange(done), tuple(xs.shape))
                 buffer[where] = tmp[:done].reshape((done,) + self._lanes_shape())
+
+    def interp_lanewise(self, xs, ys):
+        """An (x, y) per channel: `xs.shape == ys.shape` ends with `data.shape[2:]` and
+        `result[..., l] = f_l(xs[..., l], ys[..., l])`, where `interp_array` evaluates every channel at one point.  The
+        result has `xs.shape` and the data's element type; numpy in -> numpy out, a device tensor in -> a tensor on its
+        device.  Works on `partial(nu_x, nu_y)` of a Bicubic too.  `InterpolateError.OutOfBounds.index` is the flat element
+        index."""
+        self._lanewise_check(xs, ys)
+        dt = np_dtype_of(self.data)
+        if is_torch(xs) and xs.is_cuda:
+            import torch
+            zs = torch.empty(tuple(xs.shape), dtype=torch_dtype(dt), device=xs.device)
+        else:
+            zs = np.zeros(tuple(xs.shape), dtype=dt)
+        self.interp_lanewise_into(xs, ys, zs, fresh=True)
+        return zs
+
+    def interp_lanewise_into(self, xs, ys, buffer, *, fresh=False, rows_after_error_unspecified=False):
+        """`interp_lanewise` into a caller's buffer of `xs.shape`: rows (one per leading index) before the row of the
+        first failing element are written, that row and all later ones stay untouched -- unless `fresh` or
+        `rows_after_error_unspecified` give them up, which saves a pass over the queries."""
+        self._lanewise_check(xs, ys)
+        if tuple(buffer.shape) != tuple(xs.shape):
+            raise Panic(f"ShapeError/IncompatibleShape: incompatible shapes expected: {list(xs.shape)}, "
+                        f"got: {list(buffer.shape)}")
+        if np_dtype_of(buffer) != np_dtype_of(self.data):
+            raise TypeError(f"buffer has element type {np_dtype_of(buffer)}, the data is {np_dtype_of(self.data)}")
+        lanes = int(np.prod(self._lanes_shape(), dtype=np.int64))
+        nq = int(np.prod(xs.shape, dtype=np.int64)) // max(lanes, 1)
+        kw = dict(fresh=fresh, rows_after_error_unspecified=rows_after_error_unspecified)
+
+        def rows(a):
+            return a.reshape(nq, lanes) if is_torch(a) else _host(a).reshape(nq, lanes)
+        if is_torch(buffer):
+            if not buffer.is_contiguous():
+                raise TypeError("device output buffers must be contiguous")
+            self.strategy.interp_lanewise_into(self, xs.reshape(nq, lanes), ys.reshape(nq, lanes), buffer.view(nq, lanes), **kw)
+            return
+        if not buffer.flags.c_contiguous:
+            raise TypeError("interp_lanewise_into needs a C-contiguous host buffer")
+        self.strategy.interp_lanewise_into(self, rows(xs), rows(ys), buffer.reshape(nq, lanes), **kw)
+
+    def _lanewise_check(self, xs, ys):
+        if not isinstance(self.strategy, _DeviceStrategy2D):
+            raise TypeError("interp_lanewise needs a built-in device strategy (Bilinear or Bicubic on f32 / f64 data, or a "
+                            f"partial derivative of a Bicubic), got {type(self.strategy).__name__}")
+        if tuple(xs.shape) != tuple(ys.shape):
+            raise Panic(f"ShapeError/IncompatibleShape: incompatible shapes expected: {list(xs.shape)}, "
+                        f"got: {list(ys.shape)}")
+        lanes_shape = self._lanes_shape()
+        k = len(lanes_shape)
+        if len(xs.shape) < k or tuple(xs.shape)[len(xs.shape) - k:] != lanes_shape:
+            raise Panic(f"ShapeError/IncompatibleShape: incompatible shapes expected: [.., "
+                        f"{', '.join(str(d) for d in lanes_shape)}], got: {list(xs.shape)}")
 
     def partial(self, nu_x=0, nu_y=0) -> "Interp2D":
         """The partial derivative d^(nu_x + nu_y) / dx^nu_x dy^nu_y of this interpolator's surface as an interpolator over

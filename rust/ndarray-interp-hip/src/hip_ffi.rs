@@ -345,6 +345,19 @@ extern "C" {
         opts: *const ndi_eval_opts,
         info: *mut ndi_oob_info,
     ) -> i32;
+    /// An (x, y) per lane: `out[j][l] = f_l(qx[j][l], qy[j][l])`, bit for bit the element `ndi_interp2d_eval` writes for
+    /// that query
+    pub fn ndi_interp2d_eval_lanewise(
+        h: *const ndi_interp2d,
+        qx: *const c_void,
+        qy: *const c_void,
+        nq: u64,
+        q_row_stride: u64,
+        out: *mut c_void,
+        out_row_stride: u64,
+        opts: *const ndi_eval_opts,
+        info: *mut ndi_oob_info,
+    ) -> i32;
     pub fn ndi_interp1d_finish(h: *const ndi_interp1d, stream: *mut c_void, info: *mut ndi_oob_info) -> i32;
     pub fn ndi_interp2d_finish(h: *const ndi_interp2d, stream: *mut c_void, info: *mut ndi_oob_info) -> i32;
     pub fn ndi_interp1d_eval_ring(
