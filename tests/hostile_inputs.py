@@ -950,3 +950,172 @@ def bicubic_periodic_top_exponent(dtype, fx, fy, axes, recorded=True):
             lo, hi = (mid, hi) if bicubic_periodic_top_ok(dtype, fx, fy, axes, mid) else (lo, mid)
         _TOP[key] = lo
     return _TOP[key]
+
+
+# ---- a query per lane (tests/test_gpu_lanewise2d_hostile.py; self-check in tests/test_hostile_inputs.py) -----------------------
+def lanewise_arrangement(qx, qy, L, s=None):
+    """(xs, ys, s): the query list (qx, qy) of length N as (N, L) arrays for a call with a query per lane: lane l holds the
+    list rotated by l s, s prime to N (by default the first such s from N // L up, so the lanes start about evenly spread over
+    the list).  Every lane meets every query exactly once -- its reference elements are a permutation of that lane's column of
+    the row-wise reference -- and the lanes of a row sit s list positions apart, in different cells wherever the list moves."""
+    N = len(qx)
+    assert N >= 1 and len(qy) == N and L >= 1
+    if s is None:
+        s = max(1, N // L)
+        while np.gcd(s, N) != 1:
+            s += 1
+    assert np.gcd(s, N) == 1, (s, N)
+    at = (np.arange(N)[:, None] + s * np.arange(L)[None, :]) % N
+    return np.ascontiguousarray(qx[at]), np.ascontiguousarray(qy[at]), s
+
+
+def bicubic_lanewise_reference(x, y, z, bc, xs, ys, tabs, order=(0, 0), periodic=None, wrap=True):
+    """(N, L): column l is the restatement's lane l on the queries (xs[:, l], ys[:, l]), evaluated on the tables `tabs` --
+    bicubic_reference, or bicubic_periodic_reference for a build periodic along `periodic` (a bit set)."""
+    N, L = xs.shape
+    assert z.shape[2] == L
+    out = np.empty((N, L), z.dtype)
+    for l in range(L):
+        one = tuple(np.ascontiguousarray(t[:, :, l:l + 1]) for t in tabs)
+        zl = np.ascontiguousarray(z[:, :, l:l + 1])
+        qx, qy = np.ascontiguousarray(xs[:, l]), np.ascontiguousarray(ys[:, l])
+        if periodic:
+            out[:, l] = bicubic_periodic_reference(x, y, zl, bc, periodic, qx, qy, tabs=one, wrap=wrap, order=order)[1][:, 0]
+        else:
+            out[:, l] = bicubic_reference(x, y, zl, bc, qx, qy, tabs=one, order=order)[1][:, 0]
+    return out
+
+
+LANEWISE_THIN = 11      # every 11th pair of the cross product: 11 is prime to the length of every y set of BICUBIC_GRIDS (19 .. 39)
+
+
+def bicubic_lanewise_queries(x, y, extrapolate, L):
+    """(xs, ys) of shape (N, L): bicubic_queries with every LANEWISE_THIN-th pair of the cross product (every point of either
+    axis' set still occurs) and all its spread points, arranged by lanewise_arrangement."""
+    qx, qy = bicubic_queries(x, y, extrapolate, thin=LANEWISE_THIN)
+    return lanewise_arrangement(qx, qy, L)[:2]
+
+
+def bicubic_lanewise_recorded(dtype, fx, fy, order=(0, 0)):
+    """tests/golden/bicubic_lanewise_exponents.json: what bicubic_lanewise_top_exponent (order (0, 0)) and
+    bicubic_lanewise_partial_top_exponent (LANEWISE_PARTIAL_ORDERS) found, recorded so that the device tests do not search
+    again; tests/test_hostile_inputs.py runs every search and holds the file to the results.  The file is a held record of
+    EVERY pair and order, also where the exponent is the row-wise one (most of them): the two functions return the recorded
+    value before they consult bicubic_top_exponent, so the self-check is what ties the file to it."""
+    import json
+    import os
+    if "lanewise" not in _SEARCH:
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bicubic_lanewise_exponents.json")) as f:
+            _SEARCH["lanewise"] = json.load(f)
+    return _SEARCH["lanewise"].get(np.dtype(dtype).name, {}).get(f"{fx} {fy}", {}).get(f"{order[0]},{order[1]}")
+
+
+def bicubic_lanewise_top_ok(dtype, fx, fy, e):
+    """integers times 2^e: tables and rows of the restatement are at least 90 % finite on the query lists of
+    bicubic_lanewise_queries -- in range and with extrapolation -- on both grids and with both end sets.  (A lane of the
+    arrangement holds a permutation of the list, so the share of a lane is the share of the list.)"""
+    for nx, ny in BICUBIC_GRIDS:
+        x, y = bicubic_grid(fx, fy, dtype, nx, ny)
+        z = bicubic_lane("top scale", dtype, nx, ny, np.random.default_rng([0, nx, ny, 7]), e)[:, :, None]
+        for bc in bicubic_ends():
+            for ext in (False, True):
+                qx, qy = bicubic_queries(x, y, ext, thin=LANEWISE_THIN)
+                tabs, rows = bicubic_reference(x, y, z, bc, qx, qy)
+                if finite_share(*tabs) < 0.9 or finite_share(rows) < 0.9:
+                    return False
+    return True
+
+
+def bicubic_lanewise_top_exponent(dtype, fx, fy, recorded=True):
+    """The exponent of the "top scale" lane in the lane-wise tests: bicubic_top_exponent where bicubic_lanewise_top_ok holds
+    for it, else the largest smaller e for which it does (bisection, as there: what overflows at e overflows at e + 1).  The
+    row-wise exponent was found on the whole cross product in range; the thinned list has a larger share of spread points,
+    which fall into the wide cells of a mixed axis, and the extrapolating list reaches 2^20 widths outside."""
+    if recorded and bicubic_lanewise_recorded(dtype, fx, fy) is not None:
+        return bicubic_lanewise_recorded(dtype, fx, fy)
+    key = (np.dtype(dtype), fx, fy, "lanewise")
+    if key not in _TOP:
+        hi = bicubic_top_exponent(dtype, fx, fy)
+        if bicubic_lanewise_top_ok(dtype, fx, fy, hi):
+            _TOP[key] = hi
+        else:
+            lo = 0
+            assert bicubic_lanewise_top_ok(dtype, fx, fy, lo), key
+            while hi - lo > 1:
+                mid = (lo + hi) // 2
+                lo, hi = (mid, hi) if bicubic_lanewise_top_ok(dtype, fx, fy, mid) else (lo, mid)
+            _TOP[key] = lo
+    return _TOP[key]
+
+
+LANEWISE_PARTIAL_ORDERS = ((1, 1), (2, 0), (0, 2))      # the orders tests/test_gpu_lanewise2d_hostile.py runs on the partial arrays
+
+
+def bicubic_lanewise_shares(dtype, fx, fy, order, z_of):
+    """the finite shares of the tables and of the rows of `order`, for the single lane z_of(nx, ny), on every list of
+    bicubic_lanewise_queries: both grids, in range and with extrapolation, default ends (the partial cases build those)"""
+    out = []
+    for nx, ny in BICUBIC_GRIDS:
+        x, y = bicubic_grid(fx, fy, dtype, nx, ny)
+        z = z_of(nx, ny)[:, :, None]
+        for ext in (False, True):
+            qx, qy = bicubic_queries(x, y, ext, thin=LANEWISE_THIN)
+            tabs, rows = bicubic_reference(x, y, z, None, qx, qy, order=order)
+            out.append((finite_share(*tabs), finite_share(rows)))
+    return out
+
+
+def bicubic_lanewise_integer_share(dtype, fx, fy, order):
+    """the smallest finite share of the integer lane's rows of `order` over those lists"""
+    return min(s[1] for s in bicubic_lanewise_shares(
+        dtype, fx, fy, order, lambda nx, ny: bicubic_lane("integers", dtype, nx, ny, np.random.default_rng([0, nx, ny, 0]))))
+
+
+def bicubic_lanewise_partial_top_ok(dtype, fx, fy, order, e):
+    return all(min(s) >= 0.9 for s in bicubic_lanewise_shares(
+        dtype, fx, fy, order, lambda nx, ny: bicubic_lane("top scale", dtype, nx, ny, np.random.default_rng([0, nx, ny, 7]), e)))
+
+
+def bicubic_lanewise_partial_top_exponent(dtype, fx, fy, order, recorded=True):
+    """The exponent of the ("top scale", order) lane in the lane-wise tests of the partial orders: bicubic_top_exponent of
+    that order where bicubic_lanewise_partial_top_ok holds for it, else the largest smaller e for which it does (bisection,
+    as there); 0 where not even the integers pass (the row-wise case of bicubic_integer_overflows: the lane repeats the
+    integers and claims nothing)."""
+    order = tuple(order)
+    if recorded and bicubic_lanewise_recorded(dtype, fx, fy, order) is not None:
+        return bicubic_lanewise_recorded(dtype, fx, fy, order)
+    key = (np.dtype(dtype), fx, fy, order, "lanewise")
+    if key not in _TOP:
+        hi = bicubic_top_exponent(dtype, fx, fy, order)
+        if bicubic_lanewise_partial_top_ok(dtype, fx, fy, order, hi):
+            _TOP[key] = hi
+        elif not bicubic_lanewise_partial_top_ok(dtype, fx, fy, order, 0):
+            _TOP[key] = 0
+        else:
+            lo = 0
+            while hi - lo > 1:
+                mid = (lo + hi) // 2
+                lo, hi = (mid, hi) if bicubic_lanewise_partial_top_ok(dtype, fx, fy, order, mid) else (lo, mid)
+            _TOP[key] = lo
+    return _TOP[key]
+
+
+def bicubic_lanewise_partial_nodes(dtype, nx, ny, fx, fy, C=25, seed=0, finite_only=False):
+    """bicubic_partial_nodes with the top-scale lanes of the lane-wise tests: the ("top scale", order) lane of each order of
+    LANEWISE_PARTIAL_ORDERS at bicubic_lanewise_partial_top_exponent, and the ("top scale", (0, 0)) lane at
+    bicubic_lanewise_top_exponent where the pair is one of bicubic_pairs.  Every other lane is that function's."""
+    z, lanes = bicubic_partial_nodes(dtype, nx, ny, fx, fy, C, seed, finite_only)
+    T = np.dtype(dtype).type
+    for l, (name, order) in enumerate(lanes):
+        if name != "top scale":
+            continue
+        if order in LANEWISE_PARTIAL_ORDERS:
+            e = bicubic_lanewise_partial_top_exponent(dtype, fx, fy, order)
+        elif order == (0, 0) and (fx, fy) in bicubic_pairs(dtype):
+            e = bicubic_lanewise_top_exponent(dtype, fx, fy)
+        else:
+            continue
+        ints = bicubic_lane("integers", dtype, nx, ny, np.random.default_rng([seed, nx, ny, BICUBIC_RECIPES.index("top scale")]))
+        with np.errstate(over="ignore"):
+            z[:, :, l] = (ints * np.ldexp(T(1), e)).astype(dtype)
+    return z, lanes

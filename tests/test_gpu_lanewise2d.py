@@ -80,15 +80,16 @@ def per_lane(it, xs, ys):
 def pool_case(it, x, y, Q, L, seed, K=16):
     """(xs, ys, ref) for rows too wide for per_lane: K points -- the four corners of the range, an interior node, its
     neighbouring floats, uniform draws -- evaluated by ONE row-wise call, rows = interp_array(px, py) of shape (K, L); the
-    queries are (px, py)[k[j, l]] with k random and the reference is rows[k[j, l], l]"""
+    queries are (px, py)[k[j, l]] with k random and the reference is rows[k[j, l], l].  K < 7: the first K of the fixed
+    points (K = 4: the corners)"""
     dt = x.dtype
     T = dt.type
     rng = np.random.default_rng(seed)
     xi, yi = x[len(x) // 2], y[len(y) // 2]
     px = np.concatenate([[x[0], x[0], x[-1], x[-1], xi, np.nextafter(xi, T(np.inf)), np.nextafter(xi, T(-np.inf))],
-                         rng.uniform(x[0], x[-1], K - 7)]).astype(dt)
+                         rng.uniform(x[0], x[-1], max(K - 7, 0))]).astype(dt)[:K]
     py = np.concatenate([[y[0], y[-1], y[0], y[-1], yi, np.nextafter(yi, T(-np.inf)), np.nextafter(yi, T(np.inf))],
-                         rng.uniform(y[0], y[-1], K - 7)]).astype(dt)
+                         rng.uniform(y[0], y[-1], max(K - 7, 0))]).astype(dt)[:K]
     px, py = np.clip(px, x[0], x[-1]), np.clip(py, y[0], y[-1])
     rows = it.interp_array(px, py).reshape(K, L)
     k = rng.integers(0, K, (Q, L))

@@ -1,4 +1,4 @@
-"""GPU: the six lazily built accelerating tables when their build fails (NDI_TEST_FAIL_LAZY_ALLOC=1 throws the
+"""GPU: the seven lazily built accelerating tables when their build fails (NDI_TEST_FAIL_LAZY_ALLOC=1 throws the
 out-of-memory failure of a hipMalloc on the host, before the allocation; no device fault is involved):
 
   DevicePyramid::ensure_bucket_index      the u16 bucket index staged in LDS behind the knot pyramid
@@ -7,19 +7,21 @@ out-of-memory failure of a hipMalloc on the host, before the allocation; no devi
   Interp1DImpl::ensure_packed             the interval-packed copy of the tables of the query-order kernel
   Interp2DImpl::ensure_slopes             the slope-record copy of a 2-D grid
   Interp1DImpl::lanewise_records          the element-record copy of the lane-wise kernel
+  Interp2DImpl::lanewise_records          the node-record copy of the 2-D lane-wise kernel (a Bicubic handle and its partials)
 
 Every scenario has a CONTROL handle (same arrays, no injection) whose plan line (NDI_TRACE_PLAN) must show the table in
 use -- a control that does not use it FAILS the scenario -- and then, on a fresh handle,
   (a) the first evaluation under the injection returns OK, its plan line shows the fallback, its rows are the control's
       rows and the yardstick's, bit for bit;
   (b) with the variable unset the same handle still takes the fallback (nothing retries) and gives the same bits;
-  (c) after trim() the bits are the same again; a rebuild is asserted only for the lane-wise records, whose
+  (c) after trim() the bits are the same again; a rebuild is asserted only for the two lane-wise record copies, whose
       LanewiseRecords::drop returns them to "not tried" (tests/test_gpu_lanewise.py:
-      test_trim_rebuilds_the_record_copy_and_a_clone_builds_its_own); the other five were observed to stay unavailable
+      test_trim_rebuilds_the_record_copy_and_a_clone_builds_its_own; the 2-D handle's trim drops the same structure); the
+      other five were observed to stay unavailable
       (DESIGN.md 4.19a), which no comment promises, so either plan is accepted for them;
   (d) a clone(0) of the failed handle, made with the variable unset, builds its own table.
 The yardstick of every scenario is the one of the test file that owns the kernel: per_lane of tests/test_gpu_lanewise.py
-for the lane-wise calls, the CPU oracle (as tests/test_gpu_short_rows.py, test_gpu_lanes.py, test_gpu_slopes2d.py take
+(and of tests/test_gpu_lanewise2d.py) for the lane-wise calls, the CPU oracle (as tests/test_gpu_short_rows.py, test_gpu_lanes.py, test_gpu_slopes2d.py take
 it) for the row-wise ones.  Every comparison is hostile_inputs.check_bits."""
 import os
 
@@ -146,6 +148,42 @@ def test_lanewise_records(pkg, monkeypatch, capfd, source):
              uses=lambda p: has(p, "lanewise form=fused", "records=1") and has(p, "lanewise records built"),
              fallback=lambda p: has(p, "lanewise form=fused", "records=0") and not has(p, "lanewise records built"),
              rebuilt_by_trim=True)
+
+
+# ---- Interp2DImpl::lanewise_records ---------------------------------------------------------------------------------------
+def test_lanewise2d_records(pkg, monkeypatch, capfd):
+    """9 x 7 x 5 Pchip f64, Q = 67, NDI_LANEWISE2D_RECORDS=1.  Injected: records=0 and no `lanewise2d records built`.  The copy
+    is LanewiseRecords, the structure of the 1-D copy, and Interp2DImpl::trim drops it: trim returns it to "not tried".  A
+    partial handle made from the failed source shares lw_records, so it takes the fallback too and nothing retries."""
+    import torch
+    import test_gpu_lanewise2d as l2
+    rng = np.random.default_rng(15)
+    nx, ny, L, Q = 9, 7, 5, 67
+    x, y = ic.knots(rng, nx, np.float64), ic.knots(rng, ny, np.float64)
+    z = l2.grid_data(rng, nx, ny, L, np.float64)
+    xs, ys = l2.queries(rng, x, y, Q, L)
+    make = lambda: l2.surface(pkg, "pchip", x, y, z)      # noqa: E731
+    ref = l2.per_lane(make(), xs, ys)
+    dx, dy = torch.as_tensor(xs, device="cuda:0"), torch.as_tensor(ys, device="cuda:0")
+    evaluate = lambda it: it.interp_lanewise(dx, dy).cpu().numpy()      # noqa: E731
+    uses = lambda p: has(p, "lanewise2d kind=bicubic", "records=1") and has(p, "lanewise2d records built")      # noqa: E731
+    fallback = lambda p: has(p, "lanewise2d kind=bicubic", "records=0") and not has(p, "lanewise2d records built")      # noqa: E731
+    monkeypatch.setenv("NDI_LANEWISE2D_RECORDS", "1")
+    scenario(capfd, "2-D lane-wise records", make, evaluate, ref, uses=uses, fallback=fallback, rebuilt_by_trim=True)
+    # a partial handle of the failed source
+    it = make()
+    with traced(capfd, inject=True) as t:
+        got = evaluate(it)
+    assert fallback(t.plans) and not uses(t.plans), t.plans
+    hostile_inputs.check_bits(got, ref, "the source of the partial, injected")
+    d = it.partial(1, 0)
+    ref_d = l2.per_lane(d, xs, ys)
+    for h, want, what in ((d, ref_d, "a partial of the failed source"), (it, ref, "the failed source after its partial"),
+                          (d, ref_d, "the partial, second call")):
+        with traced(capfd) as t:
+            got = evaluate(h)
+        assert fallback(t.plans) and not uses(t.plans), f"{what}: nothing retries: {t.plans}"
+        hostile_inputs.check_bits(got, want, what)
 
 
 # ---- Interp1DImpl::ensure_packed ------------------------------------------------------------------------------------------

@@ -13,7 +13,10 @@
   mutants of H1 / H2 told apart, and the cases that claim nothing named in literals;
 * the same grids made periodic (tests/test_gpu_bicubic_periodic_hostile.py): every family on a wrapping axis under every
   periodic-axes setting, hostile wrapped queries whose wrapped coordinates are never NaN and never below k0, finite tables
-  and rows in every lane that claims them, a +0 / -0 seam lane, and the periodic top-scale exponents searched and recorded.
+  and rows in every lane that claims them, a +0 / -0 seam lane, and the periodic top-scale exponents searched and recorded;
+* the arrangement with a query per lane (tests/test_gpu_lanewise2d_hostile.py): every lane a permutation of the list, the
+  lanes of a row in different places, every finite lane's reference at least 90 % finite in range and with extrapolation,
+  and the top-scale exponents it needs searched and recorded.
 """
 import os
 
@@ -764,3 +767,117 @@ def test_bicubic_periodic_top_scale_is_the_largest(dt):
             found[fx, fy, axes] = (e, hostile.bicubic_top_exponent(dt, fx, fy))
     below = {k: v for k, v in found.items() if v[0] < v[1]}
     print(f"{np.dtype(dt).name}: periodic top scales 2^e (beside the not-a-knot build's) = {found}; below it: {below}")
+
+
+# ---- a query per lane (tests/test_gpu_lanewise2d_hostile.py) ------------------------------------------------------------------
+def test_lanewise_arrangement_is_what_it_claims():
+    """lane l holds the list rotated by l s with s prime to N: every lane meets every query once, and (L <= N) no two lanes of
+    a row hold the same list position"""
+    for N, L in ((1, 1), (7, 3), (12, 5), (625, 9), (2057, 25)):
+        qx, qy = np.arange(N, dtype=np.float64), -np.arange(N, dtype=np.float64)
+        xs, ys, s = hostile.lanewise_arrangement(qx, qy, L)
+        assert xs.shape == ys.shape == (N, L) and np.gcd(s, N) == 1
+        check_bits(ys, -xs, "the two coordinates stay paired")
+        for l in range(L):
+            assert np.array_equal(np.sort(xs[:, l]), qx) and xs[0, l] == (l * s) % N
+        if L <= N:
+            assert all(len(set(row)) == L for row in xs)
+    with pytest.raises(AssertionError):
+        hostile.lanewise_arrangement(np.arange(6.0), np.arange(6.0), 2, s=3)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_bicubic_lanewise_lanes_are_what_they_claim(dt):
+    """The arrays of the lane-wise hostile tests, nine recipes side by side: with a query per lane (lanewise_arrangement of the
+    thinned list, in range and with extrapolation) the restatement's reference of every lane outside the planted inf / NaN
+    lanes is at least 90 % finite, on both grids and with both end sets; so are the tables.  The top-scale exponent is
+    searched again for every pair and equals the recorded one (tests/golden/bicubic_lanewise_exponents.json): the row-wise
+    exponent where that holds the share on these lists, else the largest below it that does."""
+    lowered = {}
+    for fx, fy in hostile.bicubic_pairs(dt):
+        e = hostile.bicubic_lanewise_top_exponent(dt, fx, fy, recorded=False)
+        row = hostile.bicubic_top_exponent(dt, fx, fy)
+        assert e == hostile.bicubic_lanewise_recorded(dt, fx, fy) and 0 <= e <= row, (fx, fy, e, row)
+        assert hostile.bicubic_lanewise_top_ok(dt, fx, fy, e), (fx, fy, e)
+        if e < row:
+            lowered[fx, fy] = (e, row)
+            assert not hostile.bicubic_lanewise_top_ok(dt, fx, fy, e + 1), (fx, fy, e)
+        for nx, ny in hostile.BICUBIC_GRIDS:
+            x, y = hostile.bicubic_grid(fx, fy, dt, nx, ny)
+            z, names = hostile.bicubic_nodes(dt, nx, ny, len(hostile.BICUBIC_RECIPES), 0, e)
+            for bi, bc in enumerate(hostile.bicubic_ends()):
+                tabs, _ = hostile.bicubic_reference(x, y, z, bc)
+                for ext in (False, True):
+                    xs, ys = hostile.bicubic_lanewise_queries(x, y, ext, len(names))
+                    rows = hostile.bicubic_lanewise_reference(x, y, z, bc, xs, ys, tabs)
+                    what = f"{np.dtype(dt).name} {fx} x {fy} {nx}x{ny} ends {bi} ext={ext}"
+                    assert not np.array_equal(xs[:, 0], xs[:, 1])
+                    for l in BICUBIC_FINITE:
+                        assert hostile.finite_share(*[t[:, :, l] for t in tabs]) >= 0.9, (what, names[l], "tables")
+                        assert hostile.finite_share(rows[:, l]) >= 0.9, (what, names[l], hostile.finite_share(rows[:, l]))
+                    for l in hostile.BICUBIC_NONFINITE:
+                        assert not np.all(np.isfinite(rows[:, l])), (what, names[l])
+    print(f"{np.dtype(dt).name}: lane-wise top scales below the row-wise ones (e, row-wise e) = {lowered}")
+
+
+BICUBIC_LANEWISE_PARTIAL_CASES = [(dt, fx, fy) for dt in DTYPES for fx, fy in hostile.bicubic_partial_pairs(dt)]
+
+
+@pytest.mark.parametrize("dt,fx,fy", BICUBIC_LANEWISE_PARTIAL_CASES,
+                         ids=[f"{np.dtype(c[0]).name}-{c[1]}-{c[2]}" for c in BICUBIC_LANEWISE_PARTIAL_CASES])
+def test_bicubic_lanewise_partial_lanes_are_what_they_claim(dt, fx, fy):
+    """The partial-order cases of the lane-wise hostile tests (hostile.LANEWISE_PARTIAL_ORDERS on the 25 lanes of
+    bicubic_lanewise_partial_nodes), as test_bicubic_partial_lanes_are_what_they_claim has the row-wise sets: with a query per
+    lane, in range and with extrapolation, on both grids, the integer lane and the order's own top-scale lane are at least
+    90 % finite in the rows of the order, and so are their tables -- but for the cases of INTEGERS_OVERFLOW, whose lane repeats
+    the integers (exponent 0) and claims nothing; that those are the only cases in which the integers fall short on these
+    lists is asserted.  The exponent of every order is searched again and equals the recorded one: the row-wise exponent of
+    that order where it holds the share on these lists, else the largest below it that does (one step up does not)."""
+    name = np.dtype(dt).name
+    found = {}
+    for order in hostile.LANEWISE_PARTIAL_ORDERS:
+        what = f"{name} {fx} x {fy} {order}"
+        e = found[order] = hostile.bicubic_lanewise_partial_top_exponent(dt, fx, fy, order, recorded=False)
+        row = hostile.bicubic_top_exponent(dt, fx, fy, order)
+        assert e == hostile.bicubic_lanewise_recorded(dt, fx, fy, order) and 0 <= e <= row, (what, e, row)
+        listed = (fx, fy, order) in INTEGERS_OVERFLOW[dt]
+        falls_short = hostile.bicubic_lanewise_integer_share(dt, fx, fy, order) < 0.9 or \
+            not hostile.bicubic_lanewise_partial_top_ok(dt, fx, fy, order, 0)
+        assert falls_short == listed, (what, "the integers on the lane-wise lists", falls_short)
+        if listed:
+            assert e == 0, what
+            continue
+        assert hostile.bicubic_lanewise_partial_top_ok(dt, fx, fy, order, e), (what, e)
+        if e < row:
+            assert not hostile.bicubic_lanewise_partial_top_ok(dt, fx, fy, order, e + 1), (what, e)
+    for nx, ny in hostile.BICUBIC_GRIDS:          # ... and on the arrays and the arrangement the device test runs
+        x, y = hostile.bicubic_grid(fx, fy, dt, nx, ny)
+        z, lanes = hostile.bicubic_lanewise_partial_nodes(dt, nx, ny, fx, fy)
+        zr, lanes_r = hostile.bicubic_partial_nodes(dt, nx, ny, fx, fy)
+        zf, lanes_f = hostile.bicubic_lanewise_partial_nodes(dt, nx, ny, fx, fy, finite_only=True)
+        assert lanes == lanes_r and len(lanes) == 25
+        tabs, _ = hostile.bicubic_reference(x, y, z, None)
+        for l, (recipe, o) in enumerate(lanes):
+            if l in hostile.BICUBIC_NONFINITE:
+                assert lanes_f[l] == ("integers", (0, 0)) and np.all(np.isfinite(zf[..., l])) and not np.all(np.isfinite(z[..., l]))
+            else:
+                check_bits(zf[..., l], z[..., l], f"finite_only, lane {l}")
+            if recipe == "top scale" and o in found:
+                ints = hostile.bicubic_lane("integers", dt, nx, ny, np.random.default_rng([0, nx, ny, 7]))
+                with np.errstate(over="ignore"):
+                    check_bits(z[..., l], (ints * np.ldexp(dt(1), found[o])).astype(dt), f"top lane {o}")
+            elif not (recipe == "top scale" and o == (0, 0)):
+                check_bits(z[..., l], zr[..., l], f"lane {l} is the row-wise array's")
+        for order in hostile.LANEWISE_PARTIAL_ORDERS:
+            if (fx, fy, order) in INTEGERS_OVERFLOW[dt]:
+                continue
+            sel = [lanes.index(("integers", (0, 0))), lanes.index(("top scale", order))]
+            for ext in (False, True):
+                xs, ys = hostile.bicubic_lanewise_queries(x, y, ext, len(lanes))
+                rows = hostile.bicubic_lanewise_reference(x, y, np.ascontiguousarray(z[..., sel]), None, np.ascontiguousarray(xs[:, sel]),
+                                                          np.ascontiguousarray(ys[:, sel]), tuple(t[..., sel] for t in tabs), order=order)
+                for k, l in enumerate(sel):
+                    what = f"{name} {fx} x {fy} {nx}x{ny} {order} ext={ext} lane {lanes[l]}"
+                    assert hostile.finite_share(*[t[:, :, l] for t in tabs]) >= 0.9, (what, "tables")
+                    assert hostile.finite_share(rows[:, k]) >= 0.9, (what, hostile.finite_share(rows[:, k]))
+    print(f"{name} {fx} x {fy}: lane-wise top scales per order {found}")
