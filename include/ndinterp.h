@@ -452,6 +452,48 @@ ndi_status ndi_interp1d_create(const ndi_interp1d_desc* desc, ndi_interp1d** out
  * there is nothing of scipy's to deviate from).  desc->strategy must be NDI_CUBIC_HERMITE; ndi_interp1d_create refuses that
  * strategy with NDI_BAD_ARG.  The handle is an ndi_interp1d like any other. */
 ndi_status ndi_interp1d_create_hermite(const ndi_interp1d_desc* desc, const void* dydx, ndi_interp1d** out);
+/* An x axis PER LANE (this project's own; np.interp per row with xp, fp and the queries all batched): `x_lanes` is
+ * T[n][lanes] in desc->memspace, C order like `data`; column l holds the knots of lane l, and lane l of the handle is the
+ * interpolant of (x_lanes[:, l], data[:, l]) alone -- a calibration curve per channel, each measured at its own abscissae.
+ * desc->x must be NULL and desc->x_len == n.  `dydx` is T[n][lanes] for NDI_CUBIC_HERMITE and NULL otherwise.  f32 / f64 only:
+ * the integer and half-precision types are NDI_UNSUPPORTED.  `*out` is cleared first.  The handle is an ndi_interp1d.
+ * Strategies: NDI_LINEAR, NDI_PCHIP, NDI_AKIMA, NDI_CUBIC_HERMITE, and NDI_CUBIC_SPLINE with the global ends desc->left /
+ * desc->right (NotAKnot, Natural, Clamped, FirstDeriv, SecondDeriv; the n == 3 NotAKnot x NotAKnot parabola rows included).
+ * desc->periodic and the four lane_* arrays (BoundaryCondition::Individual) are NDI_UNSUPPORTED with a message that names
+ * the reason.  The minimum lengths are the strategies' own (NDI_NOT_ENOUGH_DATA below them).  desc->validate and
+ * desc->build_flags are not read: the columns are always checked, and the build is always in the reference's order.
+ * Validation: every column must be strictly rising with no NaN, else NDI_MONOTONIC with the text
+ * "Values in the x axis need to be strictly monotonic rising (lane L)", L the lowest offending lane.  Host arrays are
+ * checked on the host before any device work (the error comes back on a machine with no GPU); device arrays by one
+ * kernel pass.  The build runs on the NULL stream and is complete on return.
+ * Build value rule: ndi_interp1d_coefficients(h, a, b, ...) returns tables whose column l is, bit for bit, what it returns for
+ * the shared-axis handle built from (x_lanes[:, l], data[:, l]) alone with the same strategy and ends and build_flags =
+ * NDI_BUILD_REFERENCE_ORDER.  Every line of the build is one IEEE operation in T, nothing fused, divisions correctly
+ * rounded: the local cubics are the stencil stated at ndi_strategy1d with h_i = x[i+1][l] - x[i][l]; the spline forms
+ * low / mid / up, w = low[i] / mid'[i-1], mid'[i] = mid[i] - w * up[i-1] and the boundary rows per lane in the reference's
+ * operation order (cubic_spline.rs:409-721; a, b :350-365).
+ * Evaluation: the handle takes both entry points,
+ *     ndi_interp1d_eval(h, q[nq], ...)                         out[j][l] = f_l(q[j])
+ *     ndi_interp1d_eval_lanewise(h, q[nq][q_row_stride], ...)  out[j][l] = f_l(q[j][l]).
+ * The search is part of the contract:  lo = 0, hi = n-1;  while (hi - lo > 1) { mid = (lo + hi) >> 1;
+ * if (x[mid][l] <= q) lo = mid; else hi = mid; }  -- the unique cell with x[i] <= q < x[i+1], clamped to [0, n-2], so
+ * q == x[n-1][l] lands in n-2 with t = 1.  Linear evaluates ((y2-y1)/(x2-x1)) * (q-x1) + y1; the cubic class t = (q - xl) /
+ * (xr - xl) and cubic_spline.rs:824-828.
+ * Evaluation value rule: out[j][l] is, bit for bit and zero signs included, element 0 of the row ndi_interp1d_eval writes for
+ * that query on the single-column handle of lane l -- with `extrapolate` too, where each lane continues its own end
+ * interval.
+ * Range and errors: ndi_interp1d_eval tests the range common to all lanes, Lo = max_l x[0][l], Hi = min_l x[n-1][l] (a
+ * query outside it is outside some lane's range; Lo > Hi is allowed, then every query fails).  Without `extrapolate` the
+ * lowest failing query index wins: info->index = j, info->value = q[j], axis 0, "x = ... is not in range"; rows before it
+ * are written and later rows are untouched (NDI_EVAL_FRESH_OUTPUT: the kernel tests the queries itself, later rows are
+ * unspecified).  With `extrapolate` a NaN gives NDI_NAN_QUERY.  ndi_interp1d_eval_lanewise tests each element against its
+ * own lane's [x[0][l], x[n-1][l]] and reports the first failing flat element j * lanes + l, as on every other handle.
+ * Not provided, each NDI_UNSUPPORTED with a message: NDI_PATH_BUCKETED (there is no common interval to group queries by),
+ * async_launch on the lane-wise call, ndi_interp1d_eval_ring, the sharded calls, ndi_interp1d_derivative, _antiderivative
+ * and _inverse.  ndi_interp1d_clone copies the tables; ndi_interp1d_data, _coefficients (cubic class), _destroy and _trim
+ * work as on any handle. */
+ndi_status ndi_interp1d_create_lane_axes(const ndi_interp1d_desc* desc, const void* x_lanes, const void* dydx,
+                                         ndi_interp1d** out);
 void ndi_interp1d_destroy(ndi_interp1d* h);
 ndi_status ndi_interp2d_create(const ndi_interp2d_desc* desc, ndi_interp2d** out);
 /* The Bicubic strategy (contract above ndi_interp1d).  `bc`: four boundaries in the order x-left, x-right, y-left, y-right,

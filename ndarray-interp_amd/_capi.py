@@ -100,6 +100,7 @@ _P = C.c_void_p
 SYMBOLS = {
     "ndi_interp1d_create": (C.c_int, [C.POINTER(Interp1DDesc), C.POINTER(_P)]),
     "ndi_interp1d_create_hermite": (C.c_int, [C.POINTER(Interp1DDesc), _P, C.POINTER(_P)]),
+    "ndi_interp1d_create_lane_axes": (C.c_int, [C.POINTER(Interp1DDesc), _P, _P, C.POINTER(_P)]),
     "ndi_interp1d_destroy": (None, [_P]),
     "ndi_interp2d_create": (C.c_int, [C.POINTER(Interp2DDesc), C.POINTER(_P)]),
     "ndi_interp2d_create_bicubic": (C.c_int, [C.POINTER(Interp2DDesc), C.POINTER(Boundary), C.POINTER(_P)]),

@@ -7,6 +7,8 @@
 //
 //   hermite_build_kernel<T, RULE, VN>   one thread per table entry (interval i, one lane or one 16-byte vector of lanes);
 //                                       consecutive threads on consecutive lanes, and on consecutive knots for scalar data
+//   ... <T, RULE, 1, true>              LANE_X: the knots are a table x[n][lanes] read per lane (lane_axes_kernels.hpp);
+//                                       the stencil is the same code on h_i = x[i+1][l] - x[i][l]
 //
 // Numerical contract (include/ndinterp.h, ndi_strategy1d): every line below is one IEEE operation in T, in the stated
 // order, nothing fused (-ffp-contract=off, correctly rounded division), so the tables are bit-identical to a numpy
@@ -21,7 +23,7 @@ enum HermiteRule : int { HR_SPLINE = 0, HR_PCHIP = 1, HR_AKIMA = 2, HR_GIVEN = 3
 template <class T>
 struct HermiteArgs {
   const T* data;   // [n][lanes]
-  const T* x;      // [n] knots (the pyramid's level 0)
+  const T* x;      // [n] knots (the pyramid's level 0); LANE_X: [n][lanes], a column of knots per lane
   const T* dydx;   // HR_GIVEN: [n][lanes] derivatives
   T* ca;           // [n-1][lanes]
   T* cb;           // [n-1][lanes]
@@ -86,9 +88,10 @@ __device__ __forceinline__ void akima_extend(T (&m)[5], uint64_t i, uint64_t n) 
 
 // One table entry: interval i, lanes [lv * VN, lv * VN + VN).  Reads rows i - HALO .. i + 1 + HALO where they exist
 // (the neighbouring rows are other threads' own rows: they come from L2), forms k_i and k_{i+1}, writes a_i, b_i.
-template <class T, int RULE, int VN>
+template <class T, int RULE, int VN, bool LANE_X = false>
 __device__ __forceinline__ void hermite_entry(const HermiteArgs<T>& A, uint64_t i, uint64_t lv) {
   using V = typename VecT<T, VN>::type;
+  static_assert(!LANE_X || VN == 1, "a knot column per lane: one lane per thread");
   const uint64_t n = A.n, L = A.lanes;
   const uint64_t off = i * L + lv * VN;
   constexpr int HALO = RULE == HR_AKIMA ? 2 : (RULE == HR_PCHIP ? 1 : 0);
@@ -102,7 +105,8 @@ __device__ __forceinline__ void hermite_entry(const HermiteArgs<T>& A, uint64_t 
     xs[w] = T(0);
     if (ok) {
       y[w] = *reinterpret_cast<const V*>(A.data + (off + (uint64_t)w * L - (uint64_t)HALO * L));
-      xs[w] = const_load(A.x, i + w - HALO);
+      if constexpr (LANE_X) xs[w] = A.x[off + (uint64_t)w * L - (uint64_t)HALO * L];
+      else xs[w] = const_load(A.x, i + w - HALO);
     }
   }
   const T hi = xs[HALO + 1] - xs[HALO];
@@ -152,7 +156,7 @@ __device__ __forceinline__ void hermite_entry(const HermiteArgs<T>& A, uint64_t 
   }
 }
 
-template <class T, int RULE, int VN>
+template <class T, int RULE, int VN, bool LANE_X = false>
 __global__ __launch_bounds__(BLOCK) void hermite_build_kernel(HermiteArgs<T> A) {
   const uint64_t LV = A.lanes / VN, total = (A.n - 1) * LV;
   const uint64_t step = (uint64_t)gridDim.x * BLOCK;
@@ -169,7 +173,7 @@ __global__ __launch_bounds__(BLOCK) void hermite_build_kernel(HermiteArgs<T> A) 
       i = e / LV;
       lv = e - i * LV;
     }
-    hermite_entry<T, RULE, VN>(A, NDI_CHK(i, A.n - 1, BC_INTERVAL), lv);
+    hermite_entry<T, RULE, VN, LANE_X>(A, NDI_CHK(i, A.n - 1, BC_INTERVAL), lv);
   }
 }
 

@@ -66,6 +66,38 @@ ndi_status check_axis_1d(const T* x, uint64_t x_len, uint64_t n, int strategy) {
   return NDI_OK;
 }
 
+// An x axis per lane (ndi_interp1d_create_lane_axes): x is T[n][lanes], column l the knots of lane l.  The lowest lane
+// whose column is not strictly rising -- a tie, a fall, or a NaN anywhere in it (n >= 2: every knot is in a pair, and a
+// NaN compares false) -- or `lanes` when every column passes.  Rows are walked in memory order.
+template <class T>
+uint64_t first_bad_lane_axis(const T* x, uint64_t n, uint64_t lanes) {
+  uint64_t bad = lanes;
+  for (uint64_t i = 1; i < n; ++i) {
+    const T* prev = x + (i - 1) * lanes;
+    const T* cur = x + i * lanes;
+    for (uint64_t l = 0; l < bad; ++l)   // (lanes at / above the lowest offender found so far cannot change the answer)
+      if (!(cur[l] > prev[l])) bad = l;
+  }
+  return bad;
+}
+
+inline ndi_status lane_axes_monotonic_error(uint64_t lane) {
+  return fail(NDI_MONOTONIC, "Values in the x axis need to be strictly monotonic rising (lane %llu)", (unsigned long long)lane);
+}
+
+// The builder's checks on host arrays, in the reference's order (interp1d/mod.rs:449-471): the strategy's minimum length,
+// then every column strictly rising.
+template <class T>
+ndi_status check_lane_axes(const T* x, uint64_t n, uint64_t lanes, int strategy) {
+  const uint64_t need = min_len_1d(strategy);
+  if (n < need)
+    return fail(NDI_NOT_ENOUGH_DATA, "The chosen Interpolation strategy needs at least %llu data points",
+                (unsigned long long)need);
+  const uint64_t bad = first_bad_lane_axis(x, n, lanes);
+  if (bad < lanes) return lane_axes_monotonic_error(bad);
+  return NDI_OK;
+}
+
 // Interp2DBuilder::build, src/interp2d/mod.rs:477-509 (check order preserved).
 template <class T>
 ndi_status check_axes_2d(const T* x, uint64_t x_len, const T* y, uint64_t y_len, uint64_t nx,

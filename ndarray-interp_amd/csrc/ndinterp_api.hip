@@ -34,6 +34,7 @@
 #include "antiderivative_kernels.hpp"
 #include "inverse_kernels.hpp"
 #include "lanewise_kernels.hpp"
+#include "lane_axes_kernels.hpp"
 #include "bicubic_kernels.hpp"
 #include "bicubic_local_kernels.hpp"
 #include "bicubic_integral_kernels.hpp"
@@ -930,6 +931,7 @@ struct Interp1DBase {
   // ndi_interp1d_inverse: the refusals come before any device work
   virtual ndi_status inverse(Interp1DBase** out) = 0;
   bool inverse_handle = false;   // an inverse handle (inverse_host.hpp): its queries are values, its rows abscissae
+  bool lane_axes_handle = false; // a handle with an x axis per lane (lane_axes_host.hpp)
   // ndi_interp1d_eval_lanewise (lanewise_host.hpp): f32 / f64 handles only
   virtual ndi_status eval_lanewise(const void* q, uint64_t nq, uint64_t q_stride, void* out, uint64_t out_stride,
                                    const ndi_eval_opts* opts, ndi_oob_info* info) {
@@ -1330,6 +1332,7 @@ struct Interp1DImpl final : Interp1DBase, FloatEngine<T, Interp1DImpl<T>> {
 #include "antiderivative_host.hpp"
 #include "inverse_host.hpp"
 #include "lanewise_host.hpp"
+#include "lane_axes_host.hpp"
 
 template <class T>
 static std::vector<T> default_axis(uint64_t n) {
@@ -2535,6 +2538,63 @@ NDI_API ndi_status ndi_interp1d_create_hermite(const ndi_interp1d_desc* desc, co
   return create1d_checked(desc, dydx, true, out);
 }
 
+// ndi_interp1d_create_lane_axes: every check that needs no device comes first -- for host arrays the column validation too.
+NDI_API ndi_status ndi_interp1d_create_lane_axes(const ndi_interp1d_desc* desc, const void* x_lanes, const void* dydx,
+                                                 ndi_interp1d** out) {
+  if (!desc || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
+  *out = nullptr;
+  if (desc->dtype < NDI_F32 || desc->dtype > NDI_BF16) return ndi::fail(NDI_BAD_ARG, "unknown dtype");
+  if (desc->dtype != NDI_F32 && desc->dtype != NDI_F64)
+    return ndi::fail(NDI_UNSUPPORTED, "an x axis per lane needs f32 / f64 data: %s handles search one shared axis of widened "
+                     "knots, which a knot column per lane does not have",
+                     (desc->dtype == NDI_I32 || desc->dtype == NDI_I64) ? "integer" : "f16 / bf16");
+  if (desc->strategy < NDI_LINEAR || desc->strategy > NDI_CUBIC_HERMITE) return ndi::fail(NDI_BAD_ARG, "unknown strategy");
+  const char* name = strategy1d_name(desc->strategy);
+  if (desc->x) return ndi::fail(NDI_BAD_ARG, "ndi_interp1d_create_lane_axes takes the knots as x_lanes: desc->x must be NULL");
+  if (desc->x_len != desc->n)
+    return ndi::fail(NDI_BAD_ARG, "desc->x_len (%llu) must equal desc->n (%llu): x_lanes has the data's shape",
+                     (unsigned long long)desc->x_len, (unsigned long long)desc->n);
+  if (desc->memspace != NDI_MEM_HOST && desc->memspace != NDI_MEM_DEVICE) return ndi::fail(NDI_BAD_ARG, "unknown memspace");
+  if (!x_lanes) return ndi::fail(NDI_BAD_ARG, "null x_lanes pointer");
+  if (!desc->data) return ndi::fail(NDI_BAD_ARG, "null data pointer");
+  if (desc->lanes == 0) return ndi::fail(NDI_BAD_ARG, "lanes must be >= 1");
+  if (desc->strategy == NDI_CUBIC_HERMITE && !dydx) return ndi::fail(NDI_BAD_ARG, "null dydx pointer (CubicHermite needs the knot derivatives)");
+  if (desc->strategy != NDI_CUBIC_HERMITE && dydx) return ndi::fail(NDI_BAD_ARG, "%s takes no dydx (it must be NULL)", name);
+  if (desc->periodic)
+    return ndi::fail(NDI_UNSUPPORTED, "%s with an x axis per lane has no periodic mode: the periodic system and the wrapped "
+                     "query need one period, and here every lane has its own end knots", name);
+  if (desc->lane_left_kind || desc->lane_left_value || desc->lane_right_kind || desc->lane_right_value)
+    return ndi::fail(NDI_UNSUPPORTED, "%s with an x axis per lane takes the global boundaries left / right only: "
+                     "BoundaryCondition::Individual (the lane_* arrays) selects among elimination plans of ONE shared axis", name);
+  if (desc->strategy == NDI_CUBIC_SPLINE) {
+    for (const ndi_boundary* bd : {&desc->left, &desc->right})
+      if (bd->kind < NDI_BC_NOT_A_KNOT || bd->kind > NDI_BC_SECOND_DERIV) return ndi::fail(NDI_BAD_ARG, "unknown boundary kind %d", (int)bd->kind);
+  } else if (desc->strategy != NDI_LINEAR) {
+    if (desc->left.kind || desc->left.value != 0.0 || desc->right.kind || desc->right.value != 0.0)
+      return ndi::fail(NDI_BAD_ARG, "%s takes no boundary condition (left / right must be zero)", name);
+  }
+  if (desc->n < ndi::min_len_1d(desc->strategy))
+    return ndi::fail(NDI_NOT_ENOUGH_DATA, "The chosen Interpolation strategy needs at least %llu data points",
+                     (unsigned long long)ndi::min_len_1d(desc->strategy));
+  if (desc->n > ndi::MAX_KNOTS) return ndi::fail(NDI_UNSUPPORTED, "more than %llu knots", (unsigned long long)ndi::MAX_KNOTS);
+  if (desc->memspace == NDI_MEM_HOST) {
+    const ndi_status vs = desc->dtype == NDI_F32
+                              ? ndi::check_lane_axes(static_cast<const float*>(x_lanes), desc->n, desc->lanes, desc->strategy)
+                              : ndi::check_lane_axes(static_cast<const double*>(x_lanes), desc->n, desc->lanes, desc->strategy);
+    if (vs != NDI_OK) return vs;
+  }
+  ndi_status ds = need_device(desc->device);
+  if (ds != NDI_OK) return ds;
+  NDI_TRY
+  ndi::Interp1DBase* impl = nullptr;
+  ndi_status st = desc->dtype == NDI_F32 ? ndi::create_lane_axes<float>(*desc, x_lanes, dydx, &impl)
+                                         : ndi::create_lane_axes<double>(*desc, x_lanes, dydx, &impl);
+  if (st != NDI_OK) return st;
+  *out = new ndi_interp1d{impl};
+  return ndi::bounds_verdict(NDI_OK, impl->device);
+  NDI_CATCH
+}
+
 NDI_API void ndi_interp1d_destroy(ndi_interp1d* h) {
   if (!h) return;
   try {
@@ -3031,17 +3091,18 @@ static ndi_status sharded_call(const ndi_interp1d* const* handles, uint32_t n, c
   const int dtype = handles[0]->impl->dtype;
   // antiderivative handles take no sharded call; a set that mixes a function with its antiderivative is no set of
   // replicas at all (the signatures differ), which is the first thing to say about it
-  bool anti = false, inv = false;
+  bool anti = false, inv = false, lax = false;
   for (uint32_t i = 0; i < n; ++i) {
     anti = anti || handles[i]->impl->is_antiderivative();
     inv = inv || handles[i]->impl->inverse_handle;
+    lax = lax || handles[i]->impl->lane_axes_handle;
   }
-  if (anti || inv) {
+  if (anti || inv || lax) {
     std::vector<ndi::Interp1DBase*> H;
     const ndi_status st = gather_handles(handles, n, dtype, H);
     if (st != NDI_OK) return st;
     return ndi::fail(NDI_UNSUPPORTED, "the sharded calls do not take %s handles (ndi_interp1d_eval per device serves them)",
-                     inv ? "inverse" : "antiderivative");
+                     lax ? "lane-axes" : inv ? "inverse" : "antiderivative");
   }
   switch (dtype) {
     case NDI_I32: return sharded_narrow_call<ndi::Interp1DIntImpl<int32_t>>(handles, n, c, info);

@@ -68,7 +68,7 @@ class _DeviceStrategy1D(Interp1DStrategy):
 
     # -- build ------------------------------------------------------------------------------
     def _create(self, x, data, *, extrapolate, periodic=False, left=(0, 0.0), right=(0, 0.0),
-                per_lane=None, device=None, build_flags=0, dydx=None):
+                per_lane=None, device=None, build_flags=0, dydx=None, lane_axes=False):
         xb_dt = np_dtype_of(data)
         tid = dtype_id(xb_dt)
         db = Buf(data)
@@ -82,8 +82,8 @@ class _DeviceStrategy1D(Interp1DStrategy):
         d = _capi.Interp1DDesc()
         d.dtype, d.strategy, d.extrapolate, d.device = tid, self._kind, int(bool(extrapolate)), device
         d.n, d.lanes = n, lanes
-        d.x_len = xb.size if xb is not None else n
-        d.x = xb.ptr if xb is not None else None
+        d.x_len = xb.size if xb is not None and not lane_axes else n
+        d.x = xb.ptr if xb is not None and not lane_axes else None   # (lane axes: the knot table is an argument of its own)
         d.data = db.ptr
         d.memspace = db.memspace
         d.validate = 0  # Interp1DBuilder.build() has validated already, as in the reference (:449-473)
@@ -100,9 +100,16 @@ class _DeviceStrategy1D(Interp1DStrategy):
             d.lane_left_kind, d.lane_left_value = lk.ctypes.data, lv.ctypes.data
             d.lane_right_kind, d.lane_right_value = rk.ctypes.data, rv.ctypes.data
         h = C.c_void_p()
+        kb = None
         if dydx is not None:   # CubicHermite: the derivatives travel in the same memory space as the data
             kb = Buf(_host(dydx), xb_dt) if db.memspace == _capi.MEM_HOST else Buf(_to_device(dydx, db.keep.device), xb_dt)
             keep.append(kb)
+        if lane_axes:   # x is the knot table (n, lanes...), a column per lane (ndi_interp1d_create_lane_axes)
+            st = _capi.lib().ndi_interp1d_create_lane_axes(C.byref(d), xb.ptr, kb.ptr if kb is not None else None,
+                                                           C.byref(h))
+            if st in (_capi.BAD_ARG, _capi.UNSUPPORTED):   # the library's refusals, with its reason
+                raise ValueError(_capi.last_error())
+        elif kb is not None:
             st = _capi.lib().ndi_interp1d_create_hermite(C.byref(d), kb.ptr, C.byref(h))
         else:
             st = _capi.lib().ndi_interp1d_create(C.byref(d), C.byref(h))
@@ -157,7 +164,7 @@ class _DeviceStrategy1D(Interp1DStrategy):
         nu = operator.index(nu)
         h = C.c_void_p()
         st = _capi.lib().ndi_interp1d_derivative(self._h, nu, C.byref(h))
-        if st == _capi.BAD_ARG:
+        if st in (_capi.BAD_ARG, _capi.UNSUPPORTED):
             raise ValueError(_capi.last_error())
         if st != _capi.OK:
             raise_builder(st)
@@ -173,7 +180,7 @@ class _DeviceStrategy1D(Interp1DStrategy):
         refuses (include/ndinterp.h lists them) raise `ValueError` with its message."""
         h = C.c_void_p()
         st = _capi.lib().ndi_interp1d_antiderivative(self._h, C.byref(h))
-        if st == _capi.BAD_ARG:
+        if st in (_capi.BAD_ARG, _capi.UNSUPPORTED):
             raise ValueError(_capi.last_error())
         if st != _capi.OK:
             raise_builder(st)
@@ -189,7 +196,7 @@ class _DeviceStrategy1D(Interp1DStrategy):
         that is not monotone raises `BuilderError.Monotonic`."""
         h = C.c_void_p()
         st = _capi.lib().ndi_interp1d_inverse(self._h, C.byref(h))
-        if st == _capi.BAD_ARG:
+        if st in (_capi.BAD_ARG, _capi.UNSUPPORTED):
             raise ValueError(_capi.last_error())
         if st != _capi.OK:
             raise_builder(st)
@@ -408,6 +415,11 @@ class Linear(Interp1DStrategyBuilder, _DeviceStrategy1D):
             return HostLinear(_host(x), _host(data), self._extrapolate)
         return self._create(x, data, extrapolate=self._extrapolate, device=self._device_req)
 
+    def build_lane_axes(self, x, data):
+        """`Interp1DBuilder.lane_axes`: `x` is the knot table of the data's shape.  Element types the library refuses
+        (integers, f16 / bf16) raise `ValueError` with its message."""
+        return self._create(x, data, extrapolate=self._extrapolate, device=self._device_req, lane_axes=True)
+
 
 # ---- boundary conditions (cubic_spline.rs:153-217) ---------------------------------------------
 class SingleBoundary:
@@ -507,7 +519,12 @@ class CubicSpline(Interp1DStrategyBuilder):
         self._boundary = boundary
         return self
 
-    def build(self, x, data) -> "CubicSplineStrategy":
+    def build_lane_axes(self, x, data) -> "CubicSplineStrategy":
+        """`Interp1DBuilder.lane_axes`: `x` is the knot table of the data's shape; the global non-periodic boundaries.
+        Periodic and `Individual` raise `ValueError` with the library's message."""
+        return self.build(x, data, lane_axes=True)
+
+    def build(self, x, data, *, lane_axes=False) -> "CubicSplineStrategy":
         if np_dtype_of(data) not in (np.dtype(np.float32), np.dtype(np.float64)):
             # the reference's trait bounds (Pow / Euclid on T) keep the spline to float element types
             got = "bfloat16" if is_bf16(np_dtype_of(data)) else np_dtype_of(data)
@@ -516,6 +533,8 @@ class CubicSpline(Interp1DStrategyBuilder):
         strat = CubicSplineStrategy()
         kw = dict(extrapolate=self._extrapolate, device=self._device_req,
                   build_flags=_capi.BUILD_REFERENCE_ORDER if self._reference_order else 0)
+        if lane_axes:
+            kw["lane_axes"] = True
         if bc.tag == "Periodic":
             kw["periodic"] = True
         elif bc.tag == "Individual":
@@ -744,6 +763,11 @@ class _LocalCubic(Interp1DStrategyBuilder):
         self._check_dtype(data)
         return self._finished()._create(x, data, extrapolate=self._extrapolate, device=self._device_req)
 
+    def build_lane_axes(self, x, data):
+        """`Interp1DBuilder.lane_axes`: `x` is the knot table of the data's shape."""
+        self._check_dtype(data)
+        return self._finished()._create(x, data, extrapolate=self._extrapolate, device=self._device_req, lane_axes=True)
+
 
 class Pchip(_LocalCubic):
     """Piecewise cubic Hermite interpolating polynomial: Fritsch-Butland derivatives with the three-point
@@ -786,13 +810,16 @@ class CubicHermite(_LocalCubic):
     def new(dydx) -> "CubicHermite":
         return CubicHermite(dydx)
 
-    def build(self, x, data):
+    def build(self, x, data, *, lane_axes=False):
         self._check_dtype(data)
         if tuple(self._dydx.shape) != tuple(data.shape):
             raise BuilderError.ShapeError(
                 f"dydx has wrong shape. Expected: {list(data.shape)}, got: {list(self._dydx.shape)}")
         return self._finished()._create(x, data, extrapolate=self._extrapolate, device=self._device_req,
-                                        dydx=self._dydx)
+                                        dydx=self._dydx, **({"lane_axes": True} if lane_axes else {}))
+
+    def build_lane_axes(self, x, data):
+        return self.build(x, data, lane_axes=True)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -831,9 +858,12 @@ def _default_axis(n, dt):
 class Interp1D:
     """One dimensional interpolator (interp1d/mod.rs:39-51)."""
 
-    def __init__(self, x, data, strategy):
+    def __init__(self, x, data, strategy, *, lane_axes=False):
         self.x, self.data, self.strategy = x, data, strategy
         self._x_host = _host(x)
+        # an x axis per lane (Interp1DBuilder.lane_axes): `x` is the knot table of the data's shape, column l the knots of
+        # lane l
+        self._lane_axes = bool(lane_axes)
 
     # construction ---------------------------------------------------------------------------
     @staticmethod
@@ -847,9 +877,14 @@ class Interp1D:
 
     # helpers the strategies use ------------------------------------------------------------------
     def index_point(self, index: int):
+        if self._lane_axes:
+            raise ValueError("index_point: this interpolator has lane axes (an x axis per lane): there is no one x per index")
         return self._x_host[index], self.data[index]
 
     def get_index_left_of(self, x) -> int:
+        if self._lane_axes:
+            raise ValueError("get_index_left_of: this interpolator has lane axes (an x axis per lane): every lane has its "
+                             "own interval for x")
         k = self._x_host
         if k.dtype in (np.float32, np.float64):
             r = int(get_lower_index(np.ascontiguousarray(k), np.array([x], dtype=k.dtype))[0])
@@ -859,6 +894,8 @@ class Interp1D:
         return int(np.clip(np.searchsorted(k, x, side="right") - 1, 0, k.size - 2))
 
     def is_in_range(self, x) -> bool:
+        if self._lane_axes:   # the range common to all lanes: what interp / interp_array test
+            return bool(self._x_host[0].max() <= x <= self._x_host[-1].min())
         return bool(self._x_host[0] <= x <= self._x_host[-1])
 
     # queries ----------------------------------------------------------------------------------
@@ -1010,7 +1047,7 @@ class Interp1D:
         what `sharding.interp_array_sharded` takes.  `interp.replicate(range(pkg.device_count()))`."""
         if not hasattr(self.strategy, "clone"):
             raise TypeError("replicate needs a built-in device strategy (f32 / f64 data)")
-        return [Interp1D(self.x, self.data, self.strategy.clone(d)) for d in devices]
+        return [Interp1D(self.x, self.data, self.strategy.clone(d), lane_axes=self._lane_axes) for d in devices]
 
     def derivative(self, nu: int = 1) -> "Interp1D":
         """The `nu`-th derivative of this interpolator as an interpolator of its own (scipy's
@@ -1094,9 +1131,10 @@ class Interp1D:
 class Interp1DBuilder:
     """Create and configure a `Interp1D` interpolator (interp1d/mod.rs:60-70, 389-477)."""
 
-    def __init__(self, data, x=None, strategy=None):
+    def __init__(self, data, x=None, strategy=None, lane_x=None):
         self._data = data
         self._x = x
+        self._lane_x = lane_x
         self._strategy = strategy if strategy is not None else Linear.new()  # :408
 
     @staticmethod
@@ -1104,10 +1142,51 @@ class Interp1DBuilder:
         return Interp1DBuilder(data)
 
     def x(self, x) -> "Interp1DBuilder":
-        return Interp1DBuilder(self._data, x, self._strategy)
+        return Interp1DBuilder(self._data, x, self._strategy, self._lane_x)
+
+    def lane_axes(self, x) -> "Interp1DBuilder":
+        """An x axis PER LANE (this mirror's own; ndi_interp1d_create_lane_axes): `x` has the data's shape, element type
+        and residence (host array or device tensor), and `x[:, l...]` holds the knots of lane `l...`, each column strictly
+        rising.  Lane `l` of the interpolator is the interpolant of `(x[:, l], data[:, l])` alone: `np.interp` per row
+        with `xp`, `fp` and the queries all batched.  Works with Linear, CubicSpline (the global non-periodic
+        boundaries), Pchip, Akima and CubicHermite on f32 / f64 data; `.x(...)` cannot be given as well."""
+        return Interp1DBuilder(self._data, self._x, self._strategy, x)
 
     def strategy(self, strategy) -> "Interp1DBuilder":
-        return Interp1DBuilder(self._data, self._x, strategy)
+        return Interp1DBuilder(self._data, self._x, strategy, self._lane_x)
+
+    def _build_lane_axes(self) -> Interp1D:
+        """`build()` with `lane_axes(x)`: the reference's check order (interp1d/mod.rs:449-471) with a column per lane."""
+        data, strategy, x = self._data, self._strategy, self._lane_x
+        if self._x is not None:
+            raise BuilderError.ValueError("both x and lane_axes were given: an interpolator has one shared x axis or an x "
+                                          "axis per lane")
+        n = tuple(data.shape)[0]
+        need = type(strategy).MINIMUM_DATA_LENGHT
+        if n < need:
+            raise BuilderError.NotEnoughData(
+                f"The chosen Interpolation strategy needs at least {need} data points")
+        on_device = is_torch(x) and x.is_cuda
+        if not on_device and len(tuple(x.shape)) >= 1:   # (device tensors: the library's kernel pass checks the columns)
+            cols = _host(x)
+            if is_torch(cols):   # (a host bf16 tensor: its f32 image orders the same way)
+                cols = cols.float().numpy()
+            cols = cols.reshape(tuple(x.shape)[0], -1)
+            rising = (cols[1:] > cols[:-1]).all(axis=0) if cols.shape[0] > 1 else np.zeros(cols.shape[1], bool)
+            if not rising.all():
+                raise BuilderError.Monotonic("Values in the x axis need to be strictly monotonic rising "
+                                             f"(lane {int(np.argmin(rising))})")
+        if tuple(x.shape) != tuple(data.shape):
+            raise BuilderError.ShapeError(
+                f"Shapes of the lane axes and the data need to match. Got x: {list(x.shape)}, data: {list(data.shape)}")
+        if np_dtype_of(x) != np_dtype_of(data):
+            raise TypeError(f"lane_axes has element type {np_dtype_of(x)}, the data is {np_dtype_of(data)}")
+        if on_device != (is_torch(data) and data.is_cuda):
+            raise TypeError("lane_axes and data must live in the same memory space (both host arrays or both device tensors)")
+        if not hasattr(strategy, "build_lane_axes"):
+            raise TypeError("lane_axes needs a built-in strategy (Linear, CubicSpline, Pchip, Akima or CubicHermite), got "
+                            f"{type(strategy).__name__}")
+        return Interp1D(x, data, strategy.build_lane_axes(x, data), lane_axes=True)
 
     def build(self) -> Interp1D:
         """Validate input data and create the configured `Interp1D` (interp1d/mod.rs:443-476)."""
@@ -1115,6 +1194,8 @@ class Interp1DBuilder:
         shape = tuple(data.shape)
         if len(shape) < 1:
             raise BuilderError.ShapeError("data dimension is 0, needs to be at least 1")
+        if self._lane_x is not None:
+            return self._build_lane_axes()
         n = shape[0]
         dt = np_dtype_of(data)
         if self._x is None:  # default axis 0..len cast to T (:402-406)

@@ -224,6 +224,12 @@ extern "C" {
         dydx: *const c_void,
         out: *mut *mut ndi_interp1d,
     ) -> i32;
+    pub fn ndi_interp1d_create_lane_axes(
+        desc: *const ndi_interp1d_desc,
+        x_lanes: *const c_void,
+        dydx: *const c_void,
+        out: *mut *mut ndi_interp1d,
+    ) -> i32;
     pub fn ndi_interp1d_destroy(h: *mut ndi_interp1d);
     pub fn ndi_interp2d_create(desc: *const ndi_interp2d_desc, out: *mut *mut ndi_interp2d) -> i32;
     pub fn ndi_interp2d_create_bicubic(
