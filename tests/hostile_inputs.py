@@ -5,7 +5,9 @@ The rules (include/ndinterp.h, ndi_strategy1d / ndi_interp1d_derivative) have da
 IEEE arithmetic: correctly rounded division, nothing fused, f32 subnormals kept.  The generators here plant every branch
 the header names, zeros of both signs, subnormal / overflowing scales and non-finite values at chosen knots, each in a
 lane of its own, so one (n, L) array carries many cases; lanes beyond the planted ones get seeded draws from the same
-recipes.  `cases()` cuts the recipe list into as many arrays as L needs, so every lane mapping sees every recipe.
+recipes.  `cases()` cuts the recipe list into as many arrays as L needs, so every lane mapping sees every recipe;
+`lane_axes_cases()` puts the same arrays over a knot TABLE whose columns cycle through the knot kinds (handles with an x
+axis per lane, tests/test_gpu_lane_axes_hostile.py).
 
 `classify()` is the generators' self-check: it evaluates the header's conditions knot by knot (its own code, not
 hermite_ref.pchip_k / akima_k) and counts how often each branch and data class occurs.
@@ -290,6 +292,38 @@ def cases(rule, dtype, n, L, classes=CLASSES, kinds=KNOT_KINDS):
         for part in range(parts(rule, n, L, cl)):
             x, y, k = generate(rule, dtype, n, L, cl, kind, part)
             yield f"{rule} {np.dtype(dtype).name} n={n} L={L} knots={kind} part={part}", x, y, k
+
+
+def lane_axes_table(dtype, n, L, part=0):
+    """x[n][L] for a handle with an x axis per lane: column l is knots(KNOT_KINDS[(l + part) % 5], dtype, n, seed=l), so every
+    array of five lanes or more holds every knot kind, neighbouring lanes never share a spacing, and the kind in a lane
+    position moves on with the part."""
+    x = np.stack([knots(KNOT_KINDS[(l + part) % len(KNOT_KINDS)], dtype, n, seed=l) for l in range(L)], axis=1)
+    assert np.all(x[1:] > x[:-1])
+    return np.ascontiguousarray(x)
+
+
+def lane_axes_cases(rule, dtype, n, L, classes=CLASSES):
+    """Every array the lane-axes tests of this (rule, dtype, n, L) run: (tag, x[n][L], y, dydx).  y and dydx are generate()'s
+    on the even axis for every part of the recipe list (the recipes are slopes on the unit grid: on another column they are
+    the same values over other spacings, which is the point); x is lane_axes_table of that part."""
+    for part in range(parts(rule, n, L, classes)):
+        _, y, k = generate(rule, dtype, n, L, classes, "even", part)
+        yield f"{rule} {np.dtype(dtype).name} n={n} L={L} lane axes part={part}", lane_axes_table(dtype, n, L, part), y, k
+
+
+def lane_axes_reference(rule, x, y, dydx=None):
+    """(a, b) of a lane-axes table, column by column: reference() of (x[:, l], y[:, l]) alone"""
+    cols = [reference(rule, np.ascontiguousarray(x[:, l]), np.ascontiguousarray(y[:, l:l + 1]),
+                      None if dydx is None else np.ascontiguousarray(dydx[:, l:l + 1])) for l in range(x.shape[1])]
+    return np.concatenate([c[0] for c in cols], axis=1), np.concatenate([c[1] for c in cols], axis=1)
+
+
+def lane_axes_queries(x, extrapolate=True):
+    """(Q, L): queries(x[:, l], extrapolate) per lane, padded to one length by repeating the lane's last query"""
+    cols = [queries(np.ascontiguousarray(x[:, l]), extrapolate) for l in range(x.shape[1])]
+    Q = max(len(c) for c in cols)
+    return np.stack([np.concatenate([c, np.full(Q - len(c), c[-1], x.dtype)]) for c in cols], axis=1)
 
 
 def reference(rule, x, y, dydx=None):

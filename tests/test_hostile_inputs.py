@@ -881,3 +881,88 @@ def test_bicubic_lanewise_partial_lanes_are_what_they_claim(dt, fx, fy):
                     assert hostile.finite_share(*[t[:, :, l] for t in tabs]) >= 0.9, (what, "tables")
                     assert hostile.finite_share(rows[:, k]) >= 0.9, (what, hostile.finite_share(rows[:, k]))
     print(f"{name} {fx} x {fy}: lane-wise top scales per order {found}")
+
+
+# ---- an x axis per lane (tests/test_gpu_lane_axes_hostile.py) -------------------------------------------------------------------
+LANE_AXES_L = 15
+LANE_AXES_NS = (2, 3, 4, 5, 6, 33)
+LANE_AXES_TWIN = ("branch", "zero", "scale")
+LANE_AXES_RULE_NS = [(rule, n) for rule in hostile.RULES for n in LANE_AXES_NS if not (rule == "akima" and n < 3)]
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("rule,n", LANE_AXES_RULE_NS)
+def test_lane_axes_cases_are_seeded_and_shaped(dt, rule, n):
+    """lane_axes_cases: the same call gives the same bits; x, y (and dydx for CubicHermite) are (n, L); every column is
+    strictly rising; column l of part p is knots(KNOT_KINDS[(l + p) % 5], seed=l), so with 15 lanes every array holds every
+    knot kind three times, neighbouring lanes never share a kind, and the kind in a lane position moves on by one with the
+    part: over P parts a position sees min(P, 5) kinds (the recipe lists give 2 to 5 parts); y and dydx are generate()'s of
+    that part on the even axis."""
+    L = LANE_AXES_L
+    for classes in (hostile.CLASSES, LANE_AXES_TWIN):
+        first = list(hostile.lane_axes_cases(rule, dt, n, L, classes))
+        again = list(hostile.lane_axes_cases(rule, dt, n, L, classes))
+        P = hostile.parts(rule, n, L, classes)
+        assert len(first) == len(again) == P >= 2
+        kinds_at = [set() for _ in range(L)]
+        for part, ((tag, x, y, k), (tag2, x2, y2, k2)) in enumerate(zip(first, again)):
+            assert tag == tag2 and f"part={part}" in tag
+            assert x.shape == y.shape == (n, L) and x.dtype == y.dtype == np.dtype(dt) and x.flags.c_contiguous
+            assert (k is None) == (rule != "hermite") and (k is None or (k.shape == (n, L) and k.dtype == np.dtype(dt)))
+            check_bits(x2, x, tag + ": x again")
+            check_bits(y2, y, tag + ": y again")
+            if k is not None:
+                check_bits(k2, k, tag + ": dydx again")
+            assert np.all(x[1:] > x[:-1]) and np.all(np.isfinite(x)), tag
+            _, gy, gk = hostile.generate(rule, dt, n, L, classes, "even", part)
+            check_bits(y, gy, tag + ": y is generate()'s")
+            seen = set()
+            for l in range(L):
+                kind = hostile.KNOT_KINDS[(l + part) % 5]
+                check_bits(x[:, l], hostile.knots(kind, dt, n, seed=l), f"{tag}: column {l} is the {kind} axis")
+                kinds_at[l].add(kind)
+                seen.add(kind)
+            assert seen == set(hostile.KNOT_KINDS), tag
+            if n > 2:          # (two knots: `adjacent` and `mixed` are the same two floats apart from the step)
+                assert all(not np.array_equal(x[:, l], x[:, l + 1]) for l in range(L - 1)), tag
+        assert all(len(s) == min(P, 5) for s in kinds_at), (rule, n, classes, [len(s) for s in kinds_at])
+    q = hostile.lane_axes_queries(first[0][1])
+    assert q.shape[1] == L and q.dtype == np.dtype(dt)
+    for l in range(L):
+        own = hostile.queries(np.ascontiguousarray(first[0][1][:, l]))
+        check_bits(q[:len(own), l], own, f"lane {l}: its own query list first")
+        assert np.all(q[len(own):, l] == own[-1]) or np.isnan(own[-1])
+
+
+def lane_axes_finite_share(rule, x, y, k):
+    """the share of finite elements among the oracle's rows, lane by lane on the lane's own in-range queries, evaluated on
+    the restatement's tables -- nothing of the library is in it"""
+    import oracle
+    finite = total = 0
+    for l in range(x.shape[1]):
+        xc, yc = np.ascontiguousarray(x[:, l]), np.ascontiguousarray(y[:, l:l + 1])
+        a, b = hostile.reference(rule, xc, yc, None if k is None else np.ascontiguousarray(k[:, l:l + 1]))
+        q = hostile.queries(xc, extrapolate=False)
+        assert np.all((q >= xc[0]) & (q <= xc[-1]))
+        st, _, rows = oracle.interp1d_cubic(xc, yc, a, b, q)
+        assert st == oracle.OK
+        finite += int(np.count_nonzero(np.isfinite(rows)))
+        total += rows.size
+    return finite / total
+
+
+def test_lane_axes_twin_arrays_are_mostly_finite():
+    """The twin arrays (classes branch, zero, scale: no planted inf or NaN) on the knot tables of lane_axes_cases: the rows of
+    every array are at least 75 % finite.  The huge and mixed columns overflow the slopes of ordinary data and the scale
+    recipes overflow on any column, so the share is well below 1; what the floor keeps out is an arrangement whose rows are
+    mostly inf and NaN, on which a bit-for-bit comparison says little.  80 arrays; measured worst 79.2 %."""
+    shares = {}
+    for dt in DTYPES:
+        for rule, n in LANE_AXES_RULE_NS:
+            for tag, x, y, k in hostile.lane_axes_cases(rule, dt, n, LANE_AXES_L, LANE_AXES_TWIN):
+                shares[tag] = lane_axes_finite_share(rule, x, y, k)
+    worst = min(shares, key=shares.get)
+    print(f"lane-axes twin arrays: {len(shares)}, worst finite share {shares[worst]:.3f} ({worst})")
+    assert len(shares) == 80
+    low = {t: round(s, 3) for t, s in shares.items() if s < 0.75}
+    assert not low, low
