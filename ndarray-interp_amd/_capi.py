@@ -168,6 +168,26 @@ SYMBOLS = {
     "ndi_interp2d_probe_ceiling": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, _P, C.c_int32, C.POINTER(C.c_double)]),
 }
 
+
+class Interp3DDesc(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32), ("extrapolate", C.c_int32), ("device", C.c_int32), ("memspace", C.c_int32),
+        ("nx", C.c_uint64), ("ny", C.c_uint64), ("nz", C.c_uint64), ("lanes", C.c_uint64),
+        ("x_len", C.c_uint64), ("y_len", C.c_uint64), ("z_len", C.c_uint64),
+        ("x", C.c_void_p), ("y", C.c_void_p), ("z", C.c_void_p), ("data", C.c_void_p),
+        ("validate", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+# every symbol include/ndinterp3d.h declares (the 3-D interface has a header and a table of its own: include/ndinterp.h
+# and SYMBOLS are a frozen pair that the Rust shim binds one to one); bound by the same loader from the same library
+SYMBOLS3D = {
+    "ndi_interp3d_create": (C.c_int, [C.POINTER(Interp3DDesc), C.POINTER(_P)]),
+    "ndi_interp3d_eval": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(EvalOpts), C.POINTER(OobInfo)]),
+    "ndi_interp3d_clone": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),
+    "ndi_interp3d_destroy": (None, [_P]),
+}
+
 _lib = None
 
 
@@ -184,7 +204,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: build it with `make -C {os.path.join(_HERE, 'csrc')}` "
                 "(hipcc, gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS3D.items()):
             fn = getattr(handle, name)  # AttributeError if the .so does not export it
             fn.restype = res
             fn.argtypes = args

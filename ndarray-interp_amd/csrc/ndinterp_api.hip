@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "../../include/ndinterp3d.h"
 #include "host_logic.hpp"
 #include "kernels.hpp"
 #include "hermite_kernels.hpp"
@@ -40,6 +41,7 @@
 #include "bicubic_integral_kernels.hpp"
 #include "bicubic_jet_kernels.hpp"
 #include "lanewise2d_kernels.hpp"
+#include "trilinear_kernels.hpp"
 
 #define NDI_API extern "C" __attribute__((visibility("default")))
 
@@ -1993,6 +1995,11 @@ static ndi_status create2d(const ndi_interp2d_desc& d, Interp2DBase** out) {
 #include "lanewise2d_host.hpp"
 
 // ---------------------------------------------------------------------------------------------
+// Interp3D (Trilinear)
+// ---------------------------------------------------------------------------------------------
+#include "trilinear_host.hpp"
+
+// ---------------------------------------------------------------------------------------------
 // Locator: VectorExtensions::get_lower_index with the knot pyramid resident on the device
 // ---------------------------------------------------------------------------------------------
 struct LocatorBase {
@@ -2438,6 +2445,7 @@ static ndi_status bounds_verdict(ndi_status st, int device) {
 struct ndi_interp1d { ndi::Interp1DBase* impl; };
 struct ndi_interp2d { ndi::Interp2DBase* impl; };
 struct ndi_locator { ndi::LocatorBase* impl; };
+struct ndi_interp3d { ndi::Interp3DBase* impl; };
 
 #define NDI_TRY try {
 #define NDI_CATCH                                                                  \
@@ -3183,6 +3191,73 @@ NDI_API ndi_status ndi_interp2d_eval_ring_sharded(const ndi_interp2d* const* han
   if (const ndi_status vs__ = ndi::take_opts(opts, c.o); vs__ != NDI_OK) return vs__;
   return sharded_call(handles, n_shards, c, info);
   NDI_CATCH
+}
+
+// ---- Interp3D (include/ndinterp3d.h) ----------------------------------------------------------
+// Every refusal is decided before any device work, and the builder's checks on host axes run on the host, so both behave
+// the same on a machine without a device.
+NDI_API ndi_status ndi_interp3d_create(const ndi_interp3d_desc* desc, ndi_interp3d** out) {
+  if (out) *out = nullptr;
+  if (!desc || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
+  if (desc->dtype != NDI_F32 && desc->dtype != NDI_F64)
+    return ndi::fail(NDI_BAD_ARG, "Trilinear takes f32 / f64 data (dtype %d): integer and f16 / bf16 element types are not "
+                     "provided in three dimensions", (int)desc->dtype);
+  if (desc->reserved != 0)
+    return ndi::fail(NDI_BAD_ARG, "ndi_interp3d_desc.reserved must be 0 (got %d): built against another header version?",
+                     (int)desc->reserved);
+  if (desc->validate && desc->memspace == NDI_MEM_HOST) {
+    const ndi_status st =
+        desc->dtype == NDI_F32
+            ? ndi::check_axes_3d<float>((const float*)desc->x, desc->x_len, (const float*)desc->y, desc->y_len,
+                                        (const float*)desc->z, desc->z_len, desc->nx, desc->ny, desc->nz)
+            : ndi::check_axes_3d<double>((const double*)desc->x, desc->x_len, (const double*)desc->y, desc->y_len,
+                                         (const double*)desc->z, desc->z_len, desc->nx, desc->ny, desc->nz);
+    if (st != NDI_OK) return st;
+  }
+  ndi_status ds = need_device(desc->device);
+  if (ds != NDI_OK) return ds;
+  NDI_TRY
+  ndi::Interp3DBase* impl = nullptr;
+  const ndi_status st = desc->dtype == NDI_F32 ? ndi::create3d<float>(*desc, &impl) : ndi::create3d<double>(*desc, &impl);
+  if (st != NDI_OK) return st;
+  *out = new ndi_interp3d{impl};
+  return NDI_OK;
+  NDI_CATCH
+}
+
+NDI_API ndi_status ndi_interp3d_eval(const ndi_interp3d* h, const void* qx, const void* qy, const void* qz, uint64_t nq,
+                                     void* out, uint64_t out_row_stride, const ndi_eval_opts* opts, ndi_oob_info* info) {
+  ndi_eval_opts o;
+  if (const ndi_status os = ndi::trilinear_take_opts(opts, o); os != NDI_OK) return os;
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  NDI_TRY
+  return ndi::bounds_verdict(h->impl->eval(qx, qy, qz, nq, out, out_row_stride, o, info), h->impl->device);
+  NDI_CATCH
+}
+
+NDI_API ndi_status ndi_interp3d_clone(const ndi_interp3d* h, int32_t device, ndi_interp3d** out) {
+  if (out) *out = nullptr;
+  if (!h || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
+  ndi_status ds = need_device(device);
+  if (ds != NDI_OK) return ds;
+  NDI_TRY
+  ndi::Range rg("ndi_interp3d_clone");
+  ndi::Interp3DBase* impl = nullptr;
+  ndi_status st = h->impl->clone_to(device, &impl);
+  if (st != NDI_OK) return st;
+  *out = new ndi_interp3d{impl};
+  return NDI_OK;
+  NDI_CATCH
+}
+
+NDI_API void ndi_interp3d_destroy(ndi_interp3d* h) {
+  if (!h) return;
+  try {
+    ndi::DeviceGuard dg(h->impl->device);
+    delete h->impl;
+  } catch (...) {
+  }
+  delete h;
 }
 
 NDI_API ndi_status ndi_interp1d_trim(const ndi_interp1d* h) {

@@ -94,7 +94,7 @@ def raise_eval(status: int, info: "_capi.OobInfo", query=None):
     if callable(query):
         query = query(int(info.axis)) if status == _capi.OUT_OF_BOUNDS else None
     if status == _capi.OUT_OF_BOUNDS:
-        name = "x" if info.axis == 0 else "y"
+        name = "x" if info.axis == 0 else "y" if info.axis == 1 else "z"   # (z: the 3-D handles)
         # linear.rs:81-83, cubic_spline.rs:799-801, bilinear.rs:72-79
         if query is not None:     # integer element types: `{x:?}` of the query element itself (no decimal point)
             raise InterpolateError.OutOfBounds(f"{name} = {int(query)} is not in range", index=int(info.index),
