@@ -1,5 +1,6 @@
-"""Hostile inputs for the Pchip / Akima / CubicHermite build and the derivative build, and a bit-level comparer; at the
-end of the file the hostile grids, lanes and queries of the 2-D Bicubic strategy and of its partial derivatives.
+"""Hostile inputs for the Pchip / Akima / CubicHermite build and the derivative build, and a bit-level comparer; further
+down the hostile grids, lanes and queries of the 2-D Bicubic strategy and of its partial derivatives; at the end of the file
+the window-edge and hostile-axis cases of the 3-D Trilinear strategy.
 
 The rules (include/ndinterp.h, ndi_strategy1d / ndi_interp1d_derivative) have data-dependent branches and rest on plain
 IEEE arithmetic: correctly rounded division, nothing fused, f32 subnormals kept.  The generators here plant every branch
@@ -1153,3 +1154,207 @@ def bicubic_lanewise_partial_nodes(dtype, nx, ny, fx, fy, C=25, seed=0, finite_o
         with np.errstate(over="ignore"):
             z[:, :, l] = (ints * np.ldexp(T(1), e)).astype(dtype)
     return z, lanes
+
+
+# ---- Trilinear: the edges of the division window and hostile axes (tests/test_gpu_trilinear_hostile.py; self-check in
+# tests/test_hostile_inputs.py) ---------------------------------------------------------------------------------------------
+# The exponent window of the shared-divisor division, restated from the comment above DivWindow in csrc/kernels.hpp: the
+# reciprocal path is taken when the divisor lies in [D_LO, D_HI], the smallest numerator magnitude of a vector is >= N_LO
+# and the sum of the vector's magnitudes is <= N_HI; everything else is the IEEE division.
+TRILINEAR_WINDOW = {np.dtype(np.float32): dict(N_LO=-60, N_HI=60, D_LO=-40, D_HI=40),
+                    np.dtype(np.float64): dict(N_LO=-500, N_HI=500, D_LO=-400, D_HI=400)}
+TRILINEAR_WINDOW_TABLES = ("low edge", "sum edge", "scalar edge")
+TRILINEAR_WINDOW_AXES = ("plain", "low divisor", "high divisor")
+TRILINEAR_LANES = 8
+
+
+def trilinear_window(dtype):
+    """{N_LO, N_HI, D_LO, D_HI} as values of `dtype`"""
+    T = np.dtype(dtype).type
+    return {k: np.ldexp(T(1), e) for k, e in TRILINEAR_WINDOW[np.dtype(dtype)].items()}
+
+
+def _prev(v):
+    return np.nextafter(v, v.dtype.type(-np.inf))
+
+
+def _next(v):
+    return np.nextafter(v, v.dtype.type(np.inf))
+
+
+def trilinear_lane_table(table, dtype):
+    """(a, b): the two planted differences of each of the 8 lanes (two 16-byte vectors in f32, four in f64).
+    low edge:    prev(N_LO), N_LO and next(N_LO) beside in-window lanes: one lane below the edge puts the whole vector on the
+                 IEEE path, the lanes on and above it stay inside.
+    sum edge:    with H = N_HI / (lanes of a vector): a vector of H alone (the sum is exactly N_HI: inside); the same with one
+                 lane next(H) (the exact sum lies above N_HI and the sum as the kernel forms it rounds back to N_HI, ties to
+                 even: inside); the same with one lane four floats above H (the rounded sum lies above N_HI: outside).
+    scalar edge: N_HI and N_HI / 2 lanes, each inside on its own, in vectors whose sum is above N_HI; next(N_HI), outside in
+                 either form; N_HI / 2 twice in an f64 vector (sum exactly N_HI).
+    nonfinite:   (not one of the 27 finite cases) plain lanes; _trilinear_window_case then plants nodes of -+0.75 max in lanes
+                 1 and 6, whose difference overflows: +inf and -inf as the lower numerator of one lane each, inside vectors
+                 that are otherwise in the window -- only the sum test sends them to the IEEE division."""
+    T = np.dtype(dtype).type
+    W = 16 // np.dtype(dtype).itemsize
+    w = trilinear_window(dtype)
+    lo, hi = w["N_LO"], w["N_HI"]
+    one = lambda *v: np.array(v, dtype)   # noqa: E731
+    if table == "low edge":
+        a = one(_prev(lo), 1.0, 3.0, 0.75, lo, _next(lo), 1.5, 2.0)
+        b = np.roll(a, 4)
+    elif table == "sum edge":
+        H = hi / T(W)
+        exact = [H] * W
+        tie = [H] * (W - 1) + [_next(H)]
+        above = [H] * (W - 1) + [H + T(4) * (_next(H) - H)]
+        if W == 4:
+            a, b = one(*exact, *tie), one(*above, *exact)
+        else:
+            a, b = one(*exact, *tie, *above, *exact), one(*above, *exact, *exact, *tie)
+    elif table == "scalar edge":
+        a = one(hi / T(2), hi / T(2), hi, lo, _next(hi), 1.0, 1.5, 2.0)
+        b = one(1.0, 3.0, 0.75, 1.5, hi / T(2), hi / T(2), lo, lo)
+    else:
+        assert table == "nonfinite", table
+        a = one(1.0, 3.0, 0.75, 1.5, 2.0, 1.25, 0.5, 1.0)
+        b = one(1.5, 2.5, 2.0, 1.0, 3.0, 0.75, 0.25, 1.25)
+    assert a.shape == b.shape == (TRILINEAR_LANES,)
+    return a, b
+
+
+def trilinear_plain_axis(dtype, seed):
+    return np.cumsum(np.random.default_rng(4321 + seed).uniform(0.5, 1.5, 3)).astype(dtype)
+
+
+def trilinear_window_axis(kind, dtype, seed=0):
+    """Three knots whose two spacings are computed exactly: plain; [-prev(D_LO), 0, D_LO] (one float below the window, and
+    its lower edge); [-next(D_HI), 0, D_HI] (one float above it, and its upper edge)."""
+    w = trilinear_window(dtype)
+    if kind == "plain":
+        return trilinear_plain_axis(dtype, seed)
+    if kind == "low divisor":
+        return np.array([-_prev(w["D_LO"]), 0.0, w["D_LO"]], dtype)
+    assert kind == "high divisor", kind
+    return np.array([-_next(w["D_HI"]), 0.0, w["D_HI"]], dtype)
+
+
+def _trilinear_window_case(dtype, vary, table, kind):
+    a, b = trilinear_lane_table(table, dtype)
+    col = np.stack([-a, np.zeros_like(a), b])                       # (3, 8): the column along the varying axis
+    if table == "nonfinite":        # finite nodes whose difference overflows: the lower numerator of lanes 1 and 6 is +-inf
+        big = np.dtype(dtype).type(0.75) * np.finfo(dtype).max
+        col[:2, 1] = [-big, big]
+        col[:2, 6] = [big, -big]
+    shape = [1, 1, 1, TRILINEAR_LANES]
+    shape[vary] = 3
+    reps = [3, 3, 3, 1]
+    reps[vary] = 1
+    data = np.ascontiguousarray(np.tile(col.reshape(shape), reps))  # constant along the two other axes
+    axes = [trilinear_window_axis(kind if ax == vary else "plain", dtype, seed=ax) for ax in range(3)]
+    import trilinear_ref
+    km = [trilinear_ref.knots_and_midpoints(k) for k in axes]
+    q = [np.ascontiguousarray(g.ravel()) for g in np.meshgrid(*km, indexing="ij")]
+    return dict(tag=f"{np.dtype(dtype).name} varying {'xyz'[vary]}, {table}, {kind} axis", vary=vary, table=table, kind=kind,
+                axes=axes, data=data, q=q, a=a, b=b)
+
+
+def trilinear_window_cases(dtype):
+    """The 27 cases of one dtype: the varying axis (x, y, z: the division level whose numerators are planted) x the lane table
+    x the kind of the varying axis.  3 x 3 x 3 x 8 data that varies along ONE axis, where its column is [-a, 0, b] per lane:
+    both differences are exactly a and b, the calc_frac steps of the two other axes return y1 exactly (0 / d = 0,
+    0 * t + y1 = y1), so (a, b) are the numerators of that level's division -- d100 - d000 for x, c10 - c00 for y, c1 - c0
+    for z.  Queries: the full product of every axis' knots and midpoints, 125.  Each case is a dict: tag, vary, table, kind,
+    axes, data, q, a, b."""
+    for vary in range(3):
+        for table in TRILINEAR_WINDOW_TABLES:
+            for kind in TRILINEAR_WINDOW_AXES:
+                yield _trilinear_window_case(dtype, vary, table, kind)
+
+
+def trilinear_nonfinite_lane_cases(dtype):
+    """Three cases more, one per varying axis on plain axes: the `nonfinite` lane table.  Their rows hold inf and NaN by
+    construction, so they are no part of the all-finite claim of trilinear_window_cases."""
+    for vary in range(3):
+        yield _trilinear_window_case(dtype, vary, "nonfinite", "plain")
+
+
+TRILINEAR_AXIS_KINDS = ("adjacent", "mixed", "huge", "minus zero", "infinite ends", "subnormal spacing")
+_TRILINEAR_SUB_DATA = {np.dtype(np.float32): -50, np.dtype(np.float64): -60}
+
+
+def trilinear_hostile_axis(kind, dtype):
+    """Five knots: knots() of the kind; an axis with -0.0 as its middle knot; an axis with -inf and +inf as end knots; an axis
+    whose spacing is three times the smallest subnormal (its reciprocal overflows: the divisor is far below the window)."""
+    if kind == "minus zero":
+        return np.array([-2.0, -0.75, -0.0, 1.0, 2.5], dtype)
+    if kind == "infinite ends":
+        return np.array([-np.inf, -1.0, 0.5, 2.0, np.inf], dtype)
+    if kind == "subnormal spacing":
+        return (np.array([-6, -3, 0, 3, 6], dtype) * np.finfo(dtype).smallest_subnormal).astype(dtype)
+    return knots(kind, dtype, 5)
+
+
+def trilinear_axis_queries(k, extrapolate):
+    """One axis: every knot, every cell midpoint, the float either side of every interior knot; both zeros where a zero is a
+    knot; with extrapolation one point a cell width below and one above.
+    An axis with infinite end knots has no outside, and the reference's search cannot place a query strictly between infinite
+    ends (its first guess is calc_frac over the whole axis: 0 * inf).  There the queries are the two end knots, which the
+    reference places without a guess, and the points of the list that lie in [k[1], k[n-2]): the cells with finite knots on
+    both sides, which trilinear_axis_reference evaluates on the finite part of the grid.  The queries inside the two end
+    cells are left out."""
+    T = k.dtype.type
+    mid = ((k[:-1].astype(np.float64) + k[1:].astype(np.float64)) / 2).astype(k.dtype)
+    q = [k, mid, np.nextafter(k[1:-1], T(-np.inf)), np.nextafter(k[1:-1], T(np.inf))]
+    if np.any(k == 0):
+        q.append(np.array([0.0, -0.0], k.dtype))
+    if np.isinf(k[0]) or np.isinf(k[-1]):
+        q = np.concatenate(q).astype(k.dtype)
+        return np.concatenate([k[[0, -1]], q[(q >= k[1]) & (q < k[-2])]])
+    if extrapolate:
+        q.append(np.array([k[0] - (k[1] - k[0]), k[-1] + (k[-1] - k[-2])], k.dtype))
+    return np.concatenate(q).astype(k.dtype)
+
+
+def trilinear_axis_cases(dtype):
+    """The 18 hostile-axis cases of one dtype: each of x, y, z in turn is one of TRILINEAR_AXIS_KINDS, the two others are
+    knots("uneven") with a seed of their own; 5 x 5 x 5 x 4 uniform data in [-1, 1] (over the subnormal spacing: integers in
+    [-4, 4] times 2^-50 / 2^-60 -- differences inside the numerator window whose slopes along that axis are finite, over a
+    divisor whose reciprocal is not).  Each case is a dict: tag, hostile (the
+    axis index), kind, axes, data, and q[extrapolate]: the full product of trilinear_axis_queries of the three axes."""
+    for hostile in range(3):
+        for kind in TRILINEAR_AXIS_KINDS:
+            axes = [trilinear_hostile_axis(kind, dtype) if ax == hostile else knots("uneven", dtype, 5, seed=ax) for ax in range(3)]
+            rng = np.random.default_rng([77, hostile, TRILINEAR_AXIS_KINDS.index(kind)])
+            if kind == "subnormal spacing":
+                data = np.ldexp(rng.integers(-4, 5, (5, 5, 5, 4)).astype(dtype), _TRILINEAR_SUB_DATA[np.dtype(dtype)]).astype(dtype)
+            else:
+                data = rng.uniform(-1, 1, (5, 5, 5, 4)).astype(dtype)
+            q = {}
+            for ext in (False, True):
+                per = [trilinear_axis_queries(k, ext) for k in axes]
+                q[ext] = [np.ascontiguousarray(g.ravel()) for g in np.meshgrid(*per, indexing="ij")]
+            yield dict(tag=f"{np.dtype(dtype).name} {kind} on {'xyz'[hostile]}", hostile=hostile, kind=kind, axes=axes, data=data, q=q)
+
+
+def trilinear_axis_reference(case, extrapolate, form=None):
+    """(fail, axis, out) of tests/trilinear_ref.py (`form`: trilinear_ref by default, or trilinear_direct) for one case.  On
+    an axis with infinite end knots the rows are the reference's in two parts: the queries on the end knots on the whole
+    grid, and the queries in [k[1], k[n-2]) on the grid without its two end planes along that axis -- by the value rule
+    (include/ndinterp3d.h) their cells have all eight corners there, and on that grid the reference's search works."""
+    import trilinear_ref
+    form = form or trilinear_ref.trilinear_ref
+    axes, data, q, h = case["axes"], case["data"], case["q"][extrapolate], case["hostile"]
+    if case["kind"] != "infinite ends":
+        return form(*axes, data, *q, extrapolate)
+    ends = np.isinf(q[h])
+    out = np.zeros((q[0].size, data.shape[3]), data.dtype)
+    fail, axis, rows = form(*axes, data, *[a[ends] for a in q], extrapolate)
+    assert fail is None
+    out[ends] = rows
+    inner_axes = [k[1:-1] if ax == h else k for ax, k in enumerate(axes)]
+    inner = np.ascontiguousarray(np.take(data, np.arange(1, data.shape[h] - 1), axis=h))
+    fail, axis, rows = form(*inner_axes, inner, *[a[~ends] for a in q], extrapolate)
+    assert fail is None
+    out[~ends] = rows
+    return None, None, out
+

@@ -16,7 +16,10 @@
   and rows in every lane that claims them, a +0 / -0 seam lane, and the periodic top-scale exponents searched and recorded;
 * the arrangement with a query per lane (tests/test_gpu_lanewise2d_hostile.py): every lane a permutation of the list, the
   lanes of a row in different places, every finite lane's reference at least 90 % finite in range and with extrapolation,
-  and the top-scale exponents it needs searched and recorded.
+  and the top-scale exponents it needs searched and recorded;
+* the Trilinear window cases (tests/test_gpu_trilinear_hostile.py): planted differences and spacings exactly on the edges of
+  the division window and one float either side, every reference output finite, vectors inside and outside the window in
+  every lane table by a restatement of the kernel's test; the hostile axes strictly rising and at least 75 % finite.
 """
 import os
 
@@ -964,5 +967,184 @@ def test_lane_axes_twin_arrays_are_mostly_finite():
     worst = min(shares, key=shares.get)
     print(f"lane-axes twin arrays: {len(shares)}, worst finite share {shares[worst]:.3f} ({worst})")
     assert len(shares) == 80
+    low = {t: round(s, 3) for t, s in shares.items() if s < 0.75}
+    assert not low, low
+
+
+# ---- Trilinear: window edges and hostile axes (tests/test_gpu_trilinear_hostile.py) ---------------------------------------------
+from fractions import Fraction                     # noqa: E402
+
+import trilinear_ref as tr                         # noqa: E402
+
+
+def vector_in_window(n, dt):
+    """nums_in_window of csrc/kernels.hpp on one 16-byte vector (4 x f32 / 2 x f64), restated: the smallest magnitude >= N_LO
+    and the sum of the magnitudes, formed in the dtype as the kernel forms it -- (|x| + |y|) + (|z| + |w|) in f32, |x| + |y|
+    in f64 -- <= N_HI.  A NaN or an infinity fails the sum test."""
+    w = hostile.trilinear_window(dt)
+    m = np.abs(np.asarray(n, dt))
+    with np.errstate(all="ignore"):
+        s = (m[0] + m[1]) + (m[2] + m[3]) if m.size == 4 else m[0] + m[1]
+        return bool(np.fmin.reduce(m) >= w["N_LO"]) and bool(s <= w["N_HI"])
+
+
+def scalar_in_window(n, dt):
+    w = hostile.trilinear_window(dt)
+    return bool(w["N_LO"] <= abs(n) <= w["N_HI"])
+
+
+def divisor_in_window(d, dt):
+    w = hostile.trilinear_window(dt)
+    return bool(w["D_LO"] <= d <= w["D_HI"])
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_trilinear_window_cases_are_what_they_claim(dt):
+    """27 cases: every planted difference is the intended edge value, every spacing of the varying axis the intended divisor
+    edge, both reference forms agree, every reference output is finite (27 000 of 27 000), and every lane table holds a
+    vector inside the window and one outside it -- and lanes that are inside on their own in a vector that is outside, so
+    that the scalar and the 16-byte form take different paths for the same lane."""
+    T = np.dtype(dt).type
+    w = hostile.trilinear_window(dt)
+    prev, nxt = hostile._prev, hostile._next
+    W = 16 // np.dtype(dt).itemsize
+    assert [w[k] for k in ("N_LO", "N_HI", "D_LO", "D_HI")] == ([2.0 ** -60, 2.0 ** 60, 2.0 ** -40, 2.0 ** 40] if dt == np.float32 else
+                                                                 [2.0 ** -500, 2.0 ** 500, 2.0 ** -400, 2.0 ** 400])
+    cases = list(hostile.trilinear_window_cases(dt))
+    assert len(cases) == 27 and len({c["tag"] for c in cases}) == 27
+    assert {(c["vary"], c["table"], c["kind"]) for c in cases} == {(v, t, k) for v in range(3) for t in hostile.TRILINEAR_WINDOW_TABLES
+                                                                     for k in hostile.TRILINEAR_WINDOW_AXES}
+    # the lane tables, value by value
+    a, b = hostile.trilinear_lane_table("low edge", dt)
+    assert list(a[[0, 4, 5]]) == [prev(w["N_LO"]), w["N_LO"], nxt(w["N_LO"])] and a[0] < w["N_LO"] < a[5]
+    assert np.array_equal(b, np.roll(a, 4))
+    a, b = hostile.trilinear_lane_table("sum edge", dt)
+    H = w["N_HI"] / T(W)
+    assert np.all(a[:W] == H) and sum(Fraction(float(e)) for e in a[:W]) == Fraction(float(w["N_HI"]))       # exactly N_HI
+    assert np.all(a[W:2 * W - 1] == H) and a[2 * W - 1] == nxt(H)
+    assert np.all(b[:W - 1] == H) and b[W - 1] > nxt(H)
+    a, b = hostile.trilinear_lane_table("scalar edge", dt)
+    assert list(a[[2, 3, 4]]) == [w["N_HI"], w["N_LO"], nxt(w["N_HI"])] and a[0] == a[1] == b[4] == b[5] == w["N_HI"] / T(2)
+    finite = total = 0
+    for c in cases:
+        tag, v, data, axes = c["tag"], c["vary"], c["data"], c["axes"]
+        assert data.shape == (3, 3, 3, 8) and data.dtype == np.dtype(dt) and data.flags.c_contiguous, tag
+        assert len(c["q"]) == 3 and all(q.size == 125 and q.dtype == np.dtype(dt) for q in c["q"]), tag
+        # the data varies along one axis only; there the two differences are exactly (a, b), computed in the dtype
+        d = np.moveaxis(data, v, 0)
+        assert np.all(d == d[:, :1, :1, :]), tag
+        col = d[:, 0, 0, :]
+        check_bits(col[1] - col[0], c["a"], tag + ": the lower difference")
+        check_bits(col[2] - col[1], c["b"], tag + ": the upper difference")
+        assert np.all(col[1] == 0) and not np.any(np.signbit(col[1])), tag
+        # the spacings of the varying axis, computed in the dtype, are the intended divisor edges
+        k = axes[v]
+        want = {"plain": None, "low divisor": [prev(w["D_LO"]), w["D_LO"]], "high divisor": [nxt(w["D_HI"]), w["D_HI"]]}[c["kind"]]
+        sp = k[1:] - k[:-1]
+        if want is None:
+            assert all(divisor_in_window(s, dt) for s in sp), tag
+        else:
+            assert list(sp) == want and not divisor_in_window(sp[0], dt) and divisor_in_window(sp[1], dt), tag
+        for o in range(3):
+            if o != v:
+                assert all(divisor_in_window(s, dt) for s in axes[o][1:] - axes[o][:-1]), tag
+        # both forms of the reference, and every output finite
+        r1 = tr.trilinear_ref(*axes, data, *c["q"])
+        r2 = tr.trilinear_direct(*axes, data, *c["q"])
+        assert r1[:2] == r2[:2] == (None, None), tag
+        check_bits(r1[2], r2[2], tag + ": the two reference forms")
+        assert np.array_equal(tr.bits(r1[2]), tr.bits(r2[2])), tag
+        finite += int(np.count_nonzero(np.isfinite(r1[2])))
+        total += r1[2].size
+        assert np.isfinite(r1[2]).all(), tag
+        # the calc_frac steps of the two constant axes return y1: at the knots of the varying axis the rows are the column
+        on = [np.full(3, axes[o][1], dt) if o != v else k for o in range(3)]
+        check_bits(tr.trilinear_ref(*axes, data, *on)[2][:2], col[:2], tag + ": rows on the knots of the varying axis")
+        # the differing-path claim, per lane table (the numerators of both cells of the varying axis)
+        vecs = [n[i:i + W] for n in (c["a"], c["b"]) for i in range(0, 8, W)]
+        inside = [vector_in_window(n, dt) for n in vecs]
+        assert any(inside) and not all(inside), (tag, inside)
+        assert any(not vector_in_window(n, dt) and any(scalar_in_window(e, dt) for e in n) for n in vecs), tag
+    print(f"trilinear window cases {np.dtype(dt).name}: finite {finite} of {total}")
+    assert (finite, total) == (27_000, 27_000)
+    # what the sum edge claims, by the restatement: N_HI exactly is inside; one float more in one lane is a tie that rounds back
+    # to N_HI (inside as the kernel sums it, although the exact sum is above); four floats more is outside
+    a, b = hostile.trilinear_lane_table("sum edge", dt)
+    assert vector_in_window(a[:W], dt) and vector_in_window(a[W:2 * W], dt) and not vector_in_window(b[:W], dt)
+    assert sum(Fraction(float(e)) for e in a[W:2 * W]) > Fraction(float(w["N_HI"]))
+    # the nonfinite table: inside by its smallest magnitude, outside by the sum alone
+    for c in hostile.trilinear_nonfinite_lane_cases(dt):
+        col = np.moveaxis(c["data"], c["vary"], 0)[:, 0, 0, :]
+        assert np.isfinite(c["data"]).all(), c["tag"]
+        with np.errstate(over="ignore"):
+            low = col[1] - col[0]
+        assert low[1] == np.inf and low[6] == -np.inf, c["tag"]
+        vecs = [low[i:i + W] for i in range(0, 8, W)]
+        bad = [n for n in vecs if not np.isfinite(n).all()]
+        assert len(bad) == 2 and all(np.abs(n).min() >= w["N_LO"] and not vector_in_window(n, dt) for n in bad), c["tag"]
+        r1, r2 = tr.trilinear_ref(*c["axes"], c["data"], *c["q"]), tr.trilinear_direct(*c["axes"], c["data"], *c["q"])
+        assert np.array_equal(tr.bits(r1[2]), tr.bits(r2[2])), c["tag"]
+        # an infinite row survives where the planted division is the last one (z); after x or y the next level's difference of
+        # two equal infinities is NaN
+        assert np.isinf(r1[2]).any() == (c["vary"] == 2) and np.isnan(r1[2][:, [1, 6]]).any(), c["tag"]
+        assert np.isfinite(r1[2][:, [0, 2, 3, 4, 5, 7]]).all(), c["tag"]
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_trilinear_axis_cases_are_what_they_claim(pkg, dt):
+    """18 cases: every axis strictly rising (infinite end knots included: the builder's scan accepts them), adjacent floats
+    where intended, -0.0 a knot and both zeros queries where intended, both reference forms agree, and at least 75 % of the
+    reference's outputs are finite in every case, in range and extrapolating (NaN only where an infinite knot bounds the
+    cell; measured: 0.8 on an axis with infinite ends -- 8 of its 10 queries -- and 1.0 everywhere else).  The reference's
+    search cannot place a query strictly between infinite end knots: that is asserted here, and is why those cases keep
+    the end knots and the queries of the inner cells only (hostile_inputs.trilinear_axis_reference)."""
+    from ndarray_interp_amd.vector_extensions import Monotonic, monotonic_prop
+    cases = list(hostile.trilinear_axis_cases(dt))
+    assert len(cases) == 18 and len({c["tag"] for c in cases}) == 18
+    shares = {}
+    for c in cases:
+        tag, h, axes, data = c["tag"], c["hostile"], c["axes"], c["data"]
+        assert data.shape == (5, 5, 5, 4) and data.dtype == np.dtype(dt) and np.isfinite(data).all(), tag
+        for o, k in enumerate(axes):
+            assert k.shape == (5,) and k.dtype == np.dtype(dt) and np.all(k[1:] > k[:-1]), tag
+            assert monotonic_prop(k) == Monotonic.Rising(True), tag
+            assert hostile.has_adjacent(k) == (o == h and c["kind"] in ("adjacent", "mixed")), tag
+            assert np.isfinite(k).all() == (not (o == h and c["kind"] == "infinite ends")), tag
+        k = axes[h]
+        if c["kind"] == "minus zero":
+            assert k[2] == 0 and np.signbit(k[2]), tag
+        if c["kind"] == "infinite ends":
+            assert k[0] == -np.inf and k[-1] == np.inf, tag
+        for ext in (False, True):
+            q = c["q"][ext]
+            per = hostile.trilinear_axis_queries(k, ext)
+            if c["kind"] == "infinite ends":        # the end knots, and every point of the list inside the inner cells
+                assert list(per[:2]) == [-np.inf, np.inf] and np.all((per[2:] >= k[1]) & (per[2:] < k[3])) and per.size == 10, tag
+                assert {k[1], k[2], np.nextafter(k[1], dt(np.inf)), np.nextafter(k[3], dt(-np.inf))} <= set(per), tag
+                import oracle                                # an interior query on the whole axis: the reference's guess is NaN
+                assert list(oracle.get_lower_index(k, np.array([-np.inf, 0.25, np.inf], dt))) == [0, -1, 3], tag
+            else:
+                assert set(tr.bits(k)) <= set(tr.bits(per)), tag                               # every knot is a query
+                assert set(tr.bits(np.nextafter(k[1:-1], dt(np.inf)))) | set(tr.bits(np.nextafter(k[1:-1], dt(-np.inf)))) <= set(tr.bits(per)), tag
+            if c["kind"] in ("minus zero", "huge"):
+                z = per[per == 0]
+                assert np.signbit(z).any() and not np.signbit(z).all(), tag
+            outside = (per < k[0]) | (per > k[-1])
+            assert outside.sum() == (2 if ext and c["kind"] != "infinite ends" else 0), tag
+            r1 = hostile.trilinear_axis_reference(c, ext)
+            r2 = hostile.trilinear_axis_reference(c, ext, tr.trilinear_direct)
+            assert r1[:2] == r2[:2] == (None, None), tag
+            assert np.array_equal(tr.bits(r1[2]), tr.bits(r2[2])), tag
+            shares[tag, ext] = hostile.finite_share(r1[2])
+            if c["kind"] == "subnormal spacing":        # the reciprocal of the spacing overflows, many numerators are in the window
+                W = 16 // np.dtype(dt).itemsize
+                with np.errstate(over="ignore"):
+                    assert np.isinf(dt(1) / (k[1:] - k[:-1])).all(), tag
+                n = np.diff(data, axis=h).reshape(-1, W)
+                assert np.mean([vector_in_window(v, dt) for v in n]) > 0.5, tag
+            if c["kind"] != "infinite ends":
+                assert shares[tag, ext] == 1.0, (tag, ext, shares[tag, ext])
+    worst = min(shares, key=shares.get)
+    print(f"trilinear axis cases {np.dtype(dt).name}: {len(shares)} query sets, worst finite share {shares[worst]:.3f} {worst}")
     low = {t: round(s, 3) for t, s in shares.items() if s < 0.75}
     assert not low, low
