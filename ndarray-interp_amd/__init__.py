@@ -4,7 +4,7 @@ Layout
   csrc/                 hand-written HIP kernels (gfx950) + the C ABI (include/ndinterp.h)
   libndinterp_hip.so    built in-tree by __graft_entry__.build() / csrc/Makefile
   interp1d, interp2d    host-side mirror of Interp1DBuilder / Interp2DBuilder + the Strategy traits
-  interp3d              Interp3D / Trilinear, this project's own (include/ndinterp3d.h)
+  interp3d              Interp3D / Trilinear / Tricubic, this project's own (include/ndinterp3d.h, ndinterp3d_cubic.h)
   vector_extensions     monotonic_prop / batched get_lower_index / Locator (resident knot pyramid)
   generic_host          the reference's generic per-query path for non-f32/f64 element types (integers)
   sharding              query sharding over the GPUs of a node (no collective on the data path)
@@ -21,7 +21,7 @@ from .interp1d import (Akima, AkimaStrategy, AntiderivativeStrategy, InverseStra
                        Pchip, PchipStrategy, RowBoundary, SingleBoundary)
 from .interp2d import (JET_PARTS, Bicubic, Bilinear, Interp2D, Interp2DBuilder, Interp2DStrategy,
                        Interp2DStrategyBuilder)
-from .interp3d import Interp3D, Interp3DBuilder, Interp3DStrategy, Interp3DStrategyBuilder, Trilinear
+from .interp3d import Interp3D, Interp3DBuilder, Interp3DStrategy, Interp3DStrategyBuilder, Tricubic, Trilinear
 from .vector_extensions import Locator, Monotonic, get_lower_index, monotonic_prop
 from . import sharding
 
@@ -54,7 +54,7 @@ __all__ = [
     "Pchip", "PchipStrategy", "Akima", "AkimaStrategy", "CubicHermite", "CubicHermiteStrategy",
     "DerivativeStrategy", "AntiderivativeStrategy", "InverseStrategy",
     "Interp2D", "Interp2DBuilder", "Interp2DStrategy", "Interp2DStrategyBuilder", "Bilinear", "Bicubic", "JET_PARTS",
-    "Interp3D", "Interp3DBuilder", "Interp3DStrategy", "Interp3DStrategyBuilder", "Trilinear",
+    "Interp3D", "Interp3DBuilder", "Interp3DStrategy", "Interp3DStrategyBuilder", "Trilinear", "Tricubic",
     "Monotonic", "monotonic_prop", "get_lower_index", "Locator", "sharding", "device_count", "striped_ring", "output_empty", "output_zeros", "output_trim",
     "profile_enable", "profile_read", "PATH_AUTO", "PATH_GATHER", "PATH_BUCKETED",
 ]

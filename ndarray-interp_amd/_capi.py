@@ -188,6 +188,12 @@ SYMBOLS3D = {
     "ndi_interp3d_destroy": (None, [_P]),
 }
 
+# every symbol include/ndinterp3d_cubic.h declares (the Tricubic strategy: a third header, since the two above are frozen)
+SYMBOLS3D_CUBIC = {
+    "ndi_interp3d_create_tricubic": (C.c_int, [C.POINTER(Interp3DDesc), C.POINTER(Boundary), C.POINTER(_P)]),
+    "ndi_interp3d_tables": (C.c_int, [_P, C.POINTER(_P), C.c_int32]),
+}
+
 _lib = None
 
 
@@ -204,7 +210,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: build it with `make -C {os.path.join(_HERE, 'csrc')}` "
                 "(hipcc, gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS3D.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS3D.items()) + list(SYMBOLS3D_CUBIC.items()):
             fn = getattr(handle, name)  # AttributeError if the .so does not export it
             fn.restype = res
             fn.argtypes = args

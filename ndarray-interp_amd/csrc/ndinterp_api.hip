@@ -27,7 +27,7 @@
 #include <vector>
 
 #include "common.hpp"
-#include "../../include/ndinterp3d.h"
+#include "../../include/ndinterp3d_cubic.h"
 #include "host_logic.hpp"
 #include "kernels.hpp"
 #include "hermite_kernels.hpp"
@@ -42,6 +42,7 @@
 #include "bicubic_jet_kernels.hpp"
 #include "lanewise2d_kernels.hpp"
 #include "trilinear_kernels.hpp"
+#include "tricubic_kernels.hpp"
 
 #define NDI_API extern "C" __attribute__((visibility("default")))
 
@@ -1998,6 +1999,7 @@ static ndi_status create2d(const ndi_interp2d_desc& d, Interp2DBase** out) {
 // Interp3D (Trilinear)
 // ---------------------------------------------------------------------------------------------
 #include "trilinear_host.hpp"
+#include "tricubic_host.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // Locator: VectorExtensions::get_lower_index with the knot pyramid resident on the device
@@ -3196,26 +3198,37 @@ NDI_API ndi_status ndi_interp2d_eval_ring_sharded(const ndi_interp2d* const* han
 // ---- Interp3D (include/ndinterp3d.h) ----------------------------------------------------------
 // Every refusal is decided before any device work, and the builder's checks on host axes run on the host, so both behave
 // the same on a machine without a device.
-NDI_API ndi_status ndi_interp3d_create(const ndi_interp3d_desc* desc, ndi_interp3d** out) {
+// The refusals of a 3-D create that need no device, for the strategy `name` with `need` knots per axis; `bc`: the six ends
+// of a Tricubic create (NULL: none to check).
+static ndi_status interp3d_create_refusals(const char* name, unsigned long long need, const ndi_interp3d_desc* desc,
+                                           const ndi_boundary* bc, ndi_interp3d** out) {
   if (out) *out = nullptr;
   if (!desc || !out) return ndi::fail(NDI_BAD_ARG, "null argument");
   if (desc->dtype != NDI_F32 && desc->dtype != NDI_F64)
-    return ndi::fail(NDI_BAD_ARG, "Trilinear takes f32 / f64 data (dtype %d): integer and f16 / bf16 element types are not "
-                     "provided in three dimensions", (int)desc->dtype);
+    return ndi::fail(NDI_BAD_ARG, "%s takes f32 / f64 data (dtype %d): integer and f16 / bf16 element types are not "
+                     "provided in three dimensions", name, (int)desc->dtype);
   if (desc->reserved != 0)
     return ndi::fail(NDI_BAD_ARG, "ndi_interp3d_desc.reserved must be 0 (got %d): built against another header version?",
                      (int)desc->reserved);
+  static const char* const END[6] = {"x-left", "x-right", "y-left", "y-right", "z-left", "z-right"};
+  for (int k = 0; bc && k < 6; ++k)
+    if (bc[k].kind < NDI_BC_NOT_A_KNOT || bc[k].kind > NDI_BC_SECOND_DERIV)
+      return ndi::fail(NDI_BAD_ARG, "%s takes one non-periodic boundary kind with a scalar value per end (ndi_bc_kind); "
+                       "periodic and per-lane boundaries are not provided (%s end: kind %d)", name, END[k], (int)bc[k].kind);
   if (desc->validate && desc->memspace == NDI_MEM_HOST) {
     const ndi_status st =
         desc->dtype == NDI_F32
             ? ndi::check_axes_3d<float>((const float*)desc->x, desc->x_len, (const float*)desc->y, desc->y_len,
-                                        (const float*)desc->z, desc->z_len, desc->nx, desc->ny, desc->nz)
+                                        (const float*)desc->z, desc->z_len, desc->nx, desc->ny, desc->nz, need)
             : ndi::check_axes_3d<double>((const double*)desc->x, desc->x_len, (const double*)desc->y, desc->y_len,
-                                         (const double*)desc->z, desc->z_len, desc->nx, desc->ny, desc->nz);
+                                         (const double*)desc->z, desc->z_len, desc->nx, desc->ny, desc->nz, need);
     if (st != NDI_OK) return st;
   }
-  ndi_status ds = need_device(desc->device);
-  if (ds != NDI_OK) return ds;
+  return need_device(desc->device);
+}
+
+NDI_API ndi_status ndi_interp3d_create(const ndi_interp3d_desc* desc, ndi_interp3d** out) {
+  if (const ndi_status rs = interp3d_create_refusals("Trilinear", 2, desc, nullptr, out); rs != NDI_OK) return rs;
   NDI_TRY
   ndi::Interp3DBase* impl = nullptr;
   const ndi_status st = desc->dtype == NDI_F32 ? ndi::create3d<float>(*desc, &impl) : ndi::create3d<double>(*desc, &impl);
@@ -3258,6 +3271,32 @@ NDI_API void ndi_interp3d_destroy(ndi_interp3d* h) {
   } catch (...) {
   }
   delete h;
+}
+
+// ---- Interp3D, Tricubic (include/ndinterp3d_cubic.h) -------------------------------------------
+// ndi_interp3d_create's refusals with 3 knots per axis and the six ends, all before any device work.
+NDI_API ndi_status ndi_interp3d_create_tricubic(const ndi_interp3d_desc* desc, const ndi_boundary* bc, ndi_interp3d** out) {
+  if (const ndi_status rs = interp3d_create_refusals("Tricubic", 3, desc, bc, out); rs != NDI_OK) return rs;
+  NDI_TRY
+  ndi_boundary b6[6];
+  for (int k = 0; k < 6; ++k) b6[k] = bc ? bc[k] : ndi_boundary{NDI_BC_NOT_A_KNOT, 0.0};
+  ndi::Interp3DBase* impl = nullptr;
+  const ndi_status st = desc->dtype == NDI_F32 ? ndi::create3d_tricubic<float>(*desc, b6, &impl)
+                                               : ndi::create3d_tricubic<double>(*desc, b6, &impl);
+  if (st != NDI_OK) return st;
+  *out = new ndi_interp3d{impl};
+  return ndi::bounds_verdict(NDI_OK, impl->device);
+  NDI_CATCH
+}
+
+NDI_API ndi_status ndi_interp3d_tables(const ndi_interp3d* h, void* const tables[7], int32_t memspace) {
+  if (!h) return ndi::fail(NDI_BAD_ARG, "null handle");
+  if (!tables) return ndi::fail(NDI_BAD_ARG, "null tables array");
+  if (memspace != NDI_MEM_HOST && memspace != NDI_MEM_DEVICE) return ndi::fail(NDI_BAD_ARG, "unknown memspace");
+  NDI_TRY
+  const ndi_status st = h->impl->tables(tables, memspace);
+  return st == NDI_BAD_ARG ? st : ndi::bounds_verdict(st, h->impl->device);
+  NDI_CATCH
 }
 
 NDI_API ndi_status ndi_interp1d_trim(const ndi_interp1d* h) {

@@ -1,7 +1,9 @@
 // csrc/trilinear_host.hpp -- the host side of the 3-D handles (ndi_interp3d_*, include/ndinterp3d.h): Interp3DImpl<T> with the
 // Trilinear strategy; included by ndinterp_api.hip inside namespace ndi, behind float_host.hpp's helpers.
 //
-// Interp3DImpl keeps a small driver of its own (run), as AntiderivImpl does: three query arrays do not fit Queries<T> /
+// Interp3DDriver<T> is what every 3-D strategy shares (the axes, eval's chunking / staging / report, the head of a chunk, the
+// launch geometry); Interp3DImpl<T> (Trilinear, here) and Tricubic3DImpl<T> (tricubic_host.hpp) add their table and enqueue.
+// The 3-D handles keep a small driver of their own, as AntiderivImpl does: three query arrays do not fit Queries<T> /
 // FirstFail, which every other family instantiates, and the 3-D handle has no ring, no sharded form, no async_launch and no
 // small-row paths to share.  It is built from the common parts -- take_opts, the workspace lease, device staging of host
 // arrays in row chunks, the status read-back, ProfScope through launch1 -- in the order: options, refusals, lease, stage,
@@ -33,8 +35,7 @@ static TrilinearKnobs trilinear_knobs() {
 // is 0..n: its length is the data's and it rises.
 template <class T>
 ndi_status check_axes_3d(const T* x, uint64_t x_len, const T* y, uint64_t y_len, const T* z, uint64_t z_len, uint64_t nx,
-                         uint64_t ny, uint64_t nz) {
-  const unsigned long long need = 2;
+                         uint64_t ny, uint64_t nz, unsigned long long need = 2) {
   const uint64_t n[3] = {nx, ny, nz}, len[3] = {x ? x_len : nx, y ? y_len : ny, z ? z_len : nz};
   const T* k[3] = {x, y, z};
   static const char* const name[3] = {"x", "y", "z"};
@@ -60,6 +61,10 @@ struct Interp3DBase {
   virtual ndi_status eval(const void* qx, const void* qy, const void* qz, uint64_t nq, void* out, uint64_t out_stride,
                           const ndi_eval_opts& o, ndi_oob_info* info) = 0;
   virtual ndi_status clone_to(int dev, Interp3DBase** out) = 0;
+  // ndi_interp3d_tables (include/ndinterp3d_cubic.h): Tricubic handles only
+  virtual ndi_status tables(void* const t[7], int memspace) {
+    return fail(NDI_BAD_ARG, "ndi_interp3d_tables takes a Tricubic handle: Trilinear keeps no node derivatives");
+  }
 };
 
 // The options of ndi_interp3d_eval and the refusals that need no handle (so they come first, and answer without a device).
@@ -72,13 +77,14 @@ static ndi_status trilinear_take_opts(const ndi_eval_opts* opts, ndi_eval_opts& 
   return NDI_OK;
 }
 
+// What the 3-D strategies share: the axes, the chunking / staging / report driver (eval) and the head of a chunk (the status
+// words and the range pre-pass).  A strategy adds its table and the ONE strategy-specific step, enqueue.
 template <class T>
-struct Interp3DImpl final : Interp3DBase {
+struct Interp3DDriver : Interp3DBase {
   int mode = EX_NO;
   uint64_t nx = 0, ny = 0, nz = 0;
   std::vector<T> hx, hy, hz;   // the axes on the host: range limits, clones
   DevBuf axes;                 // [x | y | z], one allocation
-  DevBuf data;                 // T[nx][ny][nz][lanes]
   SpaceSet spaces;
 
   const T* dev_axis(int a) const { return axes.as<T>() + (a == 0 ? 0 : a == 1 ? nx : nx + ny); }
@@ -91,8 +97,11 @@ struct Interp3DImpl final : Interp3DBase {
   }
 
   // One chunk on device pointers through scratch set 0: the pre-pass unless `check`, then ONE evaluation launch.
-  void enqueue(hipStream_t s, Workspace& ws, const T* qx, const T* qy, const T* qz, uint64_t nq, T* out, uint64_t out_stride,
-               bool check) {
+  virtual void enqueue(hipStream_t s, Workspace& ws, const T* qx, const T* qy, const T* qz, uint64_t nq, T* out,
+                       uint64_t out_stride, bool check) = 0;
+
+  // The head of a chunk: the status words cleared, and the range pre-pass unless the kernel tests the queries itself.
+  TrilinearStatus* begin_chunk(hipStream_t s, Workspace& ws, const T* qx, const T* qy, const T* qz, uint64_t nq, bool check) {
     g_last_path.store(NDI_PATH_GATHER);
     TrilinearStatus* st = ws.sc[0].status.as<TrilinearStatus>();
     NDI_HIP(hipMemsetAsync(st, 0xFF, sizeof(TrilinearStatus), s));   // NO_FAIL on every axis
@@ -104,41 +113,69 @@ struct Interp3DImpl final : Interp3DBase {
       NDI_HIP(hipGetLastError());
       ps.done();
     }
-    const TrilinearKnobs K = trilinear_knobs();
+    return st;
+  }
+
+  // the axes and the scalars of a replica on `dev` (the strategy copies its table)
+  void clone_driver_to(int dev, Interp3DDriver<T>& h) const {
+    h.dtype = dtype; h.device = dev; h.lanes = lanes;
+    h.mode = mode;
+    h.nx = nx; h.ny = ny; h.nz = nz;
+    h.hx = hx; h.hy = hy; h.hz = hz;
+    {
+      DeviceGuard dg(dev);
+      h.axes.reserve((nx + ny + nz) * sizeof(T));
+    }
+    copy_across_devices(h.axes.p, dev, axes.p, device, (nx + ny + nz) * sizeof(T));
+  }
+
+  // The fields of a descriptor and its axes, checked as the builder checks them with `need` knots per axis.
+  ndi_status take_desc(const ndi_interp3d_desc& d, unsigned long long need) {
+    dtype = d.dtype;
+    device = d.device;
+    mode = d.extrapolate ? EX_YES : EX_NO;
+    nx = d.nx; ny = d.ny; nz = d.nz;
+    lanes = d.lanes;
+    hx = d.x ? fetch_axis<T>(d.x, d.x_len, d.memspace) : default_axis<T>(d.nx);
+    hy = d.y ? fetch_axis<T>(d.y, d.y_len, d.memspace) : default_axis<T>(d.ny);
+    hz = d.z ? fetch_axis<T>(d.z, d.z_len, d.memspace) : default_axis<T>(d.nz);
+    if (d.validate) {
+      const ndi_status st = check_axes_3d<T>(hx.data(), hx.size(), hy.data(), hy.size(), hz.data(), hz.size(), d.nx, d.ny, d.nz,
+                                             need);
+      if (st != NDI_OK) return st;
+    } else if (hx.size() != d.nx || hy.size() != d.ny || hz.size() != d.nz || d.nx < need || d.ny < need || d.nz < need) {
+      return fail(NDI_BAD_ARG, "unvalidated create with inconsistent sizes");
+    }
+    if (d.lanes == 0) return fail(NDI_BAD_ARG, "lanes must be >= 1");
+    if (d.nx > MAX_KNOTS || d.ny > MAX_KNOTS || d.nz > MAX_KNOTS) return fail(NDI_UNSUPPORTED, "too many knots");
+    if (!d.data) return fail(NDI_BAD_ARG, "null data pointer");
+    return NDI_OK;
+  }
+
+  // The launch geometry both strategies take: 16-byte vectors where lanes, stride and alignment allow, the axes in LDS where
+  // they fit, a resident grid over the items and its stride as a (rows, vectors) carry.  `stage_knob` / `vec_knob`: the
+  // strategy's NDI_*_STAGE / NDI_*_VEC.
+  struct Geometry {
+    bool wide, stage;
+    int vec;
+    size_t shmem;
+    uint64_t vpr, step_rows, step_vecs;
+    unsigned grid;
+  };
+  Geometry geometry(int stage_knob, int vec_knob, const void* table, const T* out, uint64_t out_stride, uint64_t nq) const {
     constexpr int W = Wide<T>::N;
-    const bool wide = K.vec != 1 && lanes % W == 0 && out_stride % W == 0 && aligned16(data.p) && aligned16(out);
-    const int vec = wide ? W : 1;
+    Geometry g{};
+    g.wide = vec_knob != 1 && lanes % W == 0 && out_stride % W == 0 && aligned16(table) && aligned16(out);
+    g.vec = g.wide ? W : 1;
     const size_t knots = ((nx + ny + nz) * sizeof(T) + 15) & ~(size_t)15;
-    const bool stage = K.stage != 0 && knots <= LDS_STAGE_LIMIT;
-    const size_t shmem = stage ? knots : 0;
-    TrilinearArgs<T> A{};
-    A.x = dev_axis(0); A.y = dev_axis(1); A.z = dev_axis(2);
-    A.data = data.as<T>();
-    A.qx = qx; A.qy = qy; A.qz = qz;
-    A.out = out;
-    A.nq = nq; A.lanes = lanes; A.out_stride = out_stride;
-    A.vpr = lanes / (uint64_t)vec;
-    const unsigned grid = resident_grid(nq * A.vpr, BLOCK, shmem, BLOCK);
-    const uint64_t step = (uint64_t)grid * BLOCK;
-    A.step_rows = step / A.vpr;
-    A.step_vecs = step % A.vpr;
-    A.nx = (uint32_t)nx; A.ny = (uint32_t)ny; A.nz = (uint32_t)nz;
-    A.mode = mode;
-    A.first_fail = &st->first_fail[0];
-    if (trace_plan())
-      std::fprintf(stderr, "[ndi plan] trilinear vec=%d stage=%d check=%d grid=%u\n", vec, (int)stage, (int)check, grid);
-    pick_bool(wide, [&](auto wide_) {
-      constexpr int VEC = wide_ ? W : 1;
-      pick_bool(stage, [&](auto stage_) {
-        constexpr bool STAGE = stage_;
-        pick_bool(check, [&](auto check_) {
-          constexpr bool CHECK = check_;
-          auto kern = eval_trilinear_kernel<T, VEC, STAGE, CHECK>;
-          if constexpr (STAGE) allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)LDS_STAGE_LIMIT);
-          launch1<T>(s, PC_EVAL, dim3(grid), dim3(BLOCK), shmem, kern, A);
-        });
-      });
-    });
+    g.stage = stage_knob != 0 && knots <= LDS_STAGE_LIMIT;
+    g.shmem = g.stage ? knots : 0;
+    g.vpr = lanes / (uint64_t)g.vec;
+    g.grid = resident_grid(nq * g.vpr, BLOCK, g.shmem, BLOCK);
+    const uint64_t step = (uint64_t)g.grid * BLOCK;
+    g.step_rows = step / g.vpr;
+    g.step_vecs = step % g.vpr;
+    return g;
   }
 
   // The reference's error for the chunk whose lowest failing queries per axis are f[0..2], relative to query `off`: the
@@ -212,20 +249,55 @@ struct Interp3DImpl final : Interp3DBase {
     }
     return NDI_OK;
   }
+};
+
+template <class T>
+struct Interp3DImpl final : Interp3DDriver<T> {
+  using D = Interp3DDriver<T>;
+  DevBuf data;                 // T[nx][ny][nz][lanes]
+
+  void enqueue(hipStream_t s, Workspace& ws, const T* qx, const T* qy, const T* qz, uint64_t nq, T* out, uint64_t out_stride,
+               bool check) override {
+    TrilinearStatus* st = D::begin_chunk(s, ws, qx, qy, qz, nq, check);
+    const TrilinearKnobs K = trilinear_knobs();
+    constexpr int W = Wide<T>::N;
+    const typename D::Geometry G = D::geometry(K.stage, K.vec, data.p, out, out_stride, nq);
+    TrilinearArgs<T> A{};
+    A.x = D::dev_axis(0); A.y = D::dev_axis(1); A.z = D::dev_axis(2);
+    A.data = data.as<T>();
+    A.qx = qx; A.qy = qy; A.qz = qz;
+    A.out = out;
+    A.nq = nq; A.lanes = D::lanes; A.out_stride = out_stride;
+    A.vpr = G.vpr;
+    A.step_rows = G.step_rows;
+    A.step_vecs = G.step_vecs;
+    A.nx = (uint32_t)D::nx; A.ny = (uint32_t)D::ny; A.nz = (uint32_t)D::nz;
+    A.mode = D::mode;
+    A.first_fail = &st->first_fail[0];
+    if (trace_plan())
+      std::fprintf(stderr, "[ndi plan] trilinear vec=%d stage=%d check=%d grid=%u\n", G.vec, (int)G.stage, (int)check, G.grid);
+    pick_bool(G.wide, [&](auto wide_) {
+      constexpr int VEC = wide_ ? W : 1;
+      pick_bool(G.stage, [&](auto stage_) {
+        constexpr bool STAGE = stage_;
+        pick_bool(check, [&](auto check_) {
+          constexpr bool CHECK = check_;
+          auto kern = eval_trilinear_kernel<T, VEC, STAGE, CHECK>;
+          if constexpr (STAGE) allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)LDS_STAGE_LIMIT);
+          launch1<T>(s, PC_EVAL, dim3(G.grid), dim3(BLOCK), G.shmem, kern, A);
+        });
+      });
+    });
+  }
 
   ndi_status clone_to(int dev, Interp3DBase** out) override {
     std::unique_ptr<Interp3DImpl<T>> h(new Interp3DImpl<T>());
-    h->dtype = dtype; h->device = dev; h->lanes = lanes;
-    h->mode = mode;
-    h->nx = nx; h->ny = ny; h->nz = nz;
-    h->hx = hx; h->hy = hy; h->hz = hz;
+    D::clone_driver_to(dev, *h);
     {
       DeviceGuard dg(dev);
-      h->axes.reserve((nx + ny + nz) * sizeof(T));
       h->data.reserve(data.bytes);
     }
-    copy_across_devices(h->axes.p, dev, axes.p, device, (nx + ny + nz) * sizeof(T));
-    copy_across_devices(h->data.p, dev, data.p, device, data.bytes);
+    copy_across_devices(h->data.p, dev, data.p, D::device, data.bytes);
     *out = h.release();
     return NDI_OK;
   }
@@ -236,24 +308,7 @@ static ndi_status create3d(const ndi_interp3d_desc& d, Interp3DBase** out) {
   DeviceGuard dg(d.device);
   Range rg("ndi_interp3d_create");
   std::unique_ptr<Interp3DImpl<T>> h(new Interp3DImpl<T>());
-  h->dtype = d.dtype;
-  h->device = d.device;
-  h->mode = d.extrapolate ? EX_YES : EX_NO;
-  h->nx = d.nx; h->ny = d.ny; h->nz = d.nz;
-  h->lanes = d.lanes;
-  h->hx = d.x ? fetch_axis<T>(d.x, d.x_len, d.memspace) : default_axis<T>(d.nx);
-  h->hy = d.y ? fetch_axis<T>(d.y, d.y_len, d.memspace) : default_axis<T>(d.ny);
-  h->hz = d.z ? fetch_axis<T>(d.z, d.z_len, d.memspace) : default_axis<T>(d.nz);
-  if (d.validate) {
-    const ndi_status st = check_axes_3d<T>(h->hx.data(), h->hx.size(), h->hy.data(), h->hy.size(), h->hz.data(), h->hz.size(),
-                                           d.nx, d.ny, d.nz);
-    if (st != NDI_OK) return st;
-  } else if (h->hx.size() != d.nx || h->hy.size() != d.ny || h->hz.size() != d.nz || d.nx < 2 || d.ny < 2 || d.nz < 2) {
-    return fail(NDI_BAD_ARG, "unvalidated create with inconsistent sizes");
-  }
-  if (d.lanes == 0) return fail(NDI_BAD_ARG, "lanes must be >= 1");
-  if (d.nx > MAX_KNOTS || d.ny > MAX_KNOTS || d.nz > MAX_KNOTS) return fail(NDI_UNSUPPORTED, "too many knots");
-  if (!d.data) return fail(NDI_BAD_ARG, "null data pointer");
+  if (const ndi_status st = h->take_desc(d, 2); st != NDI_OK) return st;
   h->upload_axes();
   const size_t bytes = (size_t)d.nx * d.ny * d.nz * d.lanes * sizeof(T);
   h->data.reserve(bytes);

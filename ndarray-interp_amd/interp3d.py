@@ -1,6 +1,6 @@
-"""Interp3D: interpolation along the first three axes of n-dimensional data, with the `Trilinear` strategy evaluated on
-the device (include/ndinterp3d.h).  The reference stops at two axes; this is its Bilinear taken one axis further, written
-like `interp2d.py`: `Interp3D.builder(data).x(x).y(y).z(z).strategy(Trilinear.new()).build()`."""
+"""Interp3D: interpolation along the first three axes of n-dimensional data, with the `Trilinear` (include/ndinterp3d.h)
+and `Tricubic` (include/ndinterp3d_cubic.h) strategies evaluated on the device.  The reference stops at two axes; these are
+its Bilinear taken one axis further and the Bicubic of this project taken one axis further, written like `interp2d.py`: `Interp3D.builder(data).x(x).y(y).z(z).strategy(Trilinear.new()).build()`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -10,7 +10,7 @@ import numpy as np
 from . import _capi
 from ._arrays import Buf, current_stream_ptr, is_torch, np_dtype_of, torch_dtype
 from .errors import BuilderError, InterpolateError, Panic, raise_builder, raise_eval
-from .interp1d import _check_out_dtype, _default_axis, _default_device, _host, _to_device
+from .interp1d import BoundaryCondition, RowBoundary, _check_out_dtype, _default_axis, _default_device, _host, _to_device
 from .vector_extensions import Monotonic, get_lower_index, monotonic_prop
 
 _FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
@@ -41,13 +41,11 @@ class Interp3DStrategy:
         pass
 
 
-class Trilinear(Interp3DStrategyBuilder, Interp3DStrategy):
-    """Trilinear strategy on a rectilinear grid (scipy: RegularGridInterpolator(method="linear"); MATLAB: interp3): seven
-    `calc_frac` per element in the reference's Bilinear order continued along z, on the device (ndi_interp3d_create /
-    ndi_interp3d_eval; include/ndinterp3d.h states the value rule).  Builder and finished strategy in one, like
-    `Bilinear`.  f32 / f64 data only."""
+class _DeviceStrategy3D(Interp3DStrategyBuilder, Interp3DStrategy):
+    """What the built-in 3-D strategies share: builder and finished strategy in one, like `Bilinear`; the handle, its
+    release and clone, and the one C-ABI call per batch.  A strategy states its name in the errors by being the class it
+    is, and its create call in `_create_call`."""
 
-    MINIMUM_DATA_LENGHT = 2
     _takes_fresh = True
 
     def __init__(self):
@@ -57,25 +55,25 @@ class Trilinear(Interp3DStrategyBuilder, Interp3DStrategy):
         self._device_req = None
         self._np_dtype = None
         self._lanes = 1
+        self._shape = None
 
-    @staticmethod
-    def new() -> "Trilinear":
-        return Trilinear()
-
-    def device(self, ordinal: int) -> "Trilinear":
+    def device(self, ordinal: int):
         """The HIP device that holds the grid (default: the data tensor's device, else LOCAL_RANK / device 0)."""
         self._device_req = int(ordinal)
         return self
 
-    def extrapolate(self, yes: bool) -> "Trilinear":
+    def extrapolate(self, yes: bool):
         self._extrapolate = bool(yes)
         return self
 
-    def build(self, x, y, z, data, device=None) -> "Trilinear":
+    def _create_call(self, desc, handle) -> int:
+        raise NotImplementedError
+
+    def build(self, x, y, z, data, device=None):
         dt = np_dtype_of(data)
         if dt not in _FLOATS:
-            raise TypeError(f"Trilinear takes float32 / float64 data, got {dt}: integer and f16 / bf16 element types are "
-                            "not provided in three dimensions")
+            raise TypeError(f"{type(self).__name__} takes float32 / float64 data, got {dt}: integer and f16 / bf16 element "
+                            "types are not provided in three dimensions")
         db = Buf(data)
 
         def axis(a):
@@ -98,10 +96,10 @@ class Trilinear(Interp3DStrategyBuilder, Interp3DStrategy):
         d.x, d.y, d.z, d.data = xb.ptr, yb.ptr, zb.ptr, db.ptr
         d.validate = 0   # Interp3DBuilder.build() validated already
         h = C.c_void_p()
-        st = _capi.lib().ndi_interp3d_create(C.byref(d), C.byref(h))
+        st = self._create_call(d, h)
         if st != _capi.OK:
             raise_builder(st)
-        self._h, self._device, self._np_dtype, self._lanes = h, device, dt, lanes
+        self._h, self._device, self._np_dtype, self._lanes, self._shape = h, device, dt, lanes, tuple(db.shape)
         return self
 
     def release(self) -> None:
@@ -115,7 +113,7 @@ class Trilinear(Interp3DStrategyBuilder, Interp3DStrategy):
         except Exception:
             pass
 
-    def clone(self, device: int) -> "Trilinear":
+    def clone(self, device: int):
         """A replica of this built strategy on `device` (ndi_interp3d_clone): axes and grid are copied device to device."""
         import copy
         h = C.c_void_p()
@@ -163,6 +161,93 @@ class Trilinear(Interp3DStrategyBuilder, Interp3DStrategy):
         one = lambda v: np.array([v], dtype=self._np_dtype)   # noqa: E731
         self.interp_array_into(interpolator, one(x), one(y), one(z), out)
         target[...] = out.reshape(target.shape)
+
+
+class Trilinear(_DeviceStrategy3D):
+    """Trilinear strategy on a rectilinear grid (scipy: RegularGridInterpolator(method="linear"); MATLAB: interp3): seven
+    `calc_frac` per element in the reference's Bilinear order continued along z, on the device (ndi_interp3d_create /
+    ndi_interp3d_eval; include/ndinterp3d.h states the value rule).  Builder and finished strategy in one, like
+    `Bilinear`.  f32 / f64 data only."""
+
+    MINIMUM_DATA_LENGHT = 2
+
+    @staticmethod
+    def new() -> "Trilinear":
+        return Trilinear()
+
+    def _create_call(self, desc, handle) -> int:
+        return _capi.lib().ndi_interp3d_create(C.byref(desc), C.byref(handle))
+
+
+class Tricubic(_DeviceStrategy3D):
+    """Tricubic strategy: the tensor-product cubic spline on a rectilinear grid, C2 in each variable (scipy:
+    RegularGridInterpolator(method="cubic") with a direct solver, for the default ends), built and evaluated on the device
+    (ndi_interp3d_create_tricubic; include/ndinterp3d_cubic.h states the numerical contract).  Seven node-derivative tables
+    from seven Bicubic passes, 21 Hermite forms per element.  Three or more knots per axis, f32 / f64 data only; the ends
+    are `BoundaryCondition` / `RowBoundary` objects used as `Bicubic` uses them."""
+
+    MINIMUM_DATA_LENGHT = 3
+
+    def __init__(self):
+        super().__init__()
+        self._bc = [RowBoundary.NotAKnot] * 3   # x, y, z
+
+    @staticmethod
+    def new() -> "Tricubic":
+        return Tricubic()
+
+    @staticmethod
+    def _ends(bc) -> RowBoundary:
+        """One axis' (left, right) pair from a BoundaryCondition (NotAKnot / Natural / Clamped) or a RowBoundary."""
+        if isinstance(bc, RowBoundary):
+            return bc
+        if isinstance(bc, BoundaryCondition) and bc.tag in ("NotAKnot", "Natural", "Clamped"):
+            return getattr(RowBoundary, bc.tag)
+        if isinstance(bc, BoundaryCondition) and bc.tag == "Periodic":
+            raise TypeError("Tricubic has no periodic ends: its boundaries are one non-periodic kind per end, and periodic "
+                            "axes are not provided in three dimensions")
+        if isinstance(bc, BoundaryCondition) and bc.tag == "Individual":
+            raise TypeError("Tricubic takes no per-lane (Individual) boundaries: one kind and scalar value per end "
+                            "(RowBoundary.Mixed(left, right) gives an axis two different ends)")
+        raise TypeError(f"Tricubic boundaries are BoundaryCondition or RowBoundary objects, got {type(bc).__name__}")
+
+    def boundary(self, bc) -> "Tricubic":
+        """The same ends on all three axes."""
+        self._bc = [self._ends(bc)] * 3
+        return self
+
+    def boundary_x(self, bc) -> "Tricubic":
+        self._bc[0] = self._ends(bc)
+        return self
+
+    def boundary_y(self, bc) -> "Tricubic":
+        self._bc[1] = self._ends(bc)
+        return self
+
+    def boundary_z(self, bc) -> "Tricubic":
+        self._bc[2] = self._ends(bc)
+        return self
+
+    def _create_call(self, desc, handle) -> int:
+        ends = [e for axis in self._bc for e in (axis.left, axis.right)]
+        bc = (_capi.Boundary * 6)(*[_capi.Boundary(int(e.kind), float(e.value)) for e in ends])
+        return _capi.lib().ndi_interp3d_create_tricubic(C.byref(desc), bc, C.byref(handle))
+
+    def tables(self, on_device=False):
+        """(fx, fy, fz, fxy, fxz, fyz, fxyz): the node derivatives, each of the data's shape (ndi_interp3d_tables), as host
+        arrays -- or, with `on_device`, as tensors on the handle's device."""
+        if on_device:
+            import torch
+            out = [torch.empty(self._shape, dtype=torch_dtype(self._np_dtype), device=f"cuda:{self._device}") for _ in range(7)]
+            ptrs, space = [t.data_ptr() for t in out], _capi.MEM_DEVICE
+        else:
+            out = [np.empty(self._shape, dtype=self._np_dtype) for _ in range(7)]
+            ptrs, space = [a.ctypes.data for a in out], _capi.MEM_HOST
+        st = _capi.lib().ndi_interp3d_tables(self._h, (C.c_void_p * 7)(*ptrs), space)
+        if st != _capi.OK:
+            from .errors import DeviceError
+            raise DeviceError(_capi.last_error())
+        return tuple(out)
 
 
 class Interp3D:
